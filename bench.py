@@ -2,7 +2,14 @@
 """bench.py -- signal samples/s of the homopolymer-calling forward pass on MI355X.
 
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` prints ONE JSON line on
-rank 0.  For N > 1 it is launched under ``torch.distributed.run`` (one rank per GPU).
+rank 0.  For N > 1 it is launched under ``torch.distributed.run`` (one rank per GPU).  Such a plain run
+does only what the headline figure needs: set-up, warm-up, the K timed steps, and the line (``metric``,
+``value``, ``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` = milliseconds of one timed step).
+``--dump-outputs DIR`` writes what the last timed step computed (rank 0's per-sample probabilities,
+float32) to ``DIR/probabilities.npy``; the inputs are seeded, so runs with the same arguments compare
+output for output.  Everything else -- the CPU baseline, the parity gate against the oracle, the
+per-kernel HIP-event pass and the roofline, the RCCL probe and the informational legs below -- runs
+with ``--full`` only.
 
 Workload (BASELINE.json configs[1], SURVEY.md 8d "config 2"): synthetic 4096-sample reads
 (seeded DAC squiggles, median/MAD normalised exactly like catfish/infer.py:96-105), cut into
@@ -11,7 +18,7 @@ the reference's bundled checkpoint ckpnt-30000.  A step = device-resident normal
 -> device-resident per-sample probabilities through the C ABI (cf_infer).  Reads shard across
 ranks with no collective on the data path (weak scaling: every rank runs K steps of its own reads).
 
-``value`` counts UN-PADDED signal samples (256 x 4096 per step and rank).  The line also carries
+``value`` counts UN-PADDED signal samples (256 x 4096 per step and rank).  With ``--full`` the line also carries
 informational objects that are never the value: ``other_precisions`` (bf16x3 / bf16 on the same
 workload, each with its own roofline), ``config4`` (BASELINE configs[3]: 10 000 variable-length reads, packed,
 bf16), ``latency`` (118- and 256-window calls), ``config5`` (BASELINE configs[4]: the training step), ``host_to_host_pipeline`` (PCIe-inclusive), ``sharded_gather`` (BASELINE configs[2]'s path:
@@ -656,19 +663,26 @@ def main():
     ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3", "bf16"],
                     help="arithmetic of the biGRU matmuls (fp32 = exact fp32 MFMA, the BASELINE configs[1] dtype)")
     ap.add_argument("--no-extra-precisions", action="store_true",
-                    help="skip the informational legs (other precisions, config 4, host-to-host pipeline)")
-    ap.add_argument("--no-sharded-leg", action="store_true", help="skip the informational sharded_gather leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: skip the informational legs (other precisions, config 4, host-to-host pipeline)")
+    ap.add_argument("--no-sharded-leg", action="store_true", help="with --full: skip the informational sharded_gather leg")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--reads-per-rank", type=int, default=SHARDED_READS_PER_RANK,
                     help="reads (files) per rank of the sharded_gather / cli_end_to_end legs (BASELINE configs[2]: 12 500 = 100 000 on 8)")
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="run untimed steps for this long before the W warm-up steps: the GPU clocks down while the CPU "
                          "baseline leg (or process start-up) keeps it idle, and a short W would time the clock ramp")
-    ap.add_argument("--no-kernel-events", action="store_true", help="disable per-kernel HIP events")
+    ap.add_argument("--no-kernel-events", action="store_true", help="with --full: disable the per-kernel HIP-event pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline, the parity gate against the oracle, "
+                         "the per-kernel HIP-event pass and the roofline, the RCCL probe (N > 1) and the informational legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0's per-sample probabilities, float32) as DIR/<name>.npy")
     ap.add_argument("--only-leg", choices=["config4"], default=None,
                     help="run ONE informational leg in its profiling form and print its JSON (the command tools/collect_traffic_config4.sh "
                          "puts under rocprofv3); no headline line")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     globals()["SHARDED_READS_PER_RANK"] = int(args.reads_per_rank)
     if args.only_leg == "config4":
         import torch
@@ -687,7 +701,7 @@ def main():
     if "CATFISH_BENCH_DEVICE" in os.environ:      # rehearsal of the N > 1 path on a box with fewer GPUs than ranks
         shared_device = local_rank = int(os.environ["CATFISH_BENCH_DEVICE"])
     cpu_res = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         progress("cpu_baseline leg (oracle on the host cores)")
         cpu_res = cpu_baseline()
 
@@ -727,8 +741,9 @@ def main():
         probe = torch.ones(1)
         dist.all_reduce(probe)
         backend, ranks_seen = "gloo", int(round(float(probe.item())))
-        rccl_probe = probe_rccl(dist, torch, local_rank)
-        nccl_error = rccl_probe.get("error")
+        if args.full:
+            rccl_probe = probe_rccl(dist, torch, local_rank)
+            nccl_error = rccl_probe.get("error")
 
     progress("process group %s; creating the engine on device %d" % (backend, local_rank))
     from catfish_amd.engine import HipEngine
@@ -769,10 +784,16 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     eng.check_error()
-    # ... then an equally long UNTIMED pass over the same batches with HIP events around every kernel of every step (on the
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path received from its last step: cf_infer's per-sample probabilities, [30208 * 35] float32
+        last = outs[(args.steps - 1) & 1].cpu().numpy()
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "probabilities.npy"), last)
+        progress("last timed step's outputs written to %s" % args.dump_outputs)
+    # ... then (--full) an equally long UNTIMED pass over the same batches with HIP events around every kernel of every step (on the
     # streams the kernels are launched on): ``kernels_ms`` and ``roofline.avg_launch_ms`` come from this pass, ``value`` from the one above
     kern, dt_events = {}, None
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         eng.profile_enable(True, every=1)
         eng.profile_reset()
         dt_events = timed_steps(eng, batches, outs, args.steps, torch)
@@ -791,8 +812,25 @@ def main():
 
     result = None
     parity_ok = True
-    progress("timed region done: %.3f ms per step; parity gate" % (dt / args.steps * 1e3))
+    progress("timed region done: %.3f ms per step%s" % (dt / args.steps * 1e3, "; parity gate" if args.full else ""))
     if rank == 0:
+        peak = PEAK_F32_MFMA_TFLOPS if args.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
+        result = {
+            "metric": "signal samples/s classified",
+            "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "prewarm_ms": args.prewarm_ms, "vs_baseline": None,
+            "dtype": {"fp32": "f32", "bf16x3": "bf16x3 (split-operand fp32 emulation, f32 accumulate)",
+                      "bf16": "bf16 (f32 accumulate)"}[args.precision], "data": "synthetic",
+            "config": {"workload": "configs[1]: synthetic 4096-sample reads, 256 reads (30208 windows of 35) "
+                                   "per step and GPU, fp32, ckpnt-30000 weights",
+                       "reads_per_step": READS_PER_STEP, "read_len": READ_LEN, "windows_per_step": READS_PER_STEP * 118,
+                       "parallelism": "reads sharded over %d GPU(s), no collective" % world},
+            "full": bool(args.full),
+            "whole_pass": {"achieved_tflops": value / world * FLOP_PER_SAMPLE / 1e12,
+                           "frac_of_mfma_peak": value / world * FLOP_PER_SAMPLE / 1e12 / peak},
+        }
+    if rank == 0 and args.full:
         # parity gate of the benchmarked configuration against the oracle (not timed): a build that fails it reports no value
         from oracle import catfish_oracle as oracle
         # the first, a middle and the last read of the launch (tile 0, the interior, the ragged tail of the last workgroup); the
@@ -814,21 +852,9 @@ def main():
         parity_ok = bool(np.isfinite(got).all() and max_dp < gate and match >= min_match)
 
         roof = mid_roofline(kern, args.precision, samples_per_step)
-        peak = PEAK_F32_MFMA_TFLOPS if args.precision == "fp32" else PEAK_BF16_MFMA_TFLOPS
-        result = {
-            "metric": "signal samples/s classified",
-            "value": value if parity_ok else None, "unit": "samples/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "prewarm_ms": args.prewarm_ms, "vs_baseline": None,
-            "dtype": {"fp32": "f32", "bf16x3": "bf16x3 (split-operand fp32 emulation, f32 accumulate)",
-                      "bf16": "bf16 (f32 accumulate)"}[args.precision], "data": "synthetic",
-            "config": {"workload": "configs[1]: synthetic 4096-sample reads, 256 reads (30208 windows of 35) "
-                                   "per step and GPU, fp32, ckpnt-30000 weights",
-                       "reads_per_step": READS_PER_STEP, "read_len": READ_LEN, "windows_per_step": READS_PER_STEP * 118,
-                       "parallelism": "reads sharded over %d GPU(s), no collective" % world},
+        result.update({
+            "value": value if parity_ok else None,
             "roofline": roof,
-            "whole_pass": {"achieved_tflops": value / world * FLOP_PER_SAMPLE / 1e12,
-                           "frac_of_mfma_peak": value / world * FLOP_PER_SAMPLE / 1e12 / peak},
             "kernels_ms": {k: v[0] / v[1] for k, v in kern.items()},
             "kernel_events": {"pass": "separate untimed pass of %d steps over the same batches right after the timed steps, HIP events "
                                       "around every kernel of every step; the timed steps run with events off" % args.steps,
@@ -838,12 +864,12 @@ def main():
                        "label_match_after_correct_short": match_corrected, "gate": gate,
                        "min_label_match": min_match, "passed": parity_ok,
                        "sample": "reads %s of the %d in one launch (first, middle, last)" % (picks, READS_PER_STEP)},
-        }
+        })
         if not parity_ok:
             result["unverified_value"] = value
         result["cpu_baseline"] = cpu_res
     # informational legs: the same workload with the other GRU arithmetics (not the headline value)
-    if world == 1 and not args.no_extra_precisions:
+    if args.full and world == 1 and not args.no_extra_precisions:
         from oracle import catfish_oracle as oracle
         extra = {}
         for prec in ("fp32", "bf16x3", "bf16"):
@@ -896,7 +922,7 @@ def main():
                                            "ms_per_batch": d3 / len(pb) * 1e3,
                                            "what": "pinned int16 DAC -> cf_normalize -> cf_infer -> cf_postprocess -> cf_spans -> "
                                                    "host span table, double-buffered; never the headline value"}
-    if not args.no_sharded_leg and args.precision == "fp32":
+    if args.full and not args.no_sharded_leg and args.precision == "fp32":
         progress("sharded_gather leg (%d reads per rank)" % SHARDED_READS_PER_RANK)
         try:
             sg = leg_sharded_gather(eng, weights, rank, world, dist, torch)
@@ -907,7 +933,7 @@ def main():
         if rank == 0:
             result["sharded_gather"] = sg
     eng.close()
-    if not args.no_sharded_leg and args.precision == "fp32":
+    if args.full and not args.no_sharded_leg and args.precision == "fp32":
         progress("cli_end_to_end leg (%d files per rank)" % SHARDED_READS_PER_RANK)
         try:
             ce = leg_cli_end_to_end(weights, rank, world, local_rank, dist, torch)

@@ -6,9 +6,7 @@ import numpy as np
 import pytest
 
 from catfish_amd import checkpoint
-from conftest import GOLDEN, REFERENCE, has_reference
-
-CKPT_DIR = os.path.join(REFERENCE, "catfish", "ResNetRNN", "checkpoints")
+from conftest import GOLDEN
 
 
 def test_crc32c_known_answers():
@@ -37,19 +35,20 @@ def test_table_fixture_shape_facts():
     assert sum(int(np.prod(table[n]["shape"])) for n in inf) == 197185
 
 
-@pytest.mark.skipif(not has_reference(), reason="reference checkpoint not mounted")
-def test_reference_bundle_matches_fixture_and_crcs(ckpt_weights):
-    entries = checkpoint.read_index(os.path.join(CKPT_DIR, "ckpnt-30000.index"))
+def test_reference_bundle_matches_fixture_and_crcs(ckpt_weights, reference_checkpoints):
+    ckpt_dir = reference_checkpoints                    # TensorFlow's .index byte for byte, the real inference tensors in the data
+    entries = checkpoint.read_index(os.path.join(ckpt_dir, "ckpnt-30000.index"))
     with open(os.path.join(GOLDEN, "ckpt_table.json")) as fh:
         table = json.load(fh)
     assert [e.as_dict() for e in entries.values()] == table
-    w = checkpoint.read_inference_weights(CKPT_DIR, "ckpnt-30000")     # verifies every CRC
+    w = checkpoint.read_inference_weights(ckpt_dir, "ckpnt-30000")     # verifies every CRC
     assert sorted(w) == sorted(ckpt_weights)
     for k in w:
         assert np.array_equal(w[k], ckpt_weights[k]), k
     # "latest" resolution (no `checkpoint` state file in the bundle -> highest step)
-    w2 = checkpoint.read_inference_weights(CKPT_DIR, "latest")
+    w2 = checkpoint.read_inference_weights(ckpt_dir, "latest")
     assert np.array_equal(w2["conv1d/kernel"], w["conv1d/kernel"])
+    assert len(checkpoint.read_optimizer_state(ckpt_dir, "ckpnt-30000")) == 116    # every slot checked against its recorded CRC
 
 
 def test_checkpoint_fingerprints(ckpt_weights):
@@ -92,25 +91,35 @@ def test_corruption_is_detected(tmp_path, ckpt_weights):
         checkpoint.read_checkpoint(prefix, ["nope"], verify_crc=False)
 
 
-@pytest.mark.skipif(not has_reference(), reason="needs the reference checkpoint")
-def test_writer_reproduces_the_reference_bundle_byte_for_byte(tmp_path):
+def test_writer_reproduces_the_reference_bundle_byte_for_byte(tmp_path, ckpt_tensors):
     """The strongest pin the reference offers for the WRITER: ckpnt-30000.{index,data-00000-of-00001} were written by
-    TensorFlow 1.10's own BundleWriter.  Reading all 190 tensors and writing them back must give the same two files, byte for
-    byte -- tensor order and packing of the data file, every BundleEntryProto (dtype, shape, offset, size, masked CRC-32C),
-    the leveldb block layout (prefix compression, restart array, block trailers), the index entry (leveldb's
-    FindShortSuccessor of the last key) and the footer.  So a bundle written here is what tf.train.Saver would have written."""
+    TensorFlow 1.10's own BundleWriter.  Writing all 190 entries back (the inference tensors, and stand-ins for the optimizer
+    slots that carry the slots' recorded CRC-32Cs, see conftest.ckpt_tensors) must give TensorFlow's .index byte for byte (size
+    and SHA-256 recorded in tests/golden/ckpnt-30000-files.json) -- every BundleEntryProto (dtype, shape, offset, size, masked
+    CRC-32C), the leveldb block layout (prefix compression, restart array, block trailers), the index entry (leveldb's
+    FindShortSuccessor of the last key) and the footer -- and a data file of TensorFlow's size in which every tensor sits at
+    the offset TensorFlow gave it.  So a bundle written here is what tf.train.Saver would have written."""
     import hashlib
-    ref = os.path.join(REFERENCE, "catfish", "ResNetRNN", "checkpoints", "ckpnt-30000")
-    tensors = checkpoint.read_checkpoint(ref)
-    assert len(tensors) == 190
+    assert len(ckpt_tensors) == 190
     out = str(tmp_path / "ckpnt-30000")
-    checkpoint.write_checkpoint(out, tensors)
-    for ext in (".index", ".data-00000-of-00001"):
-        with open(ref + ext, "rb") as a, open(out + ext, "rb") as b:
-            assert a.read() == b.read(), ext
-    # fingerprints of the reference's files (so a reader of this test sees what was compared)
-    assert hashlib.sha256(open(out + ".index", "rb").read()).hexdigest().startswith("471de3f2a6280c50")
-    assert hashlib.sha256(open(out + ".data-00000-of-00001", "rb").read()).hexdigest().startswith("8d3af93055b35b16")
+    checkpoint.write_checkpoint(out, ckpt_tensors)
+    with open(os.path.join(GOLDEN, "ckpnt-30000-files.json")) as fh:
+        ref = json.load(fh)
+    index = open(out + ".index", "rb").read()
+    assert len(index) == ref["index"]["bytes"] and hashlib.sha256(index).hexdigest() == ref["index"]["sha256"]
+    # fingerprint of the reference's file (so a reader of this test sees what was compared)
+    assert hashlib.sha256(index).hexdigest().startswith("471de3f2a6280c50")
+    data = open(out + ".data-00000-of-00001", "rb").read()
+    assert len(data) == ref["data-00000-of-00001"]["bytes"]
+    with open(os.path.join(GOLDEN, "ckpt_table.json")) as fh:
+        table = json.load(fh)
+    for e in table:
+        assert data[e["offset"]:e["offset"] + e["size"]] == np.ascontiguousarray(ckpt_tensors[e["name"]]).tobytes(), e["name"]
+    # ... and the reader gets every tensor back from it, CRCs verified
+    back = checkpoint.read_checkpoint(out)
+    assert list(back) == [e["name"] for e in table]
+    for k, v in back.items():
+        assert v.dtype == ckpt_tensors[k].dtype and v.tobytes() == np.ascontiguousarray(ckpt_tensors[k]).tobytes(), k
 
 
 def test_native_crc32c_equals_the_python_loop():

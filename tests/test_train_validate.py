@@ -1,5 +1,6 @@
 """Host logic of the training / validation driver (reference networks/train_validate.py) and of the model report
 (rnn_class.py:264-270, resnet_class.py:28-32) -- no GPU needed."""
+import json
 import os
 
 import numpy as np
@@ -8,7 +9,7 @@ import pytest
 from catfish_amd import metrics, neural_network, train_validate as tv
 from catfish_amd.resnet_class import ResNetRNN
 from catfish_amd.rnn_class import RNN, sigmoid_cross_entropy_from_logits
-from conftest import REFERENCE, has_reference
+from conftest import GOLDEN
 
 
 def test_padding_of_the_training_driver_differs_from_infer():
@@ -114,9 +115,9 @@ def test_save_info_writes_the_reference_report(tmp_path, monkeypatch, hp):
     assert text == ("MODEL TYPE: ResNet-RNN\n\nbatch_size: 256\noptimizer_choice: RMSProp\nlearning_rate: 0.001\n"
                     "layer_size: 64\nn_layers: 3\nkeep_prob: 0.8\nlayer_size_res: 32\nn_layers_res: 2\n\n")
     assert open(os.path.join(m.model_path, "ResNetRNN.txt")).read() == text
-    if has_reference():                                                        # the shipped model's own report header
-        shipped = open(os.path.join(REFERENCE, "catfish", "ResNetRNN", "ResNetRNN.txt")).read()
-        assert shipped.startswith(text)
+    with open(os.path.join(GOLDEN, "shipped_report.json")) as fh:             # the shipped model's own report header
+        shipped = json.load(fh)["header"]
+    assert shipped.startswith(text)
     assert neural_network.retrieve_hyperparams(os.path.join(m.model_path, "ResNetRNN.txt")) == hp
     m2 = ResNetRNN(save=True, **hp)
     assert m2.model_path.endswith("ResNet-RNN_1")

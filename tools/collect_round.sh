@@ -7,13 +7,13 @@ OUT="$ROOT/gpurun_out/round"
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 echo "commit $COMMIT" > $OUT/commit.txt
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 echo "bench done" >> $OUT/commit.txt
 rm -rf /tmp/kt_f32
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_f32 -o kt -- python3 bench.py --no-cpu-baseline --no-extra-precisions --no-sharded-leg > $OUT/bench_prof_f32.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_f32 -o kt -- python3 bench.py --full --no-cpu-baseline --no-extra-precisions --no-sharded-leg > $OUT/bench_prof_f32.json 2>/dev/null
 cp $(find /tmp/kt_f32 -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats_f32.csv
 rm -rf /tmp/kt_bf16
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_bf16 -o kt -- python3 bench.py --precision bf16 --no-cpu-baseline --no-extra-precisions --no-sharded-leg > $OUT/bench_prof_bf16.json 2>/dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_bf16 -o kt -- python3 bench.py --full --precision bf16 --no-cpu-baseline --no-extra-precisions --no-sharded-leg > $OUT/bench_prof_bf16.json 2>/dev/null
 cp $(find /tmp/kt_bf16 -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats_bf16.csv
 echo "kernel stats done" >> $OUT/commit.txt
 bash tools/collect_traffic.sh $COMMIT fp32 > $OUT/traffic_fp32.log 2>&1

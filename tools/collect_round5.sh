@@ -12,11 +12,11 @@ for S in $STAGES; do
   case $S in
     probe) bash tools/probe_sysfs.sh > $OUT/sysfs_probe.log 2>&1 ;;
     tests) timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/gpu_tests.log 2>&1 || { echo "gpu tests FAILED" >> $OUT/commit.txt; tail -30 $OUT/gpu_tests.log; exit 1; } ;;
-    bench) timeout -k 10 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo "bench FAILED" >> $OUT/commit.txt; tail -20 $OUT/bench_default.err; exit 1; } ;;
+    bench) timeout -k 10 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo "bench FAILED" >> $OUT/commit.txt; tail -20 $OUT/bench_default.err; exit 1; } ;;
     rehearse)
       for N in 2 4; do
         CATFISH_BENCH_DEVICE=0 CATFISH_DEVICE=0 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-          --master-port $((29500 + N)) bench.py --gpus $N --steps 20 --warmup 5 > $OUT/bench_${N}ranks_one_gpu.json 2> $OUT/bench_${N}ranks.err \
+          --master-port $((29500 + N)) bench.py --full --gpus $N --steps 20 --warmup 5 > $OUT/bench_${N}ranks_one_gpu.json 2> $OUT/bench_${N}ranks.err \
           || { echo "rehearsal $N FAILED" >> $OUT/commit.txt; tail -20 $OUT/bench_${N}ranks.err; exit 1; }
       done ;;
     x3abl)   # upper bounds for the bf16x3 layer-0 experiment: timing-only ablations, interleaved rounds on one box
@@ -29,7 +29,7 @@ for S in $STAGES; do
     prof)
       for P in fp32 bf16 bf16x3; do
         rm -rf /tmp/kt_$P
-        rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$P -o kt -- python3 bench.py --precision $P --no-cpu-baseline --no-extra-precisions --no-sharded-leg > $OUT/bench_prof_$P.json 2>/dev/null
+        rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$P -o kt -- python3 bench.py --full --precision $P --no-cpu-baseline --no-extra-precisions --no-sharded-leg > $OUT/bench_prof_$P.json 2>/dev/null
         cp $(find /tmp/kt_$P -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats_$P.csv
       done ;;
   esac

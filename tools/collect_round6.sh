@@ -12,7 +12,7 @@ echo "commit $COMMIT stages $STAGES" > $OUT/commit.txt
 for S in $STAGES; do
   case $S in
     tests) timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $OUT/gpu_tests.log 2>&1 || { echo "gpu tests FAILED" >> $OUT/commit.txt; tail -40 $OUT/gpu_tests.log; exit 1; } ;;
-    bench) timeout -k 10 700 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo "bench FAILED" >> $OUT/commit.txt; tail -20 $OUT/bench_default.err; exit 1; } ;;
+    bench) timeout -k 10 700 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo "bench FAILED" >> $OUT/commit.txt; tail -20 $OUT/bench_default.err; exit 1; } ;;
     train)   # config 5 (the training step): host/device breakdown of a step + rocprofv3 kernel trace of the same command, at 256 and 4096 windows,
              # weight gradients beside the next layer's backward (default) and in round 5's order (--no-overlap), interleaved twice
       for B in 256 4096; do
@@ -38,7 +38,7 @@ for S in $STAGES; do
       done; done; done ;;
     rehearse5)   # the N > 1 launch path over a directory of configs[2]'s full size (100 000 files), FIVE ranks on ONE card (the box allows at most 6 processes on its GPU and the launcher counts: a 6-rank try was stopped by its process guard): a rehearsal (value null), never a measurement
       CATFISH_BENCH_DEVICE=0 CATFISH_DEVICE=0 CATFISH_RCCL_PROBE_TIMEOUT_S=60 timeout -k 10 1000 python -m torch.distributed.run --nnodes=1 --nproc-per-node 5 \
-        --master-addr 127.0.0.1 --master-port 29506 bench.py --gpus 5 --steps 20 --warmup 5 --reads-per-rank 20000 \
+        --master-addr 127.0.0.1 --master-port 29506 bench.py --full --gpus 5 --steps 20 --warmup 5 --reads-per-rank 20000 \
         > $OUT/bench_5ranks_100k_files_one_gpu.json 2> $OUT/bench_5ranks.err || { echo "rehearsal FAILED" >> $OUT/commit.txt; tail -30 $OUT/bench_5ranks.err; exit 1; } ;;
     traffic)   # counter traffic (FETCH_SIZE / WRITE_SIZE, separate passes) and MFMA-busy of the fp32 headline kernels at this commit
       bash tools/collect_traffic.sh $COMMIT fp32 > $OUT/traffic_fp32.log 2>&1 || { echo "traffic FAILED" >> $OUT/commit.txt; tail -20 $OUT/traffic_fp32.log; exit 1; }
@@ -49,7 +49,7 @@ for S in $STAGES; do
     prof)
       for P in ${PRECS:-fp32}; do
         rm -rf /tmp/kt_$P
-        rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$P -o kt -- python3 bench.py --precision $P --no-cpu-baseline --no-extra-precisions --no-sharded-leg > $OUT/bench_prof_$P.json 2>/dev/null
+        rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt_$P -o kt -- python3 bench.py --full --precision $P --no-cpu-baseline --no-extra-precisions --no-sharded-leg > $OUT/bench_prof_$P.json 2>/dev/null
         cp $(find /tmp/kt_$P -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats_$P.csv
       done ;;
     streams)   # two engines on two streams, alternate steps, configs[1] -- the gated look at the fp32 tail
