@@ -243,7 +243,7 @@ def _build_click_main():
                   help="MI355X devices of this node to shard the reads over (one process per GPU)")
     @click.option("--network-path", default="ResNetRNN", show_default=True, help="Directory of the trained network")
     @click.option("--precision", default="fp32", show_default=True, type=click.Choice(["fp32", "bf16x3", "bf16"]),
-                  help="Arithmetic of the biGRU matmuls")
+                  help="Arithmetic of the matmuls (bf16: the 64 / 32 ResNetRNN geometry only)")
     def main(input_dir, split_dir, chunk_size, gpus, network_path, precision):
         """
         A tool with a neural network as basis to predict the presence of

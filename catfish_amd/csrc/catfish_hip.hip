@@ -1192,7 +1192,8 @@ extern "C" int cf_model_create(const cf_weights* w, const cf_hparams* hp, int de
     *out = nullptr;
     if (hp->window != CF_T) return fail(CF_ERR_INVALID, "window must be 35 (rnn_class.py:27)");
     if (hp->n_layers < 1 || hp->n_layers_res < 0) return fail(CF_ERR_INVALID, "n_layers must be >= 1 and n_layers_res >= 0");
-    // the shipped geometry (64 GRU units, 32 conv channels) runs on the tuned kernels, every other one on generic.hpp
+    // the shipped geometry (64 GRU units, 32 conv channels) runs on the tuned kernels, every other one on generic.hpp (and so
+    // does the plain RNN type in bf16x3; in bf16 it is refused here or by gen_build)
     const bool generic = gen_wanted(hp);
     if (!generic && hp->n_layers_res == 0 && hp->precision != CF_PREC_FP32)
         return fail(CF_ERR_INVALID, "the plain RNN type (n_layers_res = 0) is only built for CF_PREC_FP32");
@@ -2106,8 +2107,8 @@ extern "C" int cf_gru_anysize_train_forward(cf_model* m, int32_t layer_size, int
     if (max_waves < 8) { h_via_y = 1; max_waves = anysize_waves(h16, 2, &lds_full); }     // as in the inference launch: h' through y above 64 units
     const int waves = std::max(1, std::min(max_waves, (2 * n_tiles + m->n_cu - 1) / m->n_cu));
     const size_t lds = lds_full / max_waves * waves;
-    HIP_TRY(hipFuncSetAttribute((const void*)gen_gru_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(gen_gru_kernel<true>, dim3((unsigned)((n_tiles + waves - 1) / waves), 2), dim3(waves * 64), lds,
+    HIP_TRY(hipFuncSetAttribute((const void*)gen_gru_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL((gen_gru_kernel<true, false>), dim3((unsigned)((n_tiles + waves - 1) / waves), 2), dim3(waves * 64), lds,
                        reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f32x4*>(wpack), reinterpret_cast<const f32x4*>(bpack),
                        reinterpret_cast<const f32x4*>(x_frag), reinterpret_cast<f32x4*>(y_frag), h16, (int)cin_blocks, h_via_y,
                        reinterpret_cast<f32x4*>(stash), n_tiles);

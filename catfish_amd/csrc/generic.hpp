@@ -5,7 +5,8 @@
 // previous layer's D tile fed back as the B operand), but with run-time sizes -- weights stream from global memory (L2 /
 // Infinity Cache resident: at most 2.4 MB per direction and layer) as pre-tiled A fragments instead of living in LDS, the
 // biGRU state of a tile (h, r.h, h') lives in LDS, and one launch computes one conv or one biGRU layer.
-// Included by catfish_hip.hip (needs f32x4, MFMA16, CF_T, CF_TILE, CF_GATE_SCALE, CF_CAND_SCALE).
+// CF_PREC_BF16X3 runs the same kernels with bf16x3 matrix products (gen_dot_x3: gen_conv_kernel<true>, gen_gru_kernel<false, true>).
+// Included by catfish_hip.hip (needs f32x4, bf16x8, MFMA16, CF_T, CF_TILE, CF_GATE_SCALE, CF_CAND_SCALE).
 #pragma once
 
 #ifndef CF_GEN_LOCKSTEP
@@ -172,6 +173,109 @@ __device__ __forceinline__ void gen_dot4(f32x4& acc0, f32x4& acc1, f32x4& acc2, 
         gen_dot4_any(acc0, acc1, acc2, acc3, w0, w1, w2, w3, xb, KBX, hb0, hb1, H16, ln);
 }
 
+// ---- bf16x3 products (CF_PREC_BF16X3): v_mfma_f32_16x16x32_bf16, fp32 accumulate -------------------------------------------
+// The activations keep the fp32 fragment layout above; only the matrix products change.  Two consecutive 16-feature tiles 2p,
+// 2p + 1 give a lane eight values of its window, and read under the k-permutation k = 8 q + j <-> feature 16 (2p + (j >> 2)) +
+// 4 q + (j & 3) (q = lane >> 4) they are one 32-deep B fragment of the bf16 MFMA (its A / B lane map: row / column lane & 15,
+// k = 8 (lane >> 4) + j).  Every fp32 operand v is split as hi = bf16(v), lo = bf16(v - hi) and a.w is evaluated as
+// a_hi w_hi + a_lo w_hi + a_hi w_lo, as gru_bf16.hpp does for the tuned kernels; the C / D layout of 16x16x32_bf16 equals that
+// of 16x16x4_f32, so every epilogue is shared with the fp32 kernels.
+// Weight pack (gen_pack_a_x3): per (output tile, pair p) 64 lanes x 8 bf16 of w_hi, then 64 lanes x 8 bf16 of w_lo -- the same
+// 2 KB as the fp32 pack's two 16-input blocks, so the f32x4 indexing (block 2p, 2p + 1) carries over.  Each K segment ([x | h])
+// is padded with zero weights to a multiple of 4 tiles (two pairs: the unroll of the weight ring below), and the B operand
+// of a padding tile re-reads the segment's last real tile (finite data times zero weights adds exactly zero).
+#define MFMA16B(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (c), 0, 0, 0)
+
+__host__ __device__ constexpr int gen_x3_pad(int n16) { return (n16 + 3) & ~3; }
+
+__device__ __forceinline__ bf16x8 gen_ldb(const f32x4* __restrict__ p, unsigned ln) {
+    return __builtin_bit_cast(bf16x8, gen_ld(p, ln));
+}
+
+// hi / lo parts of the 32-deep B fragment made of tiles (a: features +0..3 of the lane's quarter, b: +16..19)
+__device__ __forceinline__ void gen_split(const f32x4& a, const f32x4& b, bf16x8& hi, bf16x8& lo) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const __bf16 ha = (__bf16)a[j], hb = (__bf16)b[j];
+        hi[j] = ha; hi[4 + j] = hb;
+        lo[j] = (__bf16)(a[j] - (float)ha); lo[4 + j] = (__bf16)(b[j] - (float)hb);
+    }
+}
+
+// N output tiles over one K sequence (the bf16x3 counterpart of gen_dot / gen_dot4): acc[n] += W_n . [x | h_(n & 1)], x from
+// global memory (KBX tiles, shared by all chains), h from LDS (hb0 for even chains, hb1 for odd ones; TWO = false: hb1 is hb0
+// and is split once).  Branch-free like gen_dot4_fast: the weight ring (two pairs = 2 x 3 N MFMAs ahead) and the one-ahead B
+// loads clamp their index instead of testing it.
+template <int N, bool TWO>
+__device__ __forceinline__ void gen_dot_x3(f32x4 (&acc)[N], const f32x4* const (&w)[N], const f32x4* __restrict__ xb, int KBX,
+                                           const f32x4* hb0, const f32x4* hb1, int H16, unsigned ln) {
+    const int XP = gen_x3_pad(KBX) >> 1, HP = gen_x3_pad(H16) >> 1, last = XP + HP - 1;      // pairs; XP, HP even
+    bf16x8 Ah[2][N], Al[2][N];
+    auto refill = [&](int j, int k) {
+        k = k < last ? k : last;
+#pragma unroll
+        for (int n = 0; n < N; ++n) { Ah[j][n] = gen_ldb(w[n] + (2 * k) * 64, ln); Al[j][n] = gen_ldb(w[n] + (2 * k + 1) * 64, ln); }
+    };
+    auto mma = [&](int j, const bf16x8& h0, const bf16x8& l0, const bf16x8& h1, const bf16x8& l1) {
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = MFMA16B(Ah[j][n], (n & 1) ? h1 : h0, acc[n]);
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = MFMA16B(Ah[j][n], (n & 1) ? l1 : l0, acc[n]);      // w_hi . a_lo
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = MFMA16B(Al[j][n], (n & 1) ? h1 : h0, acc[n]);      // w_lo . a_hi
+    };
+    refill(0, 0);
+    refill(1, 1);
+    if (XP > 0) {
+        auto ldx = [&](int p, f32x4 (&b)[2]) {
+            const int t0 = 2 * p < KBX ? 2 * p : KBX - 1, t1 = 2 * p + 1 < KBX ? 2 * p + 1 : KBX - 1;
+            b[0] = gen_ld(xb + t0 * 64, ln); b[1] = gen_ld(xb + t1 * 64, ln);
+        };
+        f32x4 b[2];
+        ldx(0, b);
+        for (int k0 = 0; k0 < XP; k0 += 2) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int k = k0 + j;
+                f32x4 nb[2];
+                ldx(k + 1 < XP ? k + 1 : XP - 1, nb);
+                bf16x8 hi, lo;
+                gen_split(b[0], b[1], hi, lo);
+                mma(j, hi, lo, hi, lo);
+                refill(j, k + 2);
+                b[0] = nb[0]; b[1] = nb[1];
+                __builtin_amdgcn_sched_barrier(0);          // keep the refill here, two slots ahead of its use
+            }
+        }
+    }
+    if (HP == 0) return;
+    auto ldh = [&](const f32x4* hb, int p, f32x4 (&b)[2]) {
+        b[0] = hb[(2 * p < H16 ? 2 * p : H16 - 1) * 64];
+        b[1] = hb[(2 * p + 1 < H16 ? 2 * p + 1 : H16 - 1) * 64];
+    };
+    f32x4 p0[2], p1[2];
+    ldh(hb0, 0, p0);
+    if (TWO) ldh(hb1, 0, p1);
+    for (int k0 = 0; k0 < HP; k0 += 2) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int kh = k0 + j, kn = kh + 1 < HP ? kh + 1 : HP - 1;
+            f32x4 n0[2], n1[2];
+            ldh(hb0, kn, n0);
+            if (TWO) ldh(hb1, kn, n1);
+            bf16x8 h0, l0, h1, l1;
+            gen_split(p0[0], p0[1], h0, l0);
+            if (TWO) gen_split(p1[0], p1[1], h1, l1);
+            else { h1 = h0; l1 = l0; }
+            mma(j, h0, l0, h1, l1);
+            refill(j, XP + kh + 2);
+            p0[0] = n0[0]; p0[1] = n0[1];
+            if (TWO) { p1[0] = n1[0]; p1[1] = n1[1]; }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+
 // ---- block 0's two k = 1 convs on the raw sample (Cin = 1): shortcut and first conv, resnet_class.py:60-66 ---------------
 __global__ __launch_bounds__(256) void gen_first_kernel(const float* __restrict__ x_nat, const f32x4* __restrict__ wb /*[4][Co16][64]: w_sc, b_sc, w_1, b_1*/,
                                                         f32x4* __restrict__ SC, f32x4* __restrict__ O1, int64_t n_windows, int n_tiles, int Co16) {
@@ -199,6 +303,8 @@ __global__ __launch_bounds__(256) void gen_first_kernel(const float* __restrict_
 
 // ---- one conv1d (k = 1 or 3, padding SAME inside the 35-sample window) with folded batch norm ---------------------------------
 // One wave per (tile, position); output tiles two at a time (two independent MFMA chains sharing the B operand).
+// X3: the bf16x3 products (gen_dot_x3; weights [taps][Co16][gen_x3_pad(Ki16)][64] in gen_pack_a_x3 order).
+template <bool X3>
 __global__ __launch_bounds__(256) void gen_conv_kernel(const f32x4* __restrict__ W /*[taps][Co16][Ki16][64]*/, const f32x4* __restrict__ Bv /*[Co16][64]*/,
                                                        const f32x4* __restrict__ X, const f32x4* __restrict__ R /*residual or null*/,
                                                        f32x4* __restrict__ Y, int n_tiles, int Ki16, int Co16, int taps, int relu /*1: before the residual add, 2: after*/) {
@@ -228,6 +334,22 @@ __global__ __launch_bounds__(256) void gen_conv_kernel(const f32x4* __restrict__
                 const int tt = t + tap - (taps >> 1);
                 if (tt < 0 || tt >= CF_T) continue;                           // zero padding at the window edges
                 const f32x4* xb = X + ((tile * CF_T + tt) * Ki16) * 64;       // uniform pointers, lane added at the access
+                if constexpr (X3) {
+                    const int Kw = gen_x3_pad(Ki16);                          // weight blocks per output tile
+                    const f32x4* wt = W + ((int64_t)tap * Co16 * Kw) * 64;
+                    if (step == 4) {
+                        f32x4 acc[4] = {acc0, acc1, acc2, acc3};
+                        const f32x4* const w[4] = {wt + (int64_t)mo * Kw * 64, wt + (int64_t)m1 * Kw * 64, wt + (int64_t)m2 * Kw * 64, wt + (int64_t)m3 * Kw * 64};
+                        gen_dot_x3<4, false>(acc, w, xb, Ki16, nullptr, nullptr, 0, ln);
+                        acc0 = acc[0]; acc1 = acc[1]; acc2 = acc[2]; acc3 = acc[3];
+                    } else {
+                        f32x4 acc[2] = {acc0, acc1};
+                        const f32x4* const w[2] = {wt + (int64_t)mo * Kw * 64, wt + (int64_t)m1 * Kw * 64};
+                        gen_dot_x3<2, false>(acc, w, xb, Ki16, nullptr, nullptr, 0, ln);
+                        acc0 = acc[0]; acc1 = acc[1];
+                    }
+                    continue;
+                }
                 const f32x4* wt = W + ((int64_t)tap * Co16 * Ki16) * 64;
                 if (step == 4)
                     gen_dot4(acc0, acc1, acc2, acc3, wt + (int64_t)mo * Ki16 * 64, wt + (int64_t)m1 * Ki16 * 64, wt + (int64_t)m2 * Ki16 * 64,
@@ -250,11 +372,14 @@ __global__ __launch_bounds__(256) void gen_conv_kernel(const f32x4* __restrict__
 // of the wave live in LDS ([H16][64] f32x4 each); only this wave touches them, in program order.
 // TRAIN: the activated gates r, u, c of every step are stashed for the backward pass (S: [tiles][35][2 dirs][3][H16][64]), the
 // buffers are the caller's (exactly n_tiles tiles: waves past the last tile exit, so no workgroup barriers in this variant).
-template <bool TRAIN>
+// X3 (inference only): the bf16x3 products (gen_dot_x3; weights [2][3][H16][gen_x3_pad(KBX) + gen_x3_pad(H16)][64] in
+// gen_pack_a_x3 order); state, epilogues and launch shapes as in fp32.
+template <bool TRAIN, bool X3>
 __global__ __launch_bounds__(512) void gen_gru_kernel(const f32x4* __restrict__ W /*[2 dirs][3: r, u, c][H16][KB][64]*/,
                                                       const f32x4* __restrict__ Bv /*[2][3][H16][64]*/, const f32x4* __restrict__ X /*[tiles][35][KBX][64]*/,
                                                       f32x4* Y /*[tiles][35][2 H16][64]*/, int H16, int KBX, int h_via_y, f32x4* __restrict__ S,
                                                       int n_tiles) {
+    static_assert(!(TRAIN && X3), "training runs in fp32");
     constexpr bool LOCKSTEP = CF_GEN_LOCKSTEP && !TRAIN;
     extern __shared__ f32x4 gen_lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;     // wave: uniform (SGPR)
@@ -267,7 +392,7 @@ __global__ __launch_bounds__(512) void gen_gru_kernel(const f32x4* __restrict__ 
     // the host rounds the buffers up to whole workgroups of tiles).
     const int64_t tile = (int64_t)grp * waves + wave;
     if (TRAIN && tile >= n_tiles) return;
-    const int KB = KBX + H16;
+    const int KB = X3 ? gen_x3_pad(KBX) + gen_x3_pad(H16) : KBX + H16;         // weight blocks per output tile
     // state: h and r.h always in LDS; h' in a third LDS array when eight waves' worth fits (H <= 64), otherwise it takes the
     // round trip through the layer's output (written anyway) and is reloaded into the h array at the end of the step
     const int arrays = h_via_y ? 2 : 3;
@@ -298,8 +423,14 @@ __global__ __launch_bounds__(512) void gen_gru_kernel(const f32x4* __restrict__ 
                 const int m1 = mo + 1 < H16 ? mo + 1 : mo, m2 = mo + 2 < H16 ? mo + 2 : mo, m3 = mo + 3 < H16 ? mo + 3 : mo;
                 if (LOCKSTEP) __syncthreads();
                 f32x4 acc0 = Br[mo * 64], acc1 = Br[m1 * 64], acc2 = Br[m2 * 64], acc3 = Br[m3 * 64];
-                gen_dot4(acc0, acc1, acc2, acc3, Wr + (size_t)mo * KB * 64, Wr + (size_t)m1 * KB * 64, Wr + (size_t)m2 * KB * 64,
-                         Wr + (size_t)m3 * KB * 64, xt, KBX, hs, hs, H16, ln);
+                if constexpr (X3) {
+                    f32x4 acc[4] = {acc0, acc1, acc2, acc3};
+                    const f32x4* const w[4] = {Wr + (size_t)mo * KB * 64, Wr + (size_t)m1 * KB * 64, Wr + (size_t)m2 * KB * 64, Wr + (size_t)m3 * KB * 64};
+                    gen_dot_x3<4, false>(acc, w, xt, KBX, hs, hs, H16, ln);
+                    acc0 = acc[0]; acc1 = acc[1]; acc2 = acc[2]; acc3 = acc[3];
+                } else
+                    gen_dot4(acc0, acc1, acc2, acc3, Wr + (size_t)mo * KB * 64, Wr + (size_t)m1 * KB * 64, Wr + (size_t)m2 * KB * 64,
+                             Wr + (size_t)m3 * KB * 64, xt, KBX, hs, hs, H16, ln);
                 reset_tile(mo, acc0); reset_tile(m1, acc1); reset_tile(m2, acc2); reset_tile(m3, acc3);
             }
         } else {
@@ -307,7 +438,13 @@ __global__ __launch_bounds__(512) void gen_gru_kernel(const f32x4* __restrict__ 
                 const int m1 = mo + 1 < H16 ? mo + 1 : mo;
                 if (LOCKSTEP) __syncthreads();
                 f32x4 acc0 = Br[mo * 64], acc1 = Br[m1 * 64];
-                gen_dot(acc0, acc1, Wr + (size_t)mo * KB * 64, Wr + (size_t)m1 * KB * 64, xt, KBX, hs, hs, H16, ln);
+                if constexpr (X3) {
+                    f32x4 acc[2] = {acc0, acc1};
+                    const f32x4* const w[2] = {Wr + (size_t)mo * KB * 64, Wr + (size_t)m1 * KB * 64};
+                    gen_dot_x3<2, false>(acc, w, xt, KBX, hs, hs, H16, ln);
+                    acc0 = acc[0]; acc1 = acc[1];
+                } else
+                    gen_dot(acc0, acc1, Wr + (size_t)mo * KB * 64, Wr + (size_t)m1 * KB * 64, xt, KBX, hs, hs, H16, ln);
                 reset_tile(mo, acc0); reset_tile(m1, acc1);
             }
         }
@@ -333,15 +470,27 @@ __global__ __launch_bounds__(512) void gen_gru_kernel(const f32x4* __restrict__ 
                 const int m1 = mo + 1 < H16 ? mo + 1 : mo;
                 if (LOCKSTEP) __syncthreads();
                 f32x4 c0 = Bc[mo * 64], u0 = Bu[mo * 64], c1 = Bc[m1 * 64], u1 = Bu[m1 * 64];
-                gen_dot4(c0, u0, c1, u1, Wc + (size_t)mo * KB * 64, Wu + (size_t)mo * KB * 64, Wc + (size_t)m1 * KB * 64,
-                         Wu + (size_t)m1 * KB * 64, xt, KBX, rh, hs, H16, ln);
+                if constexpr (X3) {
+                    f32x4 acc[4] = {c0, u0, c1, u1};
+                    const f32x4* const w[4] = {Wc + (size_t)mo * KB * 64, Wu + (size_t)mo * KB * 64, Wc + (size_t)m1 * KB * 64, Wu + (size_t)m1 * KB * 64};
+                    gen_dot_x3<4, true>(acc, w, xt, KBX, rh, hs, H16, ln);
+                    c0 = acc[0]; u0 = acc[1]; c1 = acc[2]; u1 = acc[3];
+                } else
+                    gen_dot4(c0, u0, c1, u1, Wc + (size_t)mo * KB * 64, Wu + (size_t)mo * KB * 64, Wc + (size_t)m1 * KB * 64,
+                             Wu + (size_t)m1 * KB * 64, xt, KBX, rh, hs, H16, ln);
                 update_tile(mo, c0, u0);
                 if (m1 != mo) update_tile(m1, c1, u1);
             }
         } else {
             if (LOCKSTEP) __syncthreads();
             f32x4 c0 = Bc[0], u0 = Bu[0];
-            gen_dot(c0, u0, Wc, Wu, xt, KBX, rh, hs, H16, ln);
+            if constexpr (X3) {
+                f32x4 acc[2] = {c0, u0};
+                const f32x4* const w[2] = {Wc, Wu};
+                gen_dot_x3<2, true>(acc, w, xt, KBX, rh, hs, H16, ln);
+                c0 = acc[0]; u0 = acc[1];
+            } else
+                gen_dot(c0, u0, Wc, Wu, xt, KBX, rh, hs, H16, ln);
             update_tile(0, c0, u0);
         }
         if (h_via_y) {
@@ -657,6 +806,7 @@ __global__ __launch_bounds__(256) void gen_head_kernel(const f32x4* __restrict__
 // ---- host side: packing ---------------------------------------------------------------------------------------------------------
 struct cf_generic {
     int C16 = 0, H16 = 0;                       // conv channels / 16 (0 = RNN type), GRU units / 16
+    bool x3 = false;                            // CF_PREC_BF16X3: gen_pack_a_x3 weights, the *_x3 kernels
     struct Block { f32x4* w_sc = nullptr; f32x4* b_sc = nullptr; f32x4* w_1 = nullptr; f32x4* b_1 = nullptr;
                    f32x4* w_3 = nullptr; f32x4* b_3 = nullptr; f32x4* w_l = nullptr; f32x4* b_l = nullptr; f32x4* first = nullptr; };
     std::vector<Block> blocks;
@@ -684,6 +834,34 @@ static void gen_pack_a(std::vector<float>& dst, size_t off, F w, int k_real, int
                     const int in = 16 * kb + 4 * (lane >> 4) + i, out = 16 * mo + (lane & 15);
                     dst[off + (((size_t)mo * K16 + kb) * 64 + lane) * 4 + i] = in < k_real ? (float)(w(in, out) * scale) : 0.f;
                 }
+}
+
+// bf16x3 A pack (gen_dot_x3): K16 (a multiple of 4, padding included) -> per (mo, pair p) w_hi [lane][8] then w_lo [lane][8] in
+// the f32x4 slots of blocks 2p, 2p + 1; element j of lane l is W[in = 16 (2p + (j >> 2)) + 4 (l >> 4) + (j & 3)][out = 16 mo + (l & 15)]
+static uint16_t gen_bf16_bits(float v) {                    // round to nearest even, as the device's v_cvt_pk_bf16_f32
+    uint32_t u;
+    memcpy(&u, &v, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+template <typename F>
+static void gen_pack_a_x3(std::vector<float>& dst, size_t off, F w, int K16, int M16, double scale) {
+    for (int mo = 0; mo < M16; ++mo)
+        for (int p = 0; p < K16 / 2; ++p) {
+            uint16_t* blk = reinterpret_cast<uint16_t*>(dst.data() + off + ((size_t)mo * K16 + 2 * p) * 256);
+            for (int lane = 0; lane < 64; ++lane)
+                for (int j = 0; j < 8; ++j) {
+                    const int in = 16 * (2 * p + (j >> 2)) + 4 * (lane >> 4) + (j & 3), out = 16 * mo + (lane & 15);
+                    const float v = (float)(w(in, out) * scale);
+                    const uint16_t hi = gen_bf16_bits(v);
+                    const uint32_t hb = (uint32_t)hi << 16;
+                    float hf;
+                    memcpy(&hf, &hb, 4);
+                    blk[lane * 8 + j] = hi;
+                    blk[(64 + lane) * 8 + j] = gen_bf16_bits(v - hf);
+                }
+        }
 }
 
 // per-output vector (bias, dense weights) in accumulator order: [mo][lane][j] = v[16 mo + 4 (lane >> 4) + j]

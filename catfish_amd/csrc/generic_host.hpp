@@ -4,8 +4,10 @@
 
 static bool gen_forced() { return cf_knob("CATFISH_GENERIC") && atoi(cf_knob("CATFISH_GENERIC")) != 0; }     // A/B and test knob, read per model
 
+// (the tuned kernels have no bf16x3 form of the plain RNN type: it runs here in that precision)
 static bool gen_wanted(const cf_hparams* hp) {
-    return gen_forced() || hp->layer_size != CF_H || (hp->n_layers_res > 0 && hp->layer_size_res != CF_C);
+    return gen_forced() || hp->layer_size != CF_H || (hp->n_layers_res > 0 && hp->layer_size_res != CF_C) ||
+           (hp->n_layers_res == 0 && hp->precision == CF_PREC_BF16X3);
 }
 
 static void gen_destroy(cf_generic* g) {
@@ -46,11 +48,13 @@ static GenConv gen_fold(const cf_conv_bn& c, float eps, int cout) {
 }
 
 static int gen_pack_conv(cf_generic* g, const GenConv& f, f32x4** w_dev, f32x4** b_dev) {
-    const int K16 = f.cin / 16, M16 = f.cout / 16;
+    const int K16 = g->x3 ? gen_x3_pad(f.cin / 16) : f.cin / 16, M16 = f.cout / 16;
     std::vector<float> wp((size_t)f.k * M16 * K16 * 256), bp((size_t)M16 * 256);
-    for (int tap = 0; tap < f.k; ++tap)
-        gen_pack_a(wp, (size_t)tap * M16 * K16 * 256,
-                   [&](int in, int out) { return f.w[((size_t)tap * f.cin + in) * f.cout + out]; }, f.cin, K16, M16, 1.0);
+    for (int tap = 0; tap < f.k; ++tap) {
+        auto w = [&](int in, int out) { return in < f.cin ? f.w[((size_t)tap * f.cin + in) * f.cout + out] : 0.0; };
+        if (g->x3) gen_pack_a_x3(wp, (size_t)tap * M16 * K16 * 256, w, K16, M16, 1.0);
+        else gen_pack_a(wp, (size_t)tap * M16 * K16 * 256, w, f.cin, K16, M16, 1.0);
+    }
     gen_pack_v(bp, 0, [&](int o) { return f.b[o]; }, M16, 1.0);
     int rc = gen_upload(g, wp, w_dev);
     return rc != CF_OK ? rc : gen_upload(g, bp, b_dev);
@@ -63,10 +67,11 @@ static int gen_build(cf_model* m, const cf_weights* w) {
         return fail(CF_ERR_INVALID, "layer_size must be a multiple of 16 between 16 and 256 (the reference draws 16, 32, 64, 128, 256)");
     if (hp.n_layers_res > 0 && (C < 16 || C > 256 || (C % 16) != 0))
         return fail(CF_ERR_INVALID, "layer_size_res must be a multiple of 16 between 16 and 256 (the reference draws 16, 32, 64, 128, 256)");
-    if (hp.precision != CF_PREC_FP32)
-        return fail(CF_ERR_INVALID, "the bf16 / bf16x3 kernels are built for layer_size = 64 and layer_size_res = 32 only; other sizes run in CF_PREC_FP32");
+    if (hp.precision != CF_PREC_FP32 && hp.precision != CF_PREC_BF16X3)
+        return fail(CF_ERR_INVALID, "the bf16 kernels are built for layer_size = 64 and layer_size_res = 32 only; other sizes run in CF_PREC_FP32 or CF_PREC_BF16X3");
     cf_generic* g = new cf_generic();
     m->gen = g;
+    g->x3 = hp.precision == CF_PREC_BF16X3;
     g->H16 = H / 16;
     g->C16 = C / 16;
     int rc = CF_OK;
@@ -98,7 +103,8 @@ static int gen_build(cf_model* m, const cf_weights* w) {
     // biGRU layers: per direction three matrices over K = [x blocks | h blocks]
     for (int l = 0; l < hp.n_layers && rc == CF_OK; ++l) {
         const int cin_real = l == 0 ? (C > 0 ? C : 1) : 2 * H;
-        const int kbx = (cin_real + 15) / 16, KB = kbx + g->H16;
+        const int kbx = (cin_real + 15) / 16;
+        const int kbx_w = g->x3 ? gen_x3_pad(kbx) : kbx, KB = kbx_w + (g->x3 ? gen_x3_pad(g->H16) : g->H16);    // weight blocks: [x | h]
         if (w->gru[2 * l].cin != cin_real || w->gru[2 * l + 1].cin != cin_real) return fail(CF_ERR_INVALID, "GRU layer input width mismatch");
         const size_t mat = (size_t)g->H16 * KB * 256, vec = (size_t)g->H16 * 256;
         std::vector<float> wp(2 * 3 * mat), bp(2 * 3 * vec);
@@ -110,10 +116,11 @@ static int gen_build(cf_model* m, const cf_weights* w) {
                 const int ld = gate < 2 ? 2 * H : H, col0 = gate == 1 ? H : 0;
                 const double scale = gate < 2 ? CF_GATE_SCALE : CF_CAND_SCALE;
                 auto acc = [&](int in, int out) -> double {
-                    if (in < 16 * kbx) return in < cin_real ? (double)kern[(size_t)in * ld + col0 + out] : 0.0;
-                    return (double)kern[(size_t)(cin_real + in - 16 * kbx) * ld + col0 + out];
+                    if (in < 16 * kbx_w) return in < cin_real ? (double)kern[(size_t)in * ld + col0 + out] : 0.0;
+                    return in - 16 * kbx_w < H ? (double)kern[(size_t)(cin_real + in - 16 * kbx_w) * ld + col0 + out] : 0.0;
                 };
-                gen_pack_a(wp, (size_t)(d * 3 + gate) * mat, acc, 16 * KB, KB, g->H16, scale);
+                if (g->x3) gen_pack_a_x3(wp, (size_t)(d * 3 + gate) * mat, acc, KB, g->H16, scale);
+                else gen_pack_a(wp, (size_t)(d * 3 + gate) * mat, acc, 16 * KB, KB, g->H16, scale);
                 gen_pack_v(bp, (size_t)(d * 3 + gate) * vec, [&](int o) { return (double)bias[col0 + o]; }, g->H16, scale);
             }
         }
@@ -124,7 +131,8 @@ static int gen_build(cf_model* m, const cf_weights* w) {
         // 64 units with 16, 32 or 128 input features is what gru_layer_kernel<CIN, false> (weights in LDS, state in registers,
         // 0.78-0.83 of the fp32-MFMA peak) is built for: such layers of an otherwise odd geometry (say 64 units behind 128
         // conv channels) run on it.  Not when CATFISH_GENERIC forces this path: that knob exists to exercise the kernels here.
-        if (rc == CF_OK && H == CF_H && !gen_forced() && (cin_real == 16 || cin_real == 32 || cin_real == 128)) {
+        // Not in bf16x3 either: the tuned bf16x3 kernels keep their activations in another layout.
+        if (rc == CF_OK && H == CF_H && !gen_forced() && !g->x3 && (cin_real == 16 || cin_real == 32 || cin_real == 128)) {
             std::vector<float> blob((size_t)2 * gru_pack_floats(cin_real));
             for (int d = 0; d < 2; ++d) pack_gru_dir(w->gru[2 * l + d], cin_real, cin_real, nullptr, blob.data() + (size_t)d * gru_pack_floats(cin_real));
             f32x4* dev = nullptr;
@@ -171,11 +179,12 @@ static int gen_build(cf_model* m, const cf_weights* w) {
     g->gru_lds = per_wave * g->gru_waves;
     // two tiles per wave (gen_gru2_kernel): two LDS arrays per tile; 8 or 4 waves per workgroup, else not used
     const size_t per_wave2 = (size_t)2 * 2 * g->H16 * 64 * sizeof(f32x4);
-    g->gru2_waves = (g->H16 % 4) != 0 || cf_knob("CATFISH_GEN_ONE_TILE") ? 0 : (per_wave2 * 8 <= (size_t)(160 * 1024) ? 8 : (per_wave2 * 4 <= (size_t)(160 * 1024) ? 4 : 0));
+    g->gru2_waves = (g->H16 % 4) != 0 || g->x3 || cf_knob("CATFISH_GEN_ONE_TILE") ? 0 : (per_wave2 * 8 <= (size_t)(160 * 1024) ? 8 : (per_wave2 * 4 <= (size_t)(160 * 1024) ? 4 : 0));
     g->gru2_lds = per_wave2 * g->gru2_waves;
     if (g->gru2_waves)
         HIP_TRY(hipFuncSetAttribute((const void*)gen_gru2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->gru2_lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)gen_gru_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->gru_lds));
+    HIP_TRY(hipFuncSetAttribute(g->x3 ? (const void*)gen_gru_kernel<false, true> : (const void*)gen_gru_kernel<false, false>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->gru_lds));
     HIP_TRY(hipFuncSetAttribute((const void*)gru_layer_kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gru_pack_floats(16) * 4));
     HIP_TRY(hipFuncSetAttribute((const void*)gru_layer_kernel<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gru_pack_floats(32) * 4));
     HIP_TRY(hipFuncSetAttribute((const void*)gru_layer_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gru_pack_floats(128) * 4));
@@ -197,7 +206,8 @@ static int gen_run_pass(cf_model* m, const float* x, int64_t n_windows, float* p
     auto conv = [&](const f32x4* wv, const f32x4* bv, const f32x4* in, const f32x4* res, f32x4* out, int taps, int relu, int slot) -> int {
         int r2;
         if ((r2 = prof_begin(m, slot, s, &pi)) != CF_OK) return r2;
-        hipLaunchKernelGGL(gen_conv_kernel, dim3(task_grid), dim3(256), 0, s, wv, bv, in, res, out, n_tiles, g->C16, g->C16, taps, relu);
+        hipLaunchKernelGGL(g->x3 ? gen_conv_kernel<true> : gen_conv_kernel<false>, dim3(task_grid), dim3(256), 0, s, wv, bv, in, res, out, n_tiles,
+                           g->C16, g->C16, taps, relu);
         HIP_TRY(hipGetLastError());
         return prof_end(m, s, pi);
     };
@@ -254,8 +264,8 @@ static int gen_run_pass(cf_model* m, const float* x, int64_t n_windows, float* p
         // small calls (the reference's one-read-per-call pattern): fewer waves per workgroup, so that the tiles spread over the CUs
         const int waves = std::max(1, std::min(g->gru_waves, (2 * n_tiles + m->n_cu - 1) / m->n_cu));
         const int gx = (n_tiles + waves - 1) / waves;
-        hipLaunchKernelGGL(gen_gru_kernel<false>, dim3((unsigned)gx, 2), dim3(waves * 64), g->gru_lds / g->gru_waves * waves, s,
-                           L.w, L.b, cur, G[l & 1], g->H16, L.kbx, g->h_via_y ? 1 : 0, (f32x4*)nullptr, n_tiles);
+        hipLaunchKernelGGL((g->x3 ? gen_gru_kernel<false, true> : gen_gru_kernel<false, false>), dim3((unsigned)gx, 2), dim3(waves * 64),
+                           g->gru_lds / g->gru_waves * waves, s, L.w, L.b, cur, G[l & 1], g->H16, L.kbx, g->h_via_y ? 1 : 0, (f32x4*)nullptr, n_tiles);
         HIP_TRY(hipGetLastError());
         if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
         cur = G[l & 1];

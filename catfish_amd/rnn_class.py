@@ -44,7 +44,7 @@ class RNN(object):
         # MI355X-specific knobs (not in the reference)
         self.device = int(kwargs.get("device", 0))
         self.max_windows_per_pass = int(kwargs.get("max_windows_per_pass", DEFAULT_MAX_WINDOWS))
-        self.precision = kwargs.get("precision", "fp32")      # "fp32" (exact) | "bf16x3" | "bf16"
+        self.precision = kwargs.get("precision", "fp32")      # "fp32" (exact) | "bf16x3" (any geometry) | "bf16" (64 / 32 ResNetRNN only)
 
         self.weights = None
         self.engine = None

@@ -44,7 +44,10 @@ extern "C" {
 /* Arithmetic of the biGRU layers (the residual blocks, the hidden state, the gates'
  * sigmoid/tanh and all accumulation are fp32 in every mode). */
 #define CF_PREC_FP32 0        /* exact fp32 MFMA (v_mfma_f32_16x16x4_f32); default            */
-#define CF_PREC_BF16X3 1      /* operands split hi+lo bf16, 3 bf16 MFMAs per product (~2^-17) */
+#define CF_PREC_BF16X3 1      /* operands split hi+lo bf16, 3 bf16 MFMAs per product (~2^-17); */
+                              /* every geometry: the tuned kernels for 64 units / 32 channels  */
+                              /* with residual blocks, the any-size kernels for all others     */
+                              /* (plain RNN type included); also the convs there               */
 #define CF_PREC_BF16 2        /* operands rounded to bf16 (BASELINE config 4)                 */
 
 /* Hyper-parameters: the keys of ResNetRNN.txt parsed by

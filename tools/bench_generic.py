@@ -1,5 +1,9 @@
 """Throughput of the any-size inference path (csrc/generic.hpp) at a few geometries of the reference's hyper-parameter search,
-next to the tuned kernels at the shipped one: samples/s and the fraction of the fp32-MFMA peak (flops from the layer sizes)."""
+next to the tuned kernels at the shipped one: samples/s and the fraction of the fp32-MFMA peak (flops from the layer sizes).
+
+--precision bf16x3 measures the same geometries in that mode (the line then carries "precision"); --latency adds the time of
+one 118-window read (the reference's one-read-per-call pattern) as "ms_one_read"."""
+import argparse
 import json
 import os
 import sys
@@ -27,6 +31,10 @@ def flops_per_sample(h, c, n_layers, n_layers_res):
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--precision", default="fp32", choices=["fp32", "bf16x3"])
+    ap.add_argument("--latency", action="store_true")
+    args = ap.parse_args()
     n = 256 * 118
     x = torch.randn(n, 35, device="cuda")
     out = torch.empty(n * 35, device="cuda")
@@ -35,7 +43,8 @@ def main():
         w = oracle.random_weights(seed=1, layer_size=h, n_layers=nl, layer_size_res=c, n_layers_res=nr)
         if force:
             os.environ["CATFISH_DEBUG_KNOBS"] = os.environ["CATFISH_GENERIC"] = "1"
-        eng = HipEngine(w, layer_size=h, n_layers=nl, layer_size_res=c, n_layers_res=nr, device=0, max_windows_per_pass=n)
+        eng = HipEngine(w, layer_size=h, n_layers=nl, layer_size_res=c, n_layers_res=nr, device=0, max_windows_per_pass=n,
+                        precision=args.precision)
         os.environ.pop("CATFISH_GENERIC", None)
         reps = 3 if h >= 128 else 10
         for _ in range(2):
@@ -50,9 +59,23 @@ def main():
         ms = e0.elapsed_time(e1) / reps
         sps = 256 * 4096 / (ms * 1e-3)
         fl = flops_per_sample(h, c, nl, nr)
-        print(json.dumps(dict(layer_size=h, layer_size_res=c, n_layers=nl, n_layers_res=nr,
-                              path="any-size" if eng.launch_regimes()["coop_max"] == 0 else "tuned", ms_per_256_reads=ms,
-                              samples_per_s=sps, flop_per_sample=fl, frac_of_fp32_mfma_peak=sps * fl / PEAK)), flush=True)
+        rec = dict(layer_size=h, layer_size_res=c, n_layers=nl, n_layers_res=nr,
+                   path="any-size" if force or (h, c) != (64, 32) else "tuned", ms_per_256_reads=ms,
+                   samples_per_s=sps, flop_per_sample=fl, frac_of_fp32_mfma_peak=sps * fl / PEAK)
+        if args.precision != "fp32":
+            rec["precision"] = args.precision
+        if args.latency:
+            x1, o1 = x[:118].contiguous(), out[:118 * 35]
+            for _ in range(3):
+                eng.infer_device(x1, out=o1)
+            torch.cuda.synchronize()
+            e0.record()
+            for _ in range(20):
+                eng.infer_device(x1, out=o1)
+            e1.record()
+            torch.cuda.synchronize()
+            rec["ms_one_read"] = e0.elapsed_time(e1) / 20
+        print(json.dumps(rec), flush=True)
         eng.close()
 
 
