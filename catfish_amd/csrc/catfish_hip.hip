@@ -2310,6 +2310,8 @@ extern "C" int cf_opt_step(cf_model* m, int32_t kind, float* params, const float
     return CF_OK;
 }
 
+#include "gen_train.hpp"      // whole-step training of any geometry (conv stack, GRU dx / dW, dropout, head)
+
 // ---- profiling ---------------------------------------------------------------------------
 static int prof_collect(cf_model* m) {
     for (auto& ev : m->ev_pending) {

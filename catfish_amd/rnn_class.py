@@ -26,6 +26,8 @@ class RNN(object):
         self.n_layers = kwargs["n_layers"]
         self.keep_prob = kwargs["keep_prob"]
         self.keep_prob_test = 1.0
+        # None: Trainer's default; True: the whole training step on the HIP kernels at any geometry (anysize_step.py)
+        self.native_training = kwargs.get("native_training", None)
 
         # set parameters (rnn_class.py:25-32)
         self.n_inputs = 1
@@ -230,7 +232,7 @@ class RNN(object):
 
         On a GPU the whole step -- forward, loss, backward, optimizer, weight re-tiling -- runs on HIP kernels through
         the C ABI (``training.Trainer`` -> ``native_step.py`` for the shipped 64 / 32 geometry, ``anysize_train.py``
-        for other sizes); the torch restatement is the CPU mode and the test reference.  The inference engine picks
+        for other sizes, ``anysize_step.py`` for other sizes with ``native_training=True``); the torch restatement is the CPU mode and the test reference.  The inference engine picks
         the updated weights up lazily, at the next ``infer``.  TensorBoard summaries (the reference's second forward,
         :206-208) are not written.
         """
@@ -240,7 +242,8 @@ class RNN(object):
             from .training import Trainer
             self._trainer = Trainer(self.weights, self.n_layers, self.n_layers_res_, self.optimizer_choice,
                                     self.learning_rate, self.keep_prob, seed=self.train_seed,
-                                    optimizer_state=getattr(self, "optimizer_state", None))
+                                    optimizer_state=getattr(self, "optimizer_state", None),
+                                    native=getattr(self, "native_training", None))
         self.train_loss = self._trainer.train_step(train_x, train_y)
         self._engine_stale = True
 

@@ -394,7 +394,8 @@ def main(argv):
     """networks/train_validate.py:298-360: ``network_type train_npz_dir n_training_examples validation_npz_dir
     max_validation_length [validation_start [max_number]]``.  The training "database" argument is a directory of NPZ
     reads (the reference takes a ZODB file); hyper-parameters are a random draw as in the reference (:328) unless
-    CATFISH_SHIPPED_HPARAMS=1 asks for the shipped network's (the reference's commented block :329-332)."""
+    CATFISH_SHIPPED_HPARAMS=1 asks for the shipped network's (the reference's commented block :329-332).
+    CATFISH_NATIVE_TRAINING=1 trains with ``native_training=True`` (the whole step on the HIP kernels at any geometry)."""
     args = list(argv[1:])
     if len(args) < 5:
         raise ValueError(_USAGE)
@@ -405,6 +406,8 @@ def main(argv):
     shipped = os.environ.get("CATFISH_SHIPPED_HPARAMS") == "1"
     hparams = dict(_SHIPPED_HPARAMS.get(kind, _SHIPPED_HPARAMS["ResNetRNN"])) if shipped \
         else generate_random_hyperparameters(kind)
+    if os.environ.get("CATFISH_NATIVE_TRAINING") == "1":          # the whole training step on the HIP kernels at any geometry
+        hparams["native_training"] = True
     network = build_model(kind, save=True, **hparams)
     network.initialize_network()
     print("Loading training database..")

@@ -306,8 +306,10 @@ class Trainer(object):
         h = int(np.asarray(weights["stack_bidirectional_rnn/cell_0/bidirectional_rnn/fw/gru_cell/candidate/bias"]).shape[0])
         c = int(np.asarray(weights["conv1d/bias"]).shape[0]) if n_layers_res > 0 else 32
         shipped = (h == 64 and c == 32)
-        if native and not shipped:
-            raise ValueError("the native training kernels are built for layer_size = 64 and layer_size_res = 32")
+        if native and (self.net.device.type != "cuda" or self.net.dtype != torch.float32):
+            raise ValueError("native=True runs the fp32 HIP training kernels: it needs device='cuda' and dtype float32")
+        # native=True at any other geometry (RNN or ResNetRNN type): the whole step on the run-time-sized kernels (anysize_step.py)
+        native_any = bool(native) and not shipped
         self.native = (self.net.device.type == "cuda" and n_layers_res > 0 and shipped) if native is None else bool(native)
         self.engine = None
         self.step_impl = None
@@ -318,7 +320,13 @@ class Trainer(object):
             from .engine import HipEngine
             self.engine = HipEngine(weights, layer_size=h, n_layers=n_layers, layer_size_res=c, n_layers_res=n_layers_res,
                                     device=self.net.device.index or 0, max_windows_per_pass=256)
-        if self.native:
+        if native_any:
+            from .anysize_step import AnySizeTrainStep
+            from .engine import HipEngine
+            self.engine = HipEngine(weights, layer_size=h, n_layers=n_layers, layer_size_res=c, n_layers_res=n_layers_res,
+                                    device=self.net.device.index or 0, max_windows_per_pass=256)
+            self.step_impl = AnySizeTrainStep(self.net, self.opt, self.engine, self.keep_prob, seed=seed)
+        elif self.native:
             from .engine import HipEngine
             self.engine = HipEngine(weights, n_layers=n_layers, n_layers_res=n_layers_res,
                                     device=self.net.device.index or 0, max_windows_per_pass=256, fuse_layers=False)

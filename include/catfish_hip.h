@@ -39,7 +39,7 @@ extern "C" {
 
 /* Bumped whenever a signature or a struct of this header changes; cf_abi_version() returns the value the library was built
  * with, so a binding can refuse a stale libcatfish_hip.so instead of calling it with the wrong arguments. */
-#define CF_ABI_VERSION 6
+#define CF_ABI_VERSION 7
 
 /* Arithmetic of the biGRU layers (the residual blocks, the hidden state, the gates'
  * sigmoid/tanh and all accumulation are fp32 in every mode). */
@@ -377,6 +377,60 @@ int cf_train_head(cf_model* m, const float* y_frag, const float* dense_kernel, c
  * same call: packed[i] = params[pack_idx[i]] * pack_scale[i] (indices from cf_gru_pack_map, rebased into params). */
 int cf_opt_step(cf_model* m, int32_t kind, float* params, const float* grads, float* slot1, float* slot2, int64_t n, float lr,
                 double* step_count, const int32_t* pack_idx, const float* pack_scale, float* packed, int64_t n_packed, void* stream);
+
+/* Whole-step training of ANY geometry (csrc/gen_train.hpp; catfish_amd/anysize_step.py drives it): the pieces around
+ * cf_gru_anysize_train_forward / _backward, so that conv stack, dropout, dense head, loss, backward and optimizer all run on these
+ * kernels.  fp32, run-time sizes, device pointers, every launch on `stream` with no host synchronisation (graph-capturable).
+ * n_windows: a positive multiple of 16 (padding windows hold zeros; their gradients arrive as exact zeros).  Every activation is a
+ * fragment plane [tiles][35][F/16][64][4] (F features; element (window n, step t, feature f) at
+ * ((((n / 16) * 35 + t) * F/16 + f / 16) * 64 + 16 ((f / 4) % 4) + n % 16) * 4 + f % 4), except a single input feature (cin = 1),
+ * which is [n_windows][35].  Channel counts (cin, cout, features) are multiples of 16 up to 512 unless stated.
+ *   unit         one conv + BN unit in TF layout: kernel [kw][cin][cout] | bias | gamma | beta | moving_mean | moving_variance;
+ *                unit_grads has the same layout (the moving statistics are not written)
+ *   layer_params one biGRU layer, per direction (fw, bw): gates kernel [cin + H][2H] | gates bias [2H] | candidate kernel [cin + H][H]
+ *                | candidate bias [H]; layer_grads the same
+ *   dense        final_fully_connected kernel [features] | bias [1]; dense_grads the same
+ * Gradients are sums over all positions, produced as per-workgroup partials over fixed chunks of 32 windows and reduced in chunk
+ * order (no atomics): the same inputs give bit-identical gradients.  Workspaces: cf_gen_train_workspace_floats(rows, cols,
+ * n_windows) for a weight gradient of rows x cols (conv: kw cin + 1 rows x cout; GRU: cin + H + 1 rows x 2H), n_windows / 16 x 2
+ * cout for cf_gen_bn_backward, cf_gen_head_workspace_floats for the head.  A bad size, a null buffer or a short workspace is
+ * CF_ERR_INVALID.
+ *   cf_gen_conv_forward        z_stash = conv(x) + bias (SAME padding inside each window, kw 1 or 3), out = [ReLU](z s + t) with
+ *                              s = gamma / sqrt(var + 1e-3), t = beta - mean s; with shortcut: out = ReLU(out + shortcut)
+ *   cf_gen_bn_backward         dz = g [mask > 0] [z s + t > 0 if relu] s (mask optional: the block output after the shortcut's
+ *                              ReLU); d gamma, d beta into unit_grads
+ *   cf_gen_conv_wgrad          d kernel, d bias of the unit (x is the unit's input) into unit_grads
+ *   cf_gen_conv_backward_data  dx = conv^T(dz) (+ add)
+ *   cf_gen_gru_dx              dx = sum over directions and gates of da W_x^T (da as written by cf_gru_anysize_train_backward)
+ *   cf_gen_gru_wgrad           [x; h_prev]^T da_{r,u}, [x; r h_prev]^T da_c and the bias sums of both directions into layer_grads
+ *                              (x_frag with ceil(cin / 16) feature tiles, y_frag the layer's output before dropout)
+ *   cf_gen_dropout             out = in * mask / keep_prob over a [tiles][35][2H/16][64][4] plane: the mask is the tuned kernels'
+ *                              hash of (seed, layer, *step_count, f32x4 index) (the same masks as cf_gru_train_forward_dropout at
+ *                              H = 64), or out = in * scale_frag when scale_frag is not NULL.  Also the backward of the dropout.
+ *   cf_gen_head                logits, mean sigmoid cross-entropy over the n_real real windows (loss[0]), d input, d dense;
+ *                              logits [n_windows][35] or NULL; labels [n_windows][35]; n_real in (n_windows - 16, n_windows]
+ *   cf_gen_x_frag              the one input feature [n_windows][35] as a 16-feature plane (zeros above feature 0) */
+int64_t cf_gen_train_workspace_floats(int32_t rows, int32_t cols, int64_t n_windows);
+int64_t cf_gen_head_workspace_floats(int32_t features, int64_t n_windows);
+int cf_gen_conv_forward(cf_model* m, int32_t kw, int32_t cin, int32_t cout, const float* unit, const float* x, const float* shortcut,
+                        int32_t relu, float* z_stash, float* out, int64_t n_windows, void* stream);
+int cf_gen_conv_backward_data(cf_model* m, int32_t kw, int32_t cin, int32_t cout, const float* unit, const float* dz, const float* add,
+                              float* dx, int64_t n_windows, void* stream);
+int cf_gen_bn_backward(cf_model* m, int32_t kw, int32_t cin, int32_t cout, const float* unit, const float* g, const float* mask,
+                       int32_t relu, const float* z_stash, float* dz, float* workspace, int64_t workspace_floats, float* unit_grads,
+                       int64_t n_windows, void* stream);
+int cf_gen_conv_wgrad(cf_model* m, int32_t kw, int32_t cin, int32_t cout, const float* x, const float* dz, float* workspace,
+                      int64_t workspace_floats, float* unit_grads, int64_t n_windows, void* stream);
+int cf_gen_gru_dx(cf_model* m, int32_t layer_size, int32_t cin, const float* layer_params, const float* da, float* dx, int64_t n_windows,
+                  void* stream);
+int cf_gen_gru_wgrad(cf_model* m, int32_t layer_size, int32_t cin, const float* x_frag, const float* y_frag, const float* stash,
+                     const float* da, float* workspace, int64_t workspace_floats, float* layer_grads, int64_t n_windows, void* stream);
+int cf_gen_dropout(cf_model* m, int32_t layer_size, float keep_prob, uint32_t seed, int32_t layer, const double* step_count,
+                   const float* scale_frag, const float* in_frag, float* out_frag, int64_t n_windows, void* stream);
+int cf_gen_head(cf_model* m, int32_t features, const float* in_frag, const float* dense, const float* labels, int64_t n_real,
+                float* din_frag, float* logits, float* workspace, int64_t workspace_floats, float* dense_grads, float* loss,
+                int64_t n_windows, void* stream);
+int cf_gen_x_frag(cf_model* m, const float* x, float* x_frag, int64_t n_windows, void* stream);
 
 /* Per-kernel device timing (HIP events on the launch stream) for bench.py's
  * roofline report.  cf_profile_enable(m, N) makes every N-th cf_infer call
