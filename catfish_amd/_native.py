@@ -32,7 +32,7 @@ def _lib_path():
 
 
 LIB_PATH = DEFAULT_LIB_PATH
-CF_ABI_VERSION = 7            # include/catfish_hip.h
+CF_ABI_VERSION = 8            # include/catfish_hip.h
 
 CF_OK = 0
 CF_ERR_INVALID = -1
@@ -153,6 +153,11 @@ SYMBOLS = {
     "cf_gen_dropout": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "cf_gen_head": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "cf_gen_x_frag": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "cf_gen_head_backward_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64]),
+    "cf_gen_head_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "cf_gen_signal_grad": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "cf_gen_bn_backward_data": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "cf_gen_bn_stat_grads": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "cf_profile_reset": (C.c_int, [C.c_void_p]),
     "cf_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

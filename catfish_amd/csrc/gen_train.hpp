@@ -17,6 +17,9 @@
 //   gt_head          dense head + sigmoid cross-entropy per position (logit, d logit, d input, loss term), padding windows 0
 //   gt_loss_reduce   mean loss, one workgroup, fixed order
 //   gt_x_frag        the plain RNN's one input feature into a 16-feature fragment plane
+//   gt_head_bwd      head backward from an upstream d probability (the operator's autograd: no labels, no loss)
+//   gt_signal_grad   d loss / d signal from block 0's two cin-1 units (ResNetRNN) or layer 0's gate gradients (plain RNN)
+//   gt_bn_stat_grads d moving_mean, d moving_variance from the unit's d gamma, d beta
 //
 // The GEMM-shaped kernels share one LDS-tiled core (64 x 64 outputs per workgroup, 4 x 4 per thread, k in steps of 16, fmaf in
 // a fixed k order: exact fp32 products, the same sum on every run).  Included by catfish_hip.hip after cf_opt_step.
@@ -233,7 +236,8 @@ struct GtHeadDw {
 };
 
 // ---- element-wise and small reductions -------------------------------------------------------------------------------------------
-// one thread per (tile, channel): dz of the tile's 560 positions and its partial sums of d gamma, d beta (part[tile][gamma C | beta C])
+// one thread per (tile, channel): dz of the tile's 560 positions and (kPart) its partial sums of d gamma, d beta (part[tile][gamma C | beta C])
+template <bool kPart>
 __global__ __launch_bounds__(256) void gt_bn_bwd_kernel(const float* __restrict__ g, const float* __restrict__ mask, int relu,
                                                         const float* __restrict__ z, const float* __restrict__ prm, int cout,
                                                         float* __restrict__ dz, float* __restrict__ part, int n_tiles) {
@@ -254,8 +258,10 @@ __global__ __launch_bounds__(256) void gt_bn_bwd_kernel(const float* __restrict_
             sg = fmaf(v, (zz - mean) * inv, sg);
             dz[o] = v * s;
         }
-    part[(int64_t)tile * 2 * cout + c] = sg;
-    part[(int64_t)tile * 2 * cout + cout + c] = sb;
+    if (kPart) {
+        part[(int64_t)tile * 2 * cout + c] = sg;
+        part[(int64_t)tile * 2 * cout + cout + c] = sb;
+    }
 }
 
 __global__ __launch_bounds__(256) void gt_dropout_kernel(const f32x4* __restrict__ in, f32x4* __restrict__ out, const f32x4* __restrict__ scale,
@@ -301,6 +307,65 @@ __global__ __launch_bounds__(256) void gt_x_frag_kernel(const float* __restrict_
     if (p >= P) return;
     const int n = (int)(p / CF_T), t = (int)(p - (int64_t)n * CF_T);
     for (int f = 0; f < 16; ++f) xf[gt_fi(n, t, f, 1)] = f == 0 ? x[p] : 0.f;
+}
+
+// ---- backward of the inference function (torch.ops.catfish.resnetrnn_forward's autograd, catfish_amd/op_grad.py) ---------------
+// head from an upstream gradient of the probabilities: p = sigmoid(z), dz = g p (1 - p) = g e / (1 + e)^2 with e = exp(-|z|) (no
+// overflow for any z); d input = dz w.  Padding windows carry g = 0, so every gradient they feed is an exact zero.
+__global__ __launch_bounds__(256) void gt_head_bwd_kernel(const float* __restrict__ in, int f16, const float* __restrict__ w, const float* __restrict__ bias,
+                                                          const float* __restrict__ dprobs, float* __restrict__ din, float* __restrict__ dl, int64_t P) {
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= P) return;
+    const int n = (int)(p / CF_T), t = (int)(p - (int64_t)n * CF_T);
+    float s = 0.f;
+    for (int f = 0; f < 16 * f16; ++f) s = fmaf(in[gt_fi(n, t, f, f16)], w[f], s);
+    s += bias[0];
+    const float e = expf(-fabsf(s)), q = 1.f + e;
+    const float d = dprobs[p] * (e / (q * q));
+    dl[p] = d;
+    for (int f = 0; f < 16 * f16; ++f) din[gt_fi(n, t, f, f16)] = d * w[f];
+}
+
+// d loss / d signal [n_windows][35], one thread per position (threads of a wave walk the 16 windows of a tile, then the steps), one
+// fixed summation order.  ResNetRNN (c > 0): the signal feeds only block 0's shortcut and first conv (kw 1, cin 1, kernel = c
+// weights): dx = sum_o dz_sc[o] w_sc[o] + dz_1[o] w_1[o].  Plain RNN (h > 0): the signal is row 0 of layer 0's input; da holds
+// (dir, gate r / u / c, unit) at the step each direction consumed x_t (both directions in natural time order, as in GtGruDx) and
+// the candidate's x part is not gated by r: dx = sum_dir (sum_j<2H da_ru[j] Wg[0][j] + sum_j<H da_c[j] Wc[0][j]).
+__global__ __launch_bounds__(256) void gt_signal_grad_kernel(int h, int c, const float* __restrict__ p0, const float* __restrict__ g0,
+                                                             const float* __restrict__ p1, const float* __restrict__ g1, float* __restrict__ dx,
+                                                             int64_t P) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= P) return;
+    const int64_t tile = i / (CF_TILE * CF_T);
+    const int r = (int)(i - tile * CF_TILE * CF_T), t = r / CF_TILE, n = (int)tile * CF_TILE + (r - t * CF_TILE);
+    float s = 0.f;
+    if (c > 0) {
+        const int c16 = c >> 4;
+        for (int o = 0; o < c; ++o) {
+            s = fmaf(g0[gt_fi(n, t, o, c16)], p0[o], s);
+            s = fmaf(g1[gt_fi(n, t, o, c16)], p1[o], s);
+        }
+    } else {
+        const int f16 = 3 * (h >> 3);
+        const int64_t dir_floats = (int64_t)(1 + h) * 3 * h + 3 * h;
+        for (int d = 0; d < 2; ++d) {
+            const float* pd = p0 + d * dir_floats;
+            const float* wc = pd + (int64_t)(1 + h) * 2 * h + 2 * h;
+            for (int j = 0; j < 2 * h; ++j) s = fmaf(g0[gt_fi(n, t, d * 3 * h + j, f16)], pd[j], s);
+            for (int j = 0; j < h; ++j) s = fmaf(g0[gt_fi(n, t, d * 3 * h + 2 * h + j, f16)], wc[j], s);
+        }
+    }
+    dx[(int64_t)n * CF_T + t] = s;
+}
+
+// BN moving statistics: y = (z - mean) gamma / sqrt(var + eps) + beta, so from the BN-output sums d gamma, d beta of the unit
+// d mean = -gamma d beta / sqrt(var + eps) and d var = -gamma d gamma / (2 (var + eps)); one thread per channel
+__global__ __launch_bounds__(256) void gt_bn_stat_grads_kernel(const float* __restrict__ prm, float* __restrict__ grads, int cout) {
+    const int c = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (c >= cout) return;
+    const float gam = prm[c], ve = prm[3 * cout + c] + GT_BN_EPS;                 // prm, grads = gamma | beta | mean | var
+    grads[2 * cout + c] = -gam * grads[cout + c] * rsqrtf(ve);
+    grads[3 * cout + c] = -gam * grads[c] / (2.f * ve);
 }
 
 // ---- C ABI (include/catfish_hip.h, "whole-step training of any geometry") --------------------------------------------------------
@@ -377,7 +442,7 @@ extern "C" int cf_gen_bn_backward(cf_model* m, int32_t kw, int32_t cin, int32_t 
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int64_t kf = (int64_t)kw * cin * cout + cout;            // gamma follows kernel | bias
     const int64_t items = (int64_t)n_tiles * cout;
-    hipLaunchKernelGGL(gt_bn_bwd_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, g, mask, relu ? 1 : 0, z_stash, unit + kf, (int)cout,
+    hipLaunchKernelGGL(gt_bn_bwd_kernel<true>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, g, mask, relu ? 1 : 0, z_stash, unit + kf, (int)cout,
                        dz, workspace, n_tiles);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(gt_reduce_kernel, dim3((unsigned)((2 * cout + 255) / 256)), dim3(256), 0, s, workspace, (int64_t)2 * cout, n_tiles,
@@ -489,6 +554,81 @@ extern "C" int cf_gen_x_frag(cf_model* m, const float* x, float* x_frag, int64_t
     HIP_TRY(hipSetDevice(m->device));
     const int64_t P = n_windows * CF_T;
     hipLaunchKernelGGL(gt_x_frag_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, x_frag, P);
+    HIP_TRY(hipGetLastError());
+    return CF_OK;
+}
+
+
+// ---- C ABI (include/catfish_hip.h, "backward of the inference function") ---------------------------------------------------------
+extern "C" int64_t cf_gen_head_backward_workspace_floats(int32_t features, int64_t n_windows) {
+    if (features <= 0 || n_windows <= 0) return 0;
+    return n_windows * CF_T + cf_gen_train_workspace_floats(features + 1, 1, n_windows);
+}
+
+extern "C" int cf_gen_head_backward(cf_model* m, int32_t features, const float* in_frag, const float* dense, const float* dprobs, float* din_frag,
+                                    float* workspace, int64_t workspace_floats, float* dense_grads, int64_t n_windows, void* stream) {
+    int rc = gt_args(m, n_windows, "cf_gen_head_backward");
+    if (rc != CF_OK) return rc;
+    if (!in_frag || !dense || !dprobs || !din_frag || !workspace) return fail(CF_ERR_INVALID, "cf_gen_head_backward: null buffer");
+    if (!gt_ch_ok(features)) return fail(CF_ERR_INVALID, "cf_gen_head_backward: features must be a multiple of 16 up to 512");
+    const int64_t P = n_windows * CF_T;
+    if (workspace_floats < cf_gen_head_backward_workspace_floats(features, n_windows))
+        return fail(CF_ERR_INVALID, "cf_gen_head_backward: workspace too small (cf_gen_head_backward_workspace_floats)");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    float* dl = workspace;
+    hipLaunchKernelGGL(gt_head_bwd_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, in_frag, (int)features / 16, dense, dense + features,
+                       dprobs, din_frag, dl, P);
+    HIP_TRY(hipGetLastError());
+    if (!dense_grads) return CF_OK;
+    GtHeadDw op{in_frag, dl, (int)features / 16};
+    return gt_wgrad(op, features + 1, 1, n_windows, workspace + P, workspace_floats - P, dense_grads, s, "cf_gen_head_backward");
+}
+
+extern "C" int cf_gen_signal_grad(cf_model* m, int32_t layer_size, int32_t channels, const float* params0, const float* grad0, const float* params1,
+                                  const float* grad1, float* dx, int64_t n_windows, void* stream) {
+    int rc = gt_args(m, n_windows, "cf_gen_signal_grad");
+    if (rc != CF_OK) return rc;
+    if (!params0 || !grad0 || !dx || (channels != 0 && (!params1 || !grad1))) return fail(CF_ERR_INVALID, "cf_gen_signal_grad: null buffer");
+    const bool res = layer_size == 0 && gt_ch_ok(channels);
+    const bool rnn = channels == 0 && layer_size >= 16 && layer_size <= 256 && (layer_size % 16) == 0;
+    if (!res && !rnn)
+        return fail(CF_ERR_INVALID, "cf_gen_signal_grad: give either channels (a multiple of 16 up to 512, layer_size 0) or layer_size "
+                                    "(a multiple of 16 up to 256, channels 0)");
+    HIP_TRY(hipSetDevice(m->device));
+    const int64_t P = n_windows * CF_T;
+    hipLaunchKernelGGL(gt_signal_grad_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), (int)layer_size,
+                       (int)channels, params0, grad0, params1, grad1, dx, P);
+    HIP_TRY(hipGetLastError());
+    return CF_OK;
+}
+
+extern "C" int cf_gen_bn_backward_data(cf_model* m, int32_t kw, int32_t cin, int32_t cout, const float* unit, const float* g, const float* mask,
+                                       int32_t relu, const float* z_stash, float* dz, int64_t n_windows, void* stream) {
+    int rc = gt_args(m, n_windows, "cf_gen_bn_backward_data");
+    if (rc != CF_OK) return rc;
+    if (!unit || !g || !z_stash || !dz) return fail(CF_ERR_INVALID, "cf_gen_bn_backward_data: null buffer");
+    if ((kw != 1 && kw != 3) || !(cin == 1 || gt_ch_ok(cin)) || !gt_ch_ok(cout))
+        return fail(CF_ERR_INVALID, "cf_gen_bn_backward_data: kw must be 1 or 3, cin 1 or a multiple of 16 up to 512, cout a multiple of 16 up to 512");
+    HIP_TRY(hipSetDevice(m->device));
+    const int n_tiles = (int)(n_windows / CF_TILE);
+    const int64_t kf = (int64_t)kw * cin * cout + cout;
+    const int64_t items = (int64_t)n_tiles * cout;
+    hipLaunchKernelGGL(gt_bn_bwd_kernel<false>, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), g, mask,
+                       relu ? 1 : 0, z_stash, unit + kf, (int)cout, dz, nullptr, n_tiles);
+    HIP_TRY(hipGetLastError());
+    return CF_OK;
+}
+
+extern "C" int cf_gen_bn_stat_grads(cf_model* m, int32_t kw, int32_t cin, int32_t cout, const float* unit, float* unit_grads, void* stream) {
+    if (!m) return fail(CF_ERR_INVALID, "cf_gen_bn_stat_grads: null model");
+    if (!unit || !unit_grads) return fail(CF_ERR_INVALID, "cf_gen_bn_stat_grads: null buffer");
+    if ((kw != 1 && kw != 3) || !(cin == 1 || gt_ch_ok(cin)) || !gt_ch_ok(cout))
+        return fail(CF_ERR_INVALID, "cf_gen_bn_stat_grads: kw must be 1 or 3, cin 1 or a multiple of 16 up to 512, cout a multiple of 16 up to 512");
+    HIP_TRY(hipSetDevice(m->device));
+    const int64_t kf = (int64_t)kw * cin * cout + cout;
+    hipLaunchKernelGGL(gt_bn_stat_grads_kernel, dim3((unsigned)((cout + 255) / 256)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), unit + kf,
+                       unit_grads + kf, (int)cout);
     HIP_TRY(hipGetLastError());
     return CF_OK;
 }

@@ -14,6 +14,11 @@ the fixed order of ``tensor_names`` (TF variable names, TF layouts), i.e. what `
 The engine built from it (BN folded, matrices re-tiled into MFMA fragment order, uploaded) is cached per (tensor storage, version,
 device): the second call with the same tensor only launches.
 
+The op is differentiable once, with respect to ``x`` and ``packed_weights`` (every tensor, the BN moving statistics included): its
+autograd formula (``op_grad``) re-runs the training forward of the engine's geometry on the HIP kernels and walks it backwards.  The
+``x`` gradient stays on the device, asynchronous; the ``packed_weights`` gradient is a float32 CPU tensor like ``packed_weights``
+(header zero) and costs one device-to-host copy.  INTEGRATION.md, "The call as a PyTorch operator", has examples.
+
     import torch, catfish_amd.torch_ops as ops
     packed = ops.pack_weights(weights)                       # once
     probs = torch.ops.catfish.resnetrnn_forward(x, packed)   # x: float32 [N, 35] or [N, 35, 1] on an MI355X -> float32 [N * 35]
@@ -146,17 +151,32 @@ def _engine_for(packed, device_index):
     if eng is None:
         weights, geom = unpack_weights(packed)
         eng = HipEngine(weights, device=int(device_index), **geom)
+        eng.op_grad = None                                     # backward state (op_grad.OpGrad), built by the first backward
         if len(_ENGINES) >= MAX_CACHED:                       # oldest out: an engine holds device workspace
-            _ENGINES.pop(next(iter(_ENGINES))).close()
+            _retire(_ENGINES.pop(next(iter(_ENGINES))))
         _ENGINES[key] = eng
     return eng
 
 
+def _retire(eng):
+    eng.op_grad = None                                         # device parameters, GRU packs and slab buffers of the backward
+    eng.close()
+
+
 def clear_engine_cache():
-    """Free the engines (device weights + workspace) the operator built so far."""
+    """Free the engines (device weights + workspace, and the backward's state) the operator built so far."""
     _SEEN.clear()
     while _ENGINES:
-        _ENGINES.popitem()[1].close()
+        _retire(_ENGINES.popitem()[1])
+
+
+def _backward_impl(x, packed, grad, need_x, need_w):
+    """(d x, d packed_weights) of the operator for the upstream gradient ``grad`` [N * 35] (``op_grad``)."""
+    from .op_grad import OpGrad
+    eng = _engine_for(packed, x.device.index)
+    if eng.op_grad is None:
+        eng.op_grad = OpGrad(eng, packed, HEADER)
+    return eng.op_grad.backward(x, grad, need_x, need_w)
 
 
 def _register():
@@ -175,6 +195,23 @@ def _register():
         n = x.shape[0]
         return x.new_empty((n * N.CF_WINDOW,), dtype=torch.float32)
 
+    def setup_context(ctx, inputs, output):
+        ctx.save_for_backward(*inputs)                        # recompute, don't stash: torch catches an in-place edit of either
+
+    def backward(ctx, grad):
+        x, packed = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[:2]
+        gx, gw = _backward_impl(x, packed, grad, need_x, need_w)
+        if torch.is_grad_enabled():                           # create_graph=True: the gradients are not differentiable again
+            grads = [t.detach().requires_grad_(True) if t is not None else None for t in (gx, gw)]
+            live = [t for t in grads if t is not None]
+            err = torch._C._functions.DelayedError(b"catfish::resnetrnn_forward is once-differentiable: its backward has no "
+                                                   b"autograd formula (double backward is not supported)", len(live) + 2)
+            out = iter(err(*live, x, packed))                     # x, packed: the error node is reached from the op's inputs
+            gx, gw = (next(out) if t is not None else None for t in grads)
+        return gx, gw
+
+    torch.library.register_autograd(OP_NAME, backward, setup_context=setup_context)
     return resnetrnn_forward
 
 

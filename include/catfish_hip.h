@@ -39,7 +39,7 @@ extern "C" {
 
 /* Bumped whenever a signature or a struct of this header changes; cf_abi_version() returns the value the library was built
  * with, so a binding can refuse a stale libcatfish_hip.so instead of calling it with the wrong arguments. */
-#define CF_ABI_VERSION 7
+#define CF_ABI_VERSION 8
 
 /* Arithmetic of the biGRU layers (the residual blocks, the hidden state, the gates'
  * sigmoid/tanh and all accumulation are fp32 in every mode). */
@@ -431,6 +431,31 @@ int cf_gen_head(cf_model* m, int32_t features, const float* in_frag, const float
                 float* din_frag, float* logits, float* workspace, int64_t workspace_floats, float* dense_grads, float* loss,
                 int64_t n_windows, void* stream);
 int cf_gen_x_frag(cf_model* m, const float* x, float* x_frag, int64_t n_windows, void* stream);
+
+/* Backward of the inference function (csrc/gen_train.hpp; catfish_amd/op_grad.py drives it for the autograd formula of
+ * torch.ops.catfish.resnetrnn_forward): inference-mode BN on the moving statistics, no dropout, p = sigmoid(logit).  The
+ * forward and the rest of the backward are the cf_gen_* calls above; conventions (fragment planes, unit / layer_params / dense
+ * layouts, n_windows, fixed-order reductions, stream, CF_ERR_INVALID on a bad size, a null buffer or a short workspace) as there.
+ *   cf_gen_head_backward       from the last layer's output plane in_frag [.., features], the dense weights and an upstream
+ *                              dprobs [n_windows][35]: dlogit = g sigmoid(z) sigmoid(-z) (stable for any z), din_frag = dlogit w;
+ *                              d dense into dense_grads unless it is NULL (then no reduction is launched).  Workspace:
+ *                              cf_gen_head_backward_workspace_floats(features, n_windows)
+ *   cf_gen_signal_grad         dx [n_windows][35], d loss / d the one input feature, one fixed summation order per position.
+ *                              ResNetRNN: layer_size 0, channels C; params0 / grad0 the shortcut unit (conv1d, kw 1, cin 1) and
+ *                              its dz, params1 / grad1 the first conv unit (conv1d_1) and its dz (cf_gen_bn_backward's output):
+ *                              dx = sum_o dz_sc[o] w_sc[o] + dz_1[o] w_1[o].  Plain RNN: channels 0, layer_size H; params0 layer
+ *                              0's layer_params (cin 1), grad0 its da; params1, grad1 NULL
+ *   cf_gen_bn_backward_data    dz of cf_gen_bn_backward without d gamma, d beta (no workspace, no reduction)
+ *   cf_gen_bn_stat_grads       the moving-statistics slots of unit_grads from its d gamma, d beta (written by
+ *                              cf_gen_bn_backward): d mean = -gamma d beta / sqrt(var + 1e-3), d var = -gamma d gamma / (2 (var + 1e-3)) */
+int64_t cf_gen_head_backward_workspace_floats(int32_t features, int64_t n_windows);
+int cf_gen_head_backward(cf_model* m, int32_t features, const float* in_frag, const float* dense, const float* dprobs, float* din_frag,
+                         float* workspace, int64_t workspace_floats, float* dense_grads, int64_t n_windows, void* stream);
+int cf_gen_signal_grad(cf_model* m, int32_t layer_size, int32_t channels, const float* params0, const float* grad0, const float* params1,
+                       const float* grad1, float* dx, int64_t n_windows, void* stream);
+int cf_gen_bn_backward_data(cf_model* m, int32_t kw, int32_t cin, int32_t cout, const float* unit, const float* g, const float* mask,
+                            int32_t relu, const float* z_stash, float* dz, int64_t n_windows, void* stream);
+int cf_gen_bn_stat_grads(cf_model* m, int32_t kw, int32_t cin, int32_t cout, const float* unit, float* unit_grads, void* stream);
 
 /* Per-kernel device timing (HIP events on the launch stream) for bench.py's
  * roofline report.  cf_profile_enable(m, N) makes every N-th cf_infer call

@@ -1,0 +1,283 @@
+"""Autograd of ``torch.ops.catfish.resnetrnn_forward`` on the HIP kernels (catfish_amd/op_grad.py): gradients with respect to the
+signal windows and to every packed tensor, the BN moving statistics included, against autograd through ``TorchResNetRNN`` in float64."""
+import os
+
+import numpy as np
+import pytest
+
+from oracle import catfish_oracle as oracle
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PLAIN_C = 32                  # layer_size_res of a plain RNN model: recorded in the header, unused
+
+
+def _ckpt():
+    with np.load(os.path.join(ROOT, "tests", "golden", "ckpnt-30000-inference.npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+# ---------------------------------------------------------------------------------------------------- CPU
+@pytest.mark.parametrize("geo", [(64, 32, 3, 2), (16, 16, 2, 2), (128, 32, 2, 0), (64, 32, 1, 0), (128, 128, 5, 5), (48, 80, 2, 1)])
+def test_packed_order_is_the_flat_training_layout(geo):
+    """After the 8-value header the operator's tensors sit at flat_layout's offsets with its shapes: the backward uploads
+    packed[8:] as the training step's flat parameter buffer."""
+    import catfish_amd.torch_ops as ops
+    from catfish_amd.anysize_step import flat_layout
+    h, c, n_layers, n_blocks = geo
+    w = oracle.random_weights(seed=1, layer_size=h, n_layers=n_layers, layer_size_res=c, n_layers_res=n_blocks)
+    packed = ops.pack_weights(w, n_layers, h, n_blocks, c)
+    entries, _, _, _, zero = flat_layout(h, c if n_blocks else 0, n_layers, n_blocks)
+    shapes = ops._shapes(n_layers, h, n_blocks, c)
+    got, off = [], 0
+    for name in ops.tensor_names(n_layers, n_blocks):
+        got.append((name, off, tuple(shapes[name])))
+        off += int(np.prod(shapes[name]))
+    assert got == [(name, o, tuple(s)) for name, o, s in entries]
+    assert packed.numel() == ops.HEADER + zero
+    flat = packed.numpy()[ops.HEADER:]
+    for name, o, s in entries:
+        np.testing.assert_array_equal(flat[o:o + int(np.prod(s))], np.asarray(w[name], np.float32).reshape(-1))
+
+
+def test_schema_is_unchanged():
+    import torch
+    import catfish_amd.torch_ops  # noqa: F401
+    assert str(torch.ops.catfish.resnetrnn_forward.default._schema) == "catfish::resnetrnn_forward(Tensor x, Tensor packed_weights) -> Tensor"
+
+
+# ---------------------------------------------------------------------------------------------------- GPU
+def _weights(geo, seed=7):
+    if geo == "ckpt":
+        return _ckpt(), (64, 32, 3, 2)
+    h, c, n_layers, n_blocks = geo
+    return oracle.random_weights(seed=seed, layer_size=h, n_layers=n_layers, layer_size_res=c, n_layers_res=n_blocks), geo
+
+
+def _reference(w, geo, x, g):
+    """d loss / d x and d loss / d every tensor (moving statistics included) of loss = (sigmoid(logits(x)) . g).sum(), float64 CPU."""
+    import torch
+    from catfish_amd.training import TorchResNetRNN
+    h, c, n_layers, n_blocks = geo
+    net = TorchResNetRNN(w, n_layers, n_blocks, device="cpu", dtype=torch.float64)
+    for t in net.params.values():
+        t.requires_grad_(True)
+    xt = torch.tensor(np.asarray(x), dtype=torch.float64, requires_grad=True)
+    probs = torch.sigmoid(net.logits(xt))
+    (probs.reshape(-1) * torch.tensor(g, dtype=torch.float64)).sum().backward()
+    return xt.grad.numpy(), {k: v.grad.numpy() for k, v in net.params.items()}
+
+
+def _op_grads(packed, x, g, need_x=True, need_w=True):
+    import torch
+    xd = torch.tensor(x, device="cuda").requires_grad_(need_x)
+    pw = packed.clone().requires_grad_(need_w)
+    out = torch.ops.catfish.resnetrnn_forward(xd, pw)
+    (out * torch.tensor(g, device="cuda")).sum().backward()
+    return out.detach(), xd.grad, pw.grad
+
+
+def _close(a, b, what=""):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    assert np.abs(a - b).max() <= 2e-4 * np.abs(b).max() + 1e-6, (what, np.abs(a - b).max(), np.abs(b).max())
+
+
+def _unpack_grad(gw, packed):
+    """The packed gradient (zero header) cut into {TF name: array} with the geometry of ``packed``."""
+    import catfish_amd.torch_ops as ops
+    g = gw.clone()
+    g[:ops.HEADER] = packed.detach()[:ops.HEADER]
+    return ops.unpack_weights(g)[0]
+
+
+def _check_all(gx, gw, rx, rw, packed):
+    _close(gx.cpu().numpy(), rx, "x")
+    back = _unpack_grad(gw, packed)
+    assert sorted(back) == sorted(rw)
+    for k in rw:
+        _close(back[k], rw[k], k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("geo,n", [("ckpt", 1), ("ckpt", 17), ("ckpt", 118), ((16, 16, 2, 2), 40), ((48, 48, 2, 1), 33),
+                                   ((128, 64, 3, 2), 50), ((256, 128, 2, 1), 20), ((128, 128, 5, 5), 20), ((64, PLAIN_C, 1, 0), 45),
+                                   ((128, PLAIN_C, 2, 0), 30)])
+def test_gradients_equal_autograd_through_the_restatement(geo, n):
+    """x, every packed tensor and the moving statistics against float64 autograd through TorchResNetRNN; the forward with grad
+    enabled is bit-identical to the same call under no_grad."""
+    import torch
+    import catfish_amd.torch_ops as ops
+    w, geo = _weights(geo)
+    h, c, n_layers, n_blocks = geo
+    packed = ops.pack_weights(w, n_layers, h, n_blocks, c)
+    rng = np.random.default_rng(n)
+    x = rng.normal(0, 1, size=(n, 35)).astype(np.float32)
+    g = rng.normal(0, 1, size=n * 35).astype(np.float32)
+    out, gx, gw = _op_grads(packed, x, g)
+    with torch.no_grad():
+        plain = torch.ops.catfish.resnetrnn_forward(torch.tensor(x, device="cuda"), packed)
+    assert torch.equal(out, plain)
+    assert gx.shape == (n, 35) and gx.dtype == torch.float32 and gx.is_cuda
+    assert gw.shape == packed.shape and gw.dtype == torch.float32 and not gw.is_cuda and not gw[:ops.HEADER].any()
+    rx, rw = _reference(w, geo, x, g)
+    _check_all(gx, gw, rx, rw, packed)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("geo", [(32, 16, 2, 1), (64, PLAIN_C, 2, 0)])
+def test_grad_subsets_shapes_and_determinism(geo):
+    """x only: bit-identical to the x gradient of the full call; weights only: x gets none; [N, 35, 1] input gives that shape;
+    two calls give bit-identical gradients."""
+    import torch
+    import catfish_amd.torch_ops as ops
+    w, geo = _weights(geo, seed=3)
+    h, c, n_layers, n_blocks = geo
+    packed = ops.pack_weights(w, n_layers, h, n_blocks, c)
+    rng = np.random.default_rng(2)
+    x = rng.normal(0, 1, size=(70, 35)).astype(np.float32)
+    g = rng.normal(0, 1, size=70 * 35).astype(np.float32)
+    _, gx, gw = _op_grads(packed, x, g)
+    _, gx2, gw2 = _op_grads(packed, x, g)
+    assert torch.equal(gx, gx2) and torch.equal(gw, gw2)
+    _, gx_only, none_w = _op_grads(packed, x, g, need_w=False)
+    assert none_w is None and torch.equal(gx_only, gx)
+    _, none_x, gw_only = _op_grads(packed, x, g, need_x=False)
+    assert none_x is None and torch.equal(gw_only, gw)
+    x3 = torch.tensor(x[:, :, None], device="cuda", requires_grad=True)
+    out = torch.ops.catfish.resnetrnn_forward(x3, packed)
+    (out * torch.tensor(g, device="cuda")).sum().backward()
+    assert x3.grad.shape == (70, 35, 1) and torch.equal(x3.grad[:, :, 0], gx)
+    empty = torch.zeros(0, 35, device="cuda", requires_grad=True)
+    pw = packed.clone().requires_grad_(True)
+    torch.ops.catfish.resnetrnn_forward(empty, pw).sum().backward()
+    assert empty.grad.shape == (0, 35) and not pw.grad.any()
+    eng = ops._engine_for(packed, 0)                       # the backward state lives with the cached engine and goes with it
+    assert eng.op_grad is not None
+    ops.clear_engine_cache()
+    assert eng.op_grad is None and not ops._ENGINES
+
+
+@pytest.mark.gpu
+def test_slabs():
+    """BACKWARD_MAX_WINDOWS = 32 on 300 windows: the x gradient is bit-identical to one slab, the weight gradients within the
+    bound; a call of several thousand windows crosses slabs at the default size and matches the restatement on a sample."""
+    import torch
+    import catfish_amd.op_grad as og
+    import catfish_amd.torch_ops as ops
+    w = _ckpt()
+    packed = ops.pack_weights(w)
+    rng = np.random.default_rng(5)
+    x = rng.normal(0, 1, size=(300, 35)).astype(np.float32)
+    g = rng.normal(0, 1, size=300 * 35).astype(np.float32)
+    _, gx, gw = _op_grads(packed, x, g)
+    old = og.BACKWARD_MAX_WINDOWS
+    try:
+        og.BACKWARD_MAX_WINDOWS = 32
+        _, gx_s, gw_s = _op_grads(packed, x, g)
+    finally:
+        og.BACKWARD_MAX_WINDOWS = old
+    assert torch.equal(gx_s, gx)
+    a, b = _unpack_grad(gw_s, packed), _unpack_grad(gw, packed)
+    for k in b:
+        _close(a[k], b[k], k)
+    # several thousand windows: more than one slab at the default budget; upstream gradient only on a sample of windows
+    n = 5000
+    eng = ops._engine_for(packed, 0)
+    assert og.OpGrad(eng, packed, ops.HEADER).slab_windows(n) < n
+    xb = rng.normal(0, 1, size=(n, 35)).astype(np.float32)
+    sample = np.sort(rng.choice(n, 24, replace=False))
+    gb = np.zeros((n, 35), np.float32)
+    gb[sample] = rng.normal(0, 1, size=(24, 35))
+    _, gxb, gwb = _op_grads(packed, xb, gb.reshape(-1))
+    rx, rw = _reference(w, (64, 32, 3, 2), xb[sample], gb[sample].reshape(-1))
+    _close(gxb.cpu().numpy()[sample], rx, "x")
+    assert not gxb.cpu().numpy()[np.setdiff1d(np.arange(n), sample)].any()
+    back = _unpack_grad(gwb, packed)
+    for k in rw:
+        _close(back[k], rw[k], k)
+
+
+@pytest.mark.gpu
+def test_sgd_through_the_operator_lowers_a_weighted_bce():
+    """Three torch.optim.SGD steps on a leaf packed_weights under a class-weighted BCE lower that loss on a fixed batch."""
+    import torch
+    import catfish_amd.torch_ops as ops
+    packed = ops.pack_weights(_ckpt()).requires_grad_(True)
+    rng = np.random.default_rng(9)
+    x = torch.tensor(rng.normal(0, 1, size=(96, 35)).astype(np.float32), device="cuda")
+    y = torch.tensor(np.repeat((rng.random(96) < 0.2)[:, None], 35, axis=1).reshape(-1).astype(np.float32), device="cuda")
+    weight = torch.where(y > 0, torch.tensor(4.0, device="cuda"), torch.tensor(1.0, device="cuda"))
+    opt = torch.optim.SGD([packed], lr=0.02)
+
+    def loss_fn():
+        probs = torch.ops.catfish.resnetrnn_forward(x, packed).clamp(1e-6, 1 - 1e-6)
+        return torch.nn.functional.binary_cross_entropy(probs, y, weight=weight)
+
+    losses = []
+    for _ in range(3):
+        opt.zero_grad()
+        loss = loss_fn()
+        loss.backward()
+        opt.step()
+        losses.append(float(loss.detach()))
+    with torch.no_grad():
+        final = float(loss_fn())
+    assert final < losses[0], (losses, final)
+    assert packed[:ops.HEADER].tolist() == ops.pack_weights(_ckpt())[:ops.HEADER].tolist()
+    ops.clear_engine_cache()
+
+
+@pytest.mark.gpu
+def test_double_backward_raises_and_opcheck_passes():
+    import torch
+    import catfish_amd.torch_ops as ops
+    w = oracle.random_weights(seed=4, layer_size=32, n_layers=1, layer_size_res=16, n_layers_res=1)
+    packed = ops.pack_weights(w, 1, 32, 1, 16)
+    x = torch.randn(20, 35, device="cuda", requires_grad=True)
+    out = torch.ops.catfish.resnetrnn_forward(x, packed)
+    gx, = torch.autograd.grad(out.pow(2).sum(), x, create_graph=True)
+    with pytest.raises(RuntimeError, match="once-differentiable"):
+        torch.autograd.grad(gx.sum(), x)
+    torch.library.opcheck(torch.ops.catfish.resnetrnn_forward.default, (x, packed.clone().requires_grad_(True)),
+                          test_utils=("test_schema", "test_autograd_registration", "test_faketensor"))
+
+
+@pytest.mark.gpu
+def test_new_entry_points_reject_bad_arguments():
+    import ctypes as C
+    import torch
+    from catfish_amd import _native as N
+    from catfish_amd.engine import HipEngine
+    w = oracle.random_weights(seed=11, layer_size=32, n_layers=1, layer_size_res=16, n_layers_res=1)
+    eng = HipEngine(w, layer_size=32, n_layers=1, layer_size_res=16, n_layers_res=1, device=0, max_windows_per_pass=256)
+    lib, hd = eng._lib, eng._handle
+    buf = torch.zeros(1 << 20, device="cuda")
+    p = C.c_void_p(buf.data_ptr())
+    s = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    big = 1 << 20
+    assert lib.cf_gen_head_backward_workspace_floats(64, 16) == 16 * 35 + 65
+    calls = [
+        lambda: lib.cf_gen_head_backward(hd, 64, p, p, p, p, p, big, p, 17, s),          # n_windows
+        lambda: lib.cf_gen_head_backward(hd, 24, p, p, p, p, p, big, p, 16, s),          # features
+        lambda: lib.cf_gen_head_backward(hd, 64, p, p, None, p, p, big, p, 16, s),       # null dprobs
+        lambda: lib.cf_gen_head_backward(hd, 64, p, p, p, p, p, 16 * 35, p, 16, s),      # workspace
+        lambda: lib.cf_gen_head_backward(None, 64, p, p, p, p, p, big, p, 16, s),        # null model
+        lambda: lib.cf_gen_signal_grad(hd, 0, 24, p, p, p, p, p, 16, s),                 # channels
+        lambda: lib.cf_gen_signal_grad(hd, 32, 16, p, p, p, p, p, 16, s),                # both kinds
+        lambda: lib.cf_gen_signal_grad(hd, 0, 0, p, p, None, None, p, 16, s),            # neither
+        lambda: lib.cf_gen_signal_grad(hd, 0, 16, p, p, None, p, p, 16, s),              # null params1
+        lambda: lib.cf_gen_signal_grad(hd, 32, 0, p, p, None, None, None, 16, s),        # null dx
+        lambda: lib.cf_gen_signal_grad(hd, 24, 0, p, p, None, None, p, 16, s),           # layer_size
+        lambda: lib.cf_gen_signal_grad(hd, 32, 0, p, p, None, None, p, 0, s),            # n_windows
+        lambda: lib.cf_gen_bn_backward_data(hd, 2, 16, 16, p, p, None, 1, p, p, 16, s),  # kw
+        lambda: lib.cf_gen_bn_backward_data(hd, 1, 16, 16, p, p, None, 1, None, p, 16, s),
+        lambda: lib.cf_gen_bn_backward_data(hd, 1, 16, 16, p, p, None, 1, p, p, 24, s),
+        lambda: lib.cf_gen_bn_stat_grads(hd, 1, 1, 24, p, p, s),                         # cout
+        lambda: lib.cf_gen_bn_stat_grads(hd, 1, 1, 16, p, None, s),
+        lambda: lib.cf_gen_bn_stat_grads(None, 1, 1, 16, p, p, s),
+    ]
+    for i, call in enumerate(calls):
+        with pytest.raises(ValueError):
+            N.check(call())
+    torch.cuda.synchronize()
+    eng.close()
