@@ -32,7 +32,7 @@ def _lib_path():
 
 
 LIB_PATH = DEFAULT_LIB_PATH
-CF_ABI_VERSION = 8            # include/catfish_hip.h
+CF_ABI_VERSION = 9            # include/catfish_hip.h
 
 CF_OK = 0
 CF_ERR_INVALID = -1
@@ -86,6 +86,8 @@ _lib = None
 SYMBOLS = {
     "cf_model_create": (C.c_int, [C.POINTER(cf_weights), C.POINTER(cf_hparams), C.c_int, C.POINTER(C.c_void_p)]),
     "cf_model_destroy": (None, [C.c_void_p]),
+    "cf_model_param_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "cf_model_load_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_infer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "cf_infer_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "cf_infer_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -28,6 +28,7 @@
 #include <cmath>
 #include <mutex>
 #include <set>
+#include <functional>
 
 #include "../../include/catfish_hip.h"
 
@@ -731,10 +732,11 @@ __global__ __launch_bounds__(256) void embed_kernel(const float* __restrict__ x_
 // Kernel 3: head -- logits = p_fw + p_bw + b, probs = sigmoid (rnn_class.py:84,179-181),
 // transposing the [tile][t][16] partials back to the reference's window-major order.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ P, float bias, float* __restrict__ probs,
+__global__ __launch_bounds__(256) void head_kernel(const float* __restrict__ P, const float* __restrict__ dense_bias, float* __restrict__ probs,
                                                    float* __restrict__ logits, int64_t n_windows, int n_tiles, int tile_shift, int raw) {
     const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= n_windows * CF_T) return;
+    const float bias = dense_bias[0];
     const int64_t w = idx / CF_T;
     const int t = (int)(idx - w * CF_T);
     const int64_t tile = w >> tile_shift;            // 16-window tiles (fp32 path) or 32-window tiles (bf16 path)
@@ -979,6 +981,9 @@ static const char* k_slot_names[CF_PROF_SLOTS] = {"res_block_first", "res_block"
                                                   "gru_layer_last",  "head",           "postprocess",     "normalize",       "gru_fused",
                                                   "res_stack2",      "unused",         "unused"};
 
+struct cf_param_map;
+static void pm_destroy(cf_param_map* pm);
+
 struct cf_model {
     cf_hparams hp;
     int device = 0;
@@ -989,7 +994,8 @@ struct cf_model {
     std::vector<char*> d_res_b;  // per residual block packed bf16 weights (precision != fp32)
     std::vector<char*> d_gru_b;  // per layer packed bf16 weights [2 dirs] (precision != fp32)
     int np = 0;                  // bf16 parts per operand: 0 = fp32 path, 1 = bf16, 2 = bf16x3
-    float dense_bias = 0.f;
+    float* d_dense_bias = nullptr;   // [1]: read by both head kernels, so that cf_model_load_params can replace it on the device
+    cf_param_map* pmap = nullptr;    // gather map of cf_model_load_params (params_dev.hpp), built by its first call
     // workspace
     int64_t cap_windows = 0;              // per workspace slot
     int64_t cap_tiles = 0;
@@ -1031,34 +1037,145 @@ struct cf_model {
 };
 
 // ---- weight packing ----------------------------------------------------------------------
-static void pack_vec(float* dst, const std::vector<double>& v) {  // [mo][q][r] order == natural order of 16mo+4q+r
-    for (size_t i = 0; i < v.size(); ++i) dst[i] = (float)v[i];
+// Every packed fp32 element is a TERM over the checkpoint's inference tensors:
+//   zero  |  raw parameter x c  |  BN-folded kernel element (parameter x s of its channel) x c  |  BN-folded bias (b s + beta - mean s) x c
+// with s = gamma / sqrt(var + eps) and c from cf_term_const.  The packers below only EMIT terms (sink(index, term)):
+// cf_model_create evaluates them on the host (cf_host_params), cf_model_load_params records them once as a gather map and
+// evaluates them on the device (params_dev.hpp).  Both sides go through cf_bn_scale / cf_bn_bias / cf_term_value: double math
+// in the same order, contraction off, rounded to fp32 at the end -- so a load gives the bits a create of the same values gives.
+enum { CF_TERM_ZERO = 0, CF_TERM_RAW = 1, CF_TERM_KERN = 2, CF_TERM_BIAS = 3 };
+enum { CF_K_ONE = 0, CF_K_GATE = 1, CF_K_CAND = 2 };
+__host__ __device__ inline double cf_term_const(int c) { return c == CF_K_GATE ? CF_GATE_SCALE : (c == CF_K_CAND ? CF_CAND_SCALE : 1.0); }
+
+__host__ __device__ inline double cf_bn_scale(float gamma, float var, float eps) {
+#pragma clang fp contract(off)
+    return (double)gamma / sqrt((double)var + (double)eps);
+}
+__host__ __device__ inline double cf_bn_bias(float bias, float beta, float mean, double s) {
+#pragma clang fp contract(off)
+    return (double)bias * s + (double)beta - (double)mean * s;
+}
+// p: the term's parameter (RAW, KERN), s / b: its channel's BN scale (KERN) / folded bias (BIAS)
+__host__ __device__ inline float cf_term_value(int kind, float p, double s, double b, int c) {
+#pragma clang fp contract(off)
+    const double base = kind == CF_TERM_RAW ? (double)p : (kind == CF_TERM_KERN ? (double)p * s : (kind == CF_TERM_BIAS ? b : 0.0));
+    return (float)(base * cf_term_const(c));
+}
+
+struct cf_term {
+    int32_t kind = CF_TERM_ZERO;
+    int32_t tensor = 0, elem = 0;      // RAW, KERN: element `elem` of tensor `tensor` (cf_tid_*)
+    int32_t ch = 0;                    // KERN, BIAS: BN channel = conv unit * cout + output channel
+    int32_t c = CF_K_ONE;              // constant factor (cf_term_const)
+};
+static inline cf_term cf_zero(int c = CF_K_ONE) { cf_term t; t.c = c; return t; }
+static inline cf_term cf_raw(int tensor, int elem) { cf_term t; t.kind = CF_TERM_RAW; t.tensor = tensor; t.elem = elem; return t; }
+static inline cf_term cf_scaled(cf_term t, int c) { t.c = c; return t; }
+
+// tensor ids = positions in the operator's order (torch_ops.tensor_names): per conv unit kernel, bias, gamma, beta, moving_mean,
+// moving_variance; per GRU layer and direction gates kernel, gates bias, candidate kernel, candidate bias; dense kernel, bias
+static inline int cf_tid_conv(int unit, int which) { return 6 * unit + which; }
+static inline int cf_tid_gru(int n_res, int layer, int dir, int which) { return 24 * n_res + 4 * (2 * layer + dir) + which; }
+static inline int cf_tid_dense(int n_res, int n_layers, int which) { return 24 * n_res + 8 * n_layers + which; }
+static inline int cf_n_tensors(int n_res, int n_layers) { return 24 * n_res + 8 * n_layers + 2; }
+
+// y = BN(conv(x)) = conv'(x): W' = W s, b' = b s + beta - mean s
+struct ConvTerms {
+    int k = 0, cin = 0, cout = 0, unit = 0;
+    cf_term w(int tap, int in, int o) const {
+        cf_term t = cf_raw(cf_tid_conv(unit, 0), (tap * cin + in) * cout + o);
+        t.kind = CF_TERM_KERN; t.ch = unit * cout + o;
+        return t;
+    }
+    cf_term b(int o) const { cf_term t; t.kind = CF_TERM_BIAS; t.ch = unit * cout + o; return t; }
+};
+static ConvTerms conv_terms(int k, int cin, int cout, int unit) { ConvTerms f; f.k = k; f.cin = cin; f.cout = cout; f.unit = unit; return f; }
+// conv unit u of the geometry hp (resnet_class.py:44-82: per block shortcut, first, middle (k = 3), last; block 0's first two see the signal)
+static ConvTerms unit_terms(const cf_hparams& hp, int u) {
+    const int C = hp.layer_size_res;
+    return conv_terms(u % 4 == 2 ? 3 : 1, (u < 2) ? 1 : C, C, u);
+}
+
+// one direction of a GRU layer of h units over cin_real inputs (kernel rows [0, cin_real) x, [cin_real, cin_real + h) state)
+struct GruTerms {
+    int t0 = 0, h = 0;                 // tensor id of the gates kernel
+    cf_term gk(int in, int o) const { return cf_raw(t0, in * 2 * h + o); }
+    cf_term gb(int o) const { return cf_raw(t0 + 1, o); }
+    cf_term ck(int in, int o) const { return cf_raw(t0 + 2, in * h + o); }
+    cf_term cb(int o) const { return cf_raw(t0 + 3, o); }
+};
+static GruTerms gru_terms(int t0, int h) { GruTerms g; g.t0 = t0; g.h = h; return g; }
+
+// host evaluation of terms (cf_model_create): tensor pointers of cf_weights, per-channel s and b'
+struct cf_host_params {
+    std::vector<const float*> t;
+    std::vector<double> s, b;
+    float param(const cf_term& x) const { return x.kind == CF_TERM_RAW || x.kind == CF_TERM_KERN ? t[x.tensor][x.elem] : 0.f; }
+    float value(const cf_term& x) const {
+        return cf_term_value(x.kind, param(x), x.kind == CF_TERM_KERN ? s[x.ch] : 0.0, x.kind == CF_TERM_BIAS ? b[x.ch] : 0.0, x.c);
+    }
+    double base(const cf_term& x) const {          // the term without its constant (the bf16x3 packers scale and split it themselves)
+        return x.kind == CF_TERM_RAW ? (double)param(x) : (x.kind == CF_TERM_KERN ? (double)param(x) * s[x.ch] : (x.kind == CF_TERM_BIAS ? b[x.ch] : 0.0));
+    }
+};
+static cf_host_params host_params(const cf_weights* w, const cf_hparams& hp, int cout) {
+    cf_host_params P;
+    P.t.assign((size_t)cf_n_tensors(hp.n_layers_res, hp.n_layers), nullptr);
+    for (int u = 0; u < 4 * hp.n_layers_res; ++u) {
+        const cf_conv_bn& c = w->conv[u];
+        const float* src[6] = {c.kernel, c.bias, c.gamma, c.beta, c.moving_mean, c.moving_variance};
+        for (int i = 0; i < 6; ++i) P.t[cf_tid_conv(u, i)] = src[i];
+        for (int o = 0; o < cout; ++o) {
+            const double s = cf_bn_scale(c.gamma[o], c.moving_variance[o], hp.bn_epsilon);
+            P.s.push_back(s);
+            P.b.push_back(cf_bn_bias(c.bias[o], c.beta[o], c.moving_mean[o], s));
+        }
+    }
+    for (int l = 0; l < hp.n_layers; ++l)
+        for (int d = 0; d < 2; ++d) {
+            const cf_gru_dir& g = w->gru[2 * l + d];
+            const float* src[4] = {g.gates_kernel, g.gates_bias, g.candidate_kernel, g.candidate_bias};
+            for (int i = 0; i < 4; ++i) P.t[cf_tid_gru(hp.n_layers_res, l, d, i)] = src[i];
+        }
+    P.t[cf_tid_dense(hp.n_layers_res, hp.n_layers, 0)] = w->dense_kernel;
+    P.t[cf_tid_dense(hp.n_layers_res, hp.n_layers, 1)] = w->dense_bias;
+    return P;
+}
+struct HostSink {                      // sink that evaluates every term into a host blob
+    const cf_host_params& p;
+    float* out;
+    void operator()(size_t i, const cf_term& t) const { out[i] = p.value(t); }
+};
+
+// [mo][q][r] order == natural order of 16mo+4q+r
+template <class E, class V>
+static void pack_vec(E& e, size_t off, V v) {
+    for (int i = 0; i < CF_C; ++i) e(off + i, v(i));
 }
 
 // 32x32 unit: dst[(ks*64 + lane)*2 + mo] = W[in = frag_feature(ks, lane>>4)][out = 16mo + (lane&15)]
-static void pack_unit(float* dst, const std::vector<double>& w /*[32 in][32 out]*/) {
+template <class E, class W>
+static void pack_unit(E& e, size_t off, W w /*(in < 32, out < 32) -> term*/) {
     for (int ks = 0; ks < 8; ++ks)
         for (int lane = 0; lane < 64; ++lane)
-            for (int mo = 0; mo < 2; ++mo)
-                dst[(ks * 64 + lane) * 2 + mo] = (float)w[frag_feature(ks, lane >> 4) * 32 + 16 * mo + (lane & 15)];
+            for (int mo = 0; mo < 2; ++mo) e(off + (ks * 64 + lane) * 2 + mo, w(frag_feature(ks, lane >> 4), 16 * mo + (lane & 15)));
 }
 
+// the bf16 packers take folded values (double) instead of terms
 struct FoldedConv {
     int k = 0, cin = 0;
     std::vector<double> w;  // [k][cin][32] scaled by BN
     std::vector<double> b;  // [32]
 };
 
-// y = BN(conv(x)) = conv'(x): W' = W*s, b' = b*s + beta - mean*s, s = gamma*rsqrt(var+eps)
 static FoldedConv fold(const cf_conv_bn& c, float eps) {
     FoldedConv f;
     f.k = c.ksize; f.cin = c.cin;
     f.w.resize((size_t)c.ksize * c.cin * CF_C);
     f.b.resize(CF_C);
     for (int o = 0; o < CF_C; ++o) {
-        // same arithmetic as the unfused graph: inv = rsqrt(var + eps) * gamma (fp32 inputs, double math)
-        const double s = (double)c.gamma[o] / std::sqrt((double)c.moving_variance[o] + (double)eps);
-        f.b[o] = (double)c.bias[o] * s + (double)c.beta[o] - (double)c.moving_mean[o] * s;
+        const double s = cf_bn_scale(c.gamma[o], c.moving_variance[o], eps);
+        f.b[o] = cf_bn_bias(c.bias[o], c.beta[o], c.moving_mean[o], s);
         for (int k = 0; k < c.ksize; ++k)
             for (int i = 0; i < c.cin; ++i)
                 f.w[((size_t)k * c.cin + i) * CF_C + o] = (double)c.kernel[((size_t)k * c.cin + i) * CF_C + o] * s;
@@ -1070,26 +1187,30 @@ static std::vector<double> tap(const FoldedConv& f, int k) {
     return std::vector<double>(f.w.begin() + (size_t)k * f.cin * CF_C, f.w.begin() + (size_t)(k + 1) * f.cin * CF_C);
 }
 
-static int pack_res_block(const cf_conv_bn* c4, bool first, float eps, std::vector<float>& out) {
-    out.assign(res_pack_floats(first), 0.f);
-    const FoldedConv sc = fold(c4[0], eps), f1 = fold(c4[1], eps), f3 = fold(c4[2], eps), fl = fold(c4[3], eps);
+// c4: the block's four units (shortcut, first, middle, last); res_pack_floats(first) elements
+template <class E>
+static int pack_res_block(E& e, const ConvTerms* c4, bool first) {
+    const ConvTerms &sc = c4[0], &f1 = c4[1], &f3 = c4[2], &fl = c4[3];
     const int cin = first ? 1 : CF_C;
     if (sc.k != 1 || f1.k != 1 || f3.k != 3 || fl.k != 1 || sc.cin != cin || f1.cin != cin || f3.cin != CF_C || fl.cin != CF_C)
         return fail(CF_ERR_INVALID, "residual block geometry not supported (need k = 1,1,3,1 and 32 channels)");
-    float* vecs = out.data() + res_units(first) * 1024;
+    const size_t vecs = (size_t)res_units(first) * 1024;
+    auto tap_of = [](const ConvTerms& f, int k) { return [&f, k](int in, int o) { return f.w(k, in, o); }; };
+    auto b_of = [](const ConvTerms& f) { return [&f](int o) { return f.b(o); }; };
+    auto w0_of = [](const ConvTerms& f) { return [&f](int o) { return f.w(0, 0, o); }; };
     if (first) {
-        for (int k = 0; k < 3; ++k) pack_unit(out.data() + k * 1024, tap(f3, k));
-        pack_unit(out.data() + 3 * 1024, tap(fl, 0));
-        pack_vec(vecs + 0 * 32, f3.b); pack_vec(vecs + 1 * 32, fl.b);
-        pack_vec(vecs + 2 * 32, sc.w); pack_vec(vecs + 3 * 32, sc.b);
-        pack_vec(vecs + 4 * 32, f1.w); pack_vec(vecs + 5 * 32, f1.b);
+        for (int k = 0; k < 3; ++k) pack_unit(e, (size_t)k * 1024, tap_of(f3, k));
+        pack_unit(e, 3 * 1024, tap_of(fl, 0));
+        pack_vec(e, vecs + 0 * 32, b_of(f3)); pack_vec(e, vecs + 1 * 32, b_of(fl));
+        pack_vec(e, vecs + 2 * 32, w0_of(sc)); pack_vec(e, vecs + 3 * 32, b_of(sc));
+        pack_vec(e, vecs + 4 * 32, w0_of(f1)); pack_vec(e, vecs + 5 * 32, b_of(f1));
     } else {
-        pack_unit(out.data() + 0 * 1024, tap(sc, 0));
-        pack_unit(out.data() + 1 * 1024, tap(f1, 0));
-        for (int k = 0; k < 3; ++k) pack_unit(out.data() + (2 + k) * 1024, tap(f3, k));
-        pack_unit(out.data() + 5 * 1024, tap(fl, 0));
-        pack_vec(vecs + 0 * 32, sc.b); pack_vec(vecs + 1 * 32, f1.b);
-        pack_vec(vecs + 2 * 32, f3.b); pack_vec(vecs + 3 * 32, fl.b);
+        pack_unit(e, 0 * 1024, tap_of(sc, 0));
+        pack_unit(e, 1 * 1024, tap_of(f1, 0));
+        for (int k = 0; k < 3; ++k) pack_unit(e, (size_t)(2 + k) * 1024, tap_of(f3, k));
+        pack_unit(e, 5 * 1024, tap_of(fl, 0));
+        pack_vec(e, vecs + 0 * 32, b_of(sc)); pack_vec(e, vecs + 1 * 32, b_of(f1));
+        pack_vec(e, vecs + 2 * 32, b_of(f3)); pack_vec(e, vecs + 3 * 32, b_of(fl));
     }
     return CF_OK;
 }
@@ -1119,37 +1240,46 @@ static int pack_res_block_bf16(const cf_conv_bn* c4, bool first, float eps, int 
     return CF_OK;
 }
 
-static void pack_gru_dir(const cf_gru_dir& g, int cin, int cin_real, const float* dense_w /*64 floats of this direction or null*/,
-                         float* out) {
+// one direction, gru_pack_floats(cin) elements from `off`; dense_t: tensor id of the dense kernel (-1: zeros), dense_e its first element
+template <class E>
+static void pack_gru_dir(E& e, size_t off, const GruTerms& g, int cin, int cin_real, int dense_t, int dense_e) {
     // cin = padded input width of the kernel instantiation, cin_real = rows of the x part in the checkpoint
-    auto wfull = [&](int in, int o) -> float {   // pre-scaled: the accumulators are exp2 arguments
-        if (in < 0) return 0.f;
-        return o < 2 * CF_H ? (float)(CF_GATE_SCALE * (double)g.gates_kernel[(size_t)in * 2 * CF_H + o])
-                            : (float)(CF_CAND_SCALE * (double)g.candidate_kernel[(size_t)in * CF_H + (o - 2 * CF_H)]);
+    auto wfull = [&](int in, int o) -> cf_term {   // pre-scaled: the accumulators are exp2 arguments
+        if (in < 0) return cf_zero();
+        return o < 2 * CF_H ? cf_scaled(g.gk(in, o), CF_K_GATE) : cf_scaled(g.ck(in, o - 2 * CF_H), CF_K_CAND);
     };
-    float* px = out;
+    const size_t px = off;
     for (int ks = 0; ks < cin / 4; ++ks)
         for (int gq = 0; gq < 3; ++gq)
             for (int lane = 0; lane < 64; ++lane)
                 for (int j = 0; j < 4; ++j)
-                    px[((ks * 3 + gq) * 64 + lane) * 4 + j] =
-                        wfull(frag_feature(ks, lane >> 4) < cin_real ? frag_feature(ks, lane >> 4) : -1, 16 * (4 * gq + j) + (lane & 15));
-    float* pg = out + gru_x_floats(cin);
+                    e(px + ((ks * 3 + gq) * 64 + lane) * 4 + j,
+                      wfull(frag_feature(ks, lane >> 4) < cin_real ? frag_feature(ks, lane >> 4) : -1, 16 * (4 * gq + j) + (lane & 15)));
+    const size_t pg = off + gru_x_floats(cin);
     for (int ks = 0; ks < 16; ++ks)
         for (int gq = 0; gq < 2; ++gq)
             for (int lane = 0; lane < 64; ++lane)
                 for (int j = 0; j < 4; ++j)
-                    pg[((ks * 2 + gq) * 64 + lane) * 4 + j] = wfull(cin_real + frag_feature(ks, lane >> 4), 16 * (4 * gq + j) + (lane & 15));
-    float* pc = pg + gru_hg_floats();
+                    e(pg + ((ks * 2 + gq) * 64 + lane) * 4 + j, wfull(cin_real + frag_feature(ks, lane >> 4), 16 * (4 * gq + j) + (lane & 15)));
+    const size_t pc = pg + gru_hg_floats();
     for (int ks = 0; ks < 16; ++ks)
         for (int lane = 0; lane < 64; ++lane)
             for (int j = 0; j < 4; ++j)
-                pc[(ks * 64 + lane) * 4 + j] = wfull(cin_real + frag_feature(ks, lane >> 4), 2 * CF_H + 16 * j + (lane & 15));
-    float* pb = out + gru_bias_off(cin);
-    for (int i = 0; i < 2 * CF_H; ++i) pb[i] = (float)(CF_GATE_SCALE * (double)g.gates_bias[i]);
-    for (int i = 0; i < CF_H; ++i) pb[2 * CF_H + i] = (float)(CF_CAND_SCALE * (double)g.candidate_bias[i]);
-    float* pd = out + gru_dense_off(cin);
-    for (int i = 0; i < CF_H; ++i) pd[i] = dense_w ? dense_w[i] : 0.f;
+                e(pc + (ks * 64 + lane) * 4 + j, wfull(cin_real + frag_feature(ks, lane >> 4), 2 * CF_H + 16 * j + (lane & 15)));
+    const size_t pb = off + gru_bias_off(cin);
+    for (int i = 0; i < 2 * CF_H; ++i) e(pb + i, cf_scaled(g.gb(i), CF_K_GATE));
+    for (int i = 0; i < CF_H; ++i) e(pb + 2 * CF_H + i, cf_scaled(g.cb(i), CF_K_CAND));
+    const size_t pd = off + gru_dense_off(cin);
+    for (int i = 0; i < CF_H; ++i) e(pd + i, dense_t >= 0 ? cf_raw(dense_t, dense_e + i) : cf_zero());
+}
+
+// the same from host arrays (cf_gru_pack_map's index-encoded weights)
+static void pack_gru_dir(const cf_gru_dir& g, int cin, int cin_real, const float* dense_w /*64 floats of this direction or null*/,
+                         float* out) {
+    cf_host_params P;
+    P.t = {g.gates_kernel, g.gates_bias, g.candidate_kernel, g.candidate_bias, dense_w};
+    HostSink e{P, out};
+    pack_gru_dir(e, 0, gru_terms(0, CF_H), cin, cin_real, dense_w ? 4 : -1, 0);
 }
 
 // ---- model lifetime ----------------------------------------------------------------------
@@ -1178,6 +1308,8 @@ extern "C" void cf_model_destroy(cf_model* m) {
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
     gen_destroy(m->gen);
+    pm_destroy(m->pmap);
+    if (m->d_dense_bias) (void)hipFree(m->d_dense_bias);
     if (m->d_xp) (void)hipFree(m->d_xp);
     if (m->d_host_x) (void)hipFree(m->d_host_x);
     if (m->h_err) (void)hipHostFree(m->h_err);
@@ -1212,18 +1344,26 @@ extern "C" int cf_model_create(const cf_weights* w, const cf_hparams* hp, int de
     m->np = hp->precision == CF_PREC_FP32 ? 0 : (hp->precision == CF_PREC_BF16X3 ? 2 : 1);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) m->n_cu = prop.multiProcessorCount;
+    {
+        hipError_t e = hipMalloc((void**)&m->d_dense_bias, sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(m->d_dense_bias, w->dense_bias, sizeof(float), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { cf_model_destroy(m); return fail(CF_ERR_HIP, std::string("dense bias upload: ") + hipGetErrorString(e)); }
+    }
     if (generic) {
-        m->dense_bias = w->dense_bias[0];
         const int grc = gen_build(m, w);
         if (grc != CF_OK) { cf_model_destroy(m); return grc; }
         *out = m;
         return CF_OK;
     }
     int rc = CF_OK;
+    const cf_host_params P = host_params(w, *hp, CF_C);
     // residual blocks
     for (int b = 0; b < hp->n_layers_res && rc == CF_OK; ++b) {
-        std::vector<float> blob;
-        rc = pack_res_block(w->conv + 4 * b, b == 0, hp->bn_epsilon, blob);
+        std::vector<float> blob(res_pack_floats(b == 0), 0.f);
+        ConvTerms c4[4];
+        for (int u = 0; u < 4; ++u) c4[u] = conv_terms(w->conv[4 * b + u].ksize, w->conv[4 * b + u].cin, CF_C, 4 * b + u);
+        HostSink e{P, blob.data()};
+        rc = pack_res_block(e, c4, b == 0);
         if (rc == CF_OK) { float* d = nullptr; rc = upload(blob, &d); m->d_res.push_back(d); }
         if (rc == CF_OK && m->np > 0) {
             std::vector<char> bblob;
@@ -1244,9 +1384,10 @@ extern "C" int cf_model_create(const cf_weights* w, const cf_hparams* hp, int de
         if (w->gru[2 * l].cin != cin_real || w->gru[2 * l + 1].cin != cin_real) { rc = fail(CF_ERR_INVALID, "GRU layer input width mismatch"); break; }
         const bool last = l == hp->n_layers - 1;
         std::vector<float> blob((size_t)2 * gru_pack_floats(cin));
+        HostSink e{P, blob.data()};
         for (int d = 0; d < 2; ++d)
-            pack_gru_dir(w->gru[2 * l + d], cin, cin_real, last ? w->dense_kernel + d * CF_H : nullptr,
-                         blob.data() + (size_t)d * gru_pack_floats(cin));
+            pack_gru_dir(e, (size_t)d * gru_pack_floats(cin), gru_terms(cf_tid_gru(hp->n_layers_res, l, d, 0), CF_H), cin, cin_real,
+                         last ? cf_tid_dense(hp->n_layers_res, hp->n_layers, 0) : -1, d * CF_H);
         float* dptr = nullptr;
         rc = upload(blob, &dptr);
         m->d_gru.push_back(dptr);
@@ -1263,7 +1404,6 @@ extern "C" int cf_model_create(const cf_weights* w, const cf_hparams* hp, int de
             m->d_gru_b.push_back(bptr);
         }
     }
-    m->dense_bias = w->dense_bias[0];
     // workspace
     if (rc == CF_OK) {
         int64_t cap = hp->max_windows_per_pass > 0 ? hp->max_windows_per_pass : 32768;
@@ -1498,6 +1638,7 @@ static int launch_gru_bf16_layer(cf_model* m, int l, bool last, const float* cur
 
 // fuse_layers = auto: the dynamically scheduled single launch pays from ~6 full-chip rounds of 8-tile groups per pass
 #include "generic_host.hpp"
+#include "params_dev.hpp"   // cf_model_param_floats / cf_model_load_params: the packers' terms as a device gather map
 
 static int cf_fuse_min_groups(int n_cu) { return 6 * std::max(1, n_cu / 2); }
 
@@ -1664,7 +1805,7 @@ static int run_pass(cf_model* m, cf_model::Slot& sl, const float* x, int64_t n_w
     if ((rc = prof_begin(m, SLOT_HEAD, s, &pi)) != CF_OK) return rc;
     const int64_t total = n_windows * CF_T;
     const int raw_partials = (m->np == 0 && !fuse_now && use_coop(m, n_tiles)) ? 1 : 0;     // what the last biGRU launch left in d_p
-    hipLaunchKernelGGL(head_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sl.d_p, m->dense_bias, probs, logits, n_windows,
+    hipLaunchKernelGGL(head_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sl.d_p, m->d_dense_bias, probs, logits, n_windows,
                        m->np > 0 ? n_tiles32 : n_tiles, m->np > 0 ? 5 : 4, raw_partials);
     HIP_TRY(hipGetLastError());
     if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;

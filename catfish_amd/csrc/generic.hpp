@@ -779,9 +779,10 @@ __global__ __launch_bounds__(512) void gen_gru_bwd_kernel(const f32x4* __restric
 
 // ---- dense 2H -> 1 + sigmoid (rnn_class.py:178-183, :84): one wave per (tile, position) ------------------------------------------
 __global__ __launch_bounds__(256) void gen_head_kernel(const f32x4* __restrict__ Y /*[tiles][35][F16][64]*/, const f32x4* __restrict__ dw /*[F16][64]*/,
-                                                       float bias, float* __restrict__ probs, float* __restrict__ logits, int64_t n_windows,
-                                                       int n_tiles, int F16) {
+                                                       const float* __restrict__ dense_bias, float* __restrict__ probs, float* __restrict__ logits,
+                                                       int64_t n_windows, int n_tiles, int F16) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float bias = dense_bias[0];
     const int64_t n_tasks = (int64_t)n_tiles * CF_T;
     for (int64_t task = (int64_t)blockIdx.x * 4 + wave; task < n_tasks; task += (int64_t)gridDim.x * 4) {
         const int64_t tile = task / CF_T;
@@ -824,18 +825,6 @@ struct cf_generic {
     size_t gru_lds = 0;
 };
 
-// W(in, out) accessor -> A pack; inputs in >= k_real are zero padding
-template <typename F>
-static void gen_pack_a(std::vector<float>& dst, size_t off, F w, int k_real, int K16, int M16, double scale) {
-    for (int mo = 0; mo < M16; ++mo)
-        for (int kb = 0; kb < K16; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int i = 0; i < 4; ++i) {
-                    const int in = 16 * kb + 4 * (lane >> 4) + i, out = 16 * mo + (lane & 15);
-                    dst[off + (((size_t)mo * K16 + kb) * 64 + lane) * 4 + i] = in < k_real ? (float)(w(in, out) * scale) : 0.f;
-                }
-}
-
 // bf16x3 A pack (gen_dot_x3): K16 (a multiple of 4, padding included) -> per (mo, pair p) w_hi [lane][8] then w_lo [lane][8] in
 // the f32x4 slots of blocks 2p, 2p + 1; element j of lane l is W[in = 16 (2p + (j >> 2)) + 4 (l >> 4) + (j & 3)][out = 16 mo + (l & 15)]
 static uint16_t gen_bf16_bits(float v) {                    // round to nearest even, as the device's v_cvt_pk_bf16_f32
@@ -864,10 +853,3 @@ static void gen_pack_a_x3(std::vector<float>& dst, size_t off, F w, int K16, int
         }
 }
 
-// per-output vector (bias, dense weights) in accumulator order: [mo][lane][j] = v[16 mo + 4 (lane >> 4) + j]
-template <typename F>
-static void gen_pack_v(std::vector<float>& dst, size_t off, F v, int M16, double scale) {
-    for (int mo = 0; mo < M16; ++mo)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int j = 0; j < 4; ++j) dst[off + ((size_t)mo * 64 + lane) * 4 + j] = (float)(v(16 * mo + 4 * (lane >> 4) + j) * scale);
-}

@@ -2,6 +2,27 @@
 // Included by catfish_hip.hip after cf_model, fail(), HIP_TRY, prof_begin / prof_end.
 #pragma once
 
+// W(in, out) accessor (a term, catfish_hip.hip "weight packing") -> A pack emitted into sink e with constant c; inputs in >= k_real
+// are zero padding
+template <typename E, typename F>
+static void gen_pack_a(E& e, size_t off, F w, int k_real, int K16, int M16, int c) {
+    for (int mo = 0; mo < M16; ++mo)
+        for (int kb = 0; kb < K16; ++kb)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int i = 0; i < 4; ++i) {
+                    const int in = 16 * kb + 4 * (lane >> 4) + i, out = 16 * mo + (lane & 15);
+                    e(off + (((size_t)mo * K16 + kb) * 64 + lane) * 4 + i, in < k_real ? cf_scaled(w(in, out), c) : cf_zero());
+                }
+}
+
+// per-output vector (bias, dense weights; v(o) a term) in accumulator order: [mo][lane][j] = v[16 mo + 4 (lane >> 4) + j] x constant c
+template <typename E, typename F>
+static void gen_pack_v(E& e, size_t off, F v, int M16, int c) {
+    for (int mo = 0; mo < M16; ++mo)
+        for (int lane = 0; lane < 64; ++lane)
+            for (int j = 0; j < 4; ++j) e(off + ((size_t)mo * 64 + lane) * 4 + j, cf_scaled(v(16 * mo + 4 * (lane >> 4) + j), c));
+}
+
 static bool gen_forced() { return cf_knob("CATFISH_GENERIC") && atoi(cf_knob("CATFISH_GENERIC")) != 0; }     // A/B and test knob, read per model
 
 // (the tuned kernels have no bf16x3 form of the plain RNN type: it runs here in that precision)
@@ -25,39 +46,73 @@ static int gen_upload(cf_generic* g, const std::vector<float>& host, f32x4** dev
     return CF_OK;
 }
 
-// y = BN(conv(x)) = conv'(x), any channel count (same arithmetic as fold(): double math on the fp32 inputs)
-struct GenConv {
-    int k = 0, cin = 0, cout = 0;
-    std::vector<double> w;      // [k][cin][cout]
-    std::vector<double> b;      // [cout]
-};
+// The fp32 packs of the any-size path, one per device buffer (the bf16x3 weight matrices: gen_pack_a_x3 on host values).
+// cf_model_create evaluates them into host blobs, cf_model_load_params records them as its gather map (params_dev.hpp).
+template <class E>
+static void gen_pack_first(E& e, const ConvTerms& sc, const ConvTerms& f1, int C16) {      // block 0's cin-1 units: [w_sc, b_sc, w_1, b_1]
+    gen_pack_v(e, (size_t)0 * C16 * 256, [&](int o) { return sc.w(0, 0, o); }, C16, CF_K_ONE);
+    gen_pack_v(e, (size_t)1 * C16 * 256, [&](int o) { return sc.b(o); }, C16, CF_K_ONE);
+    gen_pack_v(e, (size_t)2 * C16 * 256, [&](int o) { return f1.w(0, 0, o); }, C16, CF_K_ONE);
+    gen_pack_v(e, (size_t)3 * C16 * 256, [&](int o) { return f1.b(o); }, C16, CF_K_ONE);
+}
+template <class E>
+static void gen_pack_conv_w(E& e, const ConvTerms& f) {                                    // [taps][Co16][Ki16][64] f32x4
+    const int K16 = f.cin / 16, M16 = f.cout / 16;
+    for (int tap = 0; tap < f.k; ++tap)
+        gen_pack_a(e, (size_t)tap * M16 * K16 * 256, [&](int in, int out) { return f.w(tap, in, out); }, f.cin, K16, M16, CF_K_ONE);
+}
+template <class E>
+static void gen_pack_conv_b(E& e, const ConvTerms& f) { gen_pack_v(e, 0, [&](int o) { return f.b(o); }, f.cout / 16, CF_K_ONE); }
 
-static GenConv gen_fold(const cf_conv_bn& c, float eps, int cout) {
-    GenConv f;
-    f.k = c.ksize; f.cin = c.cin; f.cout = cout;
-    f.w.resize((size_t)c.ksize * c.cin * cout);
-    f.b.resize(cout);
-    for (int o = 0; o < cout; ++o) {
-        const double s = (double)c.gamma[o] / std::sqrt((double)c.moving_variance[o] + (double)eps);
-        f.b[o] = (double)c.bias[o] * s + (double)c.beta[o] - (double)c.moving_mean[o] * s;
-        for (int k = 0; k < c.ksize; ++k)
-            for (int i = 0; i < c.cin; ++i)
-                f.w[((size_t)k * c.cin + i) * cout + o] = (double)c.kernel[((size_t)k * c.cin + i) * cout + o] * s;
+// biGRU weight of gate 0 = r, 1 = u (gates kernel columns [0, H) and [H, 2H)), 2 = candidate over K = [x blocks (kbx_w) | h blocks]
+static cf_term gen_gru_w(const GruTerms& g, int gate, int in, int out, int cin_real, int kbx_w) {
+    const int H = g.h, col0 = gate == 1 ? H : 0;
+    auto k = [&](int row) { return gate < 2 ? g.gk(row, col0 + out) : g.ck(row, out); };
+    if (in < 16 * kbx_w) return in < cin_real ? k(in) : cf_zero();
+    return in - 16 * kbx_w < H ? k(cin_real + in - 16 * kbx_w) : cf_zero();
+}
+static int gen_gru_c(int gate) { return gate < 2 ? CF_K_GATE : CF_K_CAND; }
+template <class E>
+static void gen_pack_gru_w(E& e, const cf_hparams& hp, int l, int cin_real, int H16) {      // [2 dirs][3 gates][H16][KB][64] (fp32)
+    const int kbx = (cin_real + 15) / 16, KB = kbx + H16;
+    const size_t mat = (size_t)H16 * KB * 256;
+    for (int d = 0; d < 2; ++d) {
+        const GruTerms g = gru_terms(cf_tid_gru(hp.n_layers_res, l, d, 0), hp.layer_size);
+        for (int gate = 0; gate < 3; ++gate)
+            gen_pack_a(e, (size_t)(d * 3 + gate) * mat, [&](int in, int out) { return gen_gru_w(g, gate, in, out, cin_real, kbx); }, 16 * KB, KB,
+                       H16, gen_gru_c(gate));
     }
-    return f;
+}
+template <class E>
+static void gen_pack_gru_b(E& e, const cf_hparams& hp, int l, int H16) {                   // [2][3][H16][64]
+    const int H = hp.layer_size;
+    for (int d = 0; d < 2; ++d) {
+        const GruTerms g = gru_terms(cf_tid_gru(hp.n_layers_res, l, d, 0), H);
+        for (int gate = 0; gate < 3; ++gate)
+            gen_pack_v(e, (size_t)(d * 3 + gate) * H16 * 256, [&](int o) { return gate < 2 ? g.gb((gate == 1 ? H : 0) + o) : g.cb(o); }, H16,
+                       gen_gru_c(gate));
+    }
+}
+template <class E>
+static void gen_pack_gru_tuned(E& e, const cf_hparams& hp, int l, int cin_real) {           // [2][gru_pack_floats(cin_real)]
+    for (int d = 0; d < 2; ++d)
+        pack_gru_dir(e, (size_t)d * gru_pack_floats(cin_real), gru_terms(cf_tid_gru(hp.n_layers_res, l, d, 0), CF_H), cin_real, cin_real, -1, 0);
+}
+template <class E>
+static void gen_pack_dense(E& e, const cf_hparams& hp, int H16) {
+    const int t = cf_tid_dense(hp.n_layers_res, hp.n_layers, 0);
+    gen_pack_v(e, 0, [&](int f) { return cf_raw(t, f); }, 2 * H16, CF_K_ONE);
+}
+// a 64-unit layer with 16, 32 or 128 inputs runs on the LDS-resident tuned kernel (see gen_build)
+static bool gen_layer_tuned(const cf_generic* g, const cf_hparams& hp, int cin_real) {
+    return hp.layer_size == CF_H && !gen_forced() && !g->x3 && (cin_real == 16 || cin_real == 32 || cin_real == 128);
 }
 
-static int gen_pack_conv(cf_generic* g, const GenConv& f, f32x4** w_dev, f32x4** b_dev) {
-    const int K16 = g->x3 ? gen_x3_pad(f.cin / 16) : f.cin / 16, M16 = f.cout / 16;
-    std::vector<float> wp((size_t)f.k * M16 * K16 * 256), bp((size_t)M16 * 256);
-    for (int tap = 0; tap < f.k; ++tap) {
-        auto w = [&](int in, int out) { return in < f.cin ? f.w[((size_t)tap * f.cin + in) * f.cout + out] : 0.0; };
-        if (g->x3) gen_pack_a_x3(wp, (size_t)tap * M16 * K16 * 256, w, K16, M16, 1.0);
-        else gen_pack_a(wp, (size_t)tap * M16 * K16 * 256, w, f.cin, K16, M16, 1.0);
-    }
-    gen_pack_v(bp, 0, [&](int o) { return f.b[o]; }, M16, 1.0);
-    int rc = gen_upload(g, wp, w_dev);
-    return rc != CF_OK ? rc : gen_upload(g, bp, b_dev);
+static int gen_upload_terms(cf_generic* g, size_t n, const cf_host_params& P, f32x4** dev, const std::function<void(HostSink&)>& pack) {
+    std::vector<float> host(n, 0.f);
+    HostSink e{P, host.data()};
+    pack(e);
+    return gen_upload(g, host, dev);
 }
 
 static int gen_build(cf_model* m, const cf_weights* w) {
@@ -75,6 +130,7 @@ static int gen_build(cf_model* m, const cf_weights* w) {
     g->H16 = H / 16;
     g->C16 = C / 16;
     int rc = CF_OK;
+    const cf_host_params P = host_params(w, hp, C);
     // residual blocks (resnet_class.py:44-82): conv order per block = shortcut, first, middle (k = 3), last
     for (int b = 0; b < hp.n_layers_res && rc == CF_OK; ++b) {
         const cf_conv_bn* c4 = w->conv + 4 * b;
@@ -82,22 +138,30 @@ static int gen_build(cf_model* m, const cf_weights* w) {
         if (c4[0].ksize != 1 || c4[1].ksize != 1 || c4[2].ksize != 3 || c4[3].ksize != 1 || c4[0].cin != cin || c4[1].cin != cin ||
             c4[2].cin != C || c4[3].cin != C)
             return fail(CF_ERR_INVALID, "residual block geometry not supported (need k = 1,1,3,1)");
-        const GenConv sc = gen_fold(c4[0], hp.bn_epsilon, C), f1 = gen_fold(c4[1], hp.bn_epsilon, C);
-        const GenConv f3 = gen_fold(c4[2], hp.bn_epsilon, C), fl = gen_fold(c4[3], hp.bn_epsilon, C);
+        const ConvTerms sc = unit_terms(hp, 4 * b), f1 = unit_terms(hp, 4 * b + 1), f3 = unit_terms(hp, 4 * b + 2), fl = unit_terms(hp, 4 * b + 3);
+        auto conv = [&](const ConvTerms& f, f32x4** w_dev, f32x4** b_dev) {
+            int r;
+            if (g->x3) {
+                const int K16 = gen_x3_pad(f.cin / 16), M16 = f.cout / 16;
+                std::vector<float> wp((size_t)f.k * M16 * K16 * 256);
+                for (int tap = 0; tap < f.k; ++tap)
+                    gen_pack_a_x3(wp, (size_t)tap * M16 * K16 * 256, [&](int in, int out) { return in < f.cin ? P.base(f.w(tap, in, out)) : 0.0; },
+                                  K16, M16, 1.0);
+                r = gen_upload(g, wp, w_dev);
+            } else {
+                r = gen_upload_terms(g, (size_t)f.k * (f.cout / 16) * (f.cin / 16) * 256, P, w_dev, [&](HostSink& e) { gen_pack_conv_w(e, f); });
+            }
+            return r != CF_OK ? r : gen_upload_terms(g, (size_t)(f.cout / 16) * 256, P, b_dev, [&](HostSink& e) { gen_pack_conv_b(e, f); });
+        };
         cf_generic::Block blk;
         if (b == 0) {
-            std::vector<float> v((size_t)4 * g->C16 * 256);
-            gen_pack_v(v, (size_t)0 * g->C16 * 256, [&](int o) { return sc.w[o]; }, g->C16, 1.0);
-            gen_pack_v(v, (size_t)1 * g->C16 * 256, [&](int o) { return sc.b[o]; }, g->C16, 1.0);
-            gen_pack_v(v, (size_t)2 * g->C16 * 256, [&](int o) { return f1.w[o]; }, g->C16, 1.0);
-            gen_pack_v(v, (size_t)3 * g->C16 * 256, [&](int o) { return f1.b[o]; }, g->C16, 1.0);
-            rc = gen_upload(g, v, &blk.first);
+            rc = gen_upload_terms(g, (size_t)4 * g->C16 * 256, P, &blk.first, [&](HostSink& e) { gen_pack_first(e, sc, f1, g->C16); });
         } else {
-            rc = gen_pack_conv(g, sc, &blk.w_sc, &blk.b_sc);
-            if (rc == CF_OK) rc = gen_pack_conv(g, f1, &blk.w_1, &blk.b_1);
+            rc = conv(sc, &blk.w_sc, &blk.b_sc);
+            if (rc == CF_OK) rc = conv(f1, &blk.w_1, &blk.b_1);
         }
-        if (rc == CF_OK) rc = gen_pack_conv(g, f3, &blk.w_3, &blk.b_3);
-        if (rc == CF_OK) rc = gen_pack_conv(g, fl, &blk.w_l, &blk.b_l);
+        if (rc == CF_OK) rc = conv(f3, &blk.w_3, &blk.b_3);
+        if (rc == CF_OK) rc = conv(fl, &blk.w_l, &blk.b_l);
         g->blocks.push_back(blk);
     }
     // biGRU layers: per direction three matrices over K = [x blocks | h blocks]
@@ -107,46 +171,34 @@ static int gen_build(cf_model* m, const cf_weights* w) {
         const int kbx_w = g->x3 ? gen_x3_pad(kbx) : kbx, KB = kbx_w + (g->x3 ? gen_x3_pad(g->H16) : g->H16);    // weight blocks: [x | h]
         if (w->gru[2 * l].cin != cin_real || w->gru[2 * l + 1].cin != cin_real) return fail(CF_ERR_INVALID, "GRU layer input width mismatch");
         const size_t mat = (size_t)g->H16 * KB * 256, vec = (size_t)g->H16 * 256;
-        std::vector<float> wp(2 * 3 * mat), bp(2 * 3 * vec);
-        for (int d = 0; d < 2; ++d) {
-            const cf_gru_dir& gd = w->gru[2 * l + d];
-            for (int gate = 0; gate < 3; ++gate) {                          // 0 = r, 1 = u (gates/kernel columns [0,H) and [H,2H)), 2 = candidate
-                const float* kern = gate < 2 ? gd.gates_kernel : gd.candidate_kernel;
-                const float* bias = gate < 2 ? gd.gates_bias : gd.candidate_bias;
-                const int ld = gate < 2 ? 2 * H : H, col0 = gate == 1 ? H : 0;
-                const double scale = gate < 2 ? CF_GATE_SCALE : CF_CAND_SCALE;
-                auto acc = [&](int in, int out) -> double {
-                    if (in < 16 * kbx_w) return in < cin_real ? (double)kern[(size_t)in * ld + col0 + out] : 0.0;
-                    return in - 16 * kbx_w < H ? (double)kern[(size_t)(cin_real + in - 16 * kbx_w) * ld + col0 + out] : 0.0;
-                };
-                if (g->x3) gen_pack_a_x3(wp, (size_t)(d * 3 + gate) * mat, acc, KB, g->H16, scale);
-                else gen_pack_a(wp, (size_t)(d * 3 + gate) * mat, acc, 16 * KB, KB, g->H16, scale);
-                gen_pack_v(bp, (size_t)(d * 3 + gate) * vec, [&](int o) { return (double)bias[col0 + o]; }, g->H16, scale);
-            }
-        }
         cf_generic::Layer L;
         L.kbx = kbx;
-        rc = gen_upload(g, wp, &L.w);
-        if (rc == CF_OK) rc = gen_upload(g, bp, &L.b);
+        if (g->x3) {
+            std::vector<float> wp(2 * 3 * mat);
+            for (int d = 0; d < 2; ++d) {
+                const GruTerms gd = gru_terms(cf_tid_gru(hp.n_layers_res, l, d, 0), H);
+                for (int gate = 0; gate < 3; ++gate)
+                    gen_pack_a_x3(wp, (size_t)(d * 3 + gate) * mat, [&](int in, int out) { return P.base(gen_gru_w(gd, gate, in, out, cin_real, kbx_w)); },
+                                  KB, g->H16, cf_term_const(gen_gru_c(gate)));
+            }
+            rc = gen_upload(g, wp, &L.w);
+        } else {
+            rc = gen_upload_terms(g, 2 * 3 * mat, P, &L.w, [&](HostSink& e) { gen_pack_gru_w(e, hp, l, cin_real, g->H16); });
+        }
+        if (rc == CF_OK) rc = gen_upload_terms(g, 2 * 3 * vec, P, &L.b, [&](HostSink& e) { gen_pack_gru_b(e, hp, l, g->H16); });
         // 64 units with 16, 32 or 128 input features is what gru_layer_kernel<CIN, false> (weights in LDS, state in registers,
         // 0.78-0.83 of the fp32-MFMA peak) is built for: such layers of an otherwise odd geometry (say 64 units behind 128
         // conv channels) run on it.  Not when CATFISH_GENERIC forces this path: that knob exists to exercise the kernels here.
         // Not in bf16x3 either: the tuned bf16x3 kernels keep their activations in another layout.
-        if (rc == CF_OK && H == CF_H && !gen_forced() && !g->x3 && (cin_real == 16 || cin_real == 32 || cin_real == 128)) {
-            std::vector<float> blob((size_t)2 * gru_pack_floats(cin_real));
-            for (int d = 0; d < 2; ++d) pack_gru_dir(w->gru[2 * l + d], cin_real, cin_real, nullptr, blob.data() + (size_t)d * gru_pack_floats(cin_real));
+        if (rc == CF_OK && gen_layer_tuned(g, hp, cin_real)) {
             f32x4* dev = nullptr;
-            rc = gen_upload(g, blob, &dev);
+            rc = gen_upload_terms(g, (size_t)2 * gru_pack_floats(cin_real), P, &dev, [&](HostSink& e) { gen_pack_gru_tuned(e, hp, l, cin_real); });
             L.tuned = reinterpret_cast<float*>(dev);
             L.tuned_cin = cin_real;
         }
         g->layers.push_back(L);
     }
-    if (rc == CF_OK) {
-        std::vector<float> dv((size_t)2 * g->H16 * 256);
-        gen_pack_v(dv, 0, [&](int f) { return (double)w->dense_kernel[f]; }, 2 * g->H16, 1.0);
-        rc = gen_upload(g, dv, &g->dense);
-    }
+    if (rc == CF_OK) rc = gen_upload_terms(g, (size_t)2 * g->H16 * 256, P, &g->dense, [&](HostSink& e) { gen_pack_dense(e, hp, g->H16); });
     if (rc != CF_OK) return rc;
     // workspace: four conv buffers (input / shortcut / two intermediates), two biGRU output buffers
     int64_t cap = hp.max_windows_per_pass > 0 ? hp.max_windows_per_pass : 32768;
@@ -271,7 +323,7 @@ static int gen_run_pass(cf_model* m, const float* x, int64_t n_windows, float* p
         cur = G[l & 1];
     }
     if ((rc = prof_begin(m, SLOT_HEAD, s, &pi)) != CF_OK) return rc;
-    hipLaunchKernelGGL(gen_head_kernel, dim3(task_grid), dim3(256), 0, s, cur, g->dense, m->dense_bias, probs, logits, n_windows, n_tiles, 2 * g->H16);
+    hipLaunchKernelGGL(gen_head_kernel, dim3(task_grid), dim3(256), 0, s, cur, g->dense, m->d_dense_bias, probs, logits, n_windows, n_tiles, 2 * g->H16);
     HIP_TRY(hipGetLastError());
     return prof_end(m, s, pi);
 }

@@ -66,6 +66,32 @@ class HipEngine(object):
     def workspace_bytes(self):
         return int(self._lib.cf_workspace_bytes(self._handle))
 
+    # ------------------------------------------------------------------ device weights
+    def param_count(self):
+        """Values of the flat parameter vector of this engine's geometry (``cf_model_param_floats``): the checkpoint's inference
+        tensors in ``torch_ops.tensor_names`` order, flattened -- ``pack_weights(...)`` without its header."""
+        if getattr(self, "_param_count", None) is None:
+            n = C.c_int64()
+            N.check(self._lib.cf_model_param_floats(self._handle, C.byref(n)))
+            self._param_count = int(n.value)
+        return self._param_count
+
+    def load_params_device(self, params, stream=None):
+        """Replace the engine's weights by ``params`` (contiguous float32 CUDA tensor of ``param_count()`` values on the engine's
+        device), folded and re-tiled on the device (``cf_model_load_params``), asynchronous on ``stream`` (default: the current
+        stream).  Afterwards the engine computes exactly what ``HipEngine`` built from the same values computes.  The first call
+        builds the gather map (host work, one upload); later calls only launch.  fp32 engines only: ValueError otherwise."""
+        import torch
+        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or not params.is_cuda:
+            raise ValueError("params must be a float32 CUDA tensor")
+        if params.device.index != self.device:
+            raise ValueError("params live on cuda:%s, model on cuda:%d" % (params.device.index, self.device))
+        if not params.is_contiguous() or params.numel() != self.param_count():
+            raise ValueError("params must be a contiguous tensor of %d values, got %d" % (self.param_count(), params.numel()))
+        if stream is None:
+            stream = torch.cuda.current_stream(params.device)
+        N.check(self._lib.cf_model_load_params(self._handle, C.c_void_p(params.data_ptr()), C.c_void_p(stream.cuda_stream)))
+
     # ------------------------------------------------------------------ inference
     @staticmethod
     def _check_windows(shape):

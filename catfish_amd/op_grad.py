@@ -12,7 +12,8 @@ With only ``x`` requiring grad no weight-gradient reduction is launched (cf_gen_
 nothing synchronises; the weight gradient ends in the one device-to-host copy of the flat gradient.
 
 The operator's packed tensor is, after its 8-value header, exactly ``flat_layout``'s buffer (``tensor_names`` order), so the device
-parameters are one upload of ``packed[HEADER:]``.  Windows are padded to a multiple of 16 and processed in slabs of at most
+parameters are one upload of ``packed[HEADER:]``.  ``resnetrnn_forward_params`` passes that buffer itself, on the device: its
+backward copies it into the state (``set_params``, stream-ordered) and returns the weight gradient on the device.  Windows are padded to a multiple of 16 and processed in slabs of at most
 ``BACKWARD_MAX_WINDOWS`` (None: as many as fit ``SLAB_BUDGET_BYTES`` of stash and workspace); the weight gradients of the slabs are
 summed in slab order, so a call gives bit-identical gradients every time.
 """
@@ -32,7 +33,10 @@ SLAB_BUDGET_BYTES = 512 << 20        # stash + workspace of one slab
 class OpGrad(object):
     """Per-engine backward state: device flat parameters, the GRU packs of ``flat_pack_map`` and the slab buffers."""
 
-    def __init__(self, engine, packed, header):
+    def __init__(self, engine, packed=None, header=0, keep_buffers=False):
+        """``packed``: the parameters (``header`` values, then the flat buffer) on the host or the device; None = set them with
+        ``set_params`` before each backward.  ``keep_buffers``: never free a slab buffer set when a larger call needs a new one
+        (a captured CUDA graph may still point at it)."""
         import torch
         self.torch = torch
         self.lib, self.handle = engine._lib, engine._handle
@@ -40,14 +44,24 @@ class OpGrad(object):
         self.h, self.n_layers, self.n_blocks = engine.layer_size, engine.n_layers, engine.n_layers_res
         self.c = engine.layer_size_res if self.n_blocks > 0 else 0
         self.entries, self.units, self.layers, self.head_off, self.zero_off = flat_layout(self.h, self.c, self.n_layers, self.n_blocks)
-        if int(packed.numel()) != header + self.zero_off:
-            raise ValueError("packed_weights has %d values, the engine's geometry needs %d" % (packed.numel(), header + self.zero_off))
         self.header = header
         self.pflat = torch.zeros(self.zero_off + 1, dtype=torch.float32, device=self.dev)
-        self.pflat[:self.zero_off].copy_(packed.detach()[header:])
         idx, scale, self.per_layer = flat_pack_map(self.h, self.layers, self.zero_off)
-        self.gru_packed = self.pflat[torch.from_numpy(idx).to(self.dev)] * torch.from_numpy(scale).to(self.dev)
+        self._idx, self._scale = torch.from_numpy(idx).to(self.dev), torch.from_numpy(scale).to(self.dev)
+        self.gru_packed = torch.empty(idx.shape[0], dtype=torch.float32, device=self.dev)
         self._bufs = None
+        self._kept = [] if keep_buffers else None
+        if packed is not None:
+            if int(packed.numel()) != header + self.zero_off:
+                raise ValueError("packed_weights has %d values, the engine's geometry needs %d" % (packed.numel(), header + self.zero_off))
+            self.set_params(packed.detach()[header:])
+
+    def set_params(self, params):
+        """The flat parameters (``zero_off`` values, host or device) into ``pflat`` and the GRU packs gathered from them: a copy and
+        two element-wise launches on the current stream."""
+        torch = self.torch
+        self.pflat[:self.zero_off].copy_(params.reshape(-1))
+        torch.mul(self.pflat[self._idx], self._scale, out=self.gru_packed)
 
     # ------------------------------------------------------------------ slab buffers
     def _plane_features(self):
@@ -95,6 +109,8 @@ class OpGrad(object):
         if self._bufs is not None and self._bufs["cap"] >= npad:
             return self._bufs
         torch = self.torch
+        if self._kept is not None and self._bufs is not None:
+            self._kept.append(self._bufs)
         self._bufs = None                                                  # free the old set before allocating the new one
         tiles, h, c = npad // 16, self.h, self.c
         f32 = dict(dtype=torch.float32, device=self.dev)
@@ -209,8 +225,10 @@ class OpGrad(object):
             N.check(lib.cf_gen_signal_grad(hd, 0, c, _p(pf[o0:]), _p(dz[0]), _p(pf[o1:]), _p(dz[1]), _p(b["dx_sig"]), npad, stream))
 
     # ------------------------------------------------------------------ the whole call
-    def backward(self, x, grad, need_x, need_w):
-        """(d x shaped like ``x`` on its device or None, d packed_weights as a float32 CPU tensor or None)."""
+    def backward(self, x, grad, need_x, need_w, device_grad=False):
+        """(d x shaped like ``x`` on its device or None, d packed_weights as a float32 CPU tensor or None).  ``device_grad``: the
+        weight gradient is instead a fresh float32 tensor of the flat buffer's ``zero_off`` values on the device (no header, no
+        synchronisation)."""
         torch = self.torch
         n = int(x.shape[0])
         xf = x.detach().reshape(n, T)
@@ -238,7 +256,9 @@ class OpGrad(object):
                 for off, kw, cin, cout in self.units:
                     N.check(self.lib.cf_gen_bn_stat_grads(self.handle, kw, cin, cout, _p(self.pflat[off:]), _p(gacc[off:]), stream))
         gw = None
-        if need_w:
+        if need_w and device_grad:
+            gw = gacc.narrow(0, 0, self.zero_off)                        # gacc is this call's own tensor
+        elif need_w:
             gw = torch.zeros(self.header + self.zero_off, dtype=torch.float32)
             gw[self.header:].copy_(gacc[:self.zero_off])                 # the one synchronisation of the backward
         if need_x:

@@ -22,8 +22,18 @@ autograd formula (``op_grad``) re-runs the training forward of the engine's geom
     import torch, catfish_amd.torch_ops as ops
     packed = ops.pack_weights(weights)                       # once
     probs = torch.ops.catfish.resnetrnn_forward(x, packed)   # x: float32 [N, 35] or [N, 35, 1] on an MI355X -> float32 [N * 35]
+
+``torch.ops.catfish.resnetrnn_forward_params(x, params, n_layers, layer_size, n_layers_res, layer_size_res)`` is the same function
+with the weights on the DEVICE: ``params`` is the flat float32 CUDA tensor ``packed[HEADER:]`` (``param_count(...)`` values), e.g. an
+``nn.Parameter`` (``torch_module.CatfishModule``).  Its engine is cached per (device, geometry), not per content: every call folds
+and re-tiles ``params`` into that engine on the device (``HipEngine.load_params_device``) and then infers, both on the current
+stream, so a weight update never builds an engine and a training step through it can be captured in a CUDA graph.  Its gradient
+with respect to ``params`` is a CUDA tensor (no host copy).  Threading: one engine serves every caller of a geometry on a device,
+so calls from two streams on the same geometry must be ordered by the caller (the C ABI's one model per device per host thread).
 """
 from __future__ import annotations
+
+import functools
 
 import numpy as np
 
@@ -32,6 +42,7 @@ from . import _native as N
 MAGIC = 35064.0          # "catfish 35-sample windows, 64 units": any float32-exact constant would do
 HEADER = 8
 OP_NAME = "catfish::resnetrnn_forward"
+OP_PARAMS_NAME = "catfish::resnetrnn_forward_params"
 
 
 def tensor_names(n_layers=3, n_layers_res=2):
@@ -88,6 +99,13 @@ def pack_weights(weights, n_layers=3, layer_size=64, n_layers_res=2, layer_size_
             raise ValueError("tensor %r has shape %s, the geometry needs %s" % (name, tuple(arr.shape), shapes[name]))
         parts.append(arr.reshape(-1))
     return torch.from_numpy(np.concatenate(parts))
+
+
+@functools.lru_cache(maxsize=64)
+def param_count(n_layers=3, layer_size=64, n_layers_res=2, layer_size_res=32):
+    """Values of the flat parameter tensor of ``resnetrnn_forward_params`` for a geometry: ``pack_weights(...).numel() - HEADER``."""
+    shapes = _shapes(n_layers, layer_size, n_layers_res, layer_size_res)
+    return sum(int(np.prod(shapes[name])) for name in tensor_names(n_layers, n_layers_res))
 
 
 def _check_packed(packed):
@@ -170,6 +188,60 @@ def clear_engine_cache():
         _retire(_ENGINES.popitem()[1])
 
 
+_PARAM_ENGINES = {}      # (device index, n_layers, layer_size, n_layers_res, layer_size_res) -> HipEngine of resnetrnn_forward_params
+
+
+def _placeholder_weights(n_layers, layer_size, n_layers_res, layer_size_res):
+    """Zeros with unit moving variance: what the first engine of a geometry is created from before its first load."""
+    shapes = _shapes(n_layers, layer_size, n_layers_res, layer_size_res)
+    return {name: (np.ones if name.endswith("moving_variance") else np.zeros)(shapes[name], np.float32)
+            for name in tensor_names(n_layers, n_layers_res)}
+
+
+def _params_engine(device_index, geo):
+    from .engine import HipEngine
+    key = (int(device_index),) + tuple(geo)
+    eng = _PARAM_ENGINES.get(key)
+    if eng is None:
+        n_layers, layer_size, n_layers_res, layer_size_res = geo
+        eng = HipEngine(_placeholder_weights(*geo), device=int(device_index), n_layers=n_layers, layer_size=layer_size,
+                        n_layers_res=n_layers_res, layer_size_res=layer_size_res)
+        eng.op_grad = None
+        _PARAM_ENGINES[key] = eng
+    return eng
+
+
+def _check_params(x, params, geo):
+    """ValueError unless ``params`` is a contiguous float32 CUDA tensor on ``x``'s device with ``param_count(*geo)`` values."""
+    import torch
+    if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or not params.is_cuda:
+        raise ValueError("params must be a float32 CUDA tensor (the flat parameters, packed_weights without its header)")
+    if params.device != x.device:
+        raise ValueError("params live on %s, x on %s" % (params.device, x.device))
+    n = param_count(*geo)
+    if not params.is_contiguous() or int(params.numel()) != n:
+        raise ValueError("params must be a contiguous tensor of %d values for this geometry, got %d" % (n, params.numel()))
+
+
+def clear_params_engine_cache():
+    """Free the engines of ``resnetrnn_forward_params`` (and their backward state).  A CUDA graph captured through the operator
+    points at them: drop such graphs first."""
+    while _PARAM_ENGINES:
+        _retire(_PARAM_ENGINES.popitem()[1])
+
+
+def _backward_params_impl(x, params, grad, need_x, need_w, geo):
+    """(d x, d params) of ``resnetrnn_forward_params``: ``op_grad`` over the engine of the geometry, its parameters set from
+    ``params`` on the device; d params is a fresh CUDA tensor shaped like ``params``."""
+    from .op_grad import OpGrad
+    eng = _params_engine(x.device.index, geo)
+    if eng.op_grad is None:
+        eng.op_grad = OpGrad(eng, keep_buffers=True)
+    eng.op_grad.set_params(params.detach())
+    gx, gw = eng.op_grad.backward(x, grad, need_x, need_w, device_grad=True)
+    return gx, (gw.view(params.shape) if gw is not None else None)
+
+
 def _backward_impl(x, packed, grad, need_x, need_w):
     """(d x, d packed_weights) of the operator for the upstream gradient ``grad`` [N * 35] (``op_grad``)."""
     from .op_grad import OpGrad
@@ -215,4 +287,49 @@ def _register():
     return resnetrnn_forward
 
 
+def _once_differentiable(torch, name, grads, inputs):
+    """create_graph=True: the gradients come back through an error node, so that differentiating them again raises."""
+    live = [t.detach().requires_grad_(True) for t in grads if t is not None]
+    err = torch._C._functions.DelayedError(("%s is once-differentiable: its backward has no autograd formula (double backward is "
+                                            "not supported)" % name).encode(), len(live) + len(inputs))
+    out = iter(err(*(live + list(inputs))))
+    return [next(out) if t is not None else None for t in grads]
+
+
+def _register_params():
+    import torch
+
+    @torch.library.custom_op(OP_PARAMS_NAME, mutates_args=(), schema="(Tensor x, Tensor params, int n_layers, int layer_size, "
+                                                                      "int n_layers_res, int layer_size_res) -> Tensor")
+    def resnetrnn_forward_params(x, params, n_layers, layer_size, n_layers_res, layer_size_res):
+        if not x.is_cuda:
+            raise ValueError("catfish::resnetrnn_forward_params runs on an MI355X only: x must be a float32 CUDA tensor [N, 35(, 1)]")
+        geo = (int(n_layers), int(layer_size), int(n_layers_res), int(layer_size_res))
+        _check_params(x, params, geo)
+        eng = _params_engine(x.device.index, geo)
+        eng.load_params_device(params.reshape(-1))            # both on torch.cuda.current_stream(x.device)
+        return eng.infer_device(x)
+
+    @resnetrnn_forward_params.register_fake
+    def _(x, params, n_layers, layer_size, n_layers_res, layer_size_res):
+        return x.new_empty((x.shape[0] * N.CF_WINDOW,), dtype=torch.float32)
+
+    def setup_context(ctx, inputs, output):
+        x, params = inputs[:2]
+        ctx.save_for_backward(x, params)
+        ctx.geo = tuple(int(v) for v in inputs[2:])
+
+    def backward(ctx, grad):
+        x, params = ctx.saved_tensors
+        need_x, need_w = ctx.needs_input_grad[:2]
+        gx, gw = _backward_params_impl(x, params, grad, need_x, need_w, ctx.geo)
+        if torch.is_grad_enabled():
+            gx, gw = _once_differentiable(torch, OP_PARAMS_NAME, [gx, gw], [x, params])
+        return gx, gw, None, None, None, None
+
+    torch.library.register_autograd(OP_PARAMS_NAME, backward, setup_context=setup_context)
+    return resnetrnn_forward_params
+
+
 resnetrnn_forward = _register()
+resnetrnn_forward_params = _register_params()

@@ -15,6 +15,11 @@
  * ctypes / N-API binding of that one call binds.  Plain pointers and sizes
  * only -- no torch / TensorFlow types.
  *
+ * Weights enter a model on the host (cf_model_create: BN folded, matrices
+ * re-tiled and uploaded) or, for an fp32 model, from a device flat parameter
+ * vector (cf_model_load_params: the same folding and re-tiling as a gather
+ * kernel on a stream, so a training loop can update the weights in place).
+ *
  * Threading: one cf_model per device per host thread; cf_infer is
  * asynchronous on the given HIP stream and keeps no global state.
  * Errors: 0 = ok, negative = failure; cf_last_error() returns the message of
@@ -39,7 +44,7 @@ extern "C" {
 
 /* Bumped whenever a signature or a struct of this header changes; cf_abi_version() returns the value the library was built
  * with, so a binding can refuse a stale libcatfish_hip.so instead of calling it with the wrong arguments. */
-#define CF_ABI_VERSION 8
+#define CF_ABI_VERSION 9
 
 /* Arithmetic of the biGRU layers (the residual blocks, the hidden state, the gates'
  * sigmoid/tanh and all accumulation are fp32 in every mode). */
@@ -110,6 +115,17 @@ typedef struct cf_model cf_model;
  * convs, re-tiles every matrix into MFMA A-fragment order and uploads it. */
 int cf_model_create(const cf_weights* w, const cf_hparams* hp, int device, cf_model** out);
 void cf_model_destroy(cf_model* m);
+
+/* Values in the flat parameter vector of this model's geometry: the checkpoint's inference tensors in the operator's
+ * order (torch_ops.tensor_names, TF layouts, flattened) -- packed_weights without its 8-value header. */
+int cf_model_param_floats(const cf_model* m, int64_t* n);
+/* BN folding and re-tiling of `params` (device fp32, cf_model_param_floats values) into this model's own weight buffers,
+ * on `stream`.  Afterwards the model computes exactly what a fresh cf_model_create of the same values computes.
+ * The first call builds a gather map (host work, one allocation, one synchronous upload); every later call is two
+ * kernel launches on `stream` -- no allocation, no copy, no synchronisation, so it can be captured in a graph.
+ * fp32 models only: a model created with CF_PREC_BF16X3 or CF_PREC_BF16 gets CF_ERR_INVALID.  `params` must stay
+ * unchanged until the launches have run; calls that overlap a cf_infer of the same model on another stream race. */
+int cf_model_load_params(cf_model* m, const float* params, void* stream);
 
 /* Replaces RNN.infer's sess.run (rnn_class.py:213-219).
  * x: device pointer, [n_windows, 35] fp32 (window-major, as reshape_input
