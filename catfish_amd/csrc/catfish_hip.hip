@@ -158,6 +158,8 @@ __host__ __device__ constexpr int gru_hc_floats() { return 16 * 256; }
 __host__ __device__ constexpr int gru_bias_off(int cin) { return gru_x_floats(cin) + gru_hg_floats() + gru_hc_floats(); }
 __host__ __device__ constexpr int gru_dense_off(int cin) { return gru_bias_off(cin) + 192; }
 __host__ __device__ constexpr int gru_pack_floats(int cin) { return gru_dense_off(cin) + 64; }
+#define CF_GRU_MAX_WAVES 8      // waves of a gru_layer_kernel workgroup: one hand-off flag (LDS) and one hand-off slot each
+#include "gru_balance.hpp"
 
 // Residual-block blob (floats): NU 32x32 units of 1024 floats [ks < 8][lane][mo < 2], then
 // bias vectors of 32 floats each in [mo][q][r] order.
@@ -418,6 +420,9 @@ __device__ __forceinline__ void gru_stage_weights(float* lds, const float* __res
 // One tile (16 windows) of one direction of one layer: the whole 35-step recurrence.
 // STASH (training forward): also write the activated gates r, u and the candidate c of every step to
 // S[tile][t][dir][12][lane] (r = 0..3, u = 4..7, c = 8..11) for the backward pass.
+// [s_begin, s_end) is the range of steps to run (gru_balance.hpp: a tile may be cut in time between two waves).  A piece that
+// starts late takes h from the hand-off slot HO ([4][64] f32x4, register layout) instead of the zero state, one that ends early
+// leaves h there; the steps themselves do not know.  Every other caller runs the whole tile and compiles to what it was.
 // One k-step region: the A-fragment reads of the NEXT k-step go out before this k-step's MFMAs (left alone the
 // scheduler sinks them behind most of the MFMAs, which leaves ~100 cycles between a read and its first use).
 #ifndef CF_SCHED_DS_FIRST
@@ -434,7 +439,8 @@ __device__ __forceinline__ void gru_stage_weights(float* lds, const float* __res
 template <int CIN, bool LAST, bool STASH = false>
 __device__ __forceinline__ void gru_tile(const float* lds, int lane, int dir, int tile, const f32x4* __restrict__ X,
                                          f32x4* __restrict__ Y, float* __restrict__ P, int n_tiles,
-                                         f32x4* __restrict__ S = nullptr, f32x4* __restrict__ YD = nullptr, cf_dropout drop = cf_dropout()) {
+                                         f32x4* __restrict__ S = nullptr, f32x4* __restrict__ YD = nullptr, cf_dropout drop = cf_dropout(),
+                                         int s_begin = 0, int s_end = CF_T, f32x4* HO = nullptr) {
     const uint32_t drop_key = (STASH && YD) ? cf_drop_key(drop) : 0u;
     constexpr int KGX = CIN / 16;   // f32x4 registers of x per lane and step
     constexpr int KSX = CIN / 4;    // k-steps of the x part
@@ -449,14 +455,18 @@ __device__ __forceinline__ void gru_tile(const float* lds, int lane, int dir, in
     const f32x4* D4 = reinterpret_cast<const f32x4*>(lds + DENSE) + q; // + m*4
     {
         f32x4 h[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};   // GRUCellZeroState
+        if (s_begin > 0) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) h[m] = HO[m * 64 + lane];
+        }
         f32x4 xc[KGX];
         {
-            const int t0 = dir ? (CF_T - 1) : 0;
+            const int t0 = dir ? (CF_T - 1 - s_begin) : s_begin;
             const f32x4* src = X + ((int64_t)tile * CF_T + t0) * KGX * 64 + lane;
 #pragma unroll
             for (int g = 0; g < KGX; ++g) xc[g] = src[g * 64];
         }
-        for (int s = 0; s < CF_T; ++s) {
+        for (int s = s_begin; s < s_end; ++s) {
             const int t = dir ? (CF_T - 1 - s) : s;    // bw = time-reversed sequence (ReverseV2)
             f32x4 acc[12];
 #pragma unroll
@@ -580,7 +590,34 @@ __device__ __forceinline__ void gru_tile(const float* lds, int lane, int dir, in
             }
             __builtin_amdgcn_sched_barrier(0);
         }
+        if (s_end < CF_T) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m) HO[m * 64 + lane] = h[m];
+        }
     }
+}
+
+// Hand-off of h between two waves of ONE workgroup (gru_balance.hpp): the flag is an LDS word, the data goes through global
+// memory.  Order as in cdna_hip_programming.md Guideline 16: drain the stores, release, drain again (ROCm 7.2 can drop the
+// fence's own wait), then the flag; the consumer polls relaxed from one lane, then acquires once.  Workgroup scope reaches every
+// wave of a workgroup: they share the CU's vector cache.  The wait is bounded like cf_wait_flag.
+__device__ __forceinline__ void cf_handoff_publish(unsigned* flag) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void cf_handoff_wait(unsigned* flag, int lane, unsigned* err) {
+    if (lane == 0) {
+        bool ok = false;
+        for (int it = 0; it < 1000000 && !ok; ++it) {
+            ok = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u;
+            if (!ok) __builtin_amdgcn_s_sleep(16);
+        }
+        if (!ok && err) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 template <int CIN, bool LAST>
@@ -588,25 +625,57 @@ __global__ __launch_bounds__(512, 2) void gru_layer_kernel(const float* __restri
                                                            const f32x4* __restrict__ X,      // [tile][t][CIN/16][lane]
                                                            f32x4* __restrict__ Y,            // [tile][t][8][lane]
                                                            float* __restrict__ P,            // [2][tile][t][16]
-                                                           int n_tiles) {
+                                                           int n_tiles,
+                                                           int balance,                      // schedule, chosen by launch_gru
+                                                           f32x4* hand,                      // [2][gridDim.x][8][4][64] hand-off slots
+                                                           unsigned* err) {                  // sticky: a hand-off wait timed out
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int dir = blockIdx.y;
     gru_stage_weights<CIN>(lds, wpack, dir);
+    unsigned* flags = reinterpret_cast<unsigned*>(lds + gru_pack_floats(CIN));     // one word per wave behind the weights
+    if (threadIdx.x < CF_GRU_MAX_WAVES) flags[threadIdx.x] = 0u;
     __syncthreads();
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int nwaves = blockDim.x >> 6;
-    // Every workgroup takes an equal contiguous share of the tiles (+-1) and deals it round-robin to its waves, so that all
-    // SIMDs of the chip end within one tile of each other whatever the wave count.
+    // Every workgroup takes an equal contiguous share of the tiles (+-1).  Round-robin deals whole tiles to the waves; the
+    // balanced schedule deals equal shares of tiles x 35 steps (gru_balance.hpp).  Either way a wave runs a list of pieces
+    // (tile, [s_begin, s_end)) through ONE call site: the step body is 576 MFMAs unrolled.
     const int t0 = (int)((int64_t)blockIdx.x * n_tiles / gridDim.x);
     const int t1 = (int)((int64_t)(blockIdx.x + 1) * n_tiles / gridDim.x);
-    for (int tile = t0 + wave; tile < t1; tile += nwaves)
-        gru_tile<CIN, LAST>(lds, lane, dir, tile, X, Y, P, n_tiles);
+    cf_gru_share sh;
+    int n_pieces;
+    if (balance) {
+        sh = cf_gru_balanced_share(t1 - t0, nwaves, wave, CF_T);
+        n_pieces = (sh.head_end > 0) + sh.whole_count + (sh.tail_begin < CF_T);
+    } else {
+        sh.head_tile = sh.head_end = 0; sh.whole_first = sh.whole_count = 0; sh.tail_tile = 0; sh.tail_begin = CF_T;
+        n_pieces = t1 - t0 > wave ? (t1 - t0 - wave + nwaves - 1) / nwaves : 0;
+    }
+    f32x4* slots = hand + ((size_t)(dir * gridDim.x + blockIdx.x) * CF_GRU_MAX_WAVES) * 4 * 64;
+    const int has_head = balance && sh.head_end > 0;
+    for (int i = 0; i < n_pieces; ++i) {
+        int tile, s_begin = 0, s_end = CF_T;
+        f32x4* ho = nullptr;
+        if (!balance) {
+            tile = t0 + wave + i * nwaves;
+        } else if (i < has_head) {                          // the head first: the next wave's tail waits for it
+            tile = t0 + sh.head_tile; s_end = sh.head_end; ho = slots + wave * 4 * 64;
+        } else if (i < has_head + sh.whole_count) {
+            tile = t0 + sh.whole_first + (i - has_head);
+        } else {                                            // the tail last: the previous wave's head is long over
+            tile = t0 + sh.tail_tile; s_begin = sh.tail_begin; ho = slots + (wave - 1) * 4 * 64;
+            cf_handoff_wait(flags + (wave - 1), lane, err);
+        }
+        gru_tile<CIN, LAST>(lds, lane, dir, tile, X, Y, P, n_tiles, nullptr, nullptr, cf_dropout(), s_begin, s_end, ho);
+        if (s_end < CF_T) cf_handoff_publish(flags + wave);
+    }
 }
 
 // ------------------------------------------------------------------------------------------
 // Kernel 2b: all biGRU layers in ONE launch.  A separate launch per layer leaves CUs idle in every
-// layer's last round (1888 tiles per direction on 1024 SIMDs = 3.69 rounds -> 7.8 % lost per launch).
+// layer's last round (1888 tiles per direction on 1024 SIMDs = 3.69 rounds: dealt as whole tiles, 7.8 % lost per launch; the
+// per-layer kernel's balanced schedule, gru_balance.hpp, brings its own loss down to 2.2 %).
 // Here workgroups are ordered layer-major (a pool per layer and direction that pulls 8-tile groups from a
 // queue), so the first groups of layer l+1 start on the CUs that layer l's tail frees.  A group of layer
 // l > 0 waits for both directions of the same group of layer l-1 through agent-scope flags
@@ -1007,6 +1076,7 @@ struct cf_model {
         float* d_y[2] = {nullptr, nullptr};   // GRU layer outputs ping-pong, F = 128
         float* d_p = nullptr;                 // dense partials [2][tiles][35][16]
         unsigned* d_flags = nullptr;          // fused launch: [n_layers][groups][2] completion flags
+        float* d_hand = nullptr;              // balanced biGRU schedule: h hand-off slots [2 dirs][workgroups][8 waves][4][64] f32x4
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr;
         int64_t last_windows = 0;             // windows of the last pass (debug hook)
@@ -1304,6 +1374,7 @@ extern "C" void cf_model_destroy(cf_model* m) {
         for (int i = 0; i < 2; ++i) { if (sl.d_a[i]) (void)hipFree(sl.d_a[i]); if (sl.d_y[i]) (void)hipFree(sl.d_y[i]); }
         if (sl.d_p) (void)hipFree(sl.d_p);
         if (sl.d_flags) (void)hipFree(sl.d_flags);
+        if (sl.d_hand) (void)hipFree(sl.d_hand);
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
@@ -1415,6 +1486,8 @@ extern "C" int cf_model_create(const cf_weights* w, const cf_hparams* hp, int de
         // dense partials: [2][tiles][35][16] from the throughput kernels, [2][tiles <= CUs][35][4][64] per-lane partials from the
         // latency-mode kernels
         const size_t p_bytes = std::max((size_t)2 * m->cap_tiles * CF_T * 16, (size_t)2 * std::min<int64_t>(m->cap_tiles, m->n_cu) * CF_T * 256) * sizeof(float);
+        // at most two workgroups per CU and direction share the chip (launch_gru)
+        const size_t hand_bytes = (size_t)2 * (2 * std::max(1, m->n_cu / 2)) * CF_GRU_MAX_WAVES * 4 * 64 * sizeof(f32x4);
         hipError_t e = hipSuccess;
         int n_slots = hp->n_streams > 0 ? hp->n_streams : 1;   // measured: splitting one call over 2 internal streams is slower
         if (n_slots > 8) n_slots = 8;
@@ -1424,6 +1497,8 @@ extern "C" int cf_model_create(const cf_weights* w, const cf_hparams* hp, int de
             for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMalloc((void**)&sl.d_y[i], y_bytes);
             if (e == hipSuccess) e = hipMalloc((void**)&sl.d_p, p_bytes);
             if (e == hipSuccess) e = hipMalloc((void**)&sl.d_flags, (size_t)3 * ((m->cap_tiles + 7) / 8) * 2 * sizeof(unsigned) + 64);
+            // (never memset: a slot is written by a head piece before the tail piece of the same launch reads it)
+            if (e == hipSuccess && m->np == 0) e = hipMalloc((void**)&sl.d_hand, hand_bytes);
             if (e == hipSuccess && n_slots > 1) e = hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking);
             if (e == hipSuccess && n_slots > 1) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
         }
@@ -1441,18 +1516,18 @@ extern "C" int cf_model_create(const cf_weights* w, const cf_hparams* hp, int de
         m->fuse = (m->np == 0 && hp->n_layers <= 3 && hp->fuse_layers >= 0) ? (hp->fuse_layers > 0 ? 1 : 2) : 0;
         if (cf_knob("CATFISH_FUSE") && m->fuse) m->fuse = atoi(cf_knob("CATFISH_FUSE")) != 0 ? 1 : 0;   // A/B knob for tools/
         if (e != hipSuccess) rc = fail(CF_ERR_NOMEM, std::string("workspace allocation: ") + hipGetErrorString(e));
-        m->ws_bytes = (int64_t)n_slots * (int64_t)(2 * a_bytes + 2 * y_bytes + p_bytes);
+        m->ws_bytes = (int64_t)n_slots * (int64_t)(2 * a_bytes + 2 * y_bytes + p_bytes + (m->np == 0 ? hand_bytes : 0));
     }
     if (rc == CF_OK) {
         // opt in to > 64 KiB dynamic LDS for every GRU instantiation we may launch
         hipError_t e = hipSuccess;
         auto optin = [&](const void* f, int bytes) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
-        optin((const void*)gru_layer_kernel<16, false>, gru_pack_floats(16) * 4);
-        optin((const void*)gru_layer_kernel<16, true>, gru_pack_floats(16) * 4);
-        optin((const void*)gru_layer_kernel<32, false>, gru_pack_floats(32) * 4);
-        optin((const void*)gru_layer_kernel<32, true>, gru_pack_floats(32) * 4);
-        optin((const void*)gru_layer_kernel<128, false>, gru_pack_floats(128) * 4);
-        optin((const void*)gru_layer_kernel<128, true>, gru_pack_floats(128) * 4);
+        optin((const void*)gru_layer_kernel<16, false>, gru_pack_floats(16) * 4 + CF_GRU_MAX_WAVES * 4);
+        optin((const void*)gru_layer_kernel<16, true>, gru_pack_floats(16) * 4 + CF_GRU_MAX_WAVES * 4);
+        optin((const void*)gru_layer_kernel<32, false>, gru_pack_floats(32) * 4 + CF_GRU_MAX_WAVES * 4);
+        optin((const void*)gru_layer_kernel<32, true>, gru_pack_floats(32) * 4 + CF_GRU_MAX_WAVES * 4);
+        optin((const void*)gru_layer_kernel<128, false>, gru_pack_floats(128) * 4 + CF_GRU_MAX_WAVES * 4);
+        optin((const void*)gru_layer_kernel<128, true>, gru_pack_floats(128) * 4 + CF_GRU_MAX_WAVES * 4);
         optin((const void*)gru_fused_kernel, gru_pack_floats(128) * 4 + 16);
         optin((const void*)gru_layer_coop_kernel<16, false>, (gru_pack_floats(16) + CF_COOP_XCH_FLOATS) * 4);
         optin((const void*)gru_layer_coop_kernel<16, true>, (gru_pack_floats(16) + CF_COOP_XCH_FLOATS) * 4);
@@ -1553,7 +1628,8 @@ static void launch_xproj(cf_model* m, const float* wpack, const float* X, int n_
 }
 
 template <int CIN, bool LAST>
-static int launch_gru(cf_model* m, const float* wpack, const float* X, float* Y, float* P, int n_tiles, hipStream_t s, int slot) {
+static int launch_gru(cf_model* m, const float* wpack, const float* X, float* Y, float* P, int n_tiles, hipStream_t s, int slot,
+                      float* hand = nullptr) {      // hand-off slots of the balanced schedule (Slot::d_hand); none: round-robin
     if (use_coop(m, n_tiles)) {
         size_t pi = 0;
         int rc = prof_begin(m, slot, s, &pi);
@@ -1576,12 +1652,32 @@ static int launch_gru(cf_model* m, const float* wpack, const float* X, float* Y,
     int per_dir = m->n_cu / 2 > 0 ? m->n_cu / 2 : 1;            // persistent: half the CUs per direction
     constexpr int lds_bytes = gru_pack_floats(CIN) * 4;
     if (lds_bytes <= 80 * 1024) per_dir *= 2;                   // two workgroups fit per CU
-    const int gx = groups < per_dir ? groups : per_dir;
+    int gx = groups < per_dir ? groups : per_dir;
     size_t pi = 0;
     int rc = prof_begin(m, slot, s, &pi);
     if (rc != CF_OK) return rc;
-    hipLaunchKernelGGL((gru_layer_kernel<CIN, LAST>), dim3(gx, 2), dim3(waves * 64), lds_bytes, s, wpack,
-                       reinterpret_cast<const f32x4*>(X), reinterpret_cast<f32x4*>(Y), P, n_tiles);
+    // Schedule (gru_balance.hpp): equal shares of steps instead of whole tiles, only where the worst SIMD gets strictly less to do, so
+    // a call that divides evenly and a small call run what they always ran.  A layer whose weights leave room for two workgroups
+    // per CU has a second candidate: ONE balanced workgroup per CU (at the benchmark's 1888 tiles, 7 or 8 tiles on 8 waves cannot be
+    // balanced inside a workgroup, 14 or 15 can: 132 steps against 140; measured).  CATFISH_GRU_BALANCE behind
+    // the debug switch forces a schedule wherever it exists, for tests and A/B: 0 round-robin, 1 balanced on the usual grid,
+    // 2 balanced on the one-workgroup-per-CU grid; read per launch.
+    int balance = 0;
+    if (hand) {
+        const int wg_per_cu = std::max(1, (2 * gx + m->n_cu - 1) / m->n_cu);
+        const int gx_one = std::max(1, m->n_cu / 2);
+        const int load_rr = cf_gru_grid_load(n_tiles, gx, waves, wg_per_cu, CF_T, 0);
+        const int load_bal = cf_gru_grid_load(n_tiles, gx, waves, wg_per_cu, CF_T, 1);
+        const int load_one = gx > gx_one ? cf_gru_grid_load(n_tiles, gx_one, waves, 1, CF_T, 1) : -1;
+        const char* env = cf_knob("CATFISH_GRU_BALANCE");
+        const int forced = env ? atoi(env) : -1;
+        int best = load_rr;
+        if (forced < 0 ? (load_bal >= 0 && load_bal < best) : (forced >= 1 && load_bal >= 0)) { balance = 1; best = load_bal; }
+        if (forced < 0 ? (load_one >= 0 && load_one < best) : (forced == 2 && load_one >= 0)) { balance = 1; gx = gx_one; }
+    }
+    hipLaunchKernelGGL((gru_layer_kernel<CIN, LAST>), dim3(gx, 2), dim3(waves * 64), lds_bytes + CF_GRU_MAX_WAVES * 4, s, wpack,
+                       reinterpret_cast<const f32x4*>(X), reinterpret_cast<f32x4*>(Y), P, n_tiles, balance, reinterpret_cast<f32x4*>(hand),
+                       m->d_err);
     HIP_TRY(hipGetLastError());
     return prof_end(m, s, pi);
 }
@@ -1789,14 +1885,14 @@ static int run_pass(cf_model* m, cf_model::Slot& sl, const float* x, int64_t n_w
             rc = m->np == 1 ? launch_gru_bf16_layer<1>(m, l, last, cur, y, sl.d_p, n_tiles32, s)
                             : launch_gru_bf16_layer<2>(m, l, last, cur, y, sl.d_p, n_tiles32, s);
         } else if (l == 0 && m->hp.n_layers_res == 0) {
-            rc = last ? launch_gru<16, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST)
-                      : launch_gru<16, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU0);
+            rc = last ? launch_gru<16, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand)
+                      : launch_gru<16, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU0, sl.d_hand);
         } else if (l == 0) {
-            rc = last ? launch_gru<32, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST)
-                      : launch_gru<32, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU0);
+            rc = last ? launch_gru<32, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand)
+                      : launch_gru<32, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU0, sl.d_hand);
         } else {
-            rc = last ? launch_gru<128, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST)
-                      : launch_gru<128, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU);
+            rc = last ? launch_gru<128, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand)
+                      : launch_gru<128, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU, sl.d_hand);
         }
         if (rc != CF_OK) return rc;
         cur = y;
