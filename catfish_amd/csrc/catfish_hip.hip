@@ -2548,6 +2548,7 @@ extern "C" int cf_opt_step(cf_model* m, int32_t kind, float* params, const float
 }
 
 #include "gen_train.hpp"      // whole-step training of any geometry (conv stack, GRU dx / dW, dropout, head)
+#include "sample_batch.hpp"   // device-resident training set: cf_sample_batch draws and gathers a training step's next batch on the card
 
 // ---- profiling ---------------------------------------------------------------------------
 static int prof_collect(cf_model* m) {

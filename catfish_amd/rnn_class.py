@@ -238,14 +238,29 @@ class RNN(object):
         """
         if self.weights is None:
             raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
+        self.train_loss = self._require_trainer().train_step(train_x, train_y)
+        self._engine_stale = True
+
+    def _require_trainer(self):
         if self._trainer is None:
             from .training import Trainer
             self._trainer = Trainer(self.weights, self.n_layers, self.n_layers_res_, self.optimizer_choice,
                                     self.learning_rate, self.keep_prob, seed=self.train_seed,
                                     optimizer_state=getattr(self, "optimizer_state", None),
                                     native=getattr(self, "native_training", None))
-        self.train_loss = self._trainer.train_step(train_x, train_y)
-        self._engine_stale = True
+        return self._trainer
+
+    def train_network_steps(self, db, n_steps):
+        """``n_steps`` optimizer steps of ``batch_size`` windows drawn from a ``device_db.DeviceExampleDb`` on the card
+        (``training.Trainer.train_steps``: the sampler is a HIP kernel inside the captured step, the steps run back to back
+        without a copy or a synchronise between them).  ``train_losses`` keeps the per-step losses, ``train_loss`` the last."""
+        if self.weights is None:
+            raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
+        self.train_losses = self._require_trainer().train_steps(db, n_steps, self.batch_size)
+        if len(self.train_losses):
+            self.train_loss = float(self.train_losses[-1])
+            self._engine_stale = True
+        return self.train_losses
 
     def save_network(self, path, step):
         """Write the current weights as a TensorFlow checkpoint-V2 bundle ``path/ckpnt-<step>`` that the

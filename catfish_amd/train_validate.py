@@ -228,7 +228,23 @@ def train_and_validate(network, db, training_nr, squiggles, max_seq_length, file
     validation = (squiggles, max_seq_length, file_path, validation_start, max_number)
     hp_labels = 0
     batch_acc = None
-    for step in range(1, steps + 1):
+    from .device_db import DeviceExampleDb
+    device_fed = isinstance(db, DeviceExampleDb) and hasattr(network, "train_network_steps")
+    if device_fed:
+        # device-fed: the steps between two checkpoint rounds are ONE call (the batches are drawn on the card); the round then
+        # scores the batch just trained on, copied back from the step's static buffers
+        step = 0
+        while step < steps:
+            upto = min(steps, (step // checkpoint_every + 1) * checkpoint_every)
+            network.train_network_steps(db, upto - step)
+            hp_labels += (upto - step) * (network.batch_size // 2) * network.window
+            step = upto
+            if step == steps - 1:
+                print("This was the final checkpoint\n")
+            windows, labels = db.last_batch()
+            batch_acc = _checkpoint_round(network, step, reshape_input(windows, network.window, network.n_inputs),
+                                          reshape_input(labels, network.window, network.n_outputs), report, validation)
+    for step in range(1, (0 if device_fed else steps) + 1):
         windows, labels, n_pos = db.get_training_set(network.batch_size, ratio=2)
         hp_labels += n_pos
         batch_x = reshape_input(windows, network.window, network.n_inputs)
@@ -395,7 +411,9 @@ def main(argv):
     max_validation_length [validation_start [max_number]]``.  The training "database" argument is a directory of NPZ
     reads (the reference takes a ZODB file); hyper-parameters are a random draw as in the reference (:328) unless
     CATFISH_SHIPPED_HPARAMS=1 asks for the shipped network's (the reference's commented block :329-332).
-    CATFISH_NATIVE_TRAINING=1 trains with ``native_training=True`` (the whole step on the HIP kernels at any geometry)."""
+    CATFISH_NATIVE_TRAINING=1 trains with ``native_training=True`` (the whole step on the HIP kernels at any geometry).
+    CATFISH_DEVICE_DB=1 keeps the training windows on the card (``device_db.DeviceExampleDb``): the steps between two
+    checkpoint rounds run back to back, each drawing its own batch."""
     args = list(argv[1:])
     if len(args) < 5:
         raise ValueError(_USAGE)
@@ -411,7 +429,11 @@ def main(argv):
     network = build_model(kind, save=True, **hparams)
     network.initialize_network()
     print("Loading training database..")
-    db_train = example_db_from_npz(_npz_files(train_dir))
+    if os.environ.get("CATFISH_DEVICE_DB") == "1":               # the training set on the card, batches drawn by a HIP kernel
+        from .device_db import device_db_from_npz
+        db_train = device_db_from_npz(_npz_files(train_dir))
+    else:
+        db_train = example_db_from_npz(_npz_files(train_dir))
     print("Loading validation database..")
     squiggles = _npz_files(val_dir)
     began = datetime.datetime.now()

@@ -283,8 +283,12 @@ class Trainer(object):
     """
 
     def __init__(self, weights, n_layers, n_layers_res, optimizer_choice, learning_rate, keep_prob, device=None,
-                 seed=None, use_graph=None, native=None, optimizer_state=None, dtype=None):
+                 seed=None, use_graph=None, native=None, optimizer_state=None, dtype=None, loss_log_capacity=4096):
         import torch
+        if int(loss_log_capacity) < 1:
+            raise ValueError("loss_log_capacity must be at least 1")
+        self.loss_log_capacity = int(loss_log_capacity)      # train_steps: losses kept on the card between two read-backs
+        self._fed = None                                     # the device-fed capture (train_steps), next to train_step's
         if device is None:
             if not torch.cuda.is_available():
                 # no silent CPU fallback: the torch-CPU mode exists as the reference for tests and is opt-in
@@ -400,6 +404,103 @@ class Trainer(object):
         self.opt.step()
         self.last_loss = float(loss.detach())
         return self.last_loss
+
+    # ------------------------------------------------------------------ device-fed loop
+    def _capture_fed(self, db, n, ratio):
+        """The device-fed step as ONE graph: cf_sample_batch_logged (draw + gather into the static input buffers; its
+        one-thread launch then moves the draw counter on and files the previous step's loss in a device log) -> the step.
+        Two launches more than the host-fed step.  A second capture next to ``train_step``'s: both work on the same variables,
+        optimizer slots and ``opt.t``."""
+        import ctypes as C
+        import torch
+        from . import _native as N
+        dev = self.net.device
+        lib = N.lib()
+        handle = self.engine._handle if self.engine is not None else None
+        pos, neg, counter = db.device_pools(dev)
+        log = torch.zeros(self.loss_log_capacity, dtype=torch.float32, device=dev)
+        log_pos = torch.zeros(1, dtype=torch.int64, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr())             # noqa: E731
+        cur = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)     # noqa: E731
+
+        def sample(x, y, loss):
+            # the call's one-thread launch moves the draw counter on and files the PREVIOUS step's loss (still in ``loss``)
+            N.check(lib.cf_sample_batch_logged(handle, ptr(pos), db.nb_pos, ptr(neg), db.nb_neg, n, ratio, db.seed, ptr(counter),
+                                               ptr(x), ptr(y), ptr(loss), ptr(log), self.loss_log_capacity, ptr(log_pos), cur()))
+
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        if self.step_impl is not None:
+            b = self.step_impl._alloc(n)
+            sx, sy, sloss = b["x"], b["y"], b["loss"]        # the native steps write their loss into a static buffer
+
+            def step(update=True):
+                self.step_impl.run(b, update=update)
+        else:
+            sx = torch.zeros((n, 35), dtype=self.net.dtype, device=dev)
+            sy = torch.zeros_like(sx)
+            sloss = torch.zeros(1, dtype=torch.float32, device=dev)
+            self.opt.keep_grads = True
+
+            def step(update=True):
+                loss = self.net.loss(sx, sy, self.keep_prob, None, self.engine)
+                loss.backward()
+                if update:
+                    self.opt.step()
+                else:
+                    for p in self.net.trainable().values():
+                        p.grad = None
+                sloss.copy_(loss.detach().reshape(1))       # autograd allocates its loss: keep it where the next replay's sampler looks
+        with torch.cuda.stream(side):                       # warm-up off the capture stream; no update, and the counters go back
+            for _ in range(2):
+                sample(sx, sy, sloss)
+                step(update=False)
+            counter.fill_(db.draw)
+            db._dev_draw = db.draw
+            log_pos.zero_()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            sample(sx, sy, sloss)
+            step()
+        self._fed = {"key": (n, ratio), "db": db, "graph": g, "x": sx, "y": sy, "loss": sloss, "log": log, "log_pos": log_pos,
+                     "pools": (pos, neg, counter)}
+
+    def train_steps(self, db, n_steps, batch_size, ratio=2):
+        """``n_steps`` optimizer steps on consecutive draws of a ``device_db.DeviceExampleDb`` -> float32 [n_steps] losses.
+
+        On a GPU with graphs the example pools live on the card and every step is one replay of the device-fed graph
+        (``_capture_fed``): no copy, no read-back and no synchronise between steps; the losses collect in a device log that is
+        read back once per chunk of ``loss_log_capacity`` steps.  The CPU reference mode and ``use_graph=False`` run
+        ``db.get_training_set`` + ``train_step`` per step, on the same batches."""
+        n_steps, n, ratio = int(n_steps), int(batch_size), int(ratio)
+        out = np.zeros(max(n_steps, 0), dtype=np.float32)
+        if n_steps <= 0:
+            return out
+        torch = __import__("torch")
+        if not (self.use_graph and self.net.device.type == "cuda" and self.net.dtype == torch.float32):
+            for i in range(n_steps):
+                x, y, _ = db.get_training_set(n, ratio)
+                out[i] = self.train_step(np.asarray(x, dtype=np.float32).reshape(n, 35), np.asarray(y, dtype=np.float32).reshape(n, 35))
+            return out
+        db.batch_indices(db.draw, n, ratio)                  # a pool smaller than its share: ValueError, before anything is enqueued
+        f = self._fed
+        if f is None or f["key"] != (n, ratio) or f["db"] is not db or f["pools"][0] is not db.device_pools(self.net.device)[0]:
+            self._capture_fed(db, n, ratio)
+            f = self._fed
+        done = 0
+        while done < n_steps:
+            k = min(self.loss_log_capacity, n_steps - done)
+            db.sync_counter()
+            f["log_pos"].zero_()
+            for _ in range(k):
+                f["graph"].replay()
+            db.device_drew(k, f["x"], f["y"], n)
+            # losses 0 .. k-2 were filed by the following replays' samplers, the last one is still in the step's loss buffer
+            out[done:done + k] = torch.cat([f["log"][:k - 1], f["loss"]]).cpu().numpy()     # the chunk's one synchronise
+            done += k
+        self.last_loss = float(out[-1])
+        return out
 
     def gradients(self, x, y, keep_prob=None, masks=None):
         """Loss and gradients of one batch WITHOUT an update: (loss, {TF name: ndarray}) -- what tests compare with the

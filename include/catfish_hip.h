@@ -473,6 +473,27 @@ int cf_gen_bn_backward_data(cf_model* m, int32_t kw, int32_t cin, int32_t cout, 
                             int32_t relu, const float* z_stash, float* dz, int64_t n_windows, void* stream);
 int cf_gen_bn_stat_grads(cf_model* m, int32_t kw, int32_t cin, int32_t cout, const float* unit, float* unit_grads, void* stream);
 
+/* Device-resident training set (csrc/sample_batch.hpp; catfish_amd/device_db.py states the sampler on the host and
+ * DeviceExampleDb.batch_indices is its definition): the next balanced batch of the reference's sampler (ExampleDb.get_training_set,
+ * networks/trainingDB/ExampleDb.py:57-83: size / ratio distinct positives, the rest distinct negatives, shuffled, uniform labels)
+ * drawn and gathered on the card, so that a captured training step feeds itself.
+ *   pos [n_pos][35], neg [n_neg][35]   the two pools of windows, device float32
+ *   draw_counter                       device int64[1]: the number of this draw.  Read by every workgroup (a replayed graph draws a
+ *                                      new batch each time) and incremented by a one-thread launch of this call after them
+ *   x [size][35], y [>= size][35]      the step's input and label buffers; rows of y past size are not touched
+ * Every slot evaluates three keyed bijections (a four-round Feistel network over the next even-bit power of two, round function
+ * the murmur3 finaliser, cycle-walking) of (seed, draw): slot -> rank over [0, size), rank -> pool row over [0, n_pos) for ranks
+ * below size / ratio and over [0, n_neg) for the others.  No state, no atomics.  m may be NULL (the current device is used).
+ * CF_ERR_INVALID when a pool is smaller than its share.
+ * cf_sample_batch_logged: the same, and its one-thread launch also keeps the losses of a chain of replayed steps on the card:
+ * with p = *log_pos (device int64[1]) it stores prev_loss[0] -- the loss of the step before this draw, still in the step's loss
+ * buffer -- to log[p - 1] when 1 <= p <= capacity, then *log_pos = p + 1.  The chain's last loss is read from prev_loss itself. */
+int cf_sample_batch(cf_model* m, const float* pos, int64_t n_pos, const float* neg, int64_t n_neg, int64_t size, int32_t ratio,
+                    uint32_t seed, int64_t* draw_counter, float* x, float* y, void* stream);
+int cf_sample_batch_logged(cf_model* m, const float* pos, int64_t n_pos, const float* neg, int64_t n_neg, int64_t size, int32_t ratio,
+                           uint32_t seed, int64_t* draw_counter, float* x, float* y, const float* prev_loss, float* log, int64_t capacity,
+                           int64_t* log_pos, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream) for bench.py's
  * roofline report.  cf_profile_enable(m, N) makes every N-th cf_infer call
  * (N = 1: every call; 0 = off) record events around each of its kernels; cf_profile_read synchronises and returns, for
