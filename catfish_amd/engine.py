@@ -272,6 +272,62 @@ class HipEngine(object):
                                        C.c_void_p(stream.cuda_stream)))
         return out
 
+    # ------------------------------------------------------------------ validation rounds on the card (csrc/validation.hpp)
+    def _check_validation_tensors(self, what, tensors):
+        import torch
+        for name, t, dtype in tensors:
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s: %s must be a contiguous %s CUDA tensor" % (what, name, str(dtype).replace("torch.", "")))
+            if t.device.index != self.device:
+                raise ValueError("%s: %s lives on cuda:%s, model on cuda:%d" % (what, name, t.device.index, self.device))
+
+    def gather_validation(self, signal, labels, src_first, length, bounds, total, longest, x_out, y_out, stream=None):
+        """``cf_validation_gather``: packed sample ``bounds[r] + i`` of ``x_out`` / ``y_out`` (float32 / uint8, at least ``total``
+        elements) becomes ``signal`` / ``labels`` ``[src_first[r] + i]`` for ``i < length[r]`` and 0 after it.  ``src_first``,
+        ``length`` [n] and ``bounds`` [n + 1] are int64 CUDA tensors; ``total`` = bounds[n] and ``longest`` = the largest packed
+        read are the caller's host copies of those numbers.  Asynchronous on the stream."""
+        import torch
+        self._check_validation_tensors("gather_validation", [
+            ("signal", signal, torch.float32), ("labels", labels, torch.uint8), ("src_first", src_first, torch.int64),
+            ("length", length, torch.int64), ("bounds", bounds, torch.int64), ("x_out", x_out, torch.float32), ("y_out", y_out, torch.uint8)])
+        n, total, longest = int(src_first.numel()), int(total), int(longest)
+        if int(length.numel()) != n or int(bounds.numel()) != n + 1:
+            raise ValueError("gather_validation: src_first and length need n entries, bounds n + 1")
+        if int(labels.numel()) != int(signal.numel()):
+            raise ValueError("gather_validation: signal and labels differ in length")
+        if total < 0 or int(x_out.numel()) < total or int(y_out.numel()) < total:
+            raise ValueError("gather_validation: x_out and y_out need %d elements" % total)
+        if stream is None:
+            stream = torch.cuda.current_stream(signal.device)
+        N.check(self._lib.cf_validation_gather(self._handle, C.c_void_p(signal.data_ptr()), C.c_void_p(labels.data_ptr()), int(signal.numel()),
+                                               C.c_void_p(src_first.data_ptr()), C.c_void_p(length.data_ptr()), C.c_void_p(bounds.data_ptr()),
+                                               n, total, longest, C.c_void_p(x_out.data_ptr()), C.c_void_p(y_out.data_ptr()),
+                                               C.c_void_p(stream.cuda_stream)))
+
+    def score_validation(self, probs, logits, y, bounds, total, longest, thresholds, right_out, ce_sum_out, counts_out, partials, stream=None):
+        """``cf_validation_score``: per read the number of samples with ``rint(p) == y`` (``right_out`` int64 [n]) and the fp64 sum
+        of the sigmoid cross-entropy of the logits (``ce_sum_out`` float64 [n]); per threshold (``thresholds`` float64 CUDA [K],
+        1 <= K <= 16) tp / fp / raw tn / fn over all ``total`` samples (``counts_out`` int64 [K * 4]).  ``partials`` is float64
+        work space of at least ``total // SCORE_CHUNK + n`` elements.  Asynchronous on the stream; equal inputs give equal bits."""
+        import torch
+        self._check_validation_tensors("score_validation", [
+            ("probs", probs, torch.float32), ("logits", logits, torch.float32), ("y", y, torch.uint8), ("bounds", bounds, torch.int64),
+            ("thresholds", thresholds, torch.float64), ("right_out", right_out, torch.int64), ("ce_sum_out", ce_sum_out, torch.float64),
+            ("counts_out", counts_out, torch.int64), ("partials", partials, torch.float64)])
+        n, k, total, longest = int(bounds.numel()) - 1, int(thresholds.numel()), int(total), int(longest)
+        if total < 0 or min(int(probs.numel()), int(logits.numel()), int(y.numel())) < total:
+            raise ValueError("score_validation: probs, logits and y need %d elements" % total)
+        if int(right_out.numel()) < n or int(ce_sum_out.numel()) < n or int(counts_out.numel()) < 4 * k:
+            raise ValueError("score_validation: right_out and ce_sum_out need n entries, counts_out 4 per threshold")
+        if stream is None:
+            stream = torch.cuda.current_stream(probs.device)
+        # n, K and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
+        N.check(self._lib.cf_validation_score(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(logits.data_ptr()), C.c_void_p(y.data_ptr()),
+                                              C.c_void_p(bounds.data_ptr()), n, total, longest, C.c_void_p(thresholds.data_ptr()), k,
+                                              C.c_void_p(right_out.data_ptr()), C.c_void_p(ce_sum_out.data_ptr()),
+                                              C.c_void_p(counts_out.data_ptr()), C.c_void_p(partials.data_ptr()), int(partials.numel()),
+                                              C.c_void_p(stream.cuda_stream)))
+
     # ------------------------------------------------------------------ profiling / debug
     def profile_enable(self, on=True, every=1):
         """Per-kernel HIP-event timing of every ``every``-th call (events cost ~1.6 % when on every call)."""

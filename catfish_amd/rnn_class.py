@@ -207,6 +207,77 @@ class RNN(object):
         self._require_engine()
         return self.engine.infer_host(np.asarray(windows), return_logits=True)
 
+    def score_validation_device(self, vset, selection, thresholds=(0.5,)):
+        """One validation round on the card: the stretches ``selection`` (``vset.select``) of a
+        ``device_validation.DeviceValidationSet`` -> what ``device_validation.score_host`` returns for them, (right int64 [n],
+        ce_sum float64 [n], counts int64 [K, 4]).
+
+        The selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes
+        probabilities and logits (the weights just trained, as ``score_windows`` uses them), ``cf_validation_score`` reduces them
+        -- more than 16 thresholds in groups of 16 over the same forward pass -- and ONE copy brings the results back; all on
+        the current stream.  The work buffers stay on the object and grow only when a round is larger than every one before
+        (``validation_buffers``: capacities and how often each was allocated or uploaded)."""
+        import torch
+        from . import device_validation as dv
+        self._require_engine()
+        thresholds = tuple(float(t) for t in thresholds)
+        if not thresholds:
+            raise ValueError("score_validation_device: no threshold given")
+        read_index, first, length = vset.check_selection(selection)
+        n = int(read_index.size)
+        if n == 0:
+            raise ValueError("score_validation_device: no read selected")
+        bounds, _tails = dv.layout(length, self.window)
+        total, longest = int(bounds[-1]), int(np.diff(bounds).max())
+        device = torch.device("cuda", self.device)
+        signal, labels = vset.device_arrays(device)
+        book = self.validation_buffers
+        k_all = len(thresholds)
+        slots = total // dv.SCORE_CHUNK + n
+        need = {"samples": max(total, 1), "reads": n, "slots": slots, "thresholds": k_all}
+        if any(book["capacity"].get(key, 0) < value for key, value in need.items()):
+            cap = {key: max(book["capacity"].get(key, 0), value) for key, value in need.items()}
+            f32 = lambda count: torch.empty(count, dtype=torch.float32, device=device)     # noqa: E731
+            book["tensors"] = {"x": f32(cap["samples"]), "probs": f32(cap["samples"]), "logits": f32(cap["samples"]),
+                               "y": torch.empty(cap["samples"], dtype=torch.uint8, device=device),
+                               "table": torch.empty(3 * (cap["reads"] + 1), dtype=torch.int64, device=device),
+                               "partials": torch.empty(cap["slots"], dtype=torch.float64, device=device),
+                               # right [reads] | ce_sum [reads], double bits | counts [4 per threshold]: one copy back
+                               "out": torch.empty(2 * cap["reads"] + 4 * cap["thresholds"], dtype=torch.int64, device=device)}
+            book["capacity"] = cap
+            book["allocations"] += 1
+        if book["thresholds"] is None or book["thresholds"][0] != thresholds or book["thresholds"][1].device != device:
+            book["thresholds"] = (thresholds, torch.tensor(thresholds, dtype=torch.float64, device=device))
+            book["threshold_uploads"] += 1
+        t = book["tensors"]
+        table = np.zeros((3, n + 1), dtype=np.int64)
+        table[0, :n] = vset.offsets[read_index] + first
+        table[1, :n] = length
+        table[2] = bounds
+        t["table"][:3 * (n + 1)].copy_(torch.from_numpy(table.reshape(-1)))
+        book["selection_uploads"] += 1
+        src_d, len_d, bounds_d = (t["table"][i * (n + 1):i * (n + 1) + count] for i, count in ((0, n), (1, n), (2, n + 1)))
+        x, y, probs, logits = t["x"][:total], t["y"][:total], t["probs"][:total], t["logits"][:total]
+        out = t["out"][:2 * n + 4 * k_all]
+        right_d, ce_d, counts_d = out[:n], out[n:2 * n].view(torch.float64), out[2 * n:]
+        self.engine.gather_validation(signal, labels, src_d, len_d, bounds_d, total, longest, x, y)
+        self.engine.infer_device(x.view(-1, self.window), out=probs, logits=logits)
+        for k0 in range(0, k_all, dv.MAX_THRESHOLDS):
+            k1 = min(k_all, k0 + dv.MAX_THRESHOLDS)
+            self.engine.score_validation(probs, logits, y, bounds_d, total, longest, book["thresholds"][1][k0:k1], right_d, ce_d,
+                                         counts_d[4 * k0:4 * k1], t["partials"])
+        back = out.cpu().numpy()                                                     # synchronises the stream
+        self.engine.check_error()
+        return back[:n].copy(), back[n:2 * n].view(np.float64).copy(), back[2 * n:].reshape(k_all, 4).copy()
+
+    @property
+    def validation_buffers(self):
+        """Bookkeeping of ``score_validation_device``'s device buffers."""
+        if getattr(self, "_validation_buffers", None) is None:
+            self._validation_buffers = {"capacity": {}, "tensors": None, "allocations": 0, "thresholds": None, "threshold_uploads": 0,
+                                        "selection_uploads": 0}
+        return self._validation_buffers
+
     def test_network(self, test_x, test_y, read_name, file_path, padding_size, threshold=0.5):
         """rnn_class.py:222-261: accuracy and loss of one padded read + running confusion counters (the per-read
         form of the surface; ``train_validate.validate`` scores a whole round in one packed call instead)."""

@@ -360,15 +360,26 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     selected -> ZeroDivisionError."""
     print("Max length is {}".format(max_seq_length))
     print("Validation start is {}".format(validation_start))
-    signals, labels = select_validation_stretches(squiggles, network.window, max_seq_length, validation_start,
-                                                  max_number)
-    n_reads = len(signals)
-    n_samples = sum(len(s) for s in signals)
-    if n_reads == 0:
-        raise ZeroDivisionError("validation selected no read")
-    x, y, bounds, tails = pack_validation_windows(signals, labels, network.window)
-    probs, logits = network.score_windows(x)
-    acc, loss, counts = score_validation_batch(probs, logits, y, bounds, tails)
+    from .device_validation import DeviceValidationSet
+    if isinstance(squiggles, DeviceValidationSet):
+        # the reads live on the card: the same stretches (same draws), gathered and scored there; only raw counts and sums come back
+        selection = squiggles.select(network.window, max_seq_length, validation_start, max_number)
+        n_reads = len(selection[0])
+        n_samples = int(selection[2].sum())
+        if n_reads == 0:
+            raise ZeroDivisionError("validation selected no read")
+        right, ce_sum, counts_k = network.score_validation_device(squiggles, selection)
+        acc, loss, counts = squiggles.finish(right, ce_sum, counts_k[0], *squiggles.layout(selection[2], network.window))
+    else:
+        signals, labels = select_validation_stretches(squiggles, network.window, max_seq_length, validation_start,
+                                                      max_number)
+        n_reads = len(signals)
+        n_samples = sum(len(s) for s in signals)
+        if n_reads == 0:
+            raise ZeroDivisionError("validation selected no read")
+        x, y, bounds, tails = pack_validation_windows(signals, labels, network.window)
+        probs, logits = network.score_windows(x)
+        acc, loss, counts = score_validation_batch(probs, logits, y, bounds, tails)
     averaged = n_reads - 1 if n_reads >= max_number else n_reads
     acc_sum = loss_sum = 0
     for a, l in zip(acc[:averaged].tolist(), loss[:averaged].tolist()):      # doubles holding float32 values, in order
@@ -389,6 +400,25 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     print("Validation accuracy: ", whole_acc)
     print("Validation loss: ", loss_sum / n_reads)
     return whole_acc, precision, recall
+
+
+def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start="complete", max_number=856):
+    """The reference's precision / recall sweep (networks/precision_recall_ROC.py:85-100: ``class_from_threshold`` --
+    ``p >= t`` -- then ``compute_f1`` per threshold) over a ``DeviceValidationSet``: ONE forward pass, every threshold counted
+    from its probabilities on the card.  The stretches are ``validate``'s (same selection, same tail rule for the true
+    negatives).  -> a list of dicts {threshold, tp, fp, tn, fn, precision, recall, f1}, one per threshold, in order."""
+    thresholds = [float(t) for t in thresholds]
+    selection = vset.select(network.window, max_seq_length, validation_start, max_number)
+    if len(selection[0]) == 0:
+        raise ZeroDivisionError("validation selected no read")
+    _right, _ce_sum, counts = network.score_validation_device(vset, selection, thresholds)
+    tail = int(vset.layout(selection[2], network.window)[1].sum())
+    rows = []
+    for t, (tp, fp, tn_raw, fn) in zip(thresholds, np.asarray(counts).tolist()):
+        precision, recall = metrics.precision_recall(tp, fp, fn)
+        rows.append({"threshold": t, "tp": tp, "fp": fp, "tn": tn_raw - tail, "fn": fn, "precision": precision, "recall": recall,
+                     "f1": metrics.f1(precision, recall)})
+    return rows
 
 
 _USAGE = ("The following arguments should be provided in this order:\n"
@@ -413,7 +443,9 @@ def main(argv):
     CATFISH_SHIPPED_HPARAMS=1 asks for the shipped network's (the reference's commented block :329-332).
     CATFISH_NATIVE_TRAINING=1 trains with ``native_training=True`` (the whole step on the HIP kernels at any geometry).
     CATFISH_DEVICE_DB=1 keeps the training windows on the card (``device_db.DeviceExampleDb``): the steps between two
-    checkpoint rounds run back to back, each drawing its own batch."""
+    checkpoint rounds run back to back, each drawing its own batch.
+    CATFISH_DEVICE_VALIDATION=1 keeps the validation reads on the card too (``device_validation.DeviceValidationSet``, loaded
+    once): a checkpoint round gathers and scores its stretches there instead of re-opening the files."""
     args = list(argv[1:])
     if len(args) < 5:
         raise ValueError(_USAGE)
@@ -436,6 +468,9 @@ def main(argv):
         db_train = example_db_from_npz(_npz_files(train_dir))
     print("Loading validation database..")
     squiggles = _npz_files(val_dir)
+    if os.environ.get("CATFISH_DEVICE_VALIDATION") == "1":       # the validation reads on the card, rounds scored by HIP kernels
+        from .device_validation import DeviceValidationSet
+        squiggles = DeviceValidationSet.from_npz(squiggles)
     began = datetime.datetime.now()
     train_and_validate(network, db_train, n_train, squiggles, stretch, network.model_path, start, most)
     print("Trained and validated network in {}".format(datetime.datetime.now() - began))

@@ -494,6 +494,31 @@ int cf_sample_batch_logged(cf_model* m, const float* pos, int64_t n_pos, const f
                            uint32_t seed, int64_t* draw_counter, float* x, float* y, const float* prev_loss, float* log, int64_t capacity,
                            int64_t* log_pos, void* stream);
 
+/* Device-resident validation set (csrc/validation.hpp; catfish_amd/device_validation.py states both steps in numpy --
+ * DeviceValidationSet.pack and score_host are their definitions): one checkpoint round (networks/train_validate.py:188-295) packed and
+ * scored on the card.  Both calls are asynchronous on `stream` and capturable; m may be NULL (the current device is used).
+ *   signal [signal_total] float32, labels [signal_total] uint8     all reads concatenated, device
+ *   src_first [n], length [n], bounds [n + 1]                      device int64: read r's stretch starts at signal[src_first[r]], has
+ *                                                                  length[r] samples and fills packed samples bounds[r] .. bounds[r + 1]
+ *   total = bounds[n]; longest = the largest bounds[r + 1] - bounds[r] (sizes the grid only: any value <= total gives the same result)
+ * cf_validation_gather: x_out / y_out [total]; packed sample bounds[r] + i is signal / labels [src_first[r] + i] for i < length[r] and
+ * 0 / 0 after it (the zero tail up to the window multiple).  A table entry that points outside signal or x_out moves nothing.
+ * cf_validation_score: with p, z the probability and the logit of a sample as doubles and y its label value,
+ *   right_out[r]  (int64)   samples of read r with rint(p) == y (half to even: p = 0.5 rounds to 0)
+ *   ce_sum_out[r] (double)  sum over read r of max(z, 0) - z y + log1p(exp(-|z|))
+ *   counts_out[4 k ..]      (int64) over ALL samples, called = p >= thresholds[k] (device double [n_thresholds], 1..16 of them):
+ *                           called & y == 1, called & y != 1, !called & y == 0 (zero tails included), !called & y != 0
+ * A read is cut into chunks of cf_validation_score_chunk() samples, one workgroup each, reduced in a fixed order into a slot of
+ * `partials` (device double [partial_slots], partial_slots >= total / chunk + n); a second launch adds a read's slots in chunk order.
+ * No floating-point atomics: equal inputs give equal bits.  CF_ERR_INVALID for n < 1, n_thresholds outside 1..16 or too few slots. */
+int cf_validation_score_chunk(void);
+int cf_validation_gather(cf_model* m, const float* signal, const uint8_t* labels, int64_t signal_total, const int64_t* src_first,
+                         const int64_t* length, const int64_t* bounds, int64_t n, int64_t total, int64_t longest, float* x_out,
+                         uint8_t* y_out, void* stream);
+int cf_validation_score(cf_model* m, const float* probs, const float* logits, const uint8_t* y, const int64_t* bounds, int64_t n,
+                        int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds, int64_t* right_out,
+                        double* ce_sum_out, int64_t* counts_out, double* partials, int64_t partial_slots, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream) for bench.py's
  * roofline report.  cf_profile_enable(m, N) makes every N-th cf_infer call
  * (N = 1: every call; 0 = off) record events around each of its kernels; cf_profile_read synchronises and returns, for

@@ -1,0 +1,143 @@
+"""One checkpoint round of validation (``train_validate.validate``), three routes in one process on the shipped checkpoint,
+alternating, at least five timed rounds each after a warm-up round:
+
+    (a) paths      today's ``validate`` on the list of NPZ files (re-opened every round)
+    (b) memory     today's ``validate`` with a loader that serves the same reads from memory: (a) without the file I/O
+    (c) resident   ``validate`` on a ``device_validation.DeviceValidationSet`` (reads on the card; gather, forward pass and scoring
+                   there, raw counts and sums back)
+
+The set is 856 synthetic labelled reads of 20 000 samples (``synthetic_labelled_read``), written as NPZ to a temporary directory;
+a round scores a stretch of 4 900 samples per read from a random start (seeded per round, the same for the three routes, whose
+reports are compared).  Every timed round ends in a synchronise.  One JSON line per (route, round) and one summary line (median
+and range of seconds per round, and whether (c)'s range lies below (a)'s and below (b)'s) are APPENDED to the output file.
+
+    python tools/bench_validation_round.py [--rounds 5] [--commit <id>] [--out profiles/validation_round_bench.jsonl]
+    python tools/bench_validation_round.py --trace-rounds 3      # route (c) alone, for rocprofv3 --kernel-trace --stats
+"""
+import argparse
+import contextlib
+import functools
+import io
+import json
+import os
+import random
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from catfish_amd import train_validate as tv  # noqa: E402
+from catfish_amd.device_validation import DeviceValidationSet  # noqa: E402
+from catfish_amd.resnet_class import ResNetRNN  # noqa: E402
+
+SHIPPED = dict(batch_size=256, optimizer_choice="RMSProp", learning_rate=0.001, layer_size=64, n_layers=3, keep_prob=0.8,
+               layer_size_res=32, n_layers_res=2)
+STRETCH, START, MOST = 4900, "random", 856
+
+
+def commit_id():
+    try:
+        return subprocess.check_output(["git", "-C", ROOT, "rev-parse", "--short=12", "HEAD"], stderr=subprocess.DEVNULL).decode().strip()
+    except (OSError, subprocess.CalledProcessError):
+        return None
+
+
+def one_round(net, source, seed, name):
+    """A seeded round -> (seconds, report text, returned tuple)."""
+    random.seed(seed)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    with contextlib.redirect_stdout(io.StringIO()):
+        got = tv.validate(net, source, STRETCH, name, START, MOST)
+    torch.cuda.synchronize()
+    seconds = time.perf_counter() - t0
+    with open(name + ".txt") as fh:
+        text = fh.read()
+    os.remove(name + ".txt")
+    return seconds, text, got
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--reads", type=int, default=856)
+    ap.add_argument("--read-len", type=int, default=20000)
+    ap.add_argument("--commit", default=None, help="stamp of the lines (default: git rev-parse HEAD)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "validation_round_bench.jsonl"))
+    ap.add_argument("--trace-rounds", type=int, default=0, help="route (c) alone for this many rounds, then exit")
+    args = ap.parse_args()
+    rounds = max(5, args.rounds)
+    commit = args.commit or commit_id()
+    with np.load(os.path.join(ROOT, "tests", "golden", "ckpnt-30000-inference.npz")) as z:
+        weights = {k: z[k] for k in z.files}
+    net = ResNetRNN(**SHIPPED)
+    with contextlib.redirect_stdout(io.StringIO()):
+        net.set_weights(weights)
+    out_path = os.path.abspath(args.out)
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)
+        paths, memory = [], {}
+        for i in range(args.reads):
+            raw, lab = tv.synthetic_labelled_read(args.read_len, seed=7000 + i)
+            paths.append(os.path.join(tmp, "read_%04d.npz" % i))
+            np.savez(paths[-1], raw=raw, base_labels=lab)
+            memory[paths[-1]] = (raw, lab)
+        t0 = time.perf_counter()
+        resident = DeviceValidationSet.from_npz(paths)
+        load_s = time.perf_counter() - t0
+        from_paths = tv.select_validation_stretches
+        from_memory = functools.partial(from_paths, loader=memory.__getitem__)
+
+        def route(name, source, select):
+            def run(seed):
+                tv.select_validation_stretches = select
+                try:
+                    return one_round(net, source, seed, name)
+                finally:
+                    tv.select_validation_stretches = from_paths
+            return name, run
+
+        routes = [route("a_paths", paths, from_paths), route("b_memory", paths, from_memory), route("c_resident", resident, from_paths)]
+        if args.trace_rounds:
+            for rnd in range(args.trace_rounds):
+                routes[2][1](rnd)
+            print(json.dumps(dict(traced="c_resident", rounds=args.trace_rounds)))
+            os.chdir(ROOT)
+            return
+        os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        with open(out_path, "a") as out:
+            def emit(rec):
+                line = json.dumps(dict(rec, commit=commit))
+                print(line, flush=True)
+                out.write(line + "\n")
+                out.flush()
+
+            for name, run in routes:                       # warm-up: allocator, page cache, the set's upload, lazy initialisation
+                run(-1)
+            seconds = {name: [] for name, _ in routes}
+            same = True
+            for rnd in range(rounds):                      # alternate, so that clock and neighbour drift hit all three alike
+                seen = []
+                for name, run in routes:
+                    s, text, got = run(rnd)
+                    seconds[name].append(s)
+                    seen.append((text.replace(name, "route"), got))
+                    emit(dict(route=name, round=rnd, seconds=s))
+                same = same and seen[0] == seen[1] == seen[2]
+            stats = {name: dict(median_s=float(np.median(v)), min_s=float(min(v)), max_s=float(max(v))) for name, v in seconds.items()}
+            emit(dict(summary=True, reads=args.reads, read_len=args.read_len, stretch=STRETCH, start=START, rounds=rounds,
+                      samples_per_round=args.reads * (STRETCH // 35 * 35), load_resident_set_s=load_s, routes=stats,
+                      reports_equal=bool(same),
+                      c_range_below_a=bool(stats["c_resident"]["max_s"] < stats["a_paths"]["min_s"]),
+                      c_range_below_b=bool(stats["c_resident"]["max_s"] < stats["b_memory"]["min_s"]),
+                      a_over_c=stats["a_paths"]["median_s"] / stats["c_resident"]["median_s"],
+                      b_over_c=stats["b_memory"]["median_s"] / stats["c_resident"]["median_s"]))
+        os.chdir(ROOT)
+    net.engine.close()
+
+
+main()
