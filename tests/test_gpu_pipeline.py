@@ -626,8 +626,10 @@ def test_trainer_uses_the_any_size_kernels_for_other_geometries():
 @pytest.mark.parametrize("n", [40, 2100])
 def test_native_gru_training_kernels_match_torch_autograd(n):
     """cf_gru_train_forward/backward (+ library GEMMs for dW) against torch autograd of the restated graph:
-    same loss, same gradients for every parameter and for the input.  40 windows run the four-waves-per-tile
-    (latency) kernels, 2100 windows (2 x 132 tiles > 256 CUs) the one-wave-per-tile (throughput) kernels."""
+    same loss, same gradients for every parameter and for the input.  Both counts run the four-waves-per-tile
+    (latency) kernels: 40 windows in one round with the x projection hoisted, 2100 windows (132 tiles, no more than one per
+    CU) in two rounds without the hoist.  The one-wave-per-tile (throughput) kernels start above one tile per CU; they are
+    covered, against float64, by tests/test_train_kernels_fp64.py."""
     torch = pytest.importorskip("torch")
     from catfish_amd.training import TorchResNetRNN
     from catfish_amd.engine import HipEngine

@@ -172,3 +172,72 @@ def test_anysize_pack_maps_follow_the_fragment_formula():
                     assert wct[mo, kb, lane, i] == wc[cin + 16 * mo + (lane & 15), 16 * kb + 4 * (lane >> 4) + i]
                 for kb in range(2 * h16):
                     assert wgt[mo, kb, lane, i] == wg[cin + 16 * mo + (lane & 15), 16 * kb + 4 * (lane >> 4) + i]
+
+
+def test_single_layer_float64_reference_reproduces_the_restated_graph():
+    """tests/test_train_kernels_fp64.py compares the HIP training kernels with its own float64 restatement of one biGRU layer
+    (input projection of all steps in one product, state products per step).  Stacked three times behind TorchResNetRNN's conv
+    stack it must give TorchResNetRNN(float64)'s loss and gradients to 1e-12 relative: that ties it to the graph pinned against
+    tests/golden/graph_train_golden.npz."""
+    from test_train_kernels_fp64 import stacked_loss
+    w = oracle.random_weights(seed=12)
+    x, y = _batch(5, seed=3)
+    a = TorchResNetRNN(w, 3, 2, dtype=torch.float64)
+    la = a.loss(x, y)
+    la.backward()
+    assert len(a.trainable()) == 58
+
+    def same(b, lb, la, a):
+        lb.backward()
+        assert abs(float(la.detach()) - float(lb.detach())) <= 1e-12 * abs(float(la.detach()))
+        for k, p in a.trainable().items():
+            g = b.params[k].grad
+            assert g is not None, k
+            assert float((g - p.grad).abs().max()) <= 1e-12 * float(p.grad.abs().max()), k
+
+    b = TorchResNetRNN(w, 3, 2, dtype=torch.float64)
+    same(b, stacked_loss(b, x, y), la, a)
+
+
+def test_bounds_of_the_float64_parity_module_follow_from_its_profile():
+    """Each bound of tests/test_train_kernels_fp64.py is at most 4 x the largest float32-torch error that
+    profiles/train_kernels_fp64_parity.jsonl records for the quantity, and at most the older tests' bound, and not so far
+    below (rounded down to three digits) that it is a different number."""
+    import test_train_kernels_fp64 as m
+    want = m.bounds_from_profile()
+    assert sorted(want) == sorted(m.BOUNDS) == sorted(m.OLDER_BOUNDS)
+    for k, b in m.BOUNDS.items():
+        assert 0.99 * want[k] <= b <= want[k], (k, b, want[k])
+
+
+@pytest.mark.parametrize("kind,steps_before", [(0, 0), (1, 0), (1, 999), (1, 50000)])
+def test_opt_step_bounds_admit_a_plain_float32_evaluation(kind, steps_before):
+    """The derived bounds tests/test_train_kernels_fp64.py holds cf_opt_step to, applied to the update written out in numpy
+    float32 in the kernel's order of operations (each operation correctly rounded): they must admit it, and must not admit
+    an update with the epsilon on the wrong side of the root or a step counter off by one."""
+    from test_train_kernels_fp64 import _opt_inputs, opt_step_bounds_hold
+    f = np.float32
+    lr = f(1e-3)
+
+    def step32(p, g, s1, s2, t, eps_inside=None):
+        if kind == 0:
+            ms = (s1.astype(np.float64) * f(0.9)).astype(f)
+            ms = ((f(0.1) * g).astype(np.float64) * g + ms).astype(f)                 # fma: one rounding
+            den = np.sqrt(ms + f(1e-10)) if eps_inside is None else np.sqrt(ms) + f(1e-10)
+            upd = g / den * lr
+            return p - upd, ms, upd
+        m = (f(0.1).astype(np.float64) * g + s1 * f(0.9)).astype(f)
+        v = ((f(0.001) * g).astype(np.float64) * g + s2 * f(0.999)).astype(f)
+        lr_t = f(float(lr) * np.sqrt(1.0 - 0.999 ** (t + 1.0)) / (1.0 - 0.9 ** (t + 1.0)))
+        den = np.sqrt(v) + f(1e-8) if eps_inside is None else np.sqrt(v + f(1e-8))
+        return p - m / den * lr_t, m, v
+
+    p, g, s1, s2 = _opt_inputs(70003, kind, seed=steps_before)
+    got = step32(p, g, s1, s2, steps_before)
+    assert all(a.dtype == np.float32 for a in got)
+    assert opt_step_bounds_hold(kind, got[0], got[1], got[2], p, g, s1, s2, float(lr), steps_before) == []
+    wrong = step32(p, g, s1, s2, steps_before, eps_inside=False)
+    assert "p" in opt_step_bounds_hold(kind, wrong[0], wrong[1], wrong[2], p, g, s1, s2, float(lr), steps_before)
+    if kind == 1 and steps_before < 10000:
+        late = step32(p, g, s1, s2, steps_before + 1)
+        assert "p" in opt_step_bounds_hold(kind, late[0], late[1], late[2], p, g, s1, s2, float(lr), steps_before)
