@@ -2315,12 +2315,7 @@ extern "C" int cf_gru_train_backward(cf_model* m, int32_t cin, const float* wpac
 // The mask / keep_prob tensor the training kernels apply to the output of `layer` (fragment layout [tiles][35][8][64][4]), written out
 // for tests and tools: the kernels themselves never store it.
 // ---- any-size biGRU layer for training (generic.hpp): forward with gate stash, backward chain -----------------------------------
-static int anysize_waves(int h16, int arrays, size_t* lds) {
-    const size_t per_wave = (size_t)arrays * h16 * 64 * sizeof(f32x4);
-    const int waves = per_wave * 8 <= (size_t)(160 * 1024) ? 8 : (per_wave * 4 <= (size_t)(160 * 1024) ? 4 : (per_wave * 2 <= (size_t)(160 * 1024) ? 2 : 1));
-    *lds = per_wave * waves;
-    return waves;
-}
+#include "anysize_launch.hpp"      // waves, grid, LDS bytes and h_via_y of the two launches below: host-only, tested on the CPU
 
 static int anysize_args_ok(const cf_model* m, int32_t layer_size, int64_t n_windows, const char* who) {
     if (!m) return fail(CF_ERR_INVALID, std::string(who) + ": null model");
@@ -2338,16 +2333,11 @@ extern "C" int cf_gru_anysize_train_forward(cf_model* m, int32_t layer_size, int
     if (cin_blocks < 1 || cin_blocks > 32) return fail(CF_ERR_INVALID, "cf_gru_anysize_train_forward: cin_blocks must be 1..32 (input features / 16)");
     HIP_TRY(hipSetDevice(m->device));
     const int h16 = layer_size / 16, n_tiles = (int)(n_windows / CF_TILE);
-    size_t lds_full = 0;
-    int h_via_y = 0;
-    int max_waves = anysize_waves(h16, 3, &lds_full);
-    if (max_waves < 8) { h_via_y = 1; max_waves = anysize_waves(h16, 2, &lds_full); }     // as in the inference launch: h' through y above 64 units
-    const int waves = std::max(1, std::min(max_waves, (2 * n_tiles + m->n_cu - 1) / m->n_cu));
-    const size_t lds = lds_full / max_waves * waves;
+    const cf_anysize_shape sh = cf_anysize_forward_shape(h16, n_tiles, m->n_cu);
     HIP_TRY(hipFuncSetAttribute((const void*)gen_gru_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((gen_gru_kernel<true, false>), dim3((unsigned)((n_tiles + waves - 1) / waves), 2), dim3(waves * 64), lds,
+    hipLaunchKernelGGL((gen_gru_kernel<true, false>), dim3((unsigned)sh.grid_x, 2), dim3(sh.waves * 64), sh.lds_bytes,
                        reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f32x4*>(wpack), reinterpret_cast<const f32x4*>(bpack),
-                       reinterpret_cast<const f32x4*>(x_frag), reinterpret_cast<f32x4*>(y_frag), h16, (int)cin_blocks, h_via_y,
+                       reinterpret_cast<const f32x4*>(x_frag), reinterpret_cast<f32x4*>(y_frag), h16, (int)cin_blocks, sh.h_via_y,
                        reinterpret_cast<f32x4*>(stash), n_tiles);
     HIP_TRY(hipGetLastError());
     return CF_OK;
@@ -2360,15 +2350,25 @@ extern "C" int cf_gru_anysize_train_backward(cf_model* m, int32_t layer_size, co
     if (!wtpack || !y_frag || !stash || !dy_frag || !da) return fail(CF_ERR_INVALID, "cf_gru_anysize_train_backward: null buffer");
     HIP_TRY(hipSetDevice(m->device));
     const int h16 = layer_size / 16, n_tiles = (int)(n_windows / CF_TILE);
-    size_t lds = 0;
-    const int max_waves = anysize_waves(h16, 4, &lds);
-    const int waves = std::max(1, std::min(max_waves, (2 * n_tiles + m->n_cu - 1) / m->n_cu));
-    lds = lds / max_waves * waves;
+    const cf_anysize_shape sh = cf_anysize_backward_shape(h16, n_tiles, m->n_cu);
     HIP_TRY(hipFuncSetAttribute((const void*)gen_gru_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(gen_gru_bwd_kernel, dim3((unsigned)((n_tiles + waves - 1) / waves), 2), dim3(waves * 64), lds,
+    hipLaunchKernelGGL(gen_gru_bwd_kernel, dim3((unsigned)sh.grid_x, 2), dim3(sh.waves * 64), sh.lds_bytes,
                        reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f32x4*>(wtpack), reinterpret_cast<const f32x4*>(y_frag),
                        reinterpret_cast<const f32x4*>(stash), reinterpret_cast<const f32x4*>(dy_frag), reinterpret_cast<f32x4*>(da), n_tiles, h16);
     HIP_TRY(hipGetLastError());
+    return CF_OK;
+}
+
+// The launch shape of the two calls above for `n_windows` windows on this model's device, for tests and tools: out = forward
+// {waves, grid_x, lds_bytes, h_via_y}, backward {waves, grid_x, lds_bytes, max_waves}.  Nothing is launched.
+extern "C" int cf_gru_anysize_train_shape(const cf_model* m, int32_t layer_size, int64_t n_windows, int64_t out[8]) {
+    int rc = anysize_args_ok(m, layer_size, n_windows, "cf_gru_anysize_train_shape");
+    if (rc != CF_OK) return rc;
+    if (!out) return fail(CF_ERR_INVALID, "cf_gru_anysize_train_shape: null output");
+    const int h16 = layer_size / 16, n_tiles = (int)(n_windows / CF_TILE);
+    const cf_anysize_shape f = cf_anysize_forward_shape(h16, n_tiles, m->n_cu), b = cf_anysize_backward_shape(h16, n_tiles, m->n_cu);
+    out[0] = f.waves; out[1] = f.grid_x; out[2] = (int64_t)f.lds_bytes; out[3] = f.h_via_y;
+    out[4] = b.waves; out[5] = b.grid_x; out[6] = (int64_t)b.lds_bytes; out[7] = b.max_waves;
     return CF_OK;
 }
 

@@ -334,6 +334,11 @@ int cf_gru_anysize_train_forward(cf_model* m, int32_t layer_size, int32_t cin_bl
                                  const float* x_frag, float* y_frag, float* stash, int64_t n_windows, void* stream);
 int cf_gru_anysize_train_backward(cf_model* m, int32_t layer_size, const float* wtpack, const float* y_frag, const float* stash,
                                   const float* dy_frag, float* da, int64_t n_windows, void* stream);
+/* The launch shape those two calls take for n_windows windows on m's device (csrc/anysize_launch.hpp), without launching anything:
+ * out = forward {waves per workgroup, grid x, dynamic LDS bytes, h_via_y}, backward {waves, grid x, LDS bytes, max waves}.  A
+ * workgroup runs `waves` tiles of one direction, so grid x * waves >= tiles and the last workgroup may be partly empty.  For
+ * tests and tools that must know which regime a size runs in; same argument checks as the two calls. */
+int cf_gru_anysize_train_shape(const cf_model* m, int32_t layer_size, int64_t n_windows, int64_t out[8]);
 /* The same two calls with the layer's OUTPUT dropout (DropoutWrapper(output_keep_prob), rnn_class.py:151-154) done inside the
  * kernels, no mask tensor: whether an output element is kept is a hash of (seed, layer, *step_count, element index).  The
  * forward additionally writes y_drop_frag = y * mask / keep_prob (what the next layer or the dense head reads; y_frag itself stays
