@@ -11,6 +11,10 @@ geometry other than the shipped 64 / 32 one, RNN or ResNetRNN type).
 The conv and biGRU launches, their buffers and the flat layout (params | grads | two optimizer slots, one layout for every
 geometry) are ``anysize_walk``'s, shared with the operator's backward; this module adds the dropout hooks, the head and the
 optimizer.  What does not depend on the kernels is ``native_step.FlatTrainStep``, shared with the step of the shipped geometry.
+
+``precision="bf16x3"``: the two recurrences read split bf16 packs from ``packed_x3``, a second buffer beside ``packed``.  Whatever
+rewrites ``packed`` -- ``retile`` and the optimizer launch, the latter inside the captured step -- is followed on the same stream
+by ``AnySizeWalk.repack_x3``, so a split pack never lags behind its fp32 pack.
 """
 from __future__ import annotations
 
@@ -22,15 +26,33 @@ from .native_train import T, dropout_scale_frag, frag_to_nat
 
 
 class AnySizeTrainStep(FlatTrainStep):
+    def __init__(self, net, opt, engine, keep_prob, seed=None, precision="fp32"):
+        self.precision = precision                              # checked by AnySizeWalk
+        self.packed_x3 = None
+        super().__init__(net, opt, engine, keep_prob, seed=seed)
+
     def _layout(self):
         p = self.net.params
         self.h = int(p[N.gru_prefix(0, "fw") + "/candidate/bias"].shape[0])
         self.c = int(p["conv1d/bias"].shape[0]) if self.n_blocks > 0 else 0
-        self.walk = w = AnySizeWalk(self.lib, self.handle, self.h, self.c, self.n_layers, self.n_blocks)
+        self.walk = w = AnySizeWalk(self.lib, self.handle, self.h, self.c, self.n_layers, self.n_blocks, precision=self.precision)
         self._set_layout(w.layout)
         self.pack_idx = self.torch.from_numpy(w.pack_idx.astype("int32")).to(self.dev)
         self.pack_scale = self.torch.from_numpy(w.pack_scale).to(self.dev)
         self.n_packed = int(w.pack_idx.size)
+
+    # ------------------------------------------------------------------ the split packs follow the fp32 packs
+    def retile(self):
+        super().retile()
+        if self.precision == "bf16x3":
+            if self.packed_x3 is None:
+                self.packed_x3 = self.torch.empty(self.walk.n_packed_x3, dtype=self.torch.float32, device=self.dev)
+            self.walk.repack_x3(self.packed, self.packed_x3, self._stream())
+
+    def _opt_step(self, stream):
+        super()._opt_step(stream)
+        if self.precision == "bf16x3":
+            self.walk.repack_x3(self.packed, self.packed_x3, stream)
 
     # ------------------------------------------------------------------ buffers per batch size
     def _alloc(self, n):
@@ -52,7 +74,7 @@ class AnySizeTrainStep(FlatTrainStep):
         kp = self.keep_prob if keep_prob is None else float(keep_prob)
         n, npad = b["n"], b["npad"]
         stream = self._stream()
-        pf, gf, packed = self.pflat, self.gflat, self.packed
+        pf, gf, packed, packed_x3 = self.pflat, self.gflat, self.packed, self.packed_x3
         # output dropout after each layer and on the gradient coming back into it: the kernel's own mask hash, or replayed masks
         after = before = None
         if kp < 1.0:
@@ -66,12 +88,12 @@ class AnySizeTrainStep(FlatTrainStep):
 
             after = lambda layer, y: dropout(layer, y, b["y_drop"][layer])          # noqa: E731
             before = lambda layer, g: dropout(layer, g, b["dy"])                    # noqa: E731
-        a, inputs = w.gru_forward(b, w.conv_forward(b, pf, npad, stream), packed, npad, stream, after=after)
+        a, inputs = w.gru_forward(b, w.conv_forward(b, pf, npad, stream), packed, npad, stream, after=after, packed_x3=packed_x3)
         # ---- dense head + loss, forward and backward
         ho = self.head_off
         N.check(lib.cf_gen_head(hd, 2 * h, _p(a), _p(pf[ho:]), _p(b["y"]), n, _p(b["dy_head"]), None, _p(b["head_ws"]),
                                 int(b["head_ws"].numel()), _p(gf[ho:]), _p(b["loss"]), npad, stream))
-        g = w.gru_backward(b, b["dy_head"], inputs, pf, gf, packed, npad, stream, before=before)
+        g = w.gru_backward(b, b["dy_head"], inputs, pf, gf, packed, npad, stream, before=before, packed_x3=packed_x3)
         w.conv_backward(b, g, pf, gf, npad, stream)
         if update:
             self._opt_step(stream)

@@ -7,6 +7,10 @@ recurrence -- in eager torch thousands of tiny kernels per step -- runs on the a
 What is a plain GEMM over all (window, step) pairs stays a library GEMM: the input gradient ``da W_x^T`` and the weight
 gradients ``[x; h]^T da``.  The weights are re-tiled on the device every step with gather maps computed here (numpy,
 once per geometry), so no host round trip.  Residual blocks, dropout, dense head, loss and optimizer stay in torch.
+
+``precision="bf16x3"`` (opt-in) runs the matrix products on the serial chain of the two recurrences as split bf16 products
+(``cf_gru_anysize_train_forward_x3`` / ``_backward_x3``): the fp32 packs are built as always and split on the device by
+``cf_gen_repack_x3``.  State, gate activations, stash and every GEMM over all (window, step) pairs stay fp32.
 """
 from __future__ import annotations
 
@@ -21,7 +25,30 @@ LOG2E = 1.4426950408889634
 GATE_SCALE = -LOG2E          # sigmoid(a) = 1 / (1 + exp2(-a log2 e))          (CF_GATE_SCALE)
 CAND_SCALE = 2.0 * LOG2E     # tanh(a)    = 1 - 2 / (1 + exp2(2 a log2 e))      (CF_CAND_SCALE)
 
+PRECISIONS = ("fp32", "bf16x3")      # training precisions of the any-size recurrences
+
 _MAPS = {}
+
+
+def check_precision(precision):
+    if precision not in PRECISIONS:
+        raise ValueError("unknown training precision %r: choose one of %s" % (precision, ", ".join(PRECISIONS)))
+    return precision
+
+
+def x3_pack_floats(lib, h, kbx):
+    """(floats of the bf16x3 forward pack, of the transposed pack) of one layer: cf_gru_anysize_x3_pack_floats."""
+    out = (C.c_int64 * 2)()
+    N.check(lib.cf_gru_anysize_x3_pack_floats(int(h), int(kbx), out))
+    return int(out[0]), int(out[1])
+
+
+def repack_x3(lib, handle, h, kbx, wpack, wpack_x3, wtpack, wtpack_x3, stream):
+    """One layer's fp32 packs -> its bf16x3 packs (cf_gen_repack_x3, on ``stream``); either pair may be None."""
+    if wpack is not None:
+        N.check(lib.cf_gen_repack_x3(handle, int(h), int(kbx), 0, N._p(wpack), N._p(wpack_x3), stream))
+    if wtpack is not None:
+        N.check(lib.cf_gen_repack_x3(handle, int(h), int(kbx), 1, N._p(wtpack), N._p(wtpack_x3), stream))
 
 
 def pack_maps(h, cin, device):
@@ -80,7 +107,7 @@ def _make_function():
         """y = biGRU_layer(x); x [N, 35, Cin] -> y [N, 35, 2H] (forward direction features first)."""
 
         @staticmethod
-        def forward(ctx, x, wg_f, bg_f, wc_f, bc_f, wg_b, bg_b, wc_b, bc_b, engine):
+        def forward(ctx, x, wg_f, bg_f, wc_f, bc_f, wg_b, bg_b, wc_b, bc_b, engine, precision="fp32"):
             lib, handle = engine._lib, engine._handle
             n, _, cin = x.shape
             h = int(wc_f.shape[1])
@@ -102,11 +129,18 @@ def _make_function():
                 y_frag = torch.empty(tiles, T, 2 * h16, 64, 4, dtype=torch.float32, device=x.device)
                 stash = torch.empty(tiles, T, 2, 3, h16, 64, 4, dtype=torch.float32, device=x.device)
                 stream = torch.cuda.current_stream(x.device).cuda_stream
-                N.check(lib.cf_gru_anysize_train_forward(handle, h, kbx, C.c_void_p(wpack.data_ptr()), C.c_void_p(bpack.data_ptr()),
-                                                         C.c_void_p(x_frag.data_ptr()), C.c_void_p(y_frag.data_ptr()),
-                                                         C.c_void_p(stash.data_ptr()), npad, C.c_void_p(stream)))
+                x3 = precision == "bf16x3"
+                forward_call = lib.cf_gru_anysize_train_forward
+                if x3:                                          # split both packs on the device; the backward keeps the split wtpack
+                    nw, nt = x3_pack_floats(lib, h, kbx)
+                    wpack_x3, wtpack_x3 = wpack.new_empty(nw), wpack.new_empty(nt)
+                    repack_x3(lib, handle, h, kbx, wpack, wpack_x3, wtpack, wtpack_x3, C.c_void_p(stream))
+                    wpack, wtpack, forward_call = wpack_x3, wtpack_x3, lib.cf_gru_anysize_train_forward_x3
+                N.check(forward_call(handle, h, kbx, C.c_void_p(wpack.data_ptr()), C.c_void_p(bpack.data_ptr()),
+                                     C.c_void_p(x_frag.data_ptr()), C.c_void_p(y_frag.data_ptr()),
+                                     C.c_void_p(stash.data_ptr()), npad, C.c_void_p(stream)))
                 y = frag_to_nat(y_frag)
-            ctx.engine, ctx.n, ctx.npad, ctx.h, ctx.cin = engine, n, npad, h, cin
+            ctx.engine, ctx.n, ctx.npad, ctx.h, ctx.cin, ctx.x3 = engine, n, npad, h, cin, x3
             ctx.save_for_backward(xp, y, y_frag, stash, wtpack, wg_f, wc_f, wg_b, wc_b)
             return y[:n].to(x.dtype)
 
@@ -122,9 +156,10 @@ def _make_function():
             dy_frag = nat_to_frag(dyp.contiguous())
             da = torch.empty_like(stash)
             stream = torch.cuda.current_stream(dev).cuda_stream
-            N.check(lib.cf_gru_anysize_train_backward(handle, h, C.c_void_p(wtpack.data_ptr()), C.c_void_p(y_frag.data_ptr()),
-                                                      C.c_void_p(stash.data_ptr()), C.c_void_p(dy_frag.data_ptr()),
-                                                      C.c_void_p(da.data_ptr()), npad, C.c_void_p(stream)))
+            backward_call = lib.cf_gru_anysize_train_backward_x3 if ctx.x3 else lib.cf_gru_anysize_train_backward
+            N.check(backward_call(handle, h, C.c_void_p(wtpack.data_ptr()), C.c_void_p(y_frag.data_ptr()),
+                                  C.c_void_p(stash.data_ptr()), C.c_void_p(dy_frag.data_ptr()),
+                                  C.c_void_p(da.data_ptr()), npad, C.c_void_p(stream)))
             x2 = xp[:, :, :cin].reshape(npad * T, cin)
             dx = None
             grads = []
@@ -145,7 +180,7 @@ def _make_function():
                 dxd = da_g @ wg[:cin].float().t() + da_c @ wc[:cin].float().t()
                 dx = dxd if dx is None else dx + dxd
             dx = dx.reshape(npad, T, cin)[:n].to(dy.dtype)
-            return (dx,) + tuple(grads) + (None,)
+            return (dx,) + tuple(grads) + (None, None)
 
     return AnySizeBiGRU
 
@@ -153,9 +188,11 @@ def _make_function():
 _FN = None
 
 
-def anysize_bigru(x, params8, engine):
-    """Differentiable biGRU layer of any geometry.  params8 = (wg_f, bg_f, wc_f, bc_f, wg_b, bg_b, wc_b, bc_b)."""
+def anysize_bigru(x, params8, engine, precision="fp32"):
+    """Differentiable biGRU layer of any geometry.  params8 = (wg_f, bg_f, wc_f, bc_f, wg_b, bg_b, wc_b, bc_b).
+    ``precision``: "fp32", or "bf16x3" for split bf16 products on the serial chain of both recurrences."""
     global _FN
+    check_precision(precision)
     if _FN is None:
         _FN = _make_function()
-    return _FN.apply(x, *params8, engine)
+    return _FN.apply(x, *params8, engine, precision)

@@ -12,6 +12,10 @@ count and workspace sizes all come from it) and the four walks
                     cf_gen_conv_backward_data
 
 The heads, the signal gradient, the optimizer and the slab loop stay with the drivers.  Every launch goes to the stream it is given.
+
+With ``precision="bf16x3"`` the two recurrences run their ``_x3`` entry points on a second buffer of packs, ``packed_x3`` (per layer
+the split wpack, then the split wtpack; ``repack_x3`` rebuilds it from ``packed`` with cf_gen_repack_x3).  The biases, the
+GEMM-shaped kernels and everything else read what they read in fp32.
 """
 from __future__ import annotations
 
@@ -85,12 +89,26 @@ class AnySizeWalk(object):
     """One geometry's layout, plane table and launch walks.  ``b`` is a buffer dict of ``alloc``, ``pf`` / ``gf`` the flat parameters
     and gradients, ``packed`` the biGRU packs gathered through ``pack_idx`` / ``pack_scale`` (numpy, ``flat_pack_map``)."""
 
-    def __init__(self, lib, handle, h, c, n_layers, n_blocks):
+    def __init__(self, lib, handle, h, c, n_layers, n_blocks, precision="fp32"):
+        from .anysize_train import check_precision, x3_pack_floats
         self.lib, self.handle = lib, handle
+        self.precision = check_precision(precision)
         self.h, self.c, self.n_layers, self.n_blocks = int(h), int(c), int(n_layers), int(n_blocks)
         self.layout = flat_layout(h, c, n_layers, n_blocks)
         self.entries, self.units, self.layers, self.head_off, self.zero_off = self.layout
         self.pack_idx, self.pack_scale, self.per_layer = flat_pack_map(h, self.layers, self.zero_off)
+        self.x3_layer, self.n_packed_x3 = [], 0              # per layer (offset of the split wpack, of the split wtpack) in packed_x3
+        if self.precision == "bf16x3":
+            for _, cin in self.layers:
+                nw, nt = x3_pack_floats(lib, self.h, (cin + 15) // 16)
+                self.x3_layer.append((self.n_packed_x3, self.n_packed_x3 + nw))
+                self.n_packed_x3 += nw + nt
+
+    def repack_x3(self, packed, packed_x3, stream):
+        """Every layer's split packs from the fp32 packs in ``packed``: call after whatever rewrites ``packed``."""
+        from .anysize_train import repack_x3
+        for (_, cin), ((wo, _), _, (to, _)), (xw, xt) in zip(self.layers, self.per_layer, self.x3_layer):
+            repack_x3(self.lib, self.handle, self.h, (cin + 15) // 16, packed[wo:], packed_x3[xw:], packed[to:], packed_x3[xt:], stream)
 
     # ------------------------------------------------------------------ the planes of one slab
     def plane_table(self):
@@ -154,34 +172,49 @@ class AnySizeWalk(object):
             a = b["x_frag"]
         return a
 
-    def gru_forward(self, b, a, packed, npad, stream, after=None):
+    def gru_forward(self, b, a, packed, npad, stream, after=None, packed_x3=None):
         """The biGRU layers over ``a``; ``after(layer, y)`` returns what the next layer reads in place of ``y``.  Returns (the last
-        activation, [the input of each layer])."""
+        activation, [the input of each layer]).  ``packed_x3``: the split packs, with ``precision="bf16x3"``."""
         lib, hd, h = self.lib, self.handle, self.h
+        x3 = self._x3(packed_x3)
         inputs = []
         for layer, (off, cin) in enumerate(self.layers):
             (wo, _), (bo, _), _ = self.per_layer[layer]
             inputs.append(a)
-            N.check(lib.cf_gru_anysize_train_forward(hd, h, (cin + 15) // 16, _p(packed[wo:]), _p(packed[bo:]), _p(a), _p(b["y_frag"][layer]),
-                                                     _p(b["stash"][layer]), npad, stream))
+            if x3:
+                N.check(lib.cf_gru_anysize_train_forward_x3(hd, h, (cin + 15) // 16, _p(packed_x3[self.x3_layer[layer][0]:]), _p(packed[bo:]),
+                                                            _p(a), _p(b["y_frag"][layer]), _p(b["stash"][layer]), npad, stream))
+            else:
+                N.check(lib.cf_gru_anysize_train_forward(hd, h, (cin + 15) // 16, _p(packed[wo:]), _p(packed[bo:]), _p(a),
+                                                         _p(b["y_frag"][layer]), _p(b["stash"][layer]), npad, stream))
             a = b["y_frag"][layer]
             if after is not None:
                 a = after(layer, a)
         return a, inputs
 
+    def _x3(self, packed_x3):
+        if (self.precision == "bf16x3") != (packed_x3 is not None):
+            raise ValueError("the split packs go with precision 'bf16x3', and only with it (this walk: %r)" % self.precision)
+        return packed_x3 is not None
+
     # ------------------------------------------------------------------ backward
-    def gru_backward(self, b, g, inputs, pf, gf, packed, npad, stream, need_w=True, before=None):
+    def gru_backward(self, b, g, inputs, pf, gf, packed, npad, stream, need_w=True, before=None, packed_x3=None):
         """The biGRU layers from the gradient ``g`` of the last one's output; ``before(layer, g)`` returns the gradient the layer
         takes in place of ``g``.  Layer 0's gate gradients stay in ``b["da"]``.  Returns the gradient of the stack's input."""
         lib, hd, h = self.lib, self.handle, self.h
+        x3 = self._x3(packed_x3)
         ws, wsn = b["wgrad_ws"], int(b["wgrad_ws"].numel())
         for layer in range(self.n_layers - 1, -1, -1):
             off, cin = self.layers[layer]
             _, _, (to, _) = self.per_layer[layer]
             if before is not None:
                 g = before(layer, g)
-            N.check(lib.cf_gru_anysize_train_backward(hd, h, _p(packed[to:]), _p(b["y_frag"][layer]), _p(b["stash"][layer]), _p(g),
-                                                      _p(b["da"]), npad, stream))
+            if x3:
+                N.check(lib.cf_gru_anysize_train_backward_x3(hd, h, _p(packed_x3[self.x3_layer[layer][1]:]), _p(b["y_frag"][layer]),
+                                                             _p(b["stash"][layer]), _p(g), _p(b["da"]), npad, stream))
+            else:
+                N.check(lib.cf_gru_anysize_train_backward(hd, h, _p(packed[to:]), _p(b["y_frag"][layer]), _p(b["stash"][layer]), _p(g),
+                                                          _p(b["da"]), npad, stream))
             if need_w:
                 N.check(lib.cf_gen_gru_wgrad(hd, h, cin, _p(inputs[layer]), _p(b["y_frag"][layer]), _p(b["stash"][layer]), _p(b["da"]),
                                              _p(ws), wsn, _p(gf[off:]), npad, stream))

@@ -2325,17 +2325,18 @@ static int anysize_args_ok(const cf_model* m, int32_t layer_size, int64_t n_wind
     return CF_OK;
 }
 
-extern "C" int cf_gru_anysize_train_forward(cf_model* m, int32_t layer_size, int32_t cin_blocks, const float* wpack, const float* bpack,
-                                            const float* x_frag, float* y_frag, float* stash, int64_t n_windows, void* stream) {
-    int rc = anysize_args_ok(m, layer_size, n_windows, "cf_gru_anysize_train_forward");
+template <bool X3>
+static int anysize_train_forward(cf_model* m, int32_t layer_size, int32_t cin_blocks, const float* wpack, const float* bpack, const float* x_frag,
+                                 float* y_frag, float* stash, int64_t n_windows, void* stream, const char* who) {
+    int rc = anysize_args_ok(m, layer_size, n_windows, who);
     if (rc != CF_OK) return rc;
-    if (!wpack || !bpack || !x_frag || !y_frag || !stash) return fail(CF_ERR_INVALID, "cf_gru_anysize_train_forward: null buffer");
-    if (cin_blocks < 1 || cin_blocks > 32) return fail(CF_ERR_INVALID, "cf_gru_anysize_train_forward: cin_blocks must be 1..32 (input features / 16)");
+    if (!wpack || !bpack || !x_frag || !y_frag || !stash) return fail(CF_ERR_INVALID, std::string(who) + ": null buffer");
+    if (cin_blocks < 1 || cin_blocks > 32) return fail(CF_ERR_INVALID, std::string(who) + ": cin_blocks must be 1..32 (input features / 16)");
     HIP_TRY(hipSetDevice(m->device));
     const int h16 = layer_size / 16, n_tiles = (int)(n_windows / CF_TILE);
-    const cf_anysize_shape sh = cf_anysize_forward_shape(h16, n_tiles, m->n_cu);
-    HIP_TRY(hipFuncSetAttribute((const void*)gen_gru_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL((gen_gru_kernel<true, false>), dim3((unsigned)sh.grid_x, 2), dim3(sh.waves * 64), sh.lds_bytes,
+    const cf_anysize_shape sh = cf_anysize_forward_shape(h16, n_tiles, m->n_cu);        // the state in LDS is fp32 in both precisions
+    HIP_TRY(hipFuncSetAttribute((const void*)gen_gru_kernel<true, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL((gen_gru_kernel<true, X3>), dim3((unsigned)sh.grid_x, 2), dim3(sh.waves * 64), sh.lds_bytes,
                        reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f32x4*>(wpack), reinterpret_cast<const f32x4*>(bpack),
                        reinterpret_cast<const f32x4*>(x_frag), reinterpret_cast<f32x4*>(y_frag), h16, (int)cin_blocks, sh.h_via_y,
                        reinterpret_cast<f32x4*>(stash), n_tiles);
@@ -2343,18 +2344,84 @@ extern "C" int cf_gru_anysize_train_forward(cf_model* m, int32_t layer_size, int
     return CF_OK;
 }
 
-extern "C" int cf_gru_anysize_train_backward(cf_model* m, int32_t layer_size, const float* wtpack, const float* y_frag, const float* stash,
-                                             const float* dy_frag, float* da, int64_t n_windows, void* stream) {
-    int rc = anysize_args_ok(m, layer_size, n_windows, "cf_gru_anysize_train_backward");
+template <bool X3>
+static int anysize_train_backward(cf_model* m, int32_t layer_size, const float* wtpack, const float* y_frag, const float* stash,
+                                  const float* dy_frag, float* da, int64_t n_windows, void* stream, const char* who) {
+    int rc = anysize_args_ok(m, layer_size, n_windows, who);
     if (rc != CF_OK) return rc;
-    if (!wtpack || !y_frag || !stash || !dy_frag || !da) return fail(CF_ERR_INVALID, "cf_gru_anysize_train_backward: null buffer");
+    if (!wtpack || !y_frag || !stash || !dy_frag || !da) return fail(CF_ERR_INVALID, std::string(who) + ": null buffer");
     HIP_TRY(hipSetDevice(m->device));
     const int h16 = layer_size / 16, n_tiles = (int)(n_windows / CF_TILE);
     const cf_anysize_shape sh = cf_anysize_backward_shape(h16, n_tiles, m->n_cu);
-    HIP_TRY(hipFuncSetAttribute((const void*)gen_gru_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    hipLaunchKernelGGL(gen_gru_bwd_kernel, dim3((unsigned)sh.grid_x, 2), dim3(sh.waves * 64), sh.lds_bytes,
+    HIP_TRY(hipFuncSetAttribute((const void*)gen_gru_bwd_kernel<X3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    hipLaunchKernelGGL(gen_gru_bwd_kernel<X3>, dim3((unsigned)sh.grid_x, 2), dim3(sh.waves * 64), sh.lds_bytes,
                        reinterpret_cast<hipStream_t>(stream), reinterpret_cast<const f32x4*>(wtpack), reinterpret_cast<const f32x4*>(y_frag),
                        reinterpret_cast<const f32x4*>(stash), reinterpret_cast<const f32x4*>(dy_frag), reinterpret_cast<f32x4*>(da), n_tiles, h16);
+    HIP_TRY(hipGetLastError());
+    return CF_OK;
+}
+
+extern "C" int cf_gru_anysize_train_forward(cf_model* m, int32_t layer_size, int32_t cin_blocks, const float* wpack, const float* bpack,
+                                            const float* x_frag, float* y_frag, float* stash, int64_t n_windows, void* stream) {
+    return anysize_train_forward<false>(m, layer_size, cin_blocks, wpack, bpack, x_frag, y_frag, stash, n_windows, stream,
+                                        "cf_gru_anysize_train_forward");
+}
+
+extern "C" int cf_gru_anysize_train_backward(cf_model* m, int32_t layer_size, const float* wtpack, const float* y_frag, const float* stash,
+                                             const float* dy_frag, float* da, int64_t n_windows, void* stream) {
+    return anysize_train_backward<false>(m, layer_size, wtpack, y_frag, stash, dy_frag, da, n_windows, stream, "cf_gru_anysize_train_backward");
+}
+
+// ---- training precision "bf16x3": the same two launches on bf16x3 packs (gen_gru_kernel<true, true>, gen_gru_bwd_kernel<true>) ----
+extern "C" int cf_gru_anysize_train_forward_x3(cf_model* m, int32_t layer_size, int32_t cin_blocks, const float* wpack_x3, const float* bpack,
+                                               const float* x_frag, float* y_frag, float* stash, int64_t n_windows, void* stream) {
+    return anysize_train_forward<true>(m, layer_size, cin_blocks, wpack_x3, bpack, x_frag, y_frag, stash, n_windows, stream,
+                                       "cf_gru_anysize_train_forward_x3");
+}
+
+extern "C" int cf_gru_anysize_train_backward_x3(cf_model* m, int32_t layer_size, const float* wtpack_x3, const float* y_frag, const float* stash,
+                                                const float* dy_frag, float* da, int64_t n_windows, void* stream) {
+    return anysize_train_backward<true>(m, layer_size, wtpack_x3, y_frag, stash, dy_frag, da, n_windows, stream,
+                                        "cf_gru_anysize_train_backward_x3");
+}
+
+static bool anysize_x3_sizes_ok(int32_t layer_size, int32_t cin_blocks) {
+    return layer_size >= 16 && layer_size <= 256 && (layer_size % 16) == 0 && cin_blocks >= 1 && cin_blocks <= 32;
+}
+
+extern "C" int cf_gru_anysize_x3_pack_floats(int32_t layer_size, int32_t cin_blocks, int64_t out[2]) {
+    if (!out) return fail(CF_ERR_INVALID, "cf_gru_anysize_x3_pack_floats: null output");
+    if (!anysize_x3_sizes_ok(layer_size, cin_blocks))
+        return fail(CF_ERR_INVALID, "cf_gru_anysize_x3_pack_floats: layer_size must be a multiple of 16 between 16 and 256, cin_blocks 1..32");
+    const int64_t h16 = layer_size / 16;
+    out[0] = 2 * 3 * h16 * (gen_x3_pad(cin_blocks) + gen_x3_pad((int)h16)) * 256;
+    out[1] = 2 * h16 * (gen_x3_pad((int)h16) + gen_x3_pad(2 * (int)h16)) * 256;
+    return CF_OK;
+}
+
+extern "C" int cf_gen_repack_x3(cf_model* m, int32_t layer_size, int32_t cin_blocks, int32_t transposed, const float* pack, float* pack_x3,
+                                void* stream) {
+    if (!m) return fail(CF_ERR_INVALID, "cf_gen_repack_x3: null model");
+    if (!pack || !pack_x3) return fail(CF_ERR_INVALID, "cf_gen_repack_x3: null buffer");
+    if (!anysize_x3_sizes_ok(layer_size, transposed ? 1 : cin_blocks))
+        return fail(CF_ERR_INVALID, "cf_gen_repack_x3: layer_size must be a multiple of 16 between 16 and 256, cin_blocks 1..32");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int h16 = layer_size / 16;
+    auto launch = [&](const float* src, float* dst, int dirs, int rows, int k0, int k1, int64_t src_stride, int64_t dst_stride) {
+        const int64_t threads = (int64_t)rows * ((gen_x3_pad(k0) + gen_x3_pad(k1)) / 2) * 64;
+        hipLaunchKernelGGL(gen_repack_x3_kernel, dim3((unsigned)((threads + 255) / 256), (unsigned)dirs), dim3(256), 0, s,
+                           reinterpret_cast<const f32x4*>(src), reinterpret_cast<f32x4*>(dst), rows, k0, k1, src_stride, dst_stride);
+    };
+    if (!transposed) {                                       // [2][3][H16] rows of [x: cin_blocks | h: H16]
+        launch(pack, pack_x3, 1, 6 * h16, cin_blocks, h16, 0, 0);
+    } else {                                                 // per direction Wc_h^T: H16 rows of [H16], then Wg_h^T: H16 rows of [2 H16]
+        const int kc = gen_x3_pad(h16), kg = gen_x3_pad(2 * h16);
+        const int64_t ss = (int64_t)3 * h16 * h16 * 64, ds = (int64_t)h16 * (kc + kg) * 64;      // f32x4 per direction
+        launch(pack, pack_x3, 2, h16, h16, 0, ss, ds);
+        HIP_TRY(hipGetLastError());
+        launch(pack + (int64_t)h16 * h16 * 256, pack_x3 + (int64_t)h16 * kc * 256, 2, h16, 2 * h16, 0, ss, ds);
+    }
     HIP_TRY(hipGetLastError());
     return CF_OK;
 }

@@ -5,7 +5,9 @@
 // previous layer's D tile fed back as the B operand), but with run-time sizes -- weights stream from global memory (L2 /
 // Infinity Cache resident: at most 2.4 MB per direction and layer) as pre-tiled A fragments instead of living in LDS, the
 // biGRU state of a tile (h, r.h, h') lives in LDS, and one launch computes one conv or one biGRU layer.
-// CF_PREC_BF16X3 runs the same kernels with bf16x3 matrix products (gen_dot_x3: gen_conv_kernel<true>, gen_gru_kernel<false, true>).
+// CF_PREC_BF16X3 runs the same kernels with bf16x3 matrix products (gen_dot_x3: gen_conv_kernel<true>, gen_gru_kernel<false, true>);
+// training precision "bf16x3" does so for the two recurrences only (gen_gru_kernel<true, true>, gen_gru_bwd_kernel<true>), on
+// packs that gen_repack_x3_kernel splits on the device after every optimizer step.
 // Included by catfish_hip.hip (needs f32x4, bf16x8, MFMA16, CF_T, CF_TILE, CF_GATE_SCALE, CF_CAND_SCALE).
 #pragma once
 
@@ -372,14 +374,13 @@ __global__ __launch_bounds__(256) void gen_conv_kernel(const f32x4* __restrict__
 // of the wave live in LDS ([H16][64] f32x4 each); only this wave touches them, in program order.
 // TRAIN: the activated gates r, u, c of every step are stashed for the backward pass (S: [tiles][35][2 dirs][3][H16][64]), the
 // buffers are the caller's (exactly n_tiles tiles: waves past the last tile exit, so no workgroup barriers in this variant).
-// X3 (inference only): the bf16x3 products (gen_dot_x3; weights [2][3][H16][gen_x3_pad(KBX) + gen_x3_pad(H16)][64] in
-// gen_pack_a_x3 order); state, epilogues and launch shapes as in fp32.
+// X3: the bf16x3 products (gen_dot_x3; weights [2][3][H16][gen_x3_pad(KBX) + gen_x3_pad(H16)][64] in gen_pack_a_x3 order, from
+// the host for inference and from gen_repack_x3_kernel for training); state, stash, epilogues and launch shapes as in fp32.
 template <bool TRAIN, bool X3>
 __global__ __launch_bounds__(512) void gen_gru_kernel(const f32x4* __restrict__ W /*[2 dirs][3: r, u, c][H16][KB][64]*/,
                                                       const f32x4* __restrict__ Bv /*[2][3][H16][64]*/, const f32x4* __restrict__ X /*[tiles][35][KBX][64]*/,
                                                       f32x4* Y /*[tiles][35][2 H16][64]*/, int H16, int KBX, int h_via_y, f32x4* __restrict__ S,
                                                       int n_tiles) {
-    static_assert(!(TRAIN && X3), "training runs in fp32");
     constexpr bool LOCKSTEP = CF_GEN_LOCKSTEP && !TRAIN;
     extern __shared__ f32x4 gen_lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;     // wave: uniform (SGPR)
@@ -697,9 +698,36 @@ __global__ __launch_bounds__(512) void gen_gru2_kernel(const f32x4* __restrict__
 
 // Matrix-vector helper of the backward pass: out[mo] = sum_k W[mo][k] . B[k] for M16 output tiles (four at a time, two when
 // M16 < 4), B a K16-block array of this wave in LDS; epi(mo, acc) once per output tile.
-template <typename EP>
+// X3: the bf16x3 products over rows of gen_x3_pad(K16) blocks in gen_pack_a_x3 order; no x part (KBX = 0: gen_dot_x3 never touches
+// xb), the padding pairs re-read B's last real tile against zero weights.
+template <bool X3, typename EP>
 __device__ __forceinline__ void gen_matvec(const f32x4* __restrict__ W /*uniform pointer [M16][K16][64]*/, int M16, int K16, const f32x4* B, EP epi, unsigned ln) {
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (X3) {
+        const size_t Kw = gen_x3_pad(K16);
+        if (M16 >= 4) {
+            for (int mo = 0; mo < M16; mo += 4) {
+                const int m1 = mo + 1 < M16 ? mo + 1 : mo, m2 = mo + 2 < M16 ? mo + 2 : mo, m3 = mo + 3 < M16 ? mo + 3 : mo;
+                f32x4 acc[4] = {z, z, z, z};
+                const f32x4* const w[4] = {W + mo * Kw * 64, W + m1 * Kw * 64, W + m2 * Kw * 64, W + m3 * Kw * 64};
+                gen_dot_x3<4, false>(acc, w, nullptr, 0, B, B, K16, ln);
+                epi(mo, acc[0]);
+                if (mo + 1 < M16) epi(m1, acc[1]);
+                if (mo + 2 < M16) epi(m2, acc[2]);
+                if (mo + 3 < M16) epi(m3, acc[3]);
+            }
+        } else {
+            for (int mo = 0; mo < M16; mo += 2) {
+                const int m1 = mo + 1 < M16 ? mo + 1 : mo;
+                f32x4 acc[2] = {z, z};
+                const f32x4* const w[2] = {W + mo * Kw * 64, W + m1 * Kw * 64};
+                gen_dot_x3<2, false>(acc, w, nullptr, 0, B, B, K16, ln);
+                epi(mo, acc[0]);
+                if (mo + 1 < M16) epi(m1, acc[1]);
+            }
+        }
+        return;
+    }
     if (M16 >= 4) {
         for (int mo = 0; mo < M16; mo += 4) {
             const int m1 = mo + 1 < M16 ? mo + 1 : mo, m2 = mo + 2 < M16 ? mo + 2 : mo, m3 = mo + 3 < M16 ? mo + 3 : mo;
@@ -729,7 +757,9 @@ __device__ __forceinline__ void gen_matvec(const f32x4* __restrict__ W /*uniform
 // (rnn_class.py:142-148 differentiated; the graph's gradient nodes of the GRU cell).  Output: the pre-activation gradients
 // DA [tiles][35][2][3: r, u, c][H16][64]; the input gradient (W_x^T da) and the weight gradients ([x; h]^T da) are plain GEMMs
 // over all (window, step) pairs and are left to the caller.  WT: per direction Wc_h^T [H16][H16][64] then Wg_h^T [H16][2 H16][64],
-// A-fragment order, unscaled.
+// A-fragment order, unscaled.  X3: the two matrix-vector products in bf16x3 (gen_matvec<true>), WT's rows padded to gen_x3_pad(H16)
+// and gen_x3_pad(2 H16) blocks in gen_pack_a_x3 order; dh, the da arrays and every elementwise term stay fp32.
+template <bool X3>
 __global__ __launch_bounds__(512) void gen_gru_bwd_kernel(const f32x4* __restrict__ WT, const f32x4* __restrict__ Y /*[tiles][35][2 H16][64]*/,
                                                           const f32x4* __restrict__ S, const f32x4* __restrict__ DY /*[tiles][35][2 H16][64]*/,
                                                           f32x4* __restrict__ DA, int n_tiles, int H16) {
@@ -743,8 +773,9 @@ __global__ __launch_bounds__(512) void gen_gru_bwd_kernel(const f32x4* __restric
     f32x4* dac = dh + (size_t)H16 * 64;
     f32x4* dar = dac + (size_t)H16 * 64;
     f32x4* dau = dar + (size_t)H16 * 64;
-    const f32x4* WcT = WT + ((size_t)dir * 3 * H16 * H16) * 64;            // uniform: the lane is added at the access
-    const f32x4* WgT = WcT + (size_t)H16 * H16 * 64;
+    // uniform pointers: the lane is added at the access (X3: rows of gen_x3_pad(H16) and gen_x3_pad(2 H16) blocks)
+    const f32x4* WcT = X3 ? WT + ((size_t)dir * H16 * (gen_x3_pad(H16) + gen_x3_pad(2 * H16))) * 64 : WT + ((size_t)dir * 3 * H16 * H16) * 64;
+    const f32x4* WgT = X3 ? WcT + (size_t)H16 * gen_x3_pad(H16) * 64 : WcT + (size_t)H16 * H16 * 64;
     for (int mo = 0; mo < H16; ++mo) dh[mo * 64] = (f32x4){0.f, 0.f, 0.f, 0.f};
     for (int s = 0; s < CF_T; ++s) {
         const int t = dir ? s : CF_T - 1 - s;                     // the forward pass ran 0..34 (dir 0) / 34..0 (dir 1)
@@ -766,15 +797,40 @@ __global__ __launch_bounds__(512) void gen_gru_bwd_kernel(const f32x4* __restric
             da[(2 * H16 + mo) * 64] = ac;
             da[(H16 + mo) * 64] = au;
         }
-        gen_matvec(WcT, H16, H16, dac, [&](int mo, const f32x4& drh) {
+        gen_matvec<X3>(WcT, H16, H16, dac, [&](int mo, const f32x4& drh) {
             const f32x4 hp = has_prev ? yp[mo * 64] : zero, r = st[mo * 64];
             const f32x4 ar = drh * hp * r * (1.0f - r);
             dh[mo * 64] = dh[mo * 64] + drh * r;
             dar[mo * 64] = ar;
             da[mo * 64] = ar;
         }, ln);
-        gen_matvec(WgT, H16, 2 * H16, dar, [&](int mo, const f32x4& g) { dh[mo * 64] = dh[mo * 64] + g; }, ln);
+        gen_matvec<X3>(WgT, H16, 2 * H16, dar, [&](int mo, const f32x4& g) { dh[mo * 64] = dh[mo * 64] + g; }, ln);
     }
+}
+
+// ---- fp32 A-fragment pack -> bf16x3 pack, on the device (training: the weights change every step) ---------------------------------
+// src [dirs][rows][k0 + k1][64] f32x4 (the packs of cf_gru_anysize_train_forward / _backward), dst [dirs][rows][gen_x3_pad(k0) +
+// gen_x3_pad(k1)][64] in gen_pack_a_x3 order: per row and K segment, pair p takes source tiles a = 2p, b = 2p + 1 (zeros past the
+// segment), hi = bf16(a | b), lo = bf16(v - hi) with gen_split's rounding, hi to slot 2p and lo to slot 2p + 1 of the padded
+// segment.  One thread per (row, pair, lane), blockIdx.y = dir; every destination slot is written, padding included.
+__global__ __launch_bounds__(256) void gen_repack_x3_kernel(const f32x4* __restrict__ src, f32x4* __restrict__ dst, int rows, int k0, int k1,
+                                                            int64_t src_dir_stride, int64_t dst_dir_stride) {
+    const int P0 = gen_x3_pad(k0) >> 1, P = P0 + (gen_x3_pad(k1) >> 1);
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)rows * P * 64) return;
+    const int lane = (int)(idx & 63);
+    const int64_t rp = idx >> 6, row = rp / P;
+    const int pr = (int)(rp - row * P);
+    const bool second = pr >= P0;
+    const int p = second ? pr - P0 : pr, k = second ? k1 : k0;
+    const f32x4* s = src + blockIdx.y * src_dir_stride + (row * (k0 + k1) + (second ? k0 : 0)) * 64 + lane;
+    f32x4* d = dst + blockIdx.y * dst_dir_stride + (row * 2 * P + (second ? 2 * P0 : 0) + 2 * p) * 64 + lane;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const f32x4 a = 2 * p < k ? s[(2 * p) * 64] : z, b = 2 * p + 1 < k ? s[(2 * p + 1) * 64] : z;
+    bf16x8 hi, lo;
+    gen_split(a, b, hi, lo);
+    d[0] = __builtin_bit_cast(f32x4, hi);
+    d[64] = __builtin_bit_cast(f32x4, lo);
 }
 
 // ---- dense 2H -> 1 + sigmoid (rnn_class.py:178-183, :84): one wave per (tile, position) ------------------------------------------

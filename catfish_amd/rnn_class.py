@@ -28,6 +28,8 @@ class RNN(object):
         self.keep_prob_test = 1.0
         # None: Trainer's default; True: the whole training step on the HIP kernels at any geometry (anysize_step.py)
         self.native_training = kwargs.get("native_training", None)
+        # "fp32" | "bf16x3" (the any-size training recurrences on split bf16 products); ``precision`` below is inference only
+        self.training_precision = kwargs.get("training_precision", "fp32")
 
         # set parameters (rnn_class.py:25-32)
         self.n_inputs = 1
@@ -318,7 +320,8 @@ class RNN(object):
             self._trainer = Trainer(self.weights, self.n_layers, self.n_layers_res_, self.optimizer_choice,
                                     self.learning_rate, self.keep_prob, seed=self.train_seed,
                                     optimizer_state=getattr(self, "optimizer_state", None),
-                                    native=getattr(self, "native_training", None))
+                                    native=getattr(self, "native_training", None),
+                                    precision=getattr(self, "training_precision", "fp32"))
         return self._trainer
 
     def train_network_steps(self, db, n_steps):

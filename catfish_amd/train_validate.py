@@ -442,6 +442,7 @@ def main(argv):
     reads (the reference takes a ZODB file); hyper-parameters are a random draw as in the reference (:328) unless
     CATFISH_SHIPPED_HPARAMS=1 asks for the shipped network's (the reference's commented block :329-332).
     CATFISH_NATIVE_TRAINING=1 trains with ``native_training=True`` (the whole step on the HIP kernels at any geometry).
+    CATFISH_TRAINING_PRECISION=bf16x3 trains with ``training_precision="bf16x3"`` (any geometry but the shipped one).
     CATFISH_DEVICE_DB=1 keeps the training windows on the card (``device_db.DeviceExampleDb``): the steps between two
     checkpoint rounds run back to back, each drawing its own batch.
     CATFISH_DEVICE_VALIDATION=1 keeps the validation reads on the card too (``device_validation.DeviceValidationSet``, loaded
@@ -458,6 +459,8 @@ def main(argv):
         else generate_random_hyperparameters(kind)
     if os.environ.get("CATFISH_NATIVE_TRAINING") == "1":          # the whole training step on the HIP kernels at any geometry
         hparams["native_training"] = True
+    if os.environ.get("CATFISH_TRAINING_PRECISION"):             # "bf16x3": split bf16 products in the any-size training recurrences
+        hparams["training_precision"] = os.environ["CATFISH_TRAINING_PRECISION"]
     network = build_model(kind, save=True, **hparams)
     network.initialize_network()
     print("Loading training database..")

@@ -26,9 +26,10 @@ def _names(n_layers, n_layers_res):
 class TorchResNetRNN(object):
     """Differentiable restatement of the ResNetRNN graph; parameters are a dict of torch tensors."""
 
-    def __init__(self, weights, n_layers, n_layers_res, device="cpu", dtype=None):
+    def __init__(self, weights, n_layers, n_layers_res, device="cpu", dtype=None, precision="fp32"):
         import torch
         self.torch = torch
+        self.precision = precision      # of the any-size HIP recurrences in _logits_anysize ("fp32" | "bf16x3"); pure torch ignores it
         self.dtype = dtype or torch.float32
         self.device = torch.device(device)
         self.n_layers = int(n_layers)
@@ -141,7 +142,7 @@ class TorchResNetRNN(object):
         for layer in range(self.n_layers):
             params8 = [p[(pre % (layer, d)) + k] for d in ("fw", "bw")
                        for k in ("/gates/kernel", "/gates/bias", "/candidate/kernel", "/candidate/bias")]
-            a = anysize_bigru(a, params8, engine)
+            a = anysize_bigru(a, params8, engine, precision=self.precision)
             if keep_prob < 1.0:                          # DropoutWrapper(output_keep_prob), one draw per direction as in the torch path
                 hsz = a.shape[2] // 2
                 parts = []
@@ -280,11 +281,17 @@ class Trainer(object):
     into a HIP graph (``torch.cuda.CUDAGraph``) and replayed per batch; batches are copied into static input buffers.
     Dropout masks inside the graph come from torch's default (graph-safe) CUDA generator.  ``native=False`` (and the CPU)
     run the torch-autograd restatement of the same graph -- the reference the native step is tested against.
+
+    ``precision="bf16x3"`` (opt-in; the default "fp32" changes nothing) evaluates the matrix products on the serial chain of the
+    any-size biGRU recurrences, forward and backward, as split bf16 products; everything else stays fp32.  It exists where those
+    kernels train: on a GPU, in float32, at a geometry other than the shipped 64 / 32, with ``native`` None or True.
     """
 
     def __init__(self, weights, n_layers, n_layers_res, optimizer_choice, learning_rate, keep_prob, device=None,
-                 seed=None, use_graph=None, native=None, optimizer_state=None, dtype=None, loss_log_capacity=4096):
+                 seed=None, use_graph=None, native=None, optimizer_state=None, dtype=None, loss_log_capacity=4096, precision="fp32"):
         import torch
+        from .anysize_train import check_precision
+        self.precision = check_precision(precision)
         if int(loss_log_capacity) < 1:
             raise ValueError("loss_log_capacity must be at least 1")
         self.loss_log_capacity = int(loss_log_capacity)      # train_steps: losses kept on the card between two read-backs
@@ -294,7 +301,7 @@ class Trainer(object):
                 # no silent CPU fallback: the torch-CPU mode exists as the reference for tests and is opt-in
                 raise RuntimeError("Trainer: no HIP device visible; pass device='cpu' explicitly for the torch reference mode")
             device = "cuda"
-        self.net = TorchResNetRNN(weights, n_layers, n_layers_res, device=device, dtype=dtype)
+        self.net = TorchResNetRNN(weights, n_layers, n_layers_res, device=device, dtype=dtype, precision=self.precision)
         self.opt = TFOptimizer(self.net.trainable(), optimizer_choice, learning_rate)
         if optimizer_state:
             self.opt.load_state_tf(optimizer_state)
@@ -310,6 +317,13 @@ class Trainer(object):
         h = int(np.asarray(weights["stack_bidirectional_rnn/cell_0/bidirectional_rnn/fw/gru_cell/candidate/bias"]).shape[0])
         c = int(np.asarray(weights["conv1d/bias"]).shape[0]) if n_layers_res > 0 else 32
         shipped = (h == 64 and c == 32)
+        if self.precision == "bf16x3":
+            why = ("the tuned training kernels of the shipped 64 / 32 geometry are fp32" if shipped else
+                   "it runs on the HIP kernels: device='cpu' has none" if self.net.device.type != "cuda" else
+                   "native=False is the pure-torch reference" if native is not None and not native else
+                   "the training kernels are float32 (dtype %s)" % self.net.dtype if self.net.dtype != torch.float32 else None)
+            if why:
+                raise ValueError("precision='bf16x3' is a mode of the any-size training recurrences; %s" % why)
         if native and (self.net.device.type != "cuda" or self.net.dtype != torch.float32):
             raise ValueError("native=True runs the fp32 HIP training kernels: it needs device='cuda' and dtype float32")
         # native=True at any other geometry (RNN or ResNetRNN type): the whole step on the run-time-sized kernels (anysize_step.py)
@@ -328,7 +342,7 @@ class Trainer(object):
                                     max_windows_per_pass=256, **sizes)
         if native_any:
             from .anysize_step import AnySizeTrainStep
-            self.step_impl = AnySizeTrainStep(self.net, self.opt, self.engine, self.keep_prob, seed=seed)
+            self.step_impl = AnySizeTrainStep(self.net, self.opt, self.engine, self.keep_prob, seed=seed, precision=self.precision)
         elif self.native and n_layers_res > 0 and self.net.dtype == torch.float32:
             from .native_step import NativeTrainStep
             self.step_impl = NativeTrainStep(self.net, self.opt, self.engine, self.keep_prob, seed=seed)

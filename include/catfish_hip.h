@@ -339,6 +339,26 @@ int cf_gru_anysize_train_backward(cf_model* m, int32_t layer_size, const float* 
  * workgroup runs `waves` tiles of one direction, so grid x * waves >= tiles and the last workgroup may be partly empty.  For
  * tests and tools that must know which regime a size runs in; same argument checks as the two calls. */
 int cf_gru_anysize_train_shape(const cf_model* m, int32_t layer_size, int64_t n_windows, int64_t out[8]);
+/* Training precision "bf16x3" for those two calls: only the matrix products on the serial chain -- forward [x | h] W_g and
+ * [x | r.h] W_c, backward Wc_h^T da_c and Wg_h^T [da_r; da_u] -- are evaluated as a_hi w_hi + a_lo w_hi + a_hi w_lo on
+ * v_mfma_f32_16x16x32_bf16 (hi = bf16(v), lo = bf16(v - hi)); state, gate activations, stash, da and all accumulation stay fp32,
+ * and so does everything GEMM-shaped around them.  Same buffers, launch shapes, argument checks and messages as the fp32 calls,
+ * except that the weights come as bf16x3 packs made on the device from the fp32 ones (the weights change every step):
+ *   the repack call     one layer's wpack (transposed = 0: rows [2][3][H/16] of K segments [cin_blocks | H/16]) or wtpack
+ *                       (transposed = 1: per direction H/16 rows of [H/16], then H/16 rows of [2 H/16]; cin_blocks is ignored) ->
+ *                       pack_x3.  Every K segment of k tiles is padded to k' = (k + 3) & ~3; pair p of a segment takes source
+ *                       tiles a = 2p, b = 2p + 1 (zeros past k) and writes, per lane, hi = bf16(a[0..3] | b[0..3]) to the
+ *                       16-byte slot 2p and lo = bf16(v - hi) to slot 2p + 1 of the padded row (round to nearest even).
+ *   the size query      out = {floats of pack_x3 for wpack, for wtpack}: 2 * 3 * H/16 * (cin_blocks' + H/16') * 256 and
+ *                       2 * H/16 * (H/16' + (2 H/16)') * 256.
+ * bpack is the fp32 call's.  An x3 pack must be rebuilt whenever its fp32 pack changes. */
+int cf_gru_anysize_x3_pack_floats(int32_t layer_size, int32_t cin_blocks, int64_t out[2]);
+int cf_gen_repack_x3(cf_model* m, int32_t layer_size, int32_t cin_blocks, int32_t transposed, const float* pack, float* pack_x3,
+                     void* stream);
+int cf_gru_anysize_train_forward_x3(cf_model* m, int32_t layer_size, int32_t cin_blocks, const float* wpack_x3, const float* bpack,
+                                    const float* x_frag, float* y_frag, float* stash, int64_t n_windows, void* stream);
+int cf_gru_anysize_train_backward_x3(cf_model* m, int32_t layer_size, const float* wtpack_x3, const float* y_frag, const float* stash,
+                                     const float* dy_frag, float* da, int64_t n_windows, void* stream);
 /* The same two calls with the layer's OUTPUT dropout (DropoutWrapper(output_keep_prob), rnn_class.py:151-154) done inside the
  * kernels, no mask tensor: whether an output element is kept is a hash of (seed, layer, *step_count, element index).  The
  * forward additionally writes y_drop_frag = y * mask / keep_prob (what the next layer or the dense head reads; y_frag itself stays
