@@ -423,6 +423,11 @@ __device__ __forceinline__ void gru_stage_weights(float* lds, const float* __res
 // [s_begin, s_end) is the range of steps to run (gru_balance.hpp: a tile may be cut in time between two waves).  A piece that
 // starts late takes h from the hand-off slot HO ([4][64] f32x4, register layout) instead of the zero state, one that ends early
 // leaves h there; the steps themselves do not know.  Every other caller runs the whole tile and compiles to what it was.
+// SKIP0 (gru_layer_kernel only; switched by the run-time flag skip0, so that the step body exists once): step 0 of a tile runs
+// on the zero state, where the 128 gate MFMAs Wh_g h and the 64 candidate MFMAs Wh_c (r*h) add exact zeros and r is never used:
+// a wave-uniform branch goes round them.  Same bits: fma(w, 0, acc) == acc for every finite w except that an acc of -0 would
+// have become +0, and the sigmoid or tanh that follows maps both zeros to one value, so h and every output are unchanged.
+// NOT covered: non-finite weights (w * 0 = NaN would have reached h).  The training forward (STASH) stores r and never skips.
 // One k-step region: the A-fragment reads of the NEXT k-step go out before this k-step's MFMAs (left alone the
 // scheduler sinks them behind most of the MFMAs, which leaves ~100 cycles between a read and its first use).
 #ifndef CF_SCHED_DS_FIRST
@@ -436,11 +441,11 @@ __device__ __forceinline__ void gru_stage_weights(float* lds, const float* __res
 #else
 #define CF_KSTEP_SCHED(nds, nmfma) __builtin_amdgcn_sched_barrier(0)
 #endif
-template <int CIN, bool LAST, bool STASH = false>
+template <int CIN, bool LAST, bool STASH = false, bool SKIP0 = false>
 __device__ __forceinline__ void gru_tile(const float* lds, int lane, int dir, int tile, const f32x4* __restrict__ X,
                                          f32x4* __restrict__ Y, float* __restrict__ P, int n_tiles,
                                          f32x4* __restrict__ S = nullptr, f32x4* __restrict__ YD = nullptr, cf_dropout drop = cf_dropout(),
-                                         int s_begin = 0, int s_end = CF_T, f32x4* HO = nullptr) {
+                                         int s_begin = 0, int s_end = CF_T, f32x4* HO = nullptr, bool skip0 = false) {
     const uint32_t drop_key = (STASH && YD) ? cf_drop_key(drop) : 0u;
     constexpr int KGX = CIN / 16;   // f32x4 registers of x per lane and step
     constexpr int KSX = CIN / 4;    // k-steps of the x part
@@ -509,6 +514,16 @@ __device__ __forceinline__ void gru_tile(const float* lds, int lane, int dir, in
 #pragma unroll
                 for (int g = 0; g < KGX; ++g) if (!(CF_ABLATE & 2)) xc[g] = src[g * 64];
             }
+            // step 0 on the zero state (SKIP0 above): nothing below changes acc[4..11] or needs r.  The fragments already fetched
+            // for the gate part are dropped; the next step starts its prefetch ring from k-step 0 like every step.
+            // (the empty asm pins the accumulators where the x part left them: without it the register allocator renames them
+            // ahead of the branch and the Cin = 32 LAST instance goes from 122 to 132 VGPRs, past four waves per SIMD)
+            const bool run_h = !SKIP0 || !(skip0 && s == 0);
+            if constexpr (SKIP0) {
+#pragma unroll
+                for (int mo = 0; mo < 12; ++mo) asm volatile("" : "+v"(acc[mo]));
+            }
+            if (run_h) {
             // h part of the gates: [r | u] += Wh_g^T h          (gru_cell/MatMul)
 #pragma unroll
             for (int ks = 0; ks < 16; ++ks) {
@@ -546,6 +561,7 @@ __device__ __forceinline__ void gru_tile(const float* lds, int lane, int dir, in
                 CF_KSTEP_SCHED(1, 4);
                 ac[0] = an[0];
                 if (PF == 2) an[0] = a2[0];
+            }
             }
             // h' = u*h + (1-u)*c                                  (gru_cell/mul_1, sub, mul_2, add)
 #pragma unroll
@@ -619,6 +635,34 @@ __device__ __forceinline__ void cf_handoff_wait(unsigned* flag, int lane, unsign
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
+// The same hand-off across a workgroup boundary (grid-wide schedule, gru_balance.hpp): producer and consumer sit on different CUs
+// and maybe different XCDs, so the flag is a word in global memory and both sides work at agent scope, as gru_fused_worker does.
+// Each flag has ONE consumer, which reads it once, as the last thing its wave does before its last piece, and stores 0 back after
+// the acquire: the buffer is zeroed at allocation and by cf_clear_error and needs neither a memset nor an epoch per launch (a
+// captured graph would replay a stale epoch).  A timeout sets the sticky error word and the wave carries on, so the grid drains;
+// the flag it may leave set is what cf_clear_error zeroes.
+__device__ __forceinline__ void cf_handoff_publish_agent(unsigned* flag) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store(flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void cf_handoff_wait_agent(unsigned* flag, int lane, unsigned* err) {
+    if (lane == 0) {
+        bool ok = false;
+        for (int it = 0; it < 1000000 && !ok; ++it) {
+            ok = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u;
+            if (!ok) __builtin_amdgcn_s_sleep(16);
+        }
+        if (!ok && err) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_store(flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// `balance` of gru_layer_kernel: the schedule in the low bits, CF_GRU_RUN_ZERO_PRODUCTS on top of it
+enum { CF_GRU_SCHED_MASK = 3, CF_GRU_RUN_ZERO_PRODUCTS = 4 };
 
 template <int CIN, bool LAST>
 __global__ __launch_bounds__(512, 2) void gru_layer_kernel(const float* __restrict__ wpack,  // [2][gru_pack_floats(CIN)]
@@ -626,8 +670,9 @@ __global__ __launch_bounds__(512, 2) void gru_layer_kernel(const float* __restri
                                                            f32x4* __restrict__ Y,            // [tile][t][8][lane]
                                                            float* __restrict__ P,            // [2][tile][t][16]
                                                            int n_tiles,
-                                                           int balance,                      // schedule, chosen by launch_gru
+                                                           int balance_arg,                  // schedule, chosen by launch_gru
                                                            f32x4* hand,                      // [2][gridDim.x][8][4][64] hand-off slots
+                                                           unsigned* gflags,                 // [2][gridDim.x] boundary flags (grid-wide)
                                                            unsigned* err) {                  // sticky: a hand-off wait timed out
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int dir = blockIdx.y;
@@ -640,19 +685,28 @@ __global__ __launch_bounds__(512, 2) void gru_layer_kernel(const float* __restri
     const int nwaves = blockDim.x >> 6;
     // Every workgroup takes an equal contiguous share of the tiles (+-1).  Round-robin deals whole tiles to the waves; the
     // balanced schedule deals equal shares of tiles x 35 steps (gru_balance.hpp).  Either way a wave runs a list of pieces
-    // (tile, [s_begin, s_end)) through ONE call site: the step body is 576 MFMAs unrolled.
-    const int t0 = (int)((int64_t)blockIdx.x * n_tiles / gridDim.x);
+    // (tile, [s_begin, s_end)) through ONE call site: the step body is 576 MFMAs unrolled.  balance == 2 is the grid-wide
+    // schedule: the same shares with the direction's tiles as the "workgroup" and the global wave index as the "wave".
+    const int balance = balance_arg & CF_GRU_SCHED_MASK;
+    const bool skip0 = !(balance_arg & CF_GRU_RUN_ZERO_PRODUCTS);
+    int t0 = (int)((int64_t)blockIdx.x * n_tiles / gridDim.x);
     const int t1 = (int)((int64_t)(blockIdx.x + 1) * n_tiles / gridDim.x);
     cf_gru_share sh;
     int n_pieces;
-    if (balance) {
+    if (balance == 2) {
+        sh = cf_gru_balanced_share(n_tiles, (int)gridDim.x * nwaves, (int)blockIdx.x * nwaves + wave, CF_T);
+        n_pieces = (sh.head_end > 0) + sh.whole_count + (sh.tail_begin < CF_T);
+        t0 = 0;
+    } else if (balance) {
         sh = cf_gru_balanced_share(t1 - t0, nwaves, wave, CF_T);
         n_pieces = (sh.head_end > 0) + sh.whole_count + (sh.tail_begin < CF_T);
     } else {
         sh.head_tile = sh.head_end = 0; sh.whole_first = sh.whole_count = 0; sh.tail_tile = 0; sh.tail_begin = CF_T;
         n_pieces = t1 - t0 > wave ? (t1 - t0 - wave + nwaves - 1) / nwaves : 0;
     }
+    // slot w of workgroup b holds the h that wave w of b hands on; the wave before wave 0 is the last wave of workgroup b - 1
     f32x4* slots = hand + ((size_t)(dir * gridDim.x + blockIdx.x) * CF_GRU_MAX_WAVES) * 4 * 64;
+    unsigned* gflag = gflags + dir * gridDim.x + blockIdx.x;                       // set by this workgroup's last wave
     const int has_head = balance && sh.head_end > 0;
     for (int i = 0; i < n_pieces; ++i) {
         int tile, s_begin = 0, s_end = CF_T;
@@ -664,11 +718,20 @@ __global__ __launch_bounds__(512, 2) void gru_layer_kernel(const float* __restri
         } else if (i < has_head + sh.whole_count) {
             tile = t0 + sh.whole_first + (i - has_head);
         } else {                                            // the tail last: the previous wave's head is long over
-            tile = t0 + sh.tail_tile; s_begin = sh.tail_begin; ho = slots + (wave - 1) * 4 * 64;
-            cf_handoff_wait(flags + (wave - 1), lane, err);
+            tile = t0 + sh.tail_tile; s_begin = sh.tail_begin;
+            if (wave > 0) {
+                ho = slots + (wave - 1) * 4 * 64;
+                cf_handoff_wait(flags + (wave - 1), lane, err);
+            } else {                                        // grid-wide only: wave 0 of a workgroup has no tail otherwise
+                ho = slots - (CF_GRU_MAX_WAVES - (nwaves - 1)) * 4 * 64;
+                cf_handoff_wait_agent(gflag - 1, lane, err);
+            }
         }
-        gru_tile<CIN, LAST>(lds, lane, dir, tile, X, Y, P, n_tiles, nullptr, nullptr, cf_dropout(), s_begin, s_end, ho);
-        if (s_end < CF_T) cf_handoff_publish(flags + wave);
+        gru_tile<CIN, LAST, false, true>(lds, lane, dir, tile, X, Y, P, n_tiles, nullptr, nullptr, cf_dropout(), s_begin, s_end, ho, skip0);
+        if (s_end < CF_T) {                                 // (a workgroup's last wave has a head only in the grid-wide schedule)
+            if (wave < nwaves - 1) cf_handoff_publish(flags + wave);
+            else cf_handoff_publish_agent(gflag);
+        }
     }
 }
 
@@ -1077,6 +1140,7 @@ struct cf_model {
         float* d_p = nullptr;                 // dense partials [2][tiles][35][16]
         unsigned* d_flags = nullptr;          // fused launch: [n_layers][groups][2] completion flags
         float* d_hand = nullptr;              // balanced biGRU schedule: h hand-off slots [2 dirs][workgroups][8 waves][4][64] f32x4
+        unsigned* d_hand_flags = nullptr;     // grid-wide schedule: boundary flags [2 dirs][workgroups]; zero between launches
         hipStream_t stream = nullptr;
         hipEvent_t done = nullptr;
         int64_t last_windows = 0;             // windows of the last pass (debug hook)
@@ -1105,6 +1169,9 @@ struct cf_model {
     double prof_ms[CF_PROF_SLOTS] = {0};
     int64_t prof_n[CF_PROF_SLOTS] = {0};
 };
+
+// boundary flags of the grid-wide biGRU schedule: at most two workgroups per CU and direction (launch_gru), padded to 16 bytes
+static size_t cf_hand_flag_bytes(int n_cu) { return ((size_t)2 * (2 * std::max(1, n_cu / 2)) * sizeof(unsigned) + 15) / 16 * 16; }
 
 // ---- weight packing ----------------------------------------------------------------------
 // Every packed fp32 element is a TERM over the checkpoint's inference tensors:
@@ -1375,6 +1442,7 @@ extern "C" void cf_model_destroy(cf_model* m) {
         if (sl.d_p) (void)hipFree(sl.d_p);
         if (sl.d_flags) (void)hipFree(sl.d_flags);
         if (sl.d_hand) (void)hipFree(sl.d_hand);
+        if (sl.d_hand_flags) (void)hipFree(sl.d_hand_flags);
         if (sl.stream) (void)hipStreamDestroy(sl.stream);
         if (sl.done) (void)hipEventDestroy(sl.done);
     }
@@ -1499,6 +1567,9 @@ extern "C" int cf_model_create(const cf_weights* w, const cf_hparams* hp, int de
             if (e == hipSuccess) e = hipMalloc((void**)&sl.d_flags, (size_t)3 * ((m->cap_tiles + 7) / 8) * 2 * sizeof(unsigned) + 64);
             // (never memset: a slot is written by a head piece before the tail piece of the same launch reads it)
             if (e == hipSuccess && m->np == 0) e = hipMalloc((void**)&sl.d_hand, hand_bytes);
+            // zeroed HERE and by cf_clear_error only: every flag's one consumer stores 0 back (cf_handoff_wait_agent)
+            if (e == hipSuccess && m->np == 0) e = hipMalloc((void**)&sl.d_hand_flags, cf_hand_flag_bytes(m->n_cu));
+            if (e == hipSuccess && m->np == 0) e = hipMemset(sl.d_hand_flags, 0, cf_hand_flag_bytes(m->n_cu));
             if (e == hipSuccess && n_slots > 1) e = hipStreamCreateWithFlags(&sl.stream, hipStreamNonBlocking);
             if (e == hipSuccess && n_slots > 1) e = hipEventCreateWithFlags(&sl.done, hipEventDisableTiming);
         }
@@ -1592,6 +1663,13 @@ static int prof_end(cf_model* m, hipStream_t s, size_t idx) {
     return CF_OK;
 }
 
+// CATFISH_GRU_GX behind the debug switch: run the biGRU throughput kernel on that many 8-wave workgroups per direction whatever
+// the size of the call, so that a test reaches a workgroup boundary of the grid-wide schedule with a few dozen tiles; read per launch.
+static int cf_forced_gx(const cf_model* m) {
+    const char* v = cf_knob("CATFISH_GRU_GX");
+    return v ? std::max(0, std::min(atoi(v), 2 * std::max(1, m->n_cu / 2))) : 0;
+}
+
 // Waves per workgroup: 8 (two per SIMD) when the pass fills the chip; fewer for small calls (a single read is
 // 8 tiles x 2 directions) so that the tiles spread over more CUs instead of sharing SIMDs -- the 35-step
 // chain is latency-bound there.
@@ -1603,6 +1681,7 @@ static int pick_waves(int n_tile_tasks, int n_cu) {
 // latency mode: up to two rounds of one (tile, direction) per CU (0.35 units each) beat one wave per tile (1 unit)
 static bool use_coop(const cf_model* m, int n_tiles) {
     static const int coop_env = cf_knob("CATFISH_COOP") ? atoi(cf_knob("CATFISH_COOP")) : -1;      // A/B knob for tools/
+    if (cf_forced_gx(m) > 0) return false;
     const bool coop = coop_env >= 0 ? coop_env != 0 : n_tiles <= m->n_cu;
     return coop && !(CF_ABLATE & 4) && n_tiles <= m->n_cu;      // (the raw dense-partial buffer is sized for n_cu tiles)
 }
@@ -1629,7 +1708,8 @@ static void launch_xproj(cf_model* m, const float* wpack, const float* X, int n_
 
 template <int CIN, bool LAST>
 static int launch_gru(cf_model* m, const float* wpack, const float* X, float* Y, float* P, int n_tiles, hipStream_t s, int slot,
-                      float* hand = nullptr) {      // hand-off slots of the balanced schedule (Slot::d_hand); none: round-robin
+                      float* hand = nullptr,        // hand-off slots of the balanced schedule (Slot::d_hand); none: round-robin
+                      unsigned* hand_flags = nullptr) {     // boundary flags of the grid-wide schedule (Slot::d_hand_flags)
     if (use_coop(m, n_tiles)) {
         size_t pi = 0;
         int rc = prof_begin(m, slot, s, &pi);
@@ -1647,12 +1727,14 @@ static int launch_gru(cf_model* m, const float* wpack, const float* X, float* Y,
     }
     static const int waves_env = cf_knob("CATFISH_WAVES") ? atoi(cf_knob("CATFISH_WAVES")) : 0;     // A/B knob for tools/
     // (12 waves = 3 per SIMD measured +0.3 % on the Cin = 128 layers and costs the Cin = 32 layer its second workgroup per CU)
-    const int waves = waves_env > 0 ? std::min(waves_env, 8) : ((CF_ABLATE & 4) ? 4 : pick_waves(2 * n_tiles, m->n_cu));
+    const int gx_env = cf_forced_gx(m);
+    const int waves = gx_env > 0 ? 8 : waves_env > 0 ? std::min(waves_env, 8) : ((CF_ABLATE & 4) ? 4 : pick_waves(2 * n_tiles, m->n_cu));
     const int groups = (n_tiles + waves - 1) / waves;             // one workgroup pass = one tile per wave
     int per_dir = m->n_cu / 2 > 0 ? m->n_cu / 2 : 1;            // persistent: half the CUs per direction
     constexpr int lds_bytes = gru_pack_floats(CIN) * 4;
     if (lds_bytes <= 80 * 1024) per_dir *= 2;                   // two workgroups fit per CU
     int gx = groups < per_dir ? groups : per_dir;
+    if (gx_env > 0) gx = std::min(gx_env, groups);
     size_t pi = 0;
     int rc = prof_begin(m, slot, s, &pi);
     if (rc != CF_OK) return rc;
@@ -1661,23 +1743,27 @@ static int launch_gru(cf_model* m, const float* wpack, const float* X, float* Y,
     // per CU has a second candidate: ONE balanced workgroup per CU (at the benchmark's 1888 tiles, 7 or 8 tiles on 8 waves cannot be
     // balanced inside a workgroup, 14 or 15 can: 132 steps against 140; measured).  CATFISH_GRU_BALANCE behind
     // the debug switch forces a schedule wherever it exists, for tests and A/B: 0 round-robin, 1 balanced on the usual grid,
-    // 2 balanced on the one-workgroup-per-CU grid; read per launch.
+    // 2 balanced on the one-workgroup-per-CU grid, 3 grid-wide; read per launch.  The grid-wide schedule (shares dealt over all
+    // waves of a direction, h handed across workgroup boundaries through Slot::d_hand_flags) is one more candidate on either grid,
+    // taken only where it beats all of the above: 130 against 132 steps at the benchmark's size, nothing at 1024 or 2048 tiles.
+    // cf_gru_choose is that decision, shared with the CPU tests.  CATFISH_GRU_ZERO_PRODUCTS=1 (debug switch, read per launch) runs
+    // step 0's products with the zero state instead of skipping them (gru_tile), for the bit-identity test and A/B.
     int balance = 0;
-    if (hand) {
+    if (hand && hand_flags) {
         const int wg_per_cu = std::max(1, (2 * gx + m->n_cu - 1) / m->n_cu);
-        const int gx_one = std::max(1, m->n_cu / 2);
-        const int load_rr = cf_gru_grid_load(n_tiles, gx, waves, wg_per_cu, CF_T, 0);
-        const int load_bal = cf_gru_grid_load(n_tiles, gx, waves, wg_per_cu, CF_T, 1);
-        const int load_one = gx > gx_one ? cf_gru_grid_load(n_tiles, gx_one, waves, 1, CF_T, 1) : -1;
+        const int gx_one = gx_env > 0 ? 0 : std::max(1, m->n_cu / 2);
         const char* env = cf_knob("CATFISH_GRU_BALANCE");
-        const int forced = env ? atoi(env) : -1;
-        int best = load_rr;
-        if (forced < 0 ? (load_bal >= 0 && load_bal < best) : (forced >= 1 && load_bal >= 0)) { balance = 1; best = load_bal; }
-        if (forced < 0 ? (load_one >= 0 && load_one < best) : (forced == 2 && load_one >= 0)) { balance = 1; gx = gx_one; }
+        const cf_gru_choice c = cf_gru_choose(n_tiles, gx, gx_one, waves, wg_per_cu, CF_T, env ? atoi(env) : -1);
+        balance = c.balance;
+        gx = c.gx;
+        const char* zp = cf_knob("CATFISH_GRU_ZERO_PRODUCTS");
+        if (zp && atoi(zp) != 0) balance |= CF_GRU_RUN_ZERO_PRODUCTS;
+    } else {
+        balance = CF_GRU_RUN_ZERO_PRODUCTS;     // no model workspace behind the call: the kernel as it always was
     }
     hipLaunchKernelGGL((gru_layer_kernel<CIN, LAST>), dim3(gx, 2), dim3(waves * 64), lds_bytes + CF_GRU_MAX_WAVES * 4, s, wpack,
                        reinterpret_cast<const f32x4*>(X), reinterpret_cast<f32x4*>(Y), P, n_tiles, balance, reinterpret_cast<f32x4*>(hand),
-                       m->d_err);
+                       hand_flags, m->d_err);
     HIP_TRY(hipGetLastError());
     return prof_end(m, s, pi);
 }
@@ -1885,14 +1971,14 @@ static int run_pass(cf_model* m, cf_model::Slot& sl, const float* x, int64_t n_w
             rc = m->np == 1 ? launch_gru_bf16_layer<1>(m, l, last, cur, y, sl.d_p, n_tiles32, s)
                             : launch_gru_bf16_layer<2>(m, l, last, cur, y, sl.d_p, n_tiles32, s);
         } else if (l == 0 && m->hp.n_layers_res == 0) {
-            rc = last ? launch_gru<16, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand)
-                      : launch_gru<16, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU0, sl.d_hand);
+            rc = last ? launch_gru<16, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand, sl.d_hand_flags)
+                      : launch_gru<16, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU0, sl.d_hand, sl.d_hand_flags);
         } else if (l == 0) {
-            rc = last ? launch_gru<32, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand)
-                      : launch_gru<32, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU0, sl.d_hand);
+            rc = last ? launch_gru<32, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand, sl.d_hand_flags)
+                      : launch_gru<32, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU0, sl.d_hand, sl.d_hand_flags);
         } else {
-            rc = last ? launch_gru<128, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand)
-                      : launch_gru<128, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU, sl.d_hand);
+            rc = last ? launch_gru<128, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand, sl.d_hand_flags)
+                      : launch_gru<128, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU, sl.d_hand, sl.d_hand_flags);
         }
         if (rc != CF_OK) return rc;
         cur = y;
@@ -1920,7 +2006,13 @@ extern "C" int cf_check_error(cf_model* m) {
 
 extern "C" int cf_clear_error(cf_model* m) {
     if (!m) return fail(CF_ERR_INVALID, "cf_clear_error: null model");
-    if (m->h_err) *m->h_err = 0u;       // every fused launch re-initialises its own queues and flags: nothing else is stale
+    if (m->h_err) *m->h_err = 0u;       // every fused launch re-initialises its own queues and flags
+    // the grid-wide biGRU schedule's boundary flags are zero between launches unless a wait timed out: a flag published after its
+    // consumer gave up stays set
+    HIP_TRY(hipSetDevice(m->device));
+    HIP_TRY(hipDeviceSynchronize());
+    for (auto& sl : m->slots)
+        if (sl.d_hand_flags) HIP_TRY(hipMemset(sl.d_hand_flags, 0, cf_hand_flag_bytes(m->n_cu)));
     return CF_OK;
 }
 

@@ -90,3 +90,73 @@ CF_BAL_HD inline int cf_gru_grid_load(int n_tiles, int gx, int nwaves, int wg_pe
     }
     return worst * wg_per_cu;
 }
+
+// ---- The grid-wide schedule: the same wrap-around rule with the whole grid as the "workgroup" ---------------------------------
+// Workgroups of one launch get floor or ceil(n_tiles / gx) tiles, and the balanced schedule above cannot move work between them
+// (1888 tiles on 128 workgroups: 14 or 15 tiles, 124 or 132 steps on the worst SIMD).  Here ALL of a direction's tiles x T steps
+// are laid end to end and global wave g = workgroup * nwaves + wave takes cf_gru_balanced_share(n_tiles, gx * nwaves, g, T):
+// shares differ by one step over the whole chip (64 or 65 at that size: 130).  Pieces, their order and the hand-off are the same;
+// the one new thing is that the tail of a workgroup's wave 0 takes h from the LAST wave of the workgroup before it.
+//
+// Progress.  A tail waits only for the wave with the next lower global index.  That wave runs the wanted head before anything
+// else and waits for nothing first, and it belongs to the same workgroup or to the one with the next lower index, which the
+// dispatcher starts no later than this one (workgroups are dispatched in index order, x fastest, and a direction is a row of the
+// grid): whenever a tail waits, its head is running or done -- no residency of the whole grid is assumed.  With every share at
+// least T steps a head is over within T steps of its wave's start while the tail that needs it begins no earlier than
+// share - T steps after ITS start (29 steps later at the benchmark's size), so in practice the wait does not spin; it is bounded
+// all the same (gru_layer_kernel).
+//
+// Feasible: no empty share and no interior piece.  n_tiles >= gx * nwaves is sufficient (every share is then at least T steps,
+// and a share of T steps or more that neither starts nor ends on a tile edge still crosses one), and it is also what the
+// progress argument's "does not spin" needs, so it is the test.
+CF_BAL_HD inline bool cf_gru_gridwide_ok(int n_tiles, int gx, int nwaves) {
+    return gx >= 1 && nwaves >= 1 && (long long)n_tiles >= (long long)gx * nwaves;
+}
+
+// Worst SIMD load of the grid-wide schedule in steps: over the workgroups, the sum of the ceil(nwaves / 4) largest shares of that
+// workgroup's waves, times the workgroups that share a CU; -1 when infeasible.
+CF_BAL_HD inline int cf_gru_gridwide_load(int n_tiles, int gx, int nwaves, int wg_per_cu, int T) {
+    if (!cf_gru_gridwide_ok(n_tiles, gx, nwaves)) return -1;
+    const int per_simd = (nwaves + 3) / 4;
+    const long long total = (long long)n_tiles * T, W = (long long)gx * nwaves;
+    // shares are floor(total / W) or one more; walk the cut points without a division per wave
+    const int q = (int)(total / W), r = (int)(total % W);
+    int worst = 0;
+    long long rem = 0;                  // (g * total) % W
+    for (int b = 0; b < gx; ++b) {
+        int big = 0;                    // waves of this workgroup with q + 1 steps
+        for (int w = 0; w < nwaves; ++w) {
+            rem += r;
+            if (rem >= W) { rem -= W; ++big; }
+        }
+        const int v = per_simd * q + (big < per_simd ? big : per_simd);
+        if (v > worst) worst = v;
+    }
+    return worst * wg_per_cu;
+}
+
+// launch_gru's choice.  gx: the usual grid (workgroups per direction), wg_per_cu of them on a CU; gx_one: the
+// one-workgroup-per-CU grid of a layer whose weights leave room for two (0: the layer has no second grid).
+// forced: CATFISH_GRU_BALANCE, -1 = unset: 0 round-robin, 1 balanced inside workgroups on the usual grid, 2 the same with the
+// second grid where it exists, 3 grid-wide wherever feasible (second grid first).  Unforced, the in-workgroup schedules are weighed
+// as they always were and the grid-wide one is taken only where its worst SIMD load is strictly below all of them, so a size
+// that divides evenly runs what it ran.
+struct cf_gru_choice {
+    int balance;    // 0 round-robin, 1 balanced inside each workgroup, 2 grid-wide
+    int gx;         // workgroups per direction
+    int load;       // worst SIMD load of the chosen schedule, steps
+};
+CF_BAL_HD inline cf_gru_choice cf_gru_choose(int n_tiles, int gx, int gx_one, int nwaves, int wg_per_cu, int T, int forced) {
+    const bool two = gx_one > 0 && gx > gx_one;
+    const int load_rr = cf_gru_grid_load(n_tiles, gx, nwaves, wg_per_cu, T, 0);
+    const int load_bal = cf_gru_grid_load(n_tiles, gx, nwaves, wg_per_cu, T, 1);
+    const int load_one = two ? cf_gru_grid_load(n_tiles, gx_one, nwaves, 1, T, 1) : -1;
+    const int load_grid = cf_gru_gridwide_load(n_tiles, gx, nwaves, wg_per_cu, T);
+    const int load_grid_one = two ? cf_gru_gridwide_load(n_tiles, gx_one, nwaves, 1, T) : -1;
+    cf_gru_choice c = {0, gx, load_rr};
+    if (forced < 0 ? (load_bal >= 0 && load_bal < c.load) : (forced >= 1 && load_bal >= 0)) { c.balance = 1; c.load = load_bal; }
+    if (forced < 0 ? (load_one >= 0 && load_one < c.load) : (forced >= 2 && load_one >= 0)) { c.balance = 1; c.gx = gx_one; c.load = load_one; }
+    if (forced < 0 ? (load_grid >= 0 && load_grid < c.load) : (forced == 3 && load_grid >= 0)) { c.balance = 2; c.gx = gx; c.load = load_grid; }
+    if (forced < 0 ? (load_grid_one >= 0 && load_grid_one < c.load) : (forced == 3 && load_grid_one >= 0)) { c.balance = 2; c.gx = gx_one; c.load = load_grid_one; }
+    return c;
+}

@@ -145,12 +145,13 @@ int cf_infer_logits(cf_model* m, const float* x, int64_t n_windows, float* probs
 int cf_infer_host_logits(cf_model* m, const float* x, int64_t n_windows, float* probs, float* logits);
 
 /* Sticky device-side error of earlier asynchronous launches on this model (today: a bounded wait of the
- * fused biGRU launch that timed out, which invalidates that launch's results).  Call it after
+ * fused biGRU launch or of a biGRU hand-off that timed out, which invalidates that launch's results).  Call it after
  * synchronising the stream a cf_infer was queued on; CF_OK, or CF_ERR_HIP with the message in
  * cf_last_error().  cf_infer / cf_infer_host also refuse to run while it is set. */
 int cf_check_error(cf_model* m);
 /* Reset that flag after the caller has dropped the results of the failed launch: the model is usable again (a fused
- * launch re-initialises its queues and flags every time; nothing else is stale). */
+ * launch re-initialises its queues and flags every time; the boundary flags of the grid-wide biGRU schedule, which are
+ * zero between launches unless a wait timed out, are zeroed here: the call synchronises the device). */
 int cf_clear_error(cf_model* m);
 
 /* Launch-regime switch points of this model on its device, for callers and tests that need to know which
