@@ -158,8 +158,7 @@ __host__ __device__ constexpr int gru_hc_floats() { return 16 * 256; }
 __host__ __device__ constexpr int gru_bias_off(int cin) { return gru_x_floats(cin) + gru_hg_floats() + gru_hc_floats(); }
 __host__ __device__ constexpr int gru_dense_off(int cin) { return gru_bias_off(cin) + 192; }
 __host__ __device__ constexpr int gru_pack_floats(int cin) { return gru_dense_off(cin) + 64; }
-#define CF_GRU_MAX_WAVES 8      // waves of a gru_layer_kernel workgroup: one hand-off flag (LDS) and one hand-off slot each
-#include "gru_balance.hpp"
+#include "tuned_launch.hpp"      // every launch decision of the kernels below (host-only, tested on the CPU); includes gru_balance.hpp
 
 // Residual-block blob (floats): NU 32x32 units of 1024 floats [ks < 8][lane][mo < 2], then
 // bias vectors of 32 floats each in [mo][q][r] order.
@@ -661,8 +660,6 @@ __device__ __forceinline__ void cf_handoff_wait_agent(unsigned* flag, int lane, 
     if (lane == 0) __hip_atomic_store(flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// `balance` of gru_layer_kernel: the schedule in the low bits, CF_GRU_RUN_ZERO_PRODUCTS on top of it
-enum { CF_GRU_SCHED_MASK = 3, CF_GRU_RUN_ZERO_PRODUCTS = 4 };
 
 template <int CIN, bool LAST>
 __global__ __launch_bounds__(512, 2) void gru_layer_kernel(const float* __restrict__ wpack,  // [2][gru_pack_floats(CIN)]
@@ -828,12 +825,10 @@ __global__ __launch_bounds__(512, 2) void gru_fused_kernel(cf_fused_args a) {
     }
 }
 
-#define CF_COOP_XCH_FLOATS (2 * 4 * 64 * 4 + 4 * 64)   // LDS exchange area of the cooperative kernel: h, r*h, dense partials
 #include "gru_coop.hpp"
 #include "gru_train.hpp"
 static_assert(gtb_pack_floats(32) == ((32 + CF_H) / 16 / 2) * 128 * 48 && gtb_pack_floats(128) == ((128 + CF_H) / 16 / 2) * 128 * 48,
               "gru_train_bwd_coop_kernel's PACK must equal gtb_pack_floats");
-#define CF_COOP_BWD_XCH_FLOATS (3 * 4 * 64 * 4)   // da_c, da_r, da_u exchange tiles
 #include "gru_wgrad.hpp"
 #include "res_train.hpp"
 #include "train_step.hpp"
@@ -1082,9 +1077,12 @@ __global__ __launch_bounds__(256) void normalize_kernel(const int16_t* __restric
 // them) that change WHICH kernels a call uses.  They are for tools/ and tests and are honoured only while
 // CATFISH_DEBUG_KNOBS=1 is set as well; every knob that takes effect is named once on stderr, so a stray variable can
 // neither change results nor do so silently.
-static const char* cf_knob(const char* name) {
+static bool cf_knobs_on() {
     const char* on = getenv("CATFISH_DEBUG_KNOBS");
-    if (!on || atoi(on) == 0) return nullptr;
+    return on && atoi(on) != 0;
+}
+static const char* cf_knob(const char* name) {
+    if (!cf_knobs_on()) return nullptr;
     const char* v = getenv(name);
     if (v) {
         static std::mutex mu;
@@ -1093,6 +1091,31 @@ static const char* cf_knob(const char* name) {
         if (seen.insert(std::string(name) + "=" + v).second) fprintf(stderr, "catfish_hip: debug knob %s=%s is active\n", name, v);
     }
     return v;
+}
+// The knobs of the tuned path's launch plans (tuned_launch.hpp), read ONCE per run_pass, per training entry and per cf_model_create:
+// with the debug switch off that is one getenv.
+static cf_knobs cf_read_knobs() {
+    cf_knobs k;
+    k.ablate_four_waves = (CF_ABLATE & 4) ? 1 : 0;
+    if (!cf_knobs_on()) return k;
+    auto num = [](const char* name) { const char* v = cf_knob(name); return v ? atoi(v) : CF_KNOB_UNSET; };
+    k.coop = num("CATFISH_COOP");
+    k.waves = num("CATFISH_WAVES");
+    k.gru_balance = num("CATFISH_GRU_BALANCE");
+    k.gru_gx = num("CATFISH_GRU_GX");
+    k.gru_zero_products = num("CATFISH_GRU_ZERO_PRODUCTS");
+    k.xproj_lds = num("CATFISH_XPROJ_LDS");
+    k.xproj_chunks = num("CATFISH_XPROJ_CHUNKS");
+    k.hoist_tiles = num("CATFISH_HOIST_TILES");
+    k.fuse = num("CATFISH_FUSE");
+    k.bf16_waves = num("CATFISH_BF16_WAVES");
+    k.bf16_wgs = num("CATFISH_BF16_WGS");
+    k.bf16_pipe = num("CATFISH_BF16_PIPE");
+    k.res_fuse = num("CATFISH_RES_FUSE");
+    k.res_tpw = num("CATFISH_RES_TPW");
+    k.res_chunks = num("CATFISH_RES_CHUNKS");
+    k.dx_chunks = num("CATFISH_DX_CHUNKS");
+    return k;
 }
 
 static thread_local std::string g_err;
@@ -1169,9 +1192,6 @@ struct cf_model {
     double prof_ms[CF_PROF_SLOTS] = {0};
     int64_t prof_n[CF_PROF_SLOTS] = {0};
 };
-
-// boundary flags of the grid-wide biGRU schedule: at most two workgroups per CU and direction (launch_gru), padded to 16 bytes
-static size_t cf_hand_flag_bytes(int n_cu) { return ((size_t)2 * (2 * std::max(1, n_cu / 2)) * sizeof(unsigned) + 15) / 16 * 16; }
 
 // ---- weight packing ----------------------------------------------------------------------
 // Every packed fp32 element is a TERM over the checkpoint's inference tensors:
@@ -1429,6 +1449,7 @@ static int upload(const std::vector<float>& host, float** dev) {
 static bool gen_wanted(const cf_hparams* hp);
 static int gen_build(cf_model* m, const cf_weights* w);
 static void gen_destroy(cf_generic* g);
+static hipError_t cf_optin_all();      // every kernel family's dynamic-LDS opt-in (defined after the last launch helper)
 
 extern "C" void cf_model_destroy(cf_model* m) {
     if (!m) return;
@@ -1551,11 +1572,11 @@ extern "C" int cf_model_create(const cf_weights* w, const cf_hparams* hp, int de
         m->cap_tiles = cap / CF_TILE;
         const size_t a_bytes = (size_t)m->cap_tiles * CF_T * 2 * 64 * sizeof(f32x4);
         const size_t y_bytes = (size_t)m->cap_tiles * CF_T * 8 * 64 * sizeof(f32x4);
-        // dense partials: [2][tiles][35][16] from the throughput kernels, [2][tiles <= CUs][35][4][64] per-lane partials from the
-        // latency-mode kernels
-        const size_t p_bytes = std::max((size_t)2 * m->cap_tiles * CF_T * 16, (size_t)2 * std::min<int64_t>(m->cap_tiles, m->n_cu) * CF_T * 256) * sizeof(float);
-        // at most two workgroups per CU and direction share the chip (launch_gru)
-        const size_t hand_bytes = (size_t)2 * (2 * std::max(1, m->n_cu / 2)) * CF_GRU_MAX_WAVES * 4 * 64 * sizeof(f32x4);
+        // bounds of the launch plans (tuned_launch.hpp): dense partials in either layout, hand-off slots and boundary flags of the
+        // largest grid any fp32 biGRU plan returns
+        const cf_knobs knobs = cf_read_knobs();
+        const size_t p_bytes = cf_dense_partial_floats(m->cap_tiles, m->n_cu) * sizeof(float);
+        const size_t hand_bytes = cf_hand_bytes(m->n_cu);
         hipError_t e = hipSuccess;
         int n_slots = hp->n_streams > 0 ? hp->n_streams : 1;   // measured: splitting one call over 2 internal streams is slower
         if (n_slots > 8) n_slots = 8;
@@ -1575,67 +1596,19 @@ extern "C" int cf_model_create(const cf_weights* w, const cf_hparams* hp, int de
         }
         if (e == hipSuccess && n_slots > 1) e = hipEventCreateWithFlags(&m->fork, hipEventDisableTiming);
         if (e == hipSuccess && n_slots == 1 && m->np == 0) {
-            // small calls: room for one layer's hoisted x projection (CATFISH_HOIST_TILES: A/B knob for tools/)
-            // measured crossover (tools/bench_latency.py with CATFISH_HOIST_TILES): hoisting pays up to ~48 tiles = 768 windows
-            int xpt = (int)std::min<int64_t>(m->cap_tiles, std::max(1, 3 * m->n_cu / 16));
-            if (cf_knob("CATFISH_HOIST_TILES")) xpt = std::max(1, std::min(atoi(cf_knob("CATFISH_HOIST_TILES")), (int)m->cap_tiles));
-            e = hipMalloc((void**)&m->d_xp, (size_t)xpt * CF_T * 2 * 12 * 64 * sizeof(f32x4));
+            // small calls: room for one layer's hoisted x projection
+            const int xpt = cf_hoist_limit(m->n_cu, m->cap_tiles, knobs);
+            e = hipMalloc((void**)&m->d_xp, cf_xp_floats(xpt) * sizeof(float));
             if (e == hipSuccess) m->xp_tiles = xpt;
         }
         if (e == hipSuccess) e = hipHostMalloc((void**)&m->h_err, sizeof(unsigned), hipHostMallocMapped);
         if (e == hipSuccess) { *m->h_err = 0u; e = hipHostGetDevicePointer((void**)&m->d_err, m->h_err, 0); }
-        m->fuse = (m->np == 0 && hp->n_layers <= 3 && hp->fuse_layers >= 0) ? (hp->fuse_layers > 0 ? 1 : 2) : 0;
-        if (cf_knob("CATFISH_FUSE") && m->fuse) m->fuse = atoi(cf_knob("CATFISH_FUSE")) != 0 ? 1 : 0;   // A/B knob for tools/
+        m->fuse = cf_fuse_mode(m->np == 0 && hp->n_layers <= 3, hp->fuse_layers, knobs);
         if (e != hipSuccess) rc = fail(CF_ERR_NOMEM, std::string("workspace allocation: ") + hipGetErrorString(e));
         m->ws_bytes = (int64_t)n_slots * (int64_t)(2 * a_bytes + 2 * y_bytes + p_bytes + (m->np == 0 ? hand_bytes : 0));
     }
     if (rc == CF_OK) {
-        // opt in to > 64 KiB dynamic LDS for every GRU instantiation we may launch
-        hipError_t e = hipSuccess;
-        auto optin = [&](const void* f, int bytes) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); };
-        optin((const void*)gru_layer_kernel<16, false>, gru_pack_floats(16) * 4 + CF_GRU_MAX_WAVES * 4);
-        optin((const void*)gru_layer_kernel<16, true>, gru_pack_floats(16) * 4 + CF_GRU_MAX_WAVES * 4);
-        optin((const void*)gru_layer_kernel<32, false>, gru_pack_floats(32) * 4 + CF_GRU_MAX_WAVES * 4);
-        optin((const void*)gru_layer_kernel<32, true>, gru_pack_floats(32) * 4 + CF_GRU_MAX_WAVES * 4);
-        optin((const void*)gru_layer_kernel<128, false>, gru_pack_floats(128) * 4 + CF_GRU_MAX_WAVES * 4);
-        optin((const void*)gru_layer_kernel<128, true>, gru_pack_floats(128) * 4 + CF_GRU_MAX_WAVES * 4);
-        optin((const void*)gru_fused_kernel, gru_pack_floats(128) * 4 + 16);
-        optin((const void*)gru_layer_coop_kernel<16, false>, (gru_pack_floats(16) + CF_COOP_XCH_FLOATS) * 4);
-        optin((const void*)gru_layer_coop_kernel<16, true>, (gru_pack_floats(16) + CF_COOP_XCH_FLOATS) * 4);
-        optin((const void*)gru_layer_coop_kernel<32, false>, (gru_pack_floats(32) + CF_COOP_XCH_FLOATS) * 4);
-        optin((const void*)gru_layer_coop_kernel<32, true>, (gru_pack_floats(32) + CF_COOP_XCH_FLOATS) * 4);
-        optin((const void*)gru_layer_coop_kernel<128, false>, (gru_pack_floats(128) + CF_COOP_XCH_FLOATS) * 4);
-        optin((const void*)gru_layer_coop_kernel<128, true>, (gru_pack_floats(128) + CF_COOP_XCH_FLOATS) * 4);
-        optin((const void*)gru_train_fwd_coop_kernel<32>, (gru_pack_floats(32) + CF_COOP_XCH_FLOATS) * 4);
-        optin((const void*)gru_train_fwd_coop_kernel<128>, (gru_pack_floats(128) + CF_COOP_XCH_FLOATS) * 4);
-        optin((const void*)gru_train_bwd_coop_kernel<32>, (gtb_pack_floats(32) + CF_COOP_BWD_XCH_FLOATS) * 4);
-        optin((const void*)gru_train_bwd_coop_kernel<128>, (gtb_pack_floats(128) + CF_COOP_BWD_XCH_FLOATS) * 4);
-        optin((const void*)gru_train_fwd_kernel<32>, gru_pack_floats(32) * 4);
-        optin((const void*)gru_train_fwd_kernel<128>, gru_pack_floats(128) * 4);
-        optin((const void*)gru_train_bwd_kernel<32>, gtb_pack_floats(32) * 4);
-        optin((const void*)gru_train_bwd_kernel<128>, gtb_pack_floats(128) * 4);
-        optin((const void*)res_stack2_kernel<true>, (res_pack_floats(true) + res_pack_floats(false) + 4 * CF_TILE * CF_T) * 4);
-        optin((const void*)res_stack2_kernel<false>, (res_pack_floats(true) + res_pack_floats(false) + 4 * CF_TILE * CF_T) * 4);
-        optin((const void*)res_train_fwd_kernel, RT_FWD_LDS_BYTES);
-        optin((const void*)res_train_bwd_kernel, RT_BWD_LDS_BYTES);
-        optin((const void*)gru_layer_bf16_kernel<32, false, 1>, gb_pack_bytes(32, 1));
-        optin((const void*)gru_layer_bf16_kernel<32, true, 1>, gb_pack_bytes(32, 1));
-        optin((const void*)gru_layer_bf16_kernel<128, false, 1>, gb_pack_bytes(128, 1));
-        optin((const void*)gru_layer_bf16_kernel<128, true, 1>, gb_pack_bytes(128, 1));
-        optin((const void*)gru_bf16_pipe_kernel<32, false>, gb_pack_bytes(32, 1));
-        optin((const void*)gru_bf16_pipe_kernel<32, true>, gb_pack_bytes(32, 1));
-        optin((const void*)gru_bf16_pipe_kernel<128, false>, gb_pack_bytes(128, 1));
-        optin((const void*)gru_bf16_pipe_kernel<128, true>, gb_pack_bytes(128, 1));
-        optin((const void*)gru_xproj_lds_kernel<32>, gru_x_floats(32) * 4);
-        optin((const void*)gru_xproj_lds_kernel<128>, gru_x_floats(128) * 4);
-        optin((const void*)gru_bf16x3_pipe_kernel<32, false>, gb_pack_bytes(32, 2));
-        optin((const void*)gru_bf16x3_pipe_kernel<32, true>, gb_pack_bytes(32, 2));
-        optin((const void*)gru_bf16x3_pipe_kernel<128, false>, gb_pack_bytes(128, 2));
-        optin((const void*)gru_bf16x3_pipe_kernel<128, true>, gb_pack_bytes(128, 2));
-        optin((const void*)gru_layer_bf16_kernel<32, false, 2>, gb_pack_bytes(32, 2));
-        optin((const void*)gru_layer_bf16_kernel<32, true, 2>, gb_pack_bytes(32, 2));
-        optin((const void*)gru_layer_bf16_kernel<128, false, 2>, gb_pack_bytes(128, 2));
-        optin((const void*)gru_layer_bf16_kernel<128, true, 2>, gb_pack_bytes(128, 2));
+        hipError_t e = cf_optin_all();
         if (e != hipSuccess) rc = fail(CF_ERR_HIP, std::string("hipFuncSetAttribute(max dynamic LDS): ") + hipGetErrorString(e));
     }
     if (rc != CF_OK) { std::string keep = g_err; cf_model_destroy(m); g_err = keep; return rc; }
@@ -1663,274 +1636,201 @@ static int prof_end(cf_model* m, hipStream_t s, size_t idx) {
     return CF_OK;
 }
 
-// CATFISH_GRU_GX behind the debug switch: run the biGRU throughput kernel on that many 8-wave workgroups per direction whatever
-// the size of the call, so that a test reaches a workgroup boundary of the grid-wide schedule with a few dozen tiles; read per launch.
-static int cf_forced_gx(const cf_model* m) {
-    const char* v = cf_knob("CATFISH_GRU_GX");
-    return v ? std::max(0, std::min(atoi(v), 2 * std::max(1, m->n_cu / 2))) : 0;
+// f(std::integral_constant<int, V>{}) for the V among Vs that equals the run-time v (the idiom of gru_bf16x3_pipe.hpp): cin
+// (16 / 32 / 128), LAST, NP, ... become template arguments inside a generic lambda, so every launch is written once.
+template <int... Vs, class F>
+static int cf_with(int v, F&& f) {
+    int rc = CF_OK;
+    const bool hit = ((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return hit ? rc : fail(CF_ERR_INVALID, "no kernel is built for template argument " + std::to_string(v));
 }
 
-// Waves per workgroup: 8 (two per SIMD) when the pass fills the chip; fewer for small calls (a single read is
-// 8 tiles x 2 directions) so that the tiles spread over more CUs instead of sharing SIMDs -- the 35-step
-// chain is latency-bound there.
-static int pick_waves(int n_tile_tasks, int n_cu) {
-    int w = (n_tile_tasks + n_cu - 1) / n_cu;
-    return w <= 1 ? 1 : (w <= 2 ? 2 : (w <= 4 ? 4 : 8));
+// Kernels launched with more than 64 KiB of dynamic LDS have to opt in.  Every family states the most it is ever launched with ONCE,
+// next to its launch helper, as the plan's own LDS function of its largest pack; cf_model_create opts in all of them (cf_optin_all),
+// gen_build the fp32 biGRU family its tuned layers run on.
+struct cf_optin {
+    hipError_t e = hipSuccess;
+    void operator()(const void* f, int bytes) { if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
+};
+
+// ---- fp32 biGRU layer: gru_layer_coop_kernel (+ hoisted x projection) or gru_layer_kernel, as cf_gru_plan_for says ----------------
+template <int CIN> constexpr int k_gru_pack_bytes = gru_pack_floats(CIN) * 4;
+template <int CIN> constexpr int k_gru_x_bytes = gru_x_floats(CIN) * 4;
+static void optin_gru_layer(cf_optin& o) {
+    for (int cin : {16, 32, 128})
+        for (int last : {0, 1})
+            cf_with<16, 32, 128>(cin, [&](auto C) { return cf_with<0, 1>(last, [&](auto L) {
+                constexpr int CIN = decltype(C)::value;
+                constexpr bool LAST = decltype(L)::value != 0;
+                o((const void*)gru_layer_kernel<CIN, LAST>, cf_gru_layer_lds(k_gru_pack_bytes<CIN>));
+                o((const void*)gru_layer_coop_kernel<CIN, LAST>, cf_gru_coop_lds(k_gru_pack_bytes<CIN>));
+                return CF_OK;
+            }); });
+    o((const void*)gru_fused_kernel, cf_fused_lds(k_gru_pack_bytes<128>));
+    o((const void*)gru_xproj_lds_kernel<32>, k_gru_x_bytes<32>);
+    o((const void*)gru_xproj_lds_kernel<128>, k_gru_x_bytes<128>);
 }
 
-// latency mode: up to two rounds of one (tile, direction) per CU (0.35 units each) beat one wave per tile (1 unit)
-static bool use_coop(const cf_model* m, int n_tiles) {
-    static const int coop_env = cf_knob("CATFISH_COOP") ? atoi(cf_knob("CATFISH_COOP")) : -1;      // A/B knob for tools/
-    if (cf_forced_gx(m) > 0) return false;
-    const bool coop = coop_env >= 0 ? coop_env != 0 : n_tiles <= m->n_cu;
-    return coop && !(CF_ABLATE & 4) && n_tiles <= m->n_cu;      // (the raw dense-partial buffer is sized for n_cu tiles)
-}
-
-// x projection of a small call on the CUs its recurrence leaves idle (gru_coop.hpp): weights through LDS, chunks sized to fill
-// the chip once; CATFISH_XPROJ_LDS=0 behind the debug switch selects round 2's kernel (fragments straight from L2), for A/B
 template <int CIN>
-static void launch_xproj(cf_model* m, const float* wpack, const float* X, int n_tiles, hipStream_t s) {
-    const int lds_env = cf_knob("CATFISH_XPROJ_LDS") ? atoi(cf_knob("CATFISH_XPROJ_LDS")) : 1;
-    if (lds_env) {
-        int chunks = cf_xproj_plan(n_tiles, m->n_cu, CIN);
-        if (cf_knob("CATFISH_XPROJ_CHUNKS")) {                                   // A/B knob for tools/: another valid chunk count
-            const int c = std::max(1, std::min(CF_T, atoi(cf_knob("CATFISH_XPROJ_CHUNKS"))));
-            const int tl = (CF_T + c - 1) / c;
-            chunks = (CF_T + tl - 1) / tl;
-        }
-        hipLaunchKernelGGL((gru_xproj_lds_kernel<CIN>), dim3(n_tiles * chunks, 2), dim3(256), gru_x_floats(CIN) * 4, s, wpack,
-                           reinterpret_cast<const f32x4*>(X), reinterpret_cast<f32x4*>(m->d_xp), n_tiles, chunks);
-    } else {
-        hipLaunchKernelGGL((gru_xproj_kernel<CIN>), dim3(n_tiles * cf_xproj_chunks(n_tiles), 2), dim3(256), 0, s, wpack,
-                           reinterpret_cast<const f32x4*>(X), reinterpret_cast<f32x4*>(m->d_xp), n_tiles, cf_xproj_chunks(n_tiles));
-    }
+static void launch_xproj(cf_model* m, const cf_xproj_launch& xp, const float* wpack, const float* X, int n_tiles, hipStream_t s) {
+    if (xp.lds_kernel)
+        hipLaunchKernelGGL((gru_xproj_lds_kernel<CIN>), dim3(xp.grid_x, 2), dim3(256), xp.lds_bytes, s, wpack,
+                           reinterpret_cast<const f32x4*>(X), reinterpret_cast<f32x4*>(m->d_xp), n_tiles, xp.chunks);
+    else
+        hipLaunchKernelGGL((gru_xproj_kernel<CIN>), dim3(xp.grid_x, 2), dim3(256), 0, s, wpack,
+                           reinterpret_cast<const f32x4*>(X), reinterpret_cast<f32x4*>(m->d_xp), n_tiles, xp.chunks);
 }
 
-template <int CIN, bool LAST>
-static int launch_gru(cf_model* m, const float* wpack, const float* X, float* Y, float* P, int n_tiles, hipStream_t s, int slot,
+// -> the plan it ran (cf_gru_plan::raw_partials tells the head what a LAST launch left in P)
+static int launch_gru(cf_model* m, const cf_knobs& k, int cin, bool last, const float* wpack, const float* X, float* Y, float* P, int n_tiles,
+                      hipStream_t s, int slot, cf_gru_plan* ran = nullptr,
                       float* hand = nullptr,        // hand-off slots of the balanced schedule (Slot::d_hand); none: round-robin
                       unsigned* hand_flags = nullptr) {     // boundary flags of the grid-wide schedule (Slot::d_hand_flags)
-    if (use_coop(m, n_tiles)) {
+    return cf_with<16, 32, 128>(cin, [&](auto C) { return cf_with<0, 1>(last, [&](auto L) {
+        constexpr int CIN = decltype(C)::value;
+        constexpr bool LAST = decltype(L)::value != 0;
+        const cf_gru_plan p = cf_gru_plan_for(n_tiles, m->n_cu, CIN, k_gru_pack_bytes<CIN>, k_gru_x_bytes<CIN>, m->xp_tiles, hand && hand_flags, k);
+        if (ran) *ran = p;
         size_t pi = 0;
         int rc = prof_begin(m, slot, s, &pi);
         if (rc != CF_OK) return rc;
-        const int gx = std::min(n_tiles, std::max(1, m->n_cu / 2));
-        const f32x4* xp = nullptr;
-        if (CIN >= 32 && n_tiles <= m->xp_tiles) {        // few tiles: the x projection runs on the idle CUs first
-            xp = reinterpret_cast<const f32x4*>(m->d_xp);
-            launch_xproj<CIN>(m, wpack, X, n_tiles, s);
+        if (p.coop) {
+            if (p.hoist) launch_xproj<CIN>(m, p.xproj, wpack, X, n_tiles, s);
+            hipLaunchKernelGGL((gru_layer_coop_kernel<CIN, LAST>), dim3(p.gx, 2), dim3(p.waves * 64), p.lds_bytes, s, wpack,
+                               reinterpret_cast<const f32x4*>(X), reinterpret_cast<f32x4*>(Y), P, n_tiles,
+                               p.hoist ? reinterpret_cast<const f32x4*>(m->d_xp) : nullptr);
+        } else {
+            hipLaunchKernelGGL((gru_layer_kernel<CIN, LAST>), dim3(p.gx, 2), dim3(p.waves * 64), p.lds_bytes, s, wpack,
+                               reinterpret_cast<const f32x4*>(X), reinterpret_cast<f32x4*>(Y), P, n_tiles, p.balance,
+                               reinterpret_cast<f32x4*>(hand), hand_flags, m->d_err);
         }
-        hipLaunchKernelGGL((gru_layer_coop_kernel<CIN, LAST>), dim3(gx, 2), dim3(256), (gru_pack_floats(CIN) + CF_COOP_XCH_FLOATS) * 4, s,
-                           wpack, reinterpret_cast<const f32x4*>(X), reinterpret_cast<f32x4*>(Y), P, n_tiles, xp);
         HIP_TRY(hipGetLastError());
         return prof_end(m, s, pi);
-    }
-    static const int waves_env = cf_knob("CATFISH_WAVES") ? atoi(cf_knob("CATFISH_WAVES")) : 0;     // A/B knob for tools/
-    // (12 waves = 3 per SIMD measured +0.3 % on the Cin = 128 layers and costs the Cin = 32 layer its second workgroup per CU)
-    const int gx_env = cf_forced_gx(m);
-    const int waves = gx_env > 0 ? 8 : waves_env > 0 ? std::min(waves_env, 8) : ((CF_ABLATE & 4) ? 4 : pick_waves(2 * n_tiles, m->n_cu));
-    const int groups = (n_tiles + waves - 1) / waves;             // one workgroup pass = one tile per wave
-    int per_dir = m->n_cu / 2 > 0 ? m->n_cu / 2 : 1;            // persistent: half the CUs per direction
-    constexpr int lds_bytes = gru_pack_floats(CIN) * 4;
-    if (lds_bytes <= 80 * 1024) per_dir *= 2;                   // two workgroups fit per CU
-    int gx = groups < per_dir ? groups : per_dir;
-    if (gx_env > 0) gx = std::min(gx_env, groups);
-    size_t pi = 0;
-    int rc = prof_begin(m, slot, s, &pi);
-    if (rc != CF_OK) return rc;
-    // Schedule (gru_balance.hpp): equal shares of steps instead of whole tiles, only where the worst SIMD gets strictly less to do, so
-    // a call that divides evenly and a small call run what they always ran.  A layer whose weights leave room for two workgroups
-    // per CU has a second candidate: ONE balanced workgroup per CU (at the benchmark's 1888 tiles, 7 or 8 tiles on 8 waves cannot be
-    // balanced inside a workgroup, 14 or 15 can: 132 steps against 140; measured).  CATFISH_GRU_BALANCE behind
-    // the debug switch forces a schedule wherever it exists, for tests and A/B: 0 round-robin, 1 balanced on the usual grid,
-    // 2 balanced on the one-workgroup-per-CU grid, 3 grid-wide; read per launch.  The grid-wide schedule (shares dealt over all
-    // waves of a direction, h handed across workgroup boundaries through Slot::d_hand_flags) is one more candidate on either grid,
-    // taken only where it beats all of the above: 130 against 132 steps at the benchmark's size, nothing at 1024 or 2048 tiles.
-    // cf_gru_choose is that decision, shared with the CPU tests.  CATFISH_GRU_ZERO_PRODUCTS=1 (debug switch, read per launch) runs
-    // step 0's products with the zero state instead of skipping them (gru_tile), for the bit-identity test and A/B.
-    int balance = 0;
-    if (hand && hand_flags) {
-        const int wg_per_cu = std::max(1, (2 * gx + m->n_cu - 1) / m->n_cu);
-        const int gx_one = gx_env > 0 ? 0 : std::max(1, m->n_cu / 2);
-        const char* env = cf_knob("CATFISH_GRU_BALANCE");
-        const cf_gru_choice c = cf_gru_choose(n_tiles, gx, gx_one, waves, wg_per_cu, CF_T, env ? atoi(env) : -1);
-        balance = c.balance;
-        gx = c.gx;
-        const char* zp = cf_knob("CATFISH_GRU_ZERO_PRODUCTS");
-        if (zp && atoi(zp) != 0) balance |= CF_GRU_RUN_ZERO_PRODUCTS;
-    } else {
-        balance = CF_GRU_RUN_ZERO_PRODUCTS;     // no model workspace behind the call: the kernel as it always was
-    }
-    hipLaunchKernelGGL((gru_layer_kernel<CIN, LAST>), dim3(gx, 2), dim3(waves * 64), lds_bytes + CF_GRU_MAX_WAVES * 4, s, wpack,
-                       reinterpret_cast<const f32x4*>(X), reinterpret_cast<f32x4*>(Y), P, n_tiles, balance, reinterpret_cast<f32x4*>(hand),
-                       hand_flags, m->d_err);
-    HIP_TRY(hipGetLastError());
-    return prof_end(m, s, pi);
+    }); });
 }
 
-template <int CIN, bool LAST, int NP>
-static int launch_gru_bf16(cf_model* m, const char* wpack, const float* X, float* Y, float* P, int n_tiles32, hipStream_t s, int slot) {
-    static const int waves_env = cf_knob("CATFISH_BF16_WAVES") ? atoi(cf_knob("CATFISH_BF16_WAVES")) : 0;     // A/B knobs for tools/
-    static const int wgs_env = cf_knob("CATFISH_BF16_WGS") ? atoi(cf_knob("CATFISH_BF16_WGS")) : 0;
-    const int waves = waves_env > 0 ? std::min(waves_env, 8) : pick_waves(2 * n_tiles32, m->n_cu);
-    const int groups = (n_tiles32 + waves - 1) / waves;           // one workgroup pass = one 32-window tile per wave
-    int per_dir = m->n_cu / 2 > 0 ? m->n_cu / 2 : 1;
-    constexpr int lds_bytes = gb_pack_bytes(CIN, NP);
-    if (lds_bytes <= 80 * 1024) per_dir *= 2;
-    if (wgs_env > 0) per_dir = wgs_env;
-    const int gx = groups < per_dir ? groups : per_dir;
-    size_t pi = 0;
-    int rc = prof_begin(m, slot, s, &pi);
-    if (rc != CF_OK) return rc;
-    const int pipe_env = cf_knob("CATFISH_BF16_PIPE") ? atoi(cf_knob("CATFISH_BF16_PIPE")) : 1;   // A/B knob for tools/ and tests, read per launch
-    if constexpr (NP == 1) {
-        if (pipe_env) {      // plain bf16: the software-pipelined kernel (vector work issued behind every MFMA)
-            hipLaunchKernelGGL((gru_bf16_pipe_kernel<CIN, LAST>), dim3(gx, 2), dim3(waves * 64), lds_bytes, s, wpack,
-                               reinterpret_cast<const bf16x8*>(X), reinterpret_cast<bf16x8*>(Y), P, n_tiles32);
-            HIP_TRY(hipGetLastError());
-            return prof_end(m, s, pi);
-        }
-    }
-    if constexpr (NP == 2) {
-        if (pipe_env) {      // bf16x3: the one-wave-per-SIMD pipelined kernel (512 registers, four waves per workgroup)
-            const int w4 = std::min(waves, 4);
-            const int g4 = (n_tiles32 + w4 - 1) / w4;
-            const int per4 = wgs_env > 0 ? wgs_env : std::max(1, m->n_cu / 2);       // one workgroup per CU whatever its LDS
-            hipLaunchKernelGGL((gru_bf16x3_pipe_kernel<CIN, LAST>), dim3(std::min(g4, per4), 2), dim3(w4 * 64), lds_bytes, s, wpack,
-                               reinterpret_cast<const bf16x8*>(X), reinterpret_cast<bf16x8*>(Y), P, n_tiles32);
-            HIP_TRY(hipGetLastError());
-            return prof_end(m, s, pi);
-        }
-    }
-    hipLaunchKernelGGL((gru_layer_bf16_kernel<CIN, LAST, NP>), dim3(gx, 2), dim3(waves * 64), lds_bytes, s, wpack,
-                       reinterpret_cast<const bf16x8*>(X), reinterpret_cast<bf16x8*>(Y), P, n_tiles32);
-    HIP_TRY(hipGetLastError());
-    return prof_end(m, s, pi);
+// ---- bf16 / bf16x3 biGRU layer: the pipelined kernel of its precision, or round 1's, as cf_gru_bf16_plan_for says ------------------
+static void optin_gru_bf16(cf_optin& o) {
+    for (int cin : {32, 128})
+        for (int last : {0, 1})
+            cf_with<32, 128>(cin, [&](auto C) { return cf_with<0, 1>(last, [&](auto L) {
+                constexpr int CIN = decltype(C)::value;
+                constexpr bool LAST = decltype(L)::value != 0;
+                o((const void*)gru_layer_bf16_kernel<CIN, LAST, 1>, gb_pack_bytes(CIN, 1));
+                o((const void*)gru_bf16_pipe_kernel<CIN, LAST>, gb_pack_bytes(CIN, 1));
+                o((const void*)gru_layer_bf16_kernel<CIN, LAST, 2>, gb_pack_bytes(CIN, 2));
+                o((const void*)gru_bf16x3_pipe_kernel<CIN, LAST>, gb_pack_bytes(CIN, 2));
+                return CF_OK;
+            }); });
 }
 
-template <int NP>
-static int launch_gru_bf16_layer(cf_model* m, int l, bool last, const float* cur, float* y, float* p, int n_tiles32, hipStream_t s) {
-    const char* wp = m->d_gru_b[l];
-    if (l == 0)
-        return last ? launch_gru_bf16<32, true, NP>(m, wp, cur, y, p, n_tiles32, s, SLOT_GRU_LAST)
-                    : launch_gru_bf16<32, false, NP>(m, wp, cur, y, p, n_tiles32, s, SLOT_GRU0);
-    return last ? launch_gru_bf16<128, true, NP>(m, wp, cur, y, p, n_tiles32, s, SLOT_GRU_LAST)
-                : launch_gru_bf16<128, false, NP>(m, wp, cur, y, p, n_tiles32, s, SLOT_GRU);
+static int launch_gru_bf16(cf_model* m, const cf_knobs& k, int cin, bool last, const char* wpack, const float* X, float* Y, float* P,
+                           int n_tiles32, hipStream_t s, int slot) {
+    return cf_with<32, 128>(cin, [&](auto C) { return cf_with<0, 1>(last, [&](auto L) { return cf_with<1, 2>(m->np, [&](auto N) {
+        constexpr int CIN = decltype(C)::value, NP = decltype(N)::value;
+        constexpr bool LAST = decltype(L)::value != 0;
+        const cf_gru_bf16_plan p = cf_gru_bf16_plan_for(n_tiles32, m->n_cu, NP, gb_pack_bytes(CIN, NP), k);
+        size_t pi = 0;
+        int rc = prof_begin(m, slot, s, &pi);
+        if (rc != CF_OK) return rc;
+        const dim3 grid(p.gx, 2), block(p.waves * 64);
+        const bf16x8* x8 = reinterpret_cast<const bf16x8*>(X);
+        bf16x8* y8 = reinterpret_cast<bf16x8*>(Y);
+        if (!p.pipe)
+            hipLaunchKernelGGL((gru_layer_bf16_kernel<CIN, LAST, NP>), grid, block, p.lds_bytes, s, wpack, x8, y8, P, n_tiles32);
+        else if constexpr (NP == 1)      // plain bf16: the software-pipelined kernel (vector work issued behind every MFMA)
+            hipLaunchKernelGGL((gru_bf16_pipe_kernel<CIN, LAST>), grid, block, p.lds_bytes, s, wpack, x8, y8, P, n_tiles32);
+        else                             // bf16x3: the one-wave-per-SIMD pipelined kernel (512 registers, four waves per workgroup)
+            hipLaunchKernelGGL((gru_bf16x3_pipe_kernel<CIN, LAST>), grid, block, p.lds_bytes, s, wpack, x8, y8, P, n_tiles32);
+        HIP_TRY(hipGetLastError());
+        return prof_end(m, s, pi);
+    }); }); });
 }
 
-// fuse_layers = auto: the dynamically scheduled single launch pays from ~6 full-chip rounds of 8-tile groups per pass
 #include "generic_host.hpp"
 #include "params_dev.hpp"   // cf_model_param_floats / cf_model_load_params: the packers' terms as a device gather map
 
-static int cf_fuse_min_groups(int n_cu) { return 6 * std::max(1, n_cu / 2); }
+// ---- residual stack: fp32 (res_block_kernel, res_stack2_kernel) and bf16 / bf16x3 (res_block_bf16_kernel, res_stack2_bf16_kernel) ----
+constexpr int k_res_first_bytes = res_pack_floats(true) * 4, k_res_other_bytes = res_pack_floats(false) * 4;
+static void optin_res(cf_optin& o) {
+    o((const void*)res_stack2_kernel<true>, cf_res_stack2_lds(k_res_first_bytes, k_res_other_bytes, 4));
+    o((const void*)res_stack2_kernel<false>, cf_res_stack2_lds(k_res_first_bytes, k_res_other_bytes, 4));
+}
+
+static int run_res_fp32(cf_model* m, cf_model::Slot& sl, const cf_knobs& k, const float* x, int64_t n_windows, int n_tiles, hipStream_t s) {
+    const cf_res_plan p = cf_res_plan_for(n_tiles, m->n_cu, m->hp.n_layers_res, k_res_first_bytes, k_res_other_bytes, k);
+    sl.last_res_fused = p.fused && !p.split;       // (latency mode also stores block 0's output, for the debug hook)
+    int rc;
+    size_t pi = 0;
+    if (p.fused) {
+        if ((rc = prof_begin(m, SLOT_RES_STACK2, s, &pi)) != CF_OK) return rc;
+        f32x4* y1 = reinterpret_cast<f32x4*>(sl.d_a[1]);
+        if (p.split)
+            hipLaunchKernelGGL(res_stack2_kernel<true>, dim3(p.stack_grid), dim3(p.stack_waves * 64), p.stack_lds, s, m->d_res[0], m->d_res[1], x,
+                               y1, reinterpret_cast<f32x4*>(sl.d_a[0]), n_windows, n_tiles, p.stack_chunks);
+        else
+            hipLaunchKernelGGL(res_stack2_kernel<false>, dim3(p.stack_grid), dim3(p.stack_waves * 64), p.stack_lds, s, m->d_res[0], m->d_res[1], x,
+                               y1, (f32x4*)nullptr, n_windows, n_tiles, 1);
+        HIP_TRY(hipGetLastError());
+        if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
+    }
+    for (int b = p.fused ? 2 : 0; b < m->hp.n_layers_res; ++b) {
+        if ((rc = prof_begin(m, b == 0 ? SLOT_RES_FIRST : SLOT_RES, s, &pi)) != CF_OK) return rc;
+        f32x4* dst = reinterpret_cast<f32x4*>(sl.d_a[b & 1]);
+        if (b == 0)
+            hipLaunchKernelGGL((res_block_kernel<true>), dim3(p.grid), dim3(p.waves * 64), p.lds_first, s, m->d_res[0], x,
+                               (const f32x4*)nullptr, dst, n_windows, n_tiles, p.chunks);
+        else
+            hipLaunchKernelGGL((res_block_kernel<false>), dim3(p.grid), dim3(p.waves * 64), p.lds_other, s, m->d_res[b], (const float*)nullptr,
+                               reinterpret_cast<const f32x4*>(sl.d_a[(b - 1) & 1]), dst, n_windows, n_tiles, p.chunks);
+        HIP_TRY(hipGetLastError());
+        if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
+    }
+    return CF_OK;
+}
+
+static int run_res_bf16(cf_model* m, cf_model::Slot& sl, const cf_knobs& k, const float* x, int64_t n_windows, int n_tiles32, hipStream_t s) {
+    return cf_with<1, 2>(m->np, [&](auto N) {
+        constexpr int NP = decltype(N)::value;
+        const cf_res_bf16_plan p = cf_res_bf16_plan_for(n_tiles32, m->n_cu, m->hp.n_layers_res, NP, rb_pack_bytes(true, NP), rb_pack_bytes(false, NP),
+                                                        CF_RES_BF16_WAVES, k);
+        sl.last_res_fused = p.fused;
+        int rc;
+        size_t pi = 0;
+        if (p.fused) {
+            if ((rc = prof_begin(m, SLOT_RES_STACK2, s, &pi)) != CF_OK) return rc;
+            rc = cf_with<1, NP == 1 ? 2 : 1>(p.tpw, [&](auto W) {      // (two tiles per wave are built for one bf16 part only)
+                hipLaunchKernelGGL((res_stack2_bf16_kernel<NP, decltype(W)::value>), dim3(p.stack_grid), dim3(256), p.stack_lds, s, m->d_res_b[0],
+                                   m->d_res_b[1], x, reinterpret_cast<bf16x8*>(sl.d_a[1]), n_windows, n_tiles32, p.chunks);
+                return CF_OK;
+            });
+            if (rc != CF_OK) return rc;
+            HIP_TRY(hipGetLastError());
+            if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
+        }
+        for (int b = p.fused ? 2 : 0; b < m->hp.n_layers_res; ++b) {
+            if ((rc = prof_begin(m, b == 0 ? SLOT_RES_FIRST : SLOT_RES, s, &pi)) != CF_OK) return rc;
+            bf16x8* dst = reinterpret_cast<bf16x8*>(sl.d_a[b & 1]);
+            if (b == 0)
+                hipLaunchKernelGGL((res_block_bf16_kernel<true, NP>), dim3(p.grid), dim3(256), p.lds_first, s, m->d_res_b[0], x, (const bf16x8*)nullptr,
+                                   dst, n_windows, n_tiles32);
+            else
+                hipLaunchKernelGGL((res_block_bf16_kernel<false, NP>), dim3(p.grid), dim3(256), p.lds_other, s, m->d_res_b[b], (const float*)nullptr,
+                                   reinterpret_cast<const bf16x8*>(sl.d_a[(b - 1) & 1]), dst, n_windows, n_tiles32);
+            HIP_TRY(hipGetLastError());
+            if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
+        }
+        return CF_OK;
+    });
+}
 
 static int run_pass(cf_model* m, cf_model::Slot& sl, const float* x, int64_t n_windows, float* probs, float* logits, hipStream_t s) {
     const int n_tiles = (int)((n_windows + CF_TILE - 1) / CF_TILE);
     const int n_tiles32 = (int)((n_windows + 2 * CF_TILE - 1) / (2 * CF_TILE));
+    const cf_knobs k = cf_read_knobs();
     int rc;
     size_t pi = 0;
-    // residual blocks
-    // latency mode (fp32): one workgroup per tile, four waves, each streaming a quarter of the 35 positions
-    const bool res_split = m->np == 0 && n_tiles <= m->n_cu;
-    const int res_chunks = res_split ? 4 : 1;
-    const int res_waves = res_split ? 4 : (pick_waves(n_tiles, m->n_cu * 2) > 4 ? 4 : pick_waves(n_tiles, m->n_cu * 2));
-    const int res_grid = res_split ? n_tiles : std::min((n_tiles + res_waves - 1) / res_waves, m->n_cu * 4);
-    // throughput mode (fp32): the first two blocks as ONE launch, block 0's output stays in registers
-    const int res_fuse_env = cf_knob("CATFISH_RES_FUSE") ? atoi(cf_knob("CATFISH_RES_FUSE")) : 1;   // A/B knob for tools/ and tests, read per pass
-    const bool res_fused = m->np == 0 && m->hp.n_layers_res >= 2 && res_fuse_env != 0;
-    const bool res_fused_bf16 = m->np > 0 && m->hp.n_layers_res >= 2 && res_fuse_env != 0;
-    sl.last_res_fused = (res_fused && !res_split) || res_fused_bf16;       // (fp32 latency mode also stores block 0's output, for the debug hook)
-    if (res_fused_bf16) {
-        // blocks 0 and 1 as one launch on the bf16 matrix pipe; positions cut into chunks for about four waves per SIMD
-        if ((rc = prof_begin(m, SLOT_RES_STACK2, s, &pi)) != CF_OK) return rc;
-        // bf16: two tiles per wave (every LDS read of a weight fragment or bias vector feeds two tiles: the kernel is bound
-        // by LDS bandwidth), two waves per SIMD; bf16x3: one tile per wave (twice the fragments), two waves per SIMD
-        const int np = m->np > 1 ? 2 : 1;
-        // A/B knob for tools/: two tiles per wave exist for one bf16 part only; any other value would launch a kernel that covers
-        // 1 / tpw of the tiles and leave the rest of the slab stale
-        const int tpw = (np == 1 && cf_knob("CATFISH_RES_TPW") && atoi(cf_knob("CATFISH_RES_TPW")) == 2) ? 2 : 1;
-        const int groups = (n_tiles32 + tpw - 1) / tpw;
-        const int slots = (np == 1 && tpw == 1 ? 4 * CF_RES_BF16_WAVES : 8) * m->n_cu;          // wave tasks resident at once on the whole chip
-        // as many chunks as keep every task resident in ONE round (a second, mostly empty round costs a whole chunk's chain)
-        int chunks = std::max(1, std::min(CF_T, slots / std::max(1, groups)));
-        if (cf_knob("CATFISH_RES_CHUNKS")) chunks = std::max(1, std::min(CF_T, atoi(cf_knob("CATFISH_RES_CHUNKS"))));   // A/B knob for tools/
-        const int len = (CF_T + chunks - 1) / chunks;
-        chunks = (CF_T + len - 1) / len;
-        const int lds_bytes = rb_pack_bytes(true, np) + rb_pack_bytes(false, np) + 4 * tpw * 32 * CF_T * 4;
-        const int per_cu = std::max(1, std::min(np == 1 && tpw == 1 ? CF_RES_BF16_WAVES : 2, (160 * 1024) / lds_bytes));
-        const int gridb = std::min((groups * chunks + 3) / 4, m->n_cu * per_cu);
-        bf16x8* yb = reinterpret_cast<bf16x8*>(sl.d_a[1]);
-        if (np == 2)
-            hipLaunchKernelGGL((res_stack2_bf16_kernel<2, 1>), dim3(gridb), dim3(256), lds_bytes, s, m->d_res_b[0], m->d_res_b[1], x, yb,
-                               n_windows, n_tiles32, chunks);
-        else if (tpw == 2)
-            hipLaunchKernelGGL((res_stack2_bf16_kernel<1, 2>), dim3(gridb), dim3(256), lds_bytes, s, m->d_res_b[0], m->d_res_b[1], x, yb,
-                               n_windows, n_tiles32, chunks);
-        else
-            hipLaunchKernelGGL((res_stack2_bf16_kernel<1, 1>), dim3(gridb), dim3(256), lds_bytes, s, m->d_res_b[0], m->d_res_b[1], x, yb,
-                               n_windows, n_tiles32, chunks);
-        HIP_TRY(hipGetLastError());
-        if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
-    }
-    if (res_fused) {
-        if ((rc = prof_begin(m, SLOT_RES_STACK2, s, &pi)) != CF_OK) return rc;
-        // latency mode: chunks of positions, one wave each, spread over the idle CUs (about four waves per CU in all)
-        int chunks = 1;
-        if (res_split) {
-            const int want = std::max(4, std::min(CF_T, (4 * m->n_cu) / std::max(1, n_tiles)));
-            const int len = (CF_T + want - 1) / want;
-            chunks = (CF_T + len - 1) / len;
-        }
-        const int waves2 = res_split ? 4 : res_waves;
-        const int lds_bytes = (res_pack_floats(true) + res_pack_floats(false) + waves2 * CF_TILE * CF_T) * 4;
-        const int grid2 = std::min((n_tiles * chunks + waves2 - 1) / waves2, m->n_cu * 3);     // 51 KB of LDS: three workgroups per CU
-        if (res_split)
-            hipLaunchKernelGGL(res_stack2_kernel<true>, dim3(grid2), dim3(waves2 * 64), lds_bytes, s, m->d_res[0], m->d_res[1], x,
-                               reinterpret_cast<f32x4*>(sl.d_a[1]), reinterpret_cast<f32x4*>(sl.d_a[0]), n_windows, n_tiles, chunks);
-        else
-            hipLaunchKernelGGL(res_stack2_kernel<false>, dim3(grid2), dim3(waves2 * 64), lds_bytes, s, m->d_res[0], m->d_res[1], x,
-                               reinterpret_cast<f32x4*>(sl.d_a[1]), (f32x4*)nullptr, n_windows, n_tiles, 1);
-        HIP_TRY(hipGetLastError());
-        if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
-    }
-    for (int b = (res_fused || res_fused_bf16) ? 2 : 0; b < m->hp.n_layers_res; ++b) {
-        float* dst = sl.d_a[b & 1];
-        if (m->np > 0) {
-            // residual blocks on the bf16 matrix pipe, 32-window tiles
-            const int grid32 = std::min((n_tiles32 + 3) / 4, m->n_cu * 4);
-            if ((rc = prof_begin(m, b == 0 ? SLOT_RES_FIRST : SLOT_RES, s, &pi)) != CF_OK) return rc;
-            const bf16x8* src = b == 0 ? nullptr : reinterpret_cast<const bf16x8*>(sl.d_a[(b - 1) & 1]);
-            if (b == 0) {
-                const int lds_bytes = rb_pack_bytes(true, m->np > 1 ? 2 : 1) + 4 * 32 * CF_T * 4;
-                if (m->np == 1)
-                    hipLaunchKernelGGL((res_block_bf16_kernel<true, 1>), dim3(grid32), dim3(256), lds_bytes, s, m->d_res_b[0], x, src,
-                                       reinterpret_cast<bf16x8*>(dst), n_windows, n_tiles32);
-                else
-                    hipLaunchKernelGGL((res_block_bf16_kernel<true, 2>), dim3(grid32), dim3(256), lds_bytes, s, m->d_res_b[0], x, src,
-                                       reinterpret_cast<bf16x8*>(dst), n_windows, n_tiles32);
-            } else {
-                const int lds_bytes = rb_pack_bytes(false, m->np > 1 ? 2 : 1);
-                if (m->np == 1)
-                    hipLaunchKernelGGL((res_block_bf16_kernel<false, 1>), dim3(grid32), dim3(256), lds_bytes, s, m->d_res_b[b],
-                                       (const float*)nullptr, src, reinterpret_cast<bf16x8*>(dst), n_windows, n_tiles32);
-                else
-                    hipLaunchKernelGGL((res_block_bf16_kernel<false, 2>), dim3(grid32), dim3(256), lds_bytes, s, m->d_res_b[b],
-                                       (const float*)nullptr, src, reinterpret_cast<bf16x8*>(dst), n_windows, n_tiles32);
-            }
-        } else if (b == 0) {
-            if ((rc = prof_begin(m, SLOT_RES_FIRST, s, &pi)) != CF_OK) return rc;
-            const int lds_bytes = (res_pack_floats(true) + res_waves * CF_TILE * CF_T) * 4;
-            hipLaunchKernelGGL((res_block_kernel<true>), dim3(res_grid), dim3(res_waves * 64), lds_bytes, s, m->d_res[0], x,
-                               (const f32x4*)nullptr, reinterpret_cast<f32x4*>(dst), n_windows, n_tiles, res_chunks);
-        } else {
-            if ((rc = prof_begin(m, SLOT_RES, s, &pi)) != CF_OK) return rc;
-            const int lds_bytes = res_pack_floats(false) * 4;
-            hipLaunchKernelGGL((res_block_kernel<false>), dim3(res_grid), dim3(res_waves * 64), lds_bytes, s, m->d_res[b], (const float*)nullptr,
-                               reinterpret_cast<const f32x4*>(sl.d_a[(b - 1) & 1]), reinterpret_cast<f32x4*>(dst), n_windows, n_tiles, res_chunks);
-        }
-        HIP_TRY(hipGetLastError());
-        if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
-    }
+    if ((rc = m->np > 0 ? run_res_bf16(m, sl, k, x, n_windows, n_tiles32, s) : run_res_fp32(m, sl, k, x, n_windows, n_tiles, s)) != CF_OK) return rc;
     if (m->hp.n_layers_res == 0) {
         if ((rc = prof_begin(m, SLOT_RES_FIRST, s, &pi)) != CF_OK) return rc;
         const int64_t n_el = (int64_t)n_tiles * CF_T * 64;
@@ -1941,9 +1841,12 @@ static int run_pass(cf_model* m, cf_model::Slot& sl, const float* x, int64_t n_w
     }
     const float* cur = m->hp.n_layers_res == 0 ? sl.d_a[0] : sl.d_a[(m->hp.n_layers_res - 1) & 1];
     // GRU layers
-    const bool fuse_now = m->fuse == 1 || (m->fuse == 2 && (n_tiles + 7) / 8 >= cf_fuse_min_groups(m->n_cu));
-    if (fuse_now) {
+    cf_gru_plan last_gru = {};      // what the last biGRU launch left in d_p: only the fp32 per-layer launch can leave raw partials
+    const int cin0 = m->hp.n_layers_res == 0 ? 16 : CF_C;     // RNN type: the raw sample embedded in 16 features
+    if (cf_fuse_now(m->fuse, n_tiles, m->n_cu)) {
         cf_fused_args a;
+        a.lds_floats = m->hp.n_layers > 1 ? gru_pack_floats(128) : gru_pack_floats(cin0);
+        const cf_fused_plan p = cf_fused_plan_for(n_tiles, m->n_cu, m->hp.n_layers, a.lds_floats * 4);
         for (int l = 0; l < 3; ++l) a.w[l] = l < m->hp.n_layers ? m->d_gru[l] : nullptr;
         a.x0 = reinterpret_cast<const f32x4*>(cur);
         a.y[0] = reinterpret_cast<f32x4*>(sl.d_y[0]);
@@ -1952,43 +1855,30 @@ static int run_pass(cf_model* m, cf_model::Slot& sl, const float* x, int64_t n_w
         a.flags = sl.d_flags;
         a.err = m->d_err;
         a.n_tiles = n_tiles;
-        a.groups = (n_tiles + 7) / 8;
+        a.groups = p.groups;
         a.n_layers = m->hp.n_layers;
-        a.cin0 = m->hp.n_layers_res == 0 ? 16 : CF_C;
+        a.cin0 = cin0;
         HIP_TRY(hipMemsetAsync(sl.d_flags, 0, ((size_t)a.n_layers * a.groups * 2 + (size_t)a.n_layers * 2) * sizeof(unsigned), s));
         if ((rc = prof_begin(m, SLOT_GRU_FUSED, s, &pi)) != CF_OK) return rc;
-        a.lds_floats = m->hp.n_layers > 1 ? gru_pack_floats(128) : gru_pack_floats(a.cin0);
-        const int lds_bytes = a.lds_floats * 4 + 16;
-        const int pool = std::min(a.groups, std::max(1, m->n_cu / 2)) * 2;     // workgroups per layer (both directions)
-        hipLaunchKernelGGL(gru_fused_kernel, dim3((unsigned)(a.n_layers * pool)), dim3(512), lds_bytes, s, a);
+        hipLaunchKernelGGL(gru_fused_kernel, dim3((unsigned)p.grid), dim3(p.threads), p.lds_bytes, s, a);
         HIP_TRY(hipGetLastError());
         if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
-    }
-    for (int l = 0; l < (fuse_now ? 0 : m->hp.n_layers); ++l) {
-        const bool last = l == m->hp.n_layers - 1;
-        float* y = sl.d_y[l & 1];
-        if (m->np > 0) {
-            rc = m->np == 1 ? launch_gru_bf16_layer<1>(m, l, last, cur, y, sl.d_p, n_tiles32, s)
-                            : launch_gru_bf16_layer<2>(m, l, last, cur, y, sl.d_p, n_tiles32, s);
-        } else if (l == 0 && m->hp.n_layers_res == 0) {
-            rc = last ? launch_gru<16, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand, sl.d_hand_flags)
-                      : launch_gru<16, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU0, sl.d_hand, sl.d_hand_flags);
-        } else if (l == 0) {
-            rc = last ? launch_gru<32, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand, sl.d_hand_flags)
-                      : launch_gru<32, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU0, sl.d_hand, sl.d_hand_flags);
-        } else {
-            rc = last ? launch_gru<128, true>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU_LAST, sl.d_hand, sl.d_hand_flags)
-                      : launch_gru<128, false>(m, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, SLOT_GRU, sl.d_hand, sl.d_hand_flags);
+    } else {
+        for (int l = 0; l < m->hp.n_layers; ++l) {
+            const bool last = l == m->hp.n_layers - 1;
+            const int slot = last ? SLOT_GRU_LAST : (l == 0 ? SLOT_GRU0 : SLOT_GRU);
+            float* y = sl.d_y[l & 1];
+            rc = m->np > 0 ? launch_gru_bf16(m, k, m->gru_cin[l], last, m->d_gru_b[l], cur, y, sl.d_p, n_tiles32, s, slot)
+                           : launch_gru(m, k, m->gru_cin[l], last, m->d_gru[l], cur, y, sl.d_p, n_tiles, s, slot, &last_gru, sl.d_hand, sl.d_hand_flags);
+            if (rc != CF_OK) return rc;
+            cur = y;
         }
-        if (rc != CF_OK) return rc;
-        cur = y;
     }
     // head
     if ((rc = prof_begin(m, SLOT_HEAD, s, &pi)) != CF_OK) return rc;
     const int64_t total = n_windows * CF_T;
-    const int raw_partials = (m->np == 0 && !fuse_now && use_coop(m, n_tiles)) ? 1 : 0;     // what the last biGRU launch left in d_p
     hipLaunchKernelGGL(head_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sl.d_p, m->d_dense_bias, probs, logits, n_windows,
-                       m->np > 0 ? n_tiles32 : n_tiles, m->np > 0 ? 5 : 4, raw_partials);
+                       m->np > 0 ? n_tiles32 : n_tiles, m->np > 0 ? 5 : 4, last_gru.raw_partials);
     HIP_TRY(hipGetLastError());
     if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
     sl.last_windows = n_windows;
@@ -2021,8 +1911,8 @@ extern "C" int cf_launch_regimes(const cf_model* m, int64_t out[4]) {
     out[0] = m->n_cu;
     if (m->gen) { out[1] = out[2] = out[3] = 0; return CF_OK; }       // one launch shape at every size
     out[1] = (int64_t)m->xp_tiles * CF_TILE;
-    out[2] = m->np == 0 ? (int64_t)m->n_cu * CF_TILE : 0;
-    out[3] = m->fuse == 1 ? 1 : (m->fuse == 2 ? ((int64_t)8 * cf_fuse_min_groups(m->n_cu) - 8) * CF_TILE + 1 : 0);
+    out[2] = m->np == 0 ? (int64_t)cf_coop_max_tiles(m->n_cu) * CF_TILE : 0;
+    out[3] = m->fuse == 1 ? 1 : (m->fuse == 2 ? cf_fuse_auto_min_windows(m->n_cu) : 0);
     return CF_OK;
 }
 
@@ -2302,32 +2192,22 @@ extern "C" int cf_gru_train_forward_dropout(cf_model* m, int32_t cin, const floa
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int n_tiles = (int)((n_windows + CF_TILE - 1) / CF_TILE);
-    if (n_tiles <= m->n_cu) {                // small batch: four waves per tile (latency mode), up to two rounds
-        const int gxc = std::min(n_tiles, std::max(1, m->n_cu / 2));
-        const bool hoist = n_tiles <= m->xp_tiles;
-        const f32x4* xp = hoist ? reinterpret_cast<const f32x4*>(m->d_xp) : nullptr;
-        if (cin == CF_C) {
-            if (hoist) launch_xproj<32>(m, wpack, x_frag, n_tiles, s);
-            hipLaunchKernelGGL((gru_train_fwd_coop_kernel<32>), dim3(gxc, 2), dim3(256), (gru_pack_floats(32) + CF_COOP_XCH_FLOATS) * 4, s, wpack,
-                               reinterpret_cast<const f32x4*>(x_frag), reinterpret_cast<f32x4*>(y_frag), reinterpret_cast<f32x4*>(stash), n_tiles, xp, yd, drop);
+    const cf_knobs k = cf_read_knobs();
+    return cf_with<32, 128>(cin, [&](auto C) {
+        constexpr int CIN = decltype(C)::value;
+        const cf_train_gru_plan p = cf_train_gru_plan_for(false, n_tiles, m->n_cu, CIN, k_gru_pack_bytes<CIN>, k_gru_x_bytes<CIN>, m->xp_tiles, k);
+        const f32x4 *x4 = reinterpret_cast<const f32x4*>(x_frag);
+        f32x4 *y4 = reinterpret_cast<f32x4*>(y_frag), *st4 = reinterpret_cast<f32x4*>(stash);
+        if (p.coop) {
+            if (p.hoist) launch_xproj<CIN>(m, p.xproj, wpack, x_frag, n_tiles, s);
+            hipLaunchKernelGGL((gru_train_fwd_coop_kernel<CIN>), dim3(p.gx, 2), dim3(p.waves * 64), p.lds_bytes, s, wpack, x4, y4, st4, n_tiles,
+                               p.hoist ? reinterpret_cast<const f32x4*>(m->d_xp) : nullptr, yd, drop);
         } else {
-            if (hoist) launch_xproj<128>(m, wpack, x_frag, n_tiles, s);
-            hipLaunchKernelGGL((gru_train_fwd_coop_kernel<128>), dim3(gxc, 2), dim3(256), (gru_pack_floats(128) + CF_COOP_XCH_FLOATS) * 4, s, wpack,
-                               reinterpret_cast<const f32x4*>(x_frag), reinterpret_cast<f32x4*>(y_frag), reinterpret_cast<f32x4*>(stash), n_tiles, xp, yd, drop);
+            hipLaunchKernelGGL((gru_train_fwd_kernel<CIN>), dim3(p.gx, 2), dim3(p.waves * 64), p.lds_bytes, s, wpack, x4, y4, st4, n_tiles, yd, drop);
         }
         HIP_TRY(hipGetLastError());
         return CF_OK;
-    }
-    const int waves = pick_waves(2 * n_tiles, m->n_cu);
-    const int gx = std::min((n_tiles + waves - 1) / waves, std::max(1, m->n_cu / 2));
-    if (cin == CF_C)
-        hipLaunchKernelGGL((gru_train_fwd_kernel<32>), dim3(gx, 2), dim3(waves * 64), gru_pack_floats(32) * 4, s, wpack,
-                           reinterpret_cast<const f32x4*>(x_frag), reinterpret_cast<f32x4*>(y_frag), reinterpret_cast<f32x4*>(stash), n_tiles, yd, drop);
-    else
-        hipLaunchKernelGGL((gru_train_fwd_kernel<128>), dim3(gx, 2), dim3(waves * 64), gru_pack_floats(128) * 4, s, wpack,
-                           reinterpret_cast<const f32x4*>(x_frag), reinterpret_cast<f32x4*>(y_frag), reinterpret_cast<f32x4*>(stash), n_tiles, yd, drop);
-    HIP_TRY(hipGetLastError());
-    return CF_OK;
+    });
 }
 
 extern "C" int cf_gru_train_forward(cf_model* m, int32_t cin, const float* wpack, const float* x_frag, float* y_frag, float* stash,
@@ -2335,13 +2215,17 @@ extern "C" int cf_gru_train_forward(cf_model* m, int32_t cin, const float* wpack
     return cf_gru_train_forward_dropout(m, cin, wpack, x_frag, y_frag, stash, n_windows, nullptr, 1.f, 0u, 0, nullptr, stream);
 }
 
-// chunks of steps per (tile, direction) of the deferred input-gradient launch (gru_dx_kernel: launch shape only, results do not depend on it)
-// -- about 2.25 workgroups per CU: at the reference's batch (256 windows = 16 tiles) 18 chunks instead of round 5's 7 took the training
-// step from 0.756 to 0.738 ms (profiles/r06_train_dx_chunks.log); few tiles keep one step per workgroup, many keep 7 chunks
-static int dx_chunks(int n_tiles, int n_cu) {
-    if (cf_knob("CATFISH_DX_CHUNKS")) return std::max(1, std::min(atoi(cf_knob("CATFISH_DX_CHUNKS")), CF_T));      // A/B knob for tools/
-    const int want = (9 * std::max(1, n_cu) / 4 + 2 * n_tiles - 1) / (2 * std::max(1, n_tiles));
-    return std::max(7, std::min(CF_T, want));
+// ---- training: biGRU forward / backward (cf_train_gru_plan_for) -------------------------------------------------------------------
+static void optin_gru_train(cf_optin& o) {
+    for (int cin : {32, 128})
+        cf_with<32, 128>(cin, [&](auto C) {
+            constexpr int CIN = decltype(C)::value, BWD = gtb_pack_floats(CIN) * 4;
+            o((const void*)gru_train_fwd_coop_kernel<CIN>, cf_train_coop_lds(false, k_gru_pack_bytes<CIN>));
+            o((const void*)gru_train_bwd_coop_kernel<CIN>, cf_train_coop_lds(true, BWD));
+            o((const void*)gru_train_fwd_kernel<CIN>, k_gru_pack_bytes<CIN>);
+            o((const void*)gru_train_bwd_kernel<CIN>, BWD);
+            return CF_OK;
+        });
 }
 
 extern "C" int cf_gru_train_backward_dropout(cf_model* m, int32_t cin, const float* wpack_bwd, const float* y_frag, const float* stash,
@@ -2357,44 +2241,25 @@ extern "C" int cf_gru_train_backward_dropout(cf_model* m, int32_t cin, const flo
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int n_tiles = (int)((n_windows + CF_TILE - 1) / CF_TILE);
-    if (n_tiles <= m->n_cu) {                // small batch: four waves per tile (latency mode), up to two rounds
-        const int gxc = std::min(n_tiles, std::max(1, m->n_cu / 2));
-        const int defer = n_tiles <= m->xp_tiles ? 1 : 0;                    // few tiles: dx is formed afterwards on the idle CUs
-        const int dxc = dx_chunks(n_tiles, m->n_cu);
-        if (cin == CF_C) {
-            hipLaunchKernelGGL((gru_train_bwd_coop_kernel<32>), dim3(gxc, 2), dim3(256), (gtb_pack_floats(32) + CF_COOP_BWD_XCH_FLOATS) * 4, s,
-                               wpack_bwd, reinterpret_cast<const f32x4*>(y_frag), reinterpret_cast<const f32x4*>(stash),
-                               reinterpret_cast<const f32x4*>(dy_frag), reinterpret_cast<const f32x4*>(dy2_frag),
-                               reinterpret_cast<const f32x4*>(dy_scale), reinterpret_cast<f32x4*>(dx_frag), reinterpret_cast<f32x4*>(da), n_tiles, defer, drop);
-            if (defer)
-                hipLaunchKernelGGL((gru_dx_kernel<32>), dim3(n_tiles * dxc, 2), dim3(256), 0, s, wpack_bwd, reinterpret_cast<const f32x4*>(da),
-                                   reinterpret_cast<f32x4*>(dx_frag), n_tiles, dxc);
+    const cf_knobs k = cf_read_knobs();
+    return cf_with<32, 128>(cin, [&](auto C) {
+        constexpr int CIN = decltype(C)::value;
+        const cf_train_gru_plan p = cf_train_gru_plan_for(true, n_tiles, m->n_cu, CIN, gtb_pack_floats(CIN) * 4, 0, m->xp_tiles, k);
+        const f32x4 *y4 = reinterpret_cast<const f32x4*>(y_frag), *st4 = reinterpret_cast<const f32x4*>(stash), *dy4 = reinterpret_cast<const f32x4*>(dy_frag),
+                    *dy24 = reinterpret_cast<const f32x4*>(dy2_frag), *sc4 = reinterpret_cast<const f32x4*>(dy_scale);
+        f32x4 *dx4 = reinterpret_cast<f32x4*>(dx_frag), *da4 = reinterpret_cast<f32x4*>(da);
+        if (p.coop) {
+            hipLaunchKernelGGL((gru_train_bwd_coop_kernel<CIN>), dim3(p.gx, 2), dim3(p.waves * 64), p.lds_bytes, s, wpack_bwd, y4, st4, dy4, dy24, sc4,
+                               dx4, da4, n_tiles, p.hoist, drop);
+            if (p.hoist)         // few tiles: dx is formed afterwards on the idle CUs
+                hipLaunchKernelGGL((gru_dx_kernel<CIN>), dim3(p.dx_grid_x, 2), dim3(256), 0, s, wpack_bwd, da4, dx4, n_tiles, p.dx_chunks);
         } else {
-            hipLaunchKernelGGL((gru_train_bwd_coop_kernel<128>), dim3(gxc, 2), dim3(256), (gtb_pack_floats(128) + CF_COOP_BWD_XCH_FLOATS) * 4, s,
-                               wpack_bwd, reinterpret_cast<const f32x4*>(y_frag), reinterpret_cast<const f32x4*>(stash),
-                               reinterpret_cast<const f32x4*>(dy_frag), reinterpret_cast<const f32x4*>(dy2_frag),
-                               reinterpret_cast<const f32x4*>(dy_scale), reinterpret_cast<f32x4*>(dx_frag), reinterpret_cast<f32x4*>(da), n_tiles, defer, drop);
-            if (defer)
-                hipLaunchKernelGGL((gru_dx_kernel<128>), dim3(n_tiles * dxc, 2), dim3(256), 0, s, wpack_bwd, reinterpret_cast<const f32x4*>(da),
-                                   reinterpret_cast<f32x4*>(dx_frag), n_tiles, dxc);
+            hipLaunchKernelGGL((gru_train_bwd_kernel<CIN>), dim3(p.gx, 2), dim3(p.waves * 64), p.lds_bytes, s, wpack_bwd, y4, st4, dy4, dy24, sc4, dx4,
+                               da4, n_tiles, drop);
         }
         HIP_TRY(hipGetLastError());
         return CF_OK;
-    }
-    const int waves = pick_waves(2 * n_tiles, m->n_cu);
-    const int gx = std::min((n_tiles + waves - 1) / waves, std::max(1, m->n_cu / 2));
-    if (cin == CF_C)
-        hipLaunchKernelGGL((gru_train_bwd_kernel<32>), dim3(gx, 2), dim3(waves * 64), gtb_pack_floats(32) * 4, s, wpack_bwd,
-                           reinterpret_cast<const f32x4*>(y_frag), reinterpret_cast<const f32x4*>(stash),
-                           reinterpret_cast<const f32x4*>(dy_frag), reinterpret_cast<const f32x4*>(dy2_frag),
-                               reinterpret_cast<const f32x4*>(dy_scale), reinterpret_cast<f32x4*>(dx_frag), reinterpret_cast<f32x4*>(da), n_tiles, drop);
-    else
-        hipLaunchKernelGGL((gru_train_bwd_kernel<128>), dim3(gx, 2), dim3(waves * 64), gtb_pack_floats(128) * 4, s, wpack_bwd,
-                           reinterpret_cast<const f32x4*>(y_frag), reinterpret_cast<const f32x4*>(stash),
-                           reinterpret_cast<const f32x4*>(dy_frag), reinterpret_cast<const f32x4*>(dy2_frag),
-                               reinterpret_cast<const f32x4*>(dy_scale), reinterpret_cast<f32x4*>(dx_frag), reinterpret_cast<f32x4*>(da), n_tiles, drop);
-    HIP_TRY(hipGetLastError());
-    return CF_OK;
+    });
 }
 
 extern "C" int cf_gru_train_backward(cf_model* m, int32_t cin, const float* wpack_bwd, const float* y_frag, const float* stash,
@@ -2404,8 +2269,6 @@ extern "C" int cf_gru_train_backward(cf_model* m, int32_t cin, const float* wpac
                                          nullptr, stream);
 }
 
-// The mask / keep_prob tensor the training kernels apply to the output of `layer` (fragment layout [tiles][35][8][64][4]), written out
-// for tests and tools: the kernels themselves never store it.
 // ---- any-size biGRU layer for training (generic.hpp): forward with gate stash, backward chain -----------------------------------
 #include "anysize_launch.hpp"      // waves, grid, LDS bytes and h_via_y of the two launches below: host-only, tested on the CPU
 
@@ -2536,6 +2399,8 @@ __global__ __launch_bounds__(256) void dropout_scale_kernel(f32x4* __restrict__ 
     if (i < n4) out[i] = cf_drop_scale4(cf_drop_key(drop), drop.keep_prob, i);
 }
 
+// The mask / keep_prob tensor the training kernels apply to the output of `layer` (fragment layout [tiles][35][8][64][4]), written out
+// for tests and tools: the kernels themselves never store it.
 extern "C" int cf_dropout_scale(cf_model* m, float keep_prob, uint32_t seed, int32_t layer, const double* step_count, int64_t n_windows,
                                 float* scale_frag, void* stream) {
     if (!m || !scale_frag) return fail(CF_ERR_INVALID, "cf_dropout_scale: null argument");
@@ -2548,18 +2413,9 @@ extern "C" int cf_dropout_scale(cf_model* m, float keep_prob, uint32_t seed, int
     return CF_OK;
 }
 
-static int wgrad_pairs_per_wg(int n_pairs, int n_cu) {
-    // two directions x n_chunks workgroups should cover the chip about once; at least 8 pairs each keeps the
-    // partial sums (148 KiB per workgroup) well below the traffic of the operands themselves
-    return std::max(8, (2 * n_pairs + n_cu - 1) / n_cu);
-}
-
 extern "C" int64_t cf_gru_wgrad_workspace_floats(cf_model* m, int32_t cin, int64_t n_windows) {
     if (!m || (cin != CF_C && cin != 2 * CF_H) || n_windows <= 0) return 0;
-    const int n_pairs = (int)((n_windows + CF_TILE - 1) / CF_TILE) * CF_T;
-    const int ppw = wgrad_pairs_per_wg(n_pairs, m->n_cu);
-    const int64_t n_chunks = (n_pairs + ppw - 1) / ppw;
-    return n_chunks * 2 * gwg_partial_floats(cin);
+    return cf_wgrad_plan_for((int)((n_windows + CF_TILE - 1) / CF_TILE), m->n_cu, gwg_partial_floats(cin)).workspace_floats;
 }
 
 extern "C" int cf_gru_train_wgrad(cf_model* m, int32_t cin, const float* x_frag, const float* y_frag, const float* stash,
@@ -2575,20 +2431,17 @@ extern "C" int cf_gru_train_wgrad(cf_model* m, int32_t cin, const float* x_frag,
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int n_tiles = (int)((n_windows + CF_TILE - 1) / CF_TILE);
-    const int n_pairs = n_tiles * CF_T;
-    const int ppw = wgrad_pairs_per_wg(n_pairs, m->n_cu);
-    const int n_chunks = (n_pairs + ppw - 1) / ppw;
-    if (cin == CF_C)
-        hipLaunchKernelGGL((gru_wgrad_kernel<32>), dim3(n_chunks, 2), dim3(CF_WGRAD_WAVES * 64), 0, s, reinterpret_cast<const f32x4*>(x_frag),
-                           reinterpret_cast<const f32x4*>(y_frag), reinterpret_cast<const f32x4*>(stash), reinterpret_cast<const f32x4*>(da),
-                           workspace, n_tiles, ppw);
-    else
-        hipLaunchKernelGGL((gru_wgrad_kernel<128>), dim3(n_chunks, 2), dim3(CF_WGRAD_WAVES * 64), 0, s, reinterpret_cast<const f32x4*>(x_frag),
-                           reinterpret_cast<const f32x4*>(y_frag), reinterpret_cast<const f32x4*>(stash), reinterpret_cast<const f32x4*>(da),
-                           workspace, n_tiles, ppw);
+    const cf_wgrad_plan p = cf_wgrad_plan_for(n_tiles, m->n_cu, gwg_partial_floats(cin));
+    rc = cf_with<32, 128>(cin, [&](auto C) {
+        hipLaunchKernelGGL((gru_wgrad_kernel<decltype(C)::value>), dim3(p.n_chunks, 2), dim3(CF_WGRAD_WAVES * 64), 0, s,
+                           reinterpret_cast<const f32x4*>(x_frag), reinterpret_cast<const f32x4*>(y_frag), reinterpret_cast<const f32x4*>(stash),
+                           reinterpret_cast<const f32x4*>(da), workspace, n_tiles, p.pairs_per_wg);
+        return CF_OK;
+    });
+    if (rc != CF_OK) return rc;
     HIP_TRY(hipGetLastError());
     const int per = gwg_partial_floats(cin);
-    hipLaunchKernelGGL(gru_wgrad_reduce_kernel, dim3((per + 63) / 64, 2), dim3(256), 0, s, workspace, grads, gwg_rows(cin), n_chunks);
+    hipLaunchKernelGGL(gru_wgrad_reduce_kernel, dim3((per + 63) / 64, 2), dim3(256), 0, s, workspace, grads, gwg_rows(cin), p.n_chunks);
     HIP_TRY(hipGetLastError());
     return CF_OK;
 }
@@ -2651,17 +2504,21 @@ extern "C" int cf_res_train_backward(cf_model* m, int32_t n_blocks, const float*
     return CF_OK;
 }
 
-// ---- dense head + loss, optimizer (training) ------------------------------------------------
-static int head_waves(const cf_model* m, int64_t n_windows) {
-    // a wave takes ~8 (tile, t) items: few enough partial sums that the fixed-order reduction stays a couple of microseconds
-    const int64_t items = ((n_windows + CF_TILE - 1) / CF_TILE) * CF_T;
-    const int64_t wgs = std::min<int64_t>((items + 31) / 32, (int64_t)m->n_cu * 2);
-    return (int)std::max<int64_t>(1, wgs) * 4;
+static hipError_t cf_optin_all() {
+    cf_optin o;
+    optin_gru_layer(o);
+    optin_gru_bf16(o);
+    optin_res(o);
+    optin_gru_train(o);
+    o((const void*)res_train_fwd_kernel, RT_FWD_LDS_BYTES);
+    o((const void*)res_train_bwd_kernel, RT_BWD_LDS_BYTES);
+    return o.e;
 }
 
+// ---- dense head + loss, optimizer (training) ------------------------------------------------
 extern "C" int64_t cf_train_head_workspace_floats(cf_model* m, int64_t n_windows) {
     if (!m || n_windows <= 0) return 0;
-    return (int64_t)head_waves(m, n_windows) * CF_HEAD_PART;
+    return cf_train_head_plan_for((n_windows + CF_TILE - 1) / CF_TILE, m->n_cu, CF_HEAD_PART).workspace_floats;
 }
 
 extern "C" int cf_train_head(cf_model* m, const float* y_frag, const float* dense_kernel, const float* dense_bias, const float* labels,
@@ -2676,12 +2533,12 @@ extern "C" int cf_train_head(cf_model* m, const float* y_frag, const float* dens
     HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int n_tiles = (int)((n_windows + CF_TILE - 1) / CF_TILE);
-    const int waves = head_waves(m, n_windows);
+    const cf_train_head_plan p = cf_train_head_plan_for(n_tiles, m->n_cu, CF_HEAD_PART);
     const float inv_count = (float)(1.0 / ((double)n_windows * CF_T));
-    hipLaunchKernelGGL(train_head_kernel, dim3(waves / 4), dim3(256), 0, s, reinterpret_cast<const f32x4*>(y_frag), dense_kernel, dense_bias,
+    hipLaunchKernelGGL(train_head_kernel, dim3(p.grid), dim3(256), 0, s, reinterpret_cast<const f32x4*>(y_frag), dense_kernel, dense_bias,
                        labels, reinterpret_cast<f32x4*>(dy_frag), logits, workspace, n_windows, n_tiles, inv_count);
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(train_head_reduce_kernel, dim3(3), dim3(256), 0, s, workspace, waves, grads, loss, inv_count);
+    hipLaunchKernelGGL(train_head_reduce_kernel, dim3(3), dim3(256), 0, s, workspace, p.waves, grads, loss, inv_count);
     HIP_TRY(hipGetLastError());
     return CF_OK;
 }

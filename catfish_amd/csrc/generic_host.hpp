@@ -237,12 +237,9 @@ static int gen_build(cf_model* m, const cf_weights* w) {
         HIP_TRY(hipFuncSetAttribute((const void*)gen_gru2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->gru2_lds));
     HIP_TRY(hipFuncSetAttribute(g->x3 ? (const void*)gen_gru_kernel<false, true> : (const void*)gen_gru_kernel<false, false>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->gru_lds));
-    HIP_TRY(hipFuncSetAttribute((const void*)gru_layer_kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gru_pack_floats(16) * 4));
-    HIP_TRY(hipFuncSetAttribute((const void*)gru_layer_kernel<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gru_pack_floats(32) * 4));
-    HIP_TRY(hipFuncSetAttribute((const void*)gru_layer_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, gru_pack_floats(128) * 4));
-    HIP_TRY(hipFuncSetAttribute((const void*)gru_layer_coop_kernel<16, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (gru_pack_floats(16) + CF_COOP_XCH_FLOATS) * 4));
-    HIP_TRY(hipFuncSetAttribute((const void*)gru_layer_coop_kernel<32, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (gru_pack_floats(32) + CF_COOP_XCH_FLOATS) * 4));
-    HIP_TRY(hipFuncSetAttribute((const void*)gru_layer_coop_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (gru_pack_floats(128) + CF_COOP_XCH_FLOATS) * 4));
+    cf_optin tuned;              // the LDS-resident kernels of gen_layer_tuned layers: the same opt-in as a model on the tuned path
+    optin_gru_layer(tuned);
+    HIP_TRY(tuned.e);
     return CF_OK;
 }
 
@@ -250,6 +247,7 @@ static int gen_run_pass(cf_model* m, const float* x, int64_t n_windows, float* p
     cf_generic* g = m->gen;
     const int n_tiles = (int)((n_windows + CF_TILE - 1) / CF_TILE);
     const int task_grid = (int)std::min<int64_t>(((int64_t)n_tiles * CF_T + 3) / 4, (int64_t)m->n_cu * 16);
+    const cf_knobs knobs = cf_read_knobs();
     int rc;
     size_t pi = 0;
     f32x4* R[4];
@@ -296,10 +294,7 @@ static int gen_run_pass(cf_model* m, const float* x, int64_t n_windows, float* p
         if (L.tuned) {               // a 64-unit layer with 16 / 32 / 128 inputs: the LDS-resident kernel (all its launch regimes)
             const float* x_in = reinterpret_cast<const float*>(cur);
             float* y_out = reinterpret_cast<float*>(G[l & 1]);
-            rc = L.tuned_cin == 16 ? launch_gru<16, false>(m, L.tuned, x_in, y_out, nullptr, n_tiles, s, slot)
-               : L.tuned_cin == 32 ? launch_gru<32, false>(m, L.tuned, x_in, y_out, nullptr, n_tiles, s, slot)
-                                   : launch_gru<128, false>(m, L.tuned, x_in, y_out, nullptr, n_tiles, s, slot);
-            if (rc != CF_OK) return rc;
+            if ((rc = launch_gru(m, knobs, L.tuned_cin, false, L.tuned, x_in, y_out, nullptr, n_tiles, s, slot)) != CF_OK) return rc;
             cur = G[l & 1];
             continue;
         }

@@ -10,9 +10,6 @@
 
 template <int W>
 __device__ __forceinline__ float pick4(const f32x4& a) { return a[W]; }
-// workgroups per tile in gru_xproj_kernel / gru_dx_kernel: one step each while the call is tiny (parallelism), five steps
-// each otherwise (the weight fragments are fetched from L2 once per workgroup)
-static inline int cf_xproj_chunks(int n_tiles) { return n_tiles <= 8 ? CF_T : 7; }
 #ifndef CF_COOP_PF
 #define CF_COOP_PF 4        // A-fragment prefetch depth (k-steps) of the cooperative forward kernel
 #endif
@@ -301,22 +298,6 @@ __global__ __launch_bounds__(256) void gru_xproj_lds_kernel(const float* __restr
 #pragma unroll
         for (int g = 0; g < KGX; ++g) xc[g] = xn[g];
     }
-}
-
-// chunks of steps per (tile, direction) for gru_xproj_lds_kernel: the count that minimises rounds x (staging + steps per chunk),
-// in 0.01 us (staging the x region ~2.5 us at Cin = 128, a step = 96 MFMAs of 32 cycles per wave)
-static inline int cf_xproj_plan(int n_tiles, int n_cu, int cin) {
-    const int stage = cin >= 128 ? 250 : 80, step = cin >= 128 ? 128 : 32;
-    const int slots = std::max(1, n_cu) * (cin >= 128 ? 1 : 4);            // resident workgroups: 96 KiB of LDS each at Cin = 128
-    int best = 1, best_cost = 1 << 30;
-    for (int c = 1; c <= CF_T; ++c) {
-        const int tl = (CF_T + c - 1) / c;
-        if ((CF_T + tl - 1) / tl != c) continue;                           // (only chunk counts that leave no empty chunk)
-        const int rounds = (2 * n_tiles * c + slots - 1) / slots;
-        const int cost = rounds * (stage + tl * step);
-        if (cost < best_cost) { best_cost = cost; best = c; }
-    }
-    return best;
 }
 
 template <int CIN, bool LAST>
