@@ -19,6 +19,13 @@ kernel reproduces it bit for bit (tests/test_device_db_gpu.py).
 
 The object is host-only until a trainer asks for the pools on a card (``device_pools``); the host's draw counter and the
 device's are one number -- whichever side drew last writes it through.
+
+``DeviceReadDb`` is the same sampler over the labelled reads themselves: the reads stay concatenated (float32 signal, uint8 labels,
+5 B per sample), a row is an entry of one of two ordered tables of window starts, and a window is ``signal[start : start + 35]``.
+``centre_tables`` states in numpy which windows the tables hold -- the reference's selection (``TrainingRead.get_pos`` / ``get_neg``,
+networks/trainingDB/TrainingRead.py:226-257; ``ExampleDb.add_training_read`` draws as many negatives as the read has positives),
+with the random subset of negatives drawn by the keyed bijection above, so that it is reproducible and a kernel could repeat it.
+It is a host database and feeds the per-step loop; building the tables and gathering on the card is not implemented.
 """
 from __future__ import annotations
 
@@ -99,41 +106,26 @@ def _pool(windows):
     return np.stack(rows) if rows else np.zeros((0, WINDOW), np.float32)
 
 
-class DeviceExampleDb(object):
-    """Two pools of 35-sample windows (``pos``: all-ones labels, ``neg``: all-zeros), float32 ``[n, 35]`` each, and the
-    stateless balanced sampler of the module docstring.  A drop-in for ``WindowExampleDb`` (``get_training_set``) and the
-    source of ``Trainer.train_steps`` / ``RNN.train_network_steps``, which sample on the card."""
+class DeviceFedDb(object):
+    """What the device-fed training loop needs of a database, whatever a "row" is: the stateless sampler over ``nb_pos`` /
+    ``nb_neg`` rows, the per-step surface of ``WindowExampleDb`` and the draw counter shared with the card.  A subclass says
+    what a row holds (``gather``) and, when it has a card side, what it keeps there (``device_pools``); one without
+    ``device_pools`` is fed by the host."""
 
-    def __init__(self, pos, neg, seed, device=None):
-        self.pos = _pool(pos)
-        self.neg = _pool(neg)
-        self.nb_pos, self.nb_neg = int(self.pos.shape[0]), int(self.neg.shape[0])
+    def __init__(self, seed, device=None):
         self.seed = int(seed) & 0xFFFFFFFF
         self.draw = 0                    # number of the NEXT draw
         self.device = device
-        self._dev = None                 # {"pos", "neg", "counter"} on the card, uploaded once
+        self._dev = None                 # what lives on the card, uploaded once; holds "counter"
         self._dev_draw = None            # what the device counter holds once everything enqueued so far has run
         self._last = None                # ("host", x, y) | ("device", x tensor, y tensor, size)
 
-    @classmethod
-    def from_window_db(cls, db, seed, device=None):
-        """The pools of a ``train_validate.WindowExampleDb``."""
-        return cls(db.pos, db.neg, seed, device)
-
     # ------------------------------------------------------------------ the sampler on the host
     def batch_indices(self, d, size, ratio=2):
-        """Draw number ``d`` -> (is_pos bool [size], row int64 [size]): slot ``j`` holds ``pos[row[j]]`` when ``is_pos[j]``,
-        else ``neg[row[j]]``.  Pure integer arithmetic; ``cf_sample_batch`` computes the same."""
+        """Draw number ``d`` -> (is_pos bool [size], row int64 [size]): slot ``j`` holds positive row ``row[j]`` when
+        ``is_pos[j]``, else negative row ``row[j]``.  Pure integer arithmetic; the sampling kernels compute the same."""
         is_pos, row = draw_indices(self.seed, [int(d)], size, ratio, self.nb_pos, self.nb_neg)
         return is_pos[0], row[0]
-
-    def gather(self, d, size, ratio=2):
-        """Draw ``d`` as arrays: (x float32 [size, 35], is_pos bool [size])."""
-        is_pos, row = self.batch_indices(d, size, ratio)
-        x = np.empty((int(size), WINDOW), np.float32)
-        x[is_pos] = self.pos[row[is_pos]]
-        x[~is_pos] = self.neg[row[~is_pos]]
-        return x, is_pos
 
     def get_training_set(self, size, ratio=2):
         """``WindowExampleDb.get_training_set``'s shapes for the next draw: (tuple of windows, tuple of label lists, number
@@ -152,21 +144,6 @@ class DeviceExampleDb(object):
         self.draw += int(k)
 
     # ------------------------------------------------------------------ the card's side (used by training.Trainer)
-    def device_pools(self, device=None):
-        """(pos tensor [max(n_pos, 1), 35], neg tensor, draw counter int64 [1]) on ``device``; uploaded on the first call."""
-        import torch
-        device = torch.device(self.device if device is None else device)
-        if device.type != "cuda":
-            raise ValueError("device_pools: the pools go to a GPU")
-        if device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        if self._dev is None or self._dev["device"] != device:
-            up = lambda a: torch.from_numpy(a if a.shape[0] else np.zeros((1, WINDOW), np.float32)).to(device)     # noqa: E731
-            self._dev = {"device": device, "pos": up(self.pos), "neg": up(self.neg),
-                         "counter": torch.zeros(1, dtype=torch.int64, device=device)}
-            self._dev_draw = 0
-        return self._dev["pos"], self._dev["neg"], self._dev["counter"]
-
     def sync_counter(self):
         """Write the host's draw number through to the device counter when the host moved it (enqueued on the current stream)."""
         if self._dev is not None and self._dev_draw != self.draw:
@@ -191,6 +168,46 @@ class DeviceExampleDb(object):
                 y[:size].detach().cpu().numpy().astype(np.int64).reshape(size, WINDOW))
 
 
+class DeviceExampleDb(DeviceFedDb):
+    """Two pools of 35-sample windows (``pos``: all-ones labels, ``neg``: all-zeros), float32 ``[n, 35]`` each, and the
+    stateless balanced sampler of the module docstring.  A drop-in for ``WindowExampleDb`` (``get_training_set``) and the
+    source of ``Trainer.train_steps`` / ``RNN.train_network_steps``, which sample on the card."""
+
+    def __init__(self, pos, neg, seed, device=None):
+        DeviceFedDb.__init__(self, seed, device)
+        self.pos = _pool(pos)
+        self.neg = _pool(neg)
+        self.nb_pos, self.nb_neg = int(self.pos.shape[0]), int(self.neg.shape[0])
+
+    @classmethod
+    def from_window_db(cls, db, seed, device=None):
+        """The pools of a ``train_validate.WindowExampleDb``."""
+        return cls(db.pos, db.neg, seed, device)
+
+    def gather(self, d, size, ratio=2):
+        """Draw ``d`` as arrays: (x float32 [size, 35], is_pos bool [size])."""
+        is_pos, row = self.batch_indices(d, size, ratio)
+        x = np.empty((int(size), WINDOW), np.float32)
+        x[is_pos] = self.pos[row[is_pos]]
+        x[~is_pos] = self.neg[row[~is_pos]]
+        return x, is_pos
+
+    def device_pools(self, device=None):
+        """(pos tensor [max(n_pos, 1), 35], neg tensor, draw counter int64 [1]) on ``device``; uploaded on the first call."""
+        import torch
+        device = torch.device(self.device if device is None else device)
+        if device.type != "cuda":
+            raise ValueError("device_pools: the pools go to a GPU")
+        if device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self._dev is None or self._dev["device"] != device:
+            up = lambda a: torch.from_numpy(a if a.shape[0] else np.zeros((1, WINDOW), np.float32)).to(device)     # noqa: E731
+            self._dev = {"device": device, "pos": up(self.pos), "neg": up(self.neg),
+                         "counter": torch.zeros(1, dtype=torch.int64, device=device)}
+            self._dev_draw = 0
+        return self._dev["pos"], self._dev["neg"], self._dev["counter"]
+
+
 def device_db_from_npz(npz_files, width=34, lessen=1, max_neg_per_read=2000, seed=0, device=None):
     """``train_validate.example_db_from_npz``'s windows (the same selection code) in a ``DeviceExampleDb``."""
     from .train_validate import example_db_from_npz
@@ -201,3 +218,141 @@ def synthetic_device_db(n_reads=8, read_len=20000, seed=0, device=None):
     """``train_validate.synthetic_example_db``'s windows in a ``DeviceExampleDb``."""
     from .train_validate import synthetic_example_db
     return DeviceExampleDb.from_window_db(synthetic_example_db(n_reads, read_len, seed), seed, device)
+
+
+# --------------------------------------------------------------------------- the training set from the labelled reads themselves
+def _neg_quota(neg_per_read, m, n_pos):
+    """How many of a read's ``m`` candidates become negatives when the read has ``n_pos`` positives."""
+    if neg_per_read is None:
+        return m
+    if isinstance(neg_per_read, str):
+        if neg_per_read != "positives":
+            raise ValueError("neg_per_read: None, an int or 'positives', got %r" % (neg_per_read,))
+        return min(m, n_pos)
+    if isinstance(neg_per_read, (bool, np.bool_)) or int(neg_per_read) != neg_per_read or int(neg_per_read) < 0:
+        raise ValueError("neg_per_read: None, a non-negative int or 'positives', got %r" % (neg_per_read,))
+    return min(m, int(neg_per_read))
+
+
+def _read_layout(labels, offsets, lessen):
+    labels = np.asarray(labels)
+    if labels.dtype != np.uint8 or labels.ndim != 1:
+        raise ValueError("labels: one uint8 array over all reads")
+    if labels.size and labels.max() > 1:
+        raise ValueError("labels must be 0 or 1")
+    offsets = np.asarray(offsets, dtype=np.int64).reshape(-1)
+    if offsets.size < 1 or offsets[0] != 0 or offsets[-1] != labels.size or np.any(np.diff(offsets) < 0):
+        raise ValueError("offsets: int64 [n_reads + 1], ascending from 0 to the number of samples")
+    if int(lessen) != lessen or int(lessen) < 1:
+        raise ValueError("lessen must be a positive int")
+    return labels, offsets, int(lessen)
+
+
+def centre_tables(labels, offsets, lessen=1, neg_per_read=None, seed=0):
+    """Which windows of the concatenated reads (``labels`` uint8 [total], ``offsets`` int64 [R + 1], the layout of
+    ``DeviceValidationSet.from_arrays``) are training examples -> (pos_start int64 [], neg_start int64 []): the index of each
+    window's first sample, in (read, centre) order.
+
+    For read ``rho`` of ``n`` samples the centres are ``c`` in ``[17, n - 17)``, ascending.  The centres with label 1 are
+    numbered k = 0, 1, ...; centre k is a positive iff ``k % lessen == 0`` and all 35 labels of ``[c - 17, c + 17]`` are 1
+    (``TrainingRead.get_pos``: the numbering runs over ALL label-1 centres).  The centres whose 35 labels are all 0 are the
+    candidates, numbered j = 0 .. m - 1; the read contributes q of them: ``neg_per_read=None`` q = m, an int q = min(m, it),
+    ``"positives"`` q = min(m, the read's positives) (the reference's rule).  Candidate j is a negative iff q == m or
+    ``keyed_permutation(j, m, key) < q`` with ``key = fmix32(seed ^ fmix32((rho + 1) * 0x9E3779B9))`` -- a bijection, so exactly
+    q are.  A read shorter than 35 samples contributes nothing."""
+    labels, offsets, lessen = _read_layout(labels, offsets, lessen)
+    _neg_quota(neg_per_read, 0, 0)                                       # a bad rule is refused even when no read has a candidate
+    seed = _U(int(seed) & 0xFFFFFFFF)
+    running = np.zeros(labels.size + 1, dtype=np.int64)
+    np.cumsum(labels, out=running[1:])
+    pos, neg = [], []
+    for rho in range(offsets.size - 1):
+        o, n = int(offsets[rho]), int(offsets[rho + 1] - offsets[rho])
+        if n < WINDOW:
+            continue
+        first = o + np.arange(n - WINDOW + 1, dtype=np.int64)            # the window of centre c starts at o + c - 17
+        ones = running[first + WINDOW] - running[first]
+        hits = np.flatnonzero(labels[first + WINDOW // 2] == 1)[::lessen]       # every lessen-th label-1 centre ...
+        hits = hits[ones[hits] == WINDOW]                                # ... whose whole window is ones
+        pos.append(first[hits])
+        cand = np.flatnonzero(ones == 0)
+        m = cand.size
+        q = _neg_quota(neg_per_read, m, hits.size)
+        if q < m:
+            with np.errstate(over="ignore"):
+                key = fmix32(seed ^ fmix32(_U(((rho + 1) * 0x9E3779B9) & 0xFFFFFFFF)))
+            cand = cand[keyed_permutation(np.arange(m, dtype=np.uint32), m, key) < q]
+        neg.append(first[cand])
+    empty = np.zeros(0, dtype=np.int64)
+    return (np.concatenate(pos) if pos else empty), (np.concatenate(neg) if neg else empty)
+
+
+def _table_sizes_fit(n_pos, n_neg):
+    """``keyed_permutation`` draws rows from [0, n) with n below 2^31."""
+    if n_pos >= 2 ** 31 or n_neg >= 2 ** 31:
+        raise ValueError("a table of 2^31 or more windows (%d positives, %d negatives): raise lessen or cap neg_per_read" % (n_pos, n_neg))
+
+
+class DeviceReadDb(DeviceFedDb):
+    """The labelled reads themselves as the training set: ``signal`` float32 [total] (cast once), ``labels`` uint8 [total],
+    ``offsets`` int64 [n_reads + 1], and two ordered tables of window starts (``centre_tables``).  The sampler and the public
+    surface are ``DeviceExampleDb``'s; row ``i`` of the positives is the window ``signal[pos_start[i] : pos_start[i] + 35]``.
+
+    The tables are computed on first use (``pos_start``, ``neg_start``, ``nb_pos``, ``nb_neg``, ``gather``).  Despite its
+    place in this module this is a HOST database: nothing of it goes to a card.  It has no ``device_pools``, so
+    ``Trainer.train_steps`` / ``RNN.train_network_steps`` and ``train_and_validate`` run it through ``get_training_set`` + one
+    host-fed step per batch, on a GPU as on the CPU -- the same steps on the same batches, slower per step than a
+    ``DeviceExampleDb``."""
+
+    def __init__(self, signal, labels, offsets, seed, lessen=1, neg_per_read=None):
+        DeviceFedDb.__init__(self, seed)
+        self.labels, self.offsets, self.lessen = _read_layout(labels, offsets, lessen)
+        self.signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1)
+        if self.signal.size != self.labels.size:
+            raise ValueError("%d samples but %d labels" % (self.signal.size, self.labels.size))
+        _neg_quota(neg_per_read, 0, 0)
+        self.neg_per_read = neg_per_read
+        self._tables = None              # (pos_start, neg_start)
+
+    @classmethod
+    def from_arrays(cls, signals, labels, seed=0, lessen=1, neg_per_read=None):
+        """One read per (signal, labels) pair, in that order."""
+        from .device_validation import DeviceValidationSet
+        v = DeviceValidationSet.from_arrays(signals, labels)
+        return cls(v.signal, v.labels, v.offsets, seed, lessen, neg_per_read)
+
+    @classmethod
+    def from_npz(cls, paths, seed=0, lessen=1, neg_per_read=None, loader=None):
+        """The reads of ``paths`` (``raw`` + ``base_labels``, ``train_validate.load_npz``), in that order."""
+        from .device_validation import DeviceValidationSet
+        v = DeviceValidationSet.from_npz(paths, loader)
+        return cls(v.signal, v.labels, v.offsets, seed, lessen, neg_per_read)
+
+    # ------------------------------------------------------------------ the tables
+    def host_tables(self):
+        if self._tables is None:
+            pos, neg = centre_tables(self.labels, self.offsets, self.lessen, self.neg_per_read, self.seed)
+            _table_sizes_fit(pos.size, neg.size)
+            self._tables = (pos, neg)
+        return self._tables
+
+    pos_start = property(lambda self: self.host_tables()[0])
+    neg_start = property(lambda self: self.host_tables()[1])
+    nb_pos = property(lambda self: int(self.host_tables()[0].size))
+    nb_neg = property(lambda self: int(self.host_tables()[1].size))
+
+    def gather(self, d, size, ratio=2):
+        """Draw ``d`` as arrays: (x float32 [size, 35], is_pos bool [size])."""
+        is_pos, row = self.batch_indices(d, size, ratio)
+        pos, neg = self.host_tables()
+        start = np.empty(int(size), dtype=np.int64)
+        start[is_pos] = pos[row[is_pos]]
+        start[~is_pos] = neg[row[~is_pos]]
+        return self.signal[start[:, None] + np.arange(WINDOW)], is_pos
+
+
+def synthetic_device_read_db(n_reads=8, read_len=20000, seed=0, lessen=1, neg_per_read=None):
+    """``train_validate.synthetic_example_db``'s reads (the same squiggles) in a ``DeviceReadDb``."""
+    from .train_validate import synthetic_labelled_read
+    reads = [synthetic_labelled_read(read_len, seed * 1000 + r) for r in range(n_reads)]
+    return DeviceReadDb.from_arrays([raw for raw, _ in reads], [lab for _, lab in reads], seed, lessen, neg_per_read)

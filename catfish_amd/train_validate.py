@@ -436,6 +436,20 @@ def _npz_files(directory):
     return sorted(os.path.join(directory, f) for f in os.listdir(directory) if f.endswith(".npz"))
 
 
+def device_read_db_from_env(npz_files):
+    """``CATFISH_DEVICE_DB=reads``: a ``device_db.DeviceReadDb`` over the NPZ reads.  CATFISH_DEVICE_NEG says how many negatives a
+    read contributes: ``positives`` (the default: as many as it has positives, the reference's rule), an integer, or ``all``.
+    A host database: it feeds the per-step loop (``get_training_set``)."""
+    from .device_db import DeviceReadDb
+    rule = os.environ.get("CATFISH_DEVICE_NEG", "positives")
+    if rule not in ("positives", "all"):
+        try:
+            rule = int(rule)
+        except ValueError:
+            raise ValueError("CATFISH_DEVICE_NEG must be 'positives', 'all' or an integer, got %r" % rule)
+    return DeviceReadDb.from_npz(npz_files, seed=0, neg_per_read=None if rule == "all" else rule)
+
+
 def main(argv):
     """networks/train_validate.py:298-360: ``network_type train_npz_dir n_training_examples validation_npz_dir
     max_validation_length [validation_start [max_number]]``.  The training "database" argument is a directory of NPZ
@@ -445,6 +459,11 @@ def main(argv):
     CATFISH_TRAINING_PRECISION=bf16x3 trains with ``training_precision="bf16x3"`` (any geometry but the shipped one).
     CATFISH_DEVICE_DB=1 keeps the training windows on the card (``device_db.DeviceExampleDb``): the steps between two
     checkpoint rounds run back to back, each drawing its own batch.
+    CATFISH_DEVICE_DB=reads trains from the labelled reads as they are (``device_db.DeviceReadDb``).  Despite the variable's name
+    this is a HOST database -- nothing of it goes to the card, every batch is gathered in numpy and copied over, so a step costs
+    more than with CATFISH_DEVICE_DB=1; what it offers is 5 B per sample and two tables of window starts instead of one array per
+    window, the reference's negative rule and a reproducible selection.  CATFISH_DEVICE_NEG=positives|<int>|all sets the
+    negatives a read contributes (``device_read_db_from_env``).
     CATFISH_DEVICE_VALIDATION=1 keeps the validation reads on the card too (``device_validation.DeviceValidationSet``, loaded
     once): a checkpoint round gathers and scores its stretches there instead of re-opening the files."""
     args = list(argv[1:])
@@ -467,6 +486,8 @@ def main(argv):
     if os.environ.get("CATFISH_DEVICE_DB") == "1":               # the training set on the card, batches drawn by a HIP kernel
         from .device_db import device_db_from_npz
         db_train = device_db_from_npz(_npz_files(train_dir))
+    elif os.environ.get("CATFISH_DEVICE_DB") == "reads":         # the labelled reads as they are, two tables of window starts: a HOST database
+        db_train = device_read_db_from_env(_npz_files(train_dir))
     else:
         db_train = example_db_from_npz(_npz_files(train_dir))
     print("Loading validation database..")

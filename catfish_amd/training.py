@@ -480,14 +480,16 @@ class Trainer(object):
 
         On a GPU with graphs the example pools live on the card and every step is one replay of the device-fed graph
         (``_capture_fed``): no copy, no read-back and no synchronise between steps; the losses collect in a device log that is
-        read back once per chunk of ``loss_log_capacity`` steps.  The CPU reference mode and ``use_graph=False`` run
-        ``db.get_training_set`` + ``train_step`` per step, on the same batches."""
+        read back once per chunk of ``loss_log_capacity`` steps.  The CPU reference mode, ``use_graph=False`` and a database
+        that keeps nothing on the card (``device_db.DeviceReadDb``) run ``db.get_training_set`` + ``train_step`` per step, on the
+        same batches."""
         n_steps, n, ratio = int(n_steps), int(batch_size), int(ratio)
         out = np.zeros(max(n_steps, 0), dtype=np.float32)
         if n_steps <= 0:
             return out
         torch = __import__("torch")
-        if not (self.use_graph and self.net.device.type == "cuda" and self.net.dtype == torch.float32):
+        on_card = hasattr(db, "device_pools")               # a database without a card side (DeviceReadDb) is fed by the host
+        if not (on_card and self.use_graph and self.net.device.type == "cuda" and self.net.dtype == torch.float32):
             for i in range(n_steps):
                 x, y, _ = db.get_training_set(n, ratio)
                 out[i] = self.train_step(np.asarray(x, dtype=np.float32).reshape(n, 35), np.asarray(y, dtype=np.float32).reshape(n, 35))
