@@ -12,7 +12,8 @@ Every random draw stays on the host, on Python's global generator and in the ref
 
 This module states both device steps in numpy and those statements are normative: ``DeviceValidationSet.pack`` is what the
 gather kernel writes (bit for bit), ``score_host`` what the scoring kernel returns (counts exactly; the double sums up to the
-summation order).  The object is host-only until ``device_arrays`` is called and usable without a GPU.
+summation order), ``run_states_host`` what the run-state step returns (``cf_validation_run_states``, csrc/validation_runs.hpp:
+how many homopolymers a round found, bit for bit).  The object is host-only until ``device_arrays`` is called and usable without a GPU.
 """
 from __future__ import annotations
 
@@ -75,6 +76,84 @@ def score_host(probs, logits, y, bounds, thresholds):
         counts[k] = (np.count_nonzero(called & (y == 1)), np.count_nonzero(called & (y != 1)),
                      np.count_nonzero(~called & (y == 0)), np.count_nonzero(~called & (y != 0)))
     return right, ce_sum, counts
+
+
+MAX_RUN_EDGES = 7           # length-bin edges per run-state call (CF_RUN_MAX_EDGES, csrc/validation_runs.hpp)
+RUN_STATES = ("complete", "incomplete", "absent")          # check_hp's states, in the order of the table's last axis
+
+
+def check_run_edges(edges):
+    """``edges`` as a tuple of ints: at most 7, positive, strictly ascending (ValueError otherwise)."""
+    out = []
+    for e in edges:
+        if isinstance(e, bool) or int(e) != e:
+            raise ValueError("run edges must be integers, got %r" % (e,))
+        out.append(int(e))
+    if len(out) > MAX_RUN_EDGES:
+        raise ValueError("at most %d run edges, got %d" % (MAX_RUN_EDGES, len(out)))
+    if any(e < 1 for e in out) or any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError("run edges must be positive and ascending, got %r" % (tuple(out),))
+    return tuple(out)
+
+
+def _runs_of(mask):
+    """(starts, ends) of the runs of a boolean array, ends inclusive, with ``hp_loc_dict``'s rule
+    (networks/process_output.py:633-636): an open run is closed AT the last index whatever that sample holds."""
+    m = np.array(mask, dtype=bool)
+    if m.size >= 2 and m[-2]:
+        m[-1] = True
+    step = np.diff(np.concatenate(([0], m.astype(np.int8), [0])))
+    return np.flatnonzero(step == 1), np.flatnonzero(step == -1) - 1
+
+
+def _states_of(starts, ends, other):
+    """``check_hp``'s state of every run against ``other``: 0 complete (all 1), 2 absent (all 0), 1 incomplete."""
+    ones = np.concatenate(([0], np.cumsum(other == 1)))
+    zeros = np.concatenate(([0], np.cumsum(other == 0)))
+    size = ends - starts + 1
+    return np.where(ones[ends + 1] - ones[starts] == size, 0, np.where(zeros[ends + 1] - zeros[starts] == size, 2, 1))
+
+
+def run_states_host(probs, y, bounds, lengths, thresholds, edges=(), min_run=15):
+    """What ``cf_validation_run_states`` returns, in numpy: int64 [K, 2, B, 3] -- per threshold, kind, length bin and state how
+    many runs (the reference's offline networks/process_output.py:235-273).
+
+    Stretch r is the ``lengths[r]`` packed samples from ``bounds[r]``; its zero tail is not part of it.  Per threshold t the
+    prediction is ``infer.correct_short((double)p >= t, min_run)`` over the stretch alone.  A run is a maximal run of ones, plus
+    ``hp_loc_dict``'s rule: a run whose last one sits at n - 2 ends at n - 1 (only the run mask changes, never the array a run is
+    judged against).  Kind 0: the runs of ``y == 1`` judged against the prediction; kind 1: the runs of the prediction judged
+    against ``y``.  State (``check_hp``) 0 = complete, the other array is 1 over the whole run; 2 = absent, it is 0 over the whole
+    run; 1 = incomplete, anything else (so a label other than 0 / 1 inside a run makes it incomplete).  A run of L samples falls
+    into bin ``searchsorted(edges, L, side="right")``; B = len(edges) + 1."""
+    from .infer import correct_short
+    edges = np.asarray(check_run_edges(edges), dtype=np.int64)
+    if int(min_run) < 1:
+        raise ValueError("min_run must be >= 1")
+    p = np.asarray(probs, dtype=np.float64).reshape(-1)
+    y = np.asarray(y).reshape(-1)
+    bounds = np.asarray(bounds, dtype=np.int64)
+    lengths = np.asarray(lengths, dtype=np.int64)
+    out = np.zeros((len(thresholds), 2, len(edges) + 1, 3), dtype=np.int64)
+    for b0, n in zip(bounds[:len(lengths)].tolist(), lengths.tolist()):
+        if n <= 0:
+            continue
+        truth = y[b0:b0 + n]
+        for k, t in enumerate(thresholds):
+            pred = np.asarray(correct_short((p[b0:b0 + n] >= float(t)).astype(np.int64), int(min_run)))
+            for kind, (mask, other) in enumerate(((truth == 1, pred), (pred == 1, truth))):
+                starts, ends = _runs_of(mask)
+                bins = np.searchsorted(edges, ends - starts + 1, side="right")
+                np.add.at(out[k, kind], (bins, _states_of(starts, ends, other)), 1)
+    return out
+
+
+def run_state_rates(table):
+    """The three rates of one threshold's [2, B, 3] table: (hp_complete, hp_found, called_absent) = complete / all true runs,
+    (complete + incomplete) / all true runs, absent / all called runs; 0 for an empty denominator (``metrics.precision_recall``)."""
+    true_runs, called = np.asarray(table)[0].sum(axis=0), np.asarray(table)[1].sum(axis=0)
+    n_true, n_called = int(true_runs.sum()), int(called.sum())
+    return (int(true_runs[0]) / n_true if n_true else 0, int(true_runs[0] + true_runs[1]) / n_true if n_true else 0,
+            int(called[2]) / n_called if n_called else 0)
 
 
 def finish(right, ce_sum, counts_k, bounds, tails):
@@ -188,6 +267,7 @@ class DeviceValidationSet(object):
         return read_index, first, length
 
     score_host = staticmethod(score_host)
+    run_states_host = staticmethod(run_states_host)
     finish = staticmethod(finish)
     layout = staticmethod(layout)
 

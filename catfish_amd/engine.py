@@ -328,6 +328,39 @@ class HipEngine(object):
                                               C.c_void_p(counts_out.data_ptr()), C.c_void_p(partials.data_ptr()), int(partials.numel()),
                                               C.c_void_p(stream.cuda_stream)))
 
+    def run_states_work_bytes(self, total, n_thresholds):
+        """Bytes of work space ``run_states_validation`` needs for ``total`` packed samples and ``n_thresholds`` thresholds."""
+        return int(self._lib.cf_validation_run_work_bytes(int(total), int(n_thresholds)))
+
+    def run_states_validation(self, probs, y, bounds, length, total, longest, thresholds, edges, counts_out, work, min_run=15, stream=None):
+        """``cf_validation_run_states``: per threshold (``thresholds``: 1..16 host floats), kind (0 = true runs judged against the
+        corrected prediction, 1 = predicted runs judged against ``y``), length bin (``edges``: up to 7 ascending host ints) and
+        state (complete / incomplete / absent) how many runs -- ``device_validation.run_states_host`` -- into ``counts_out``
+        (int64 CUDA, ``K * 2 * (len(edges) + 1) * 3`` elements).  ``bounds`` [n + 1] and ``length`` [n] are int64 CUDA tensors;
+        ``work`` is a uint8 CUDA tensor of at least ``run_states_work_bytes(total, K)`` bytes.  Asynchronous on the stream; equal
+        inputs give equal bits."""
+        import torch
+        self._check_validation_tensors("run_states_validation", [
+            ("probs", probs, torch.float32), ("y", y, torch.uint8), ("bounds", bounds, torch.int64), ("length", length, torch.int64),
+            ("counts_out", counts_out, torch.int64), ("work", work, torch.uint8)])
+        thresholds = [float(t) for t in thresholds]
+        edges = [int(e) for e in edges]
+        n, k, total, longest = int(length.numel()), len(thresholds), int(total), int(longest)
+        if int(bounds.numel()) != n + 1:
+            raise ValueError("run_states_validation: length needs n entries, bounds n + 1")
+        if total < 0 or min(int(probs.numel()), int(y.numel())) < total:
+            raise ValueError("run_states_validation: probs and y need %d elements" % total)
+        if int(counts_out.numel()) < k * 2 * (len(edges) + 1) * 3:
+            raise ValueError("run_states_validation: counts_out needs 2 * (edges + 1) * 3 entries per threshold")
+        if stream is None:
+            stream = torch.cuda.current_stream(probs.device)
+        # n, K, the edges, min_run and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
+        N.check(self._lib.cf_validation_run_states(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()),
+                                                   C.c_void_p(bounds.data_ptr()), C.c_void_p(length.data_ptr()), n, total, longest,
+                                                   (C.c_double * max(k, 1))(*thresholds), k, (C.c_int64 * max(len(edges), 1))(*edges),
+                                                   len(edges), int(min_run), C.c_void_p(counts_out.data_ptr()),
+                                                   C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
+
     # ------------------------------------------------------------------ profiling / debug
     def profile_enable(self, on=True, every=1):
         """Per-kernel HIP-event timing of every ``every``-th call (events cost ~1.6 % when on every call)."""

@@ -209,10 +209,14 @@ class RNN(object):
         self._require_engine()
         return self.engine.infer_host(np.asarray(windows), return_logits=True)
 
-    def score_validation_device(self, vset, selection, thresholds=(0.5,)):
+    def score_validation_device(self, vset, selection, thresholds=(0.5,), run_edges=None):
         """One validation round on the card: the stretches ``selection`` (``vset.select``) of a
         ``device_validation.DeviceValidationSet`` -> what ``device_validation.score_host`` returns for them, (right int64 [n],
-        ce_sum float64 [n], counts int64 [K, 4]).
+        ce_sum float64 [n], counts int64 [K, 4]).  With ``run_edges`` (a tuple of up to 7 ascending run lengths, possibly empty)
+        a fourth result follows: what ``device_validation.run_states_host`` returns for the round's probabilities, int64
+        [K, 2, len(run_edges) + 1, 3] -- how many true homopolymers were found completely, partly or not at all and how many
+        called stretches hold one, per length bin (``cf_validation_run_states`` after the same gather and forward pass, in the
+        same copy back; its label work space and the larger result buffer follow the grow-only rule below).
 
         The selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes
         probabilities and logits (the weights just trained, as ``score_windows`` uses them), ``cf_validation_score`` reduces them
@@ -225,6 +229,8 @@ class RNN(object):
         thresholds = tuple(float(t) for t in thresholds)
         if not thresholds:
             raise ValueError("score_validation_device: no threshold given")
+        if run_edges is not None:
+            run_edges = dv.check_run_edges(run_edges)
         read_index, first, length = vset.check_selection(selection)
         n = int(read_index.size)
         if n == 0:
@@ -237,6 +243,11 @@ class RNN(object):
         k_all = len(thresholds)
         slots = total // dv.SCORE_CHUNK + n
         need = {"samples": max(total, 1), "reads": n, "slots": slots, "thresholds": k_all}
+        run_cells = 0
+        if run_edges is not None:
+            run_cells = k_all * 2 * (len(run_edges) + 1) * 3
+            need.update({"run_cells": run_cells,
+                         "run_work": max(self.engine.run_states_work_bytes(total, min(k_all, dv.MAX_THRESHOLDS)), 1)})
         if any(book["capacity"].get(key, 0) < value for key, value in need.items()):
             cap = {key: max(book["capacity"].get(key, 0), value) for key, value in need.items()}
             f32 = lambda count: torch.empty(count, dtype=torch.float32, device=device)     # noqa: E731
@@ -244,8 +255,11 @@ class RNN(object):
                                "y": torch.empty(cap["samples"], dtype=torch.uint8, device=device),
                                "table": torch.empty(3 * (cap["reads"] + 1), dtype=torch.int64, device=device),
                                "partials": torch.empty(cap["slots"], dtype=torch.float64, device=device),
-                               # right [reads] | ce_sum [reads], double bits | counts [4 per threshold]: one copy back
-                               "out": torch.empty(2 * cap["reads"] + 4 * cap["thresholds"], dtype=torch.int64, device=device)}
+                               # right [reads] | ce_sum [reads], double bits | counts [4 per threshold] | run states: one copy back
+                               "out": torch.empty(2 * cap["reads"] + 4 * cap["thresholds"] + cap.get("run_cells", 0), dtype=torch.int64,
+                                                  device=device)}
+            if "run_work" in cap:                                                    # corrected labels, one array per threshold of a group
+                book["tensors"]["run_work"] = torch.empty(cap["run_work"], dtype=torch.uint8, device=device)
             book["capacity"] = cap
             book["allocations"] += 1
         if book["thresholds"] is None or book["thresholds"][0] != thresholds or book["thresholds"][1].device != device:
@@ -260,17 +274,24 @@ class RNN(object):
         book["selection_uploads"] += 1
         src_d, len_d, bounds_d = (t["table"][i * (n + 1):i * (n + 1) + count] for i, count in ((0, n), (1, n), (2, n + 1)))
         x, y, probs, logits = t["x"][:total], t["y"][:total], t["probs"][:total], t["logits"][:total]
-        out = t["out"][:2 * n + 4 * k_all]
-        right_d, ce_d, counts_d = out[:n], out[n:2 * n].view(torch.float64), out[2 * n:]
+        out = t["out"][:2 * n + 4 * k_all + run_cells]
+        right_d, ce_d, counts_d, runs_d = out[:n], out[n:2 * n].view(torch.float64), out[2 * n:2 * n + 4 * k_all], out[2 * n + 4 * k_all:]
         self.engine.gather_validation(signal, labels, src_d, len_d, bounds_d, total, longest, x, y)
         self.engine.infer_device(x.view(-1, self.window), out=probs, logits=logits)
         for k0 in range(0, k_all, dv.MAX_THRESHOLDS):
             k1 = min(k_all, k0 + dv.MAX_THRESHOLDS)
             self.engine.score_validation(probs, logits, y, bounds_d, total, longest, book["thresholds"][1][k0:k1], right_d, ce_d,
                                          counts_d[4 * k0:4 * k1], t["partials"])
+            if run_edges is not None:
+                per_k = run_cells // k_all
+                self.engine.run_states_validation(probs, y, bounds_d, len_d, total, longest, thresholds[k0:k1], run_edges,
+                                                  runs_d[per_k * k0:per_k * k1], t["run_work"])
         back = out.cpu().numpy()                                                     # synchronises the stream
         self.engine.check_error()
-        return back[:n].copy(), back[n:2 * n].view(np.float64).copy(), back[2 * n:].reshape(k_all, 4).copy()
+        three = (back[:n].copy(), back[n:2 * n].view(np.float64).copy(), back[2 * n:2 * n + 4 * k_all].reshape(k_all, 4).copy())
+        if run_edges is None:
+            return three
+        return three + (back[2 * n + 4 * k_all:].reshape(k_all, 2, len(run_edges) + 1, 3).copy(),)
 
     @property
     def validation_buffers(self):

@@ -15,12 +15,14 @@ expose the same ``get_training_set(size, ratio=2) -> (x_out, y_out, pos_count)``
 from __future__ import annotations
 
 import datetime
+import json
 import os
 import random
 
 import numpy as np
 
 from . import metrics
+from .device_validation import RUN_STATES, run_state_rates
 from .neural_network import build_model as _build_model
 
 
@@ -205,7 +207,18 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     print("Validated in {}".format(datetime.datetime.now() - clock))
     _append(report, "\nTraining accuracy: {}\nTraining loss: {}\n".format(batch_acc, batch_loss))
     clock = datetime.datetime.now()
-    _acc, precision, recall = validate(network, *validation)
+    run_edges = getattr(network, "validation_run_edges", None)
+    if run_edges is None:
+        _acc, precision, recall = validate(network, *validation)
+    else:
+        # the homopolymers the round found, next to the report (which stays the reference's): one JSON line per round
+        _acc, precision, recall = validate(network, *validation, run_edges=run_edges)
+        table = np.asarray(network.validation_run_states)
+        complete, found, called_absent = run_state_rates(table)
+        _append(report[:-len(".txt")] + "_hp_states.jsonl", json.dumps({
+            "step": int(step), "threshold": 0.5, "edges": list(run_edges), "states": list(RUN_STATES),
+            "hp_states": table[0].tolist(), "called_states": table[1].tolist(), "hp_complete": complete, "hp_found": found,
+            "called_absent": called_absent}) + "\n")
     print("Validated in {}".format(datetime.datetime.now() - clock))
     _append(report, "Validation precision: {}\nValidation recall: {}\n".format(precision, recall))
     return batch_acc
@@ -345,7 +358,7 @@ def score_validation_batch(probs32, logits32, y, bounds, tails, threshold=0.5):
     return acc, loss.astype(np.float32), counts
 
 
-def validate(network, squiggles, max_seq_length, file_path, validation_start="random", max_number=856):
+def validate(network, squiggles, max_seq_length, file_path, validation_start="random", max_number=856, run_edges=None):
     """networks/train_validate.py:188-295 as one packed launch.
 
     The reference pushes every read through ``test_network`` (one ``sess.run`` each, up to 856 per round); windows are
@@ -357,7 +370,11 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
 
     Kept behaviour of the loop being replaced: the read that reaches ``max_number`` is scored and counted but its
     accuracy / loss are left out of the averages, which still divide by the number of reads (:248-256); no read
-    selected -> ZeroDivisionError."""
+    selected -> ZeroDivisionError.
+
+    ``run_edges`` (a ``DeviceValidationSet`` only): the round also counts the homopolymers found at threshold 0.5
+    (``device_validation.run_states_host``, on the card); the [2, B, 3] table is left in ``network.validation_run_states``.
+    Report, prints and return value stay as they are."""
     print("Max length is {}".format(max_seq_length))
     print("Validation start is {}".format(validation_start))
     from .device_validation import DeviceValidationSet
@@ -368,9 +385,15 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
         n_samples = int(selection[2].sum())
         if n_reads == 0:
             raise ZeroDivisionError("validation selected no read")
-        right, ce_sum, counts_k = network.score_validation_device(squiggles, selection)
+        if run_edges is None:
+            right, ce_sum, counts_k = network.score_validation_device(squiggles, selection)
+        else:
+            right, ce_sum, counts_k, run_states = network.score_validation_device(squiggles, selection, (0.5,), run_edges=run_edges)
+            network.validation_run_states = run_states[0]
         acc, loss, counts = squiggles.finish(right, ce_sum, counts_k[0], *squiggles.layout(selection[2], network.window))
     else:
+        if run_edges is not None:
+            raise ValueError("validate: run_edges needs a DeviceValidationSet (the run states are counted on the card)")
         signals, labels = select_validation_stretches(squiggles, network.window, max_seq_length, validation_start,
                                                       max_number)
         n_reads = len(signals)
@@ -402,24 +425,40 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     return whole_acc, precision, recall
 
 
-def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start="complete", max_number=856):
+def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start="complete", max_number=856, run_edges=None):
     """The reference's precision / recall sweep (networks/precision_recall_ROC.py:85-100: ``class_from_threshold`` --
     ``p >= t`` -- then ``compute_f1`` per threshold) over a ``DeviceValidationSet``: ONE forward pass, every threshold counted
     from its probabilities on the card.  The stretches are ``validate``'s (same selection, same tail rule for the true
-    negatives).  -> a list of dicts {threshold, tp, fp, tn, fn, precision, recall, f1}, one per threshold, in order."""
+    negatives).  -> a list of dicts {threshold, tp, fp, tn, fn, precision, recall, f1}, one per threshold, in order.
+
+    With ``run_edges`` (up to 7 ascending run lengths, possibly none) every row also says how many homopolymers that threshold
+    finds (``device_validation.run_states_host``; the reference's offline networks/process_output.py:235-273): ``hp_states`` and
+    ``called_states`` -- per length bin [complete, incomplete, absent] of the true runs against the corrected prediction and of
+    the called runs against the truth --, ``hp_complete`` and ``hp_found`` (complete, complete + incomplete over all true runs)
+    and ``called_absent`` (called runs that hold no homopolymer sample over all called runs); 0 for an empty denominator."""
     thresholds = [float(t) for t in thresholds]
     selection = vset.select(network.window, max_seq_length, validation_start, max_number)
     if len(selection[0]) == 0:
         raise ZeroDivisionError("validation selected no read")
-    _right, _ce_sum, counts = network.score_validation_device(vset, selection, thresholds)
+    run_states = None
+    if run_edges is None:
+        _right, _ce_sum, counts = network.score_validation_device(vset, selection, thresholds)
+    else:
+        _right, _ce_sum, counts, run_states = network.score_validation_device(vset, selection, thresholds, run_edges=run_edges)
     tail = int(vset.layout(selection[2], network.window)[1].sum())
     rows = []
-    for t, (tp, fp, tn_raw, fn) in zip(thresholds, np.asarray(counts).tolist()):
+    for k, (t, (tp, fp, tn_raw, fn)) in enumerate(zip(thresholds, np.asarray(counts).tolist())):
         precision, recall = metrics.precision_recall(tp, fp, fn)
         rows.append({"threshold": t, "tp": tp, "fp": fp, "tn": tn_raw - tail, "fn": fn, "precision": precision, "recall": recall,
                      "f1": metrics.f1(precision, recall)})
+        if run_states is not None:
+            complete, found, called_absent = run_state_rates(run_states[k])
+            rows[-1].update({"hp_states": run_states[k][0].tolist(), "called_states": run_states[k][1].tolist(),
+                             "hp_complete": complete, "hp_found": found, "called_absent": called_absent})
     return rows
 
+
+VALIDATION_RUN_EDGES = (35, 70, 140)        # length bins of the per-round homopolymer table: one, two and four windows
 
 _USAGE = ("The following arguments should be provided in this order:\n"
           "\t-network type\n\t-path to training db"
@@ -465,7 +504,10 @@ def main(argv):
     window, the reference's negative rule and a reproducible selection.  CATFISH_DEVICE_NEG=positives|<int>|all sets the
     negatives a read contributes (``device_read_db_from_env``).
     CATFISH_DEVICE_VALIDATION=1 keeps the validation reads on the card too (``device_validation.DeviceValidationSet``, loaded
-    once): a checkpoint round gathers and scores its stretches there instead of re-opening the files."""
+    once): a checkpoint round gathers and scores its stretches there instead of re-opening the files.
+    CATFISH_VALIDATION_RUNS=1 (with CATFISH_DEVICE_VALIDATION=1) also counts, per round, the homopolymers found at threshold 0.5
+    in the length bins ``VALIDATION_RUN_EDGES`` and appends them as one JSON line to ``<model path>_hp_states.jsonl``; the
+    ``.txt`` report is unchanged."""
     args = list(argv[1:])
     if len(args) < 5:
         raise ValueError(_USAGE)
@@ -495,6 +537,8 @@ def main(argv):
     if os.environ.get("CATFISH_DEVICE_VALIDATION") == "1":       # the validation reads on the card, rounds scored by HIP kernels
         from .device_validation import DeviceValidationSet
         squiggles = DeviceValidationSet.from_npz(squiggles)
+        if os.environ.get("CATFISH_VALIDATION_RUNS") == "1":     # ... and the homopolymers found, one JSON line per round
+            network.validation_run_edges = VALIDATION_RUN_EDGES
     began = datetime.datetime.now()
     train_and_validate(network, db_train, n_train, squiggles, stretch, network.model_path, start, most)
     print("Trained and validated network in {}".format(datetime.datetime.now() - began))

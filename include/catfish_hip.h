@@ -545,6 +545,26 @@ int cf_validation_score(cf_model* m, const float* probs, const float* logits, co
                         int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds, int64_t* right_out,
                         double* ce_sum_out, int64_t* counts_out, double* partials, int64_t partial_slots, void* stream);
 
+/* Event-level validation (csrc/validation_runs.hpp; device_validation.run_states_host is its definition): the reference's offline
+ * networks/process_output.py:235-273 on the card.  Stretch r is the first length[r] packed samples from bounds[r] (its zero tail is not
+ * part of it).  Per threshold t: pred = correct_short((double)p >= t, min_run) inside every stretch; a run is a maximal run of ones,
+ * and -- hp_loc_dict's rule (:633-636) -- a run whose last one sits at n - 2 ends at n - 1.  Kind 0 = the runs of y == 1 judged against
+ * pred, kind 1 = the runs of pred judged against y; state 0 = complete (the other array is 1 over the whole run), 2 = absent (0 over
+ * the whole run), 1 = incomplete; a run of L samples falls into bin #{j : edges[j] <= L}.
+ *   counts_out   device int64 [n_thresholds][2][n_edges + 1][3], zeroed and written by the call
+ *   thresholds   HOST double [n_thresholds], 1..16 of them;  edges  HOST int64 [n_edges], 0..7, positive and strictly ascending
+ *   work         device bytes, >= cf_validation_run_work_bytes(total, n_thresholds) (one corrected-label array per threshold);
+ *                16-byte aligned for the bit-mask post-processing kernel, otherwise the per-sample one runs
+ * A workgroup walks a stretch in pieces of cf_validation_run_piece() samples and counts a run once, where it ends; integer
+ * arithmetic only, so equal inputs give equal results whatever `longest` (a hint, as above) or the grid.  Asynchronous on `stream`;
+ * m may be NULL.  CF_ERR_INVALID before any launch for a null pointer, n outside [1, 2^31), total >= 2^31, n_thresholds outside 1..16,
+ * more than 7 edges, edges not positive and ascending, min_run < 1 or too small a work buffer. */
+int cf_validation_run_piece(void);
+int64_t cf_validation_run_work_bytes(int64_t total, int32_t n_thresholds);
+int cf_validation_run_states(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length, int64_t n,
+                             int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds, const int64_t* edges,
+                             int32_t n_edges, int32_t min_run, int64_t* counts_out, void* work, int64_t work_bytes, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream) for bench.py's
  * roofline report.  cf_profile_enable(m, N) makes every N-th cf_infer call
  * (N = 1: every call; 0 = off) record events around each of its kernels; cf_profile_read synchronises and returns, for

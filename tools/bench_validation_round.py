@@ -13,6 +13,14 @@ and range of seconds per round, and whether (c)'s range lies below (a)'s and bel
 
     python tools/bench_validation_round.py [--rounds 5] [--commit <id>] [--out profiles/validation_round_bench.jsonl]
     python tools/bench_validation_round.py --trace-rounds 3      # route (c) alone, for rocprofv3 --kernel-trace --stats
+    python tools/bench_validation_round.py --resident-rounds 15  # route (c) alone, timed: one summary line (to compare two builds,
+                                                                 # run them alternately and compare against the spread of each)
+    python tools/bench_validation_round.py --run-states          # the run-state leg, see below
+
+The run-state leg (``--run-states``) times the device-resident round itself (``RNN.score_validation_device`` on a seeded selection,
+ending in its copy back), alternating per round: without run states, with ``run_edges=(35, 70, 140)``, and the forward pass of
+that round alone -- at 1 and at 16 thresholds.  Its summary line gives the medians, the time the run-state step adds to the round
+and the forward pass's share of the round.
 """
 import argparse
 import contextlib
@@ -61,6 +69,42 @@ def one_round(net, source, seed, name):
     return seconds, text, got
 
 
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def spread(values):
+    return dict(median_s=float(np.median(values)), min_s=float(min(values)), max_s=float(max(values)))
+
+
+def run_states_leg(net, resident, rounds, emit, edges=(35, 70, 140)):
+    for thresholds in ((0.5,), tuple(float(t) for t in np.linspace(0.2, 0.95, 16))):
+        seconds = {"plain": [], "run_states": [], "forward": []}
+        for rnd in range(-1, rounds):                      # round -1 warms up (buffers grow once)
+            random.seed(rnd)
+            selection = resident.select(net.window, STRETCH, START, MOST)
+            plain = timed(lambda: net.score_validation_device(resident, selection, thresholds))
+            with_runs = timed(lambda: net.score_validation_device(resident, selection, thresholds, run_edges=edges))
+            t = net.validation_buffers["tensors"]
+            total = int(np.sum(-(-selection[2] // net.window) * net.window))
+            forward = timed(lambda: net.engine.infer_device(t["x"][:total].view(-1, net.window), out=t["probs"][:total],
+                                                            logits=t["logits"][:total]))
+            if rnd >= 0:
+                for key, value in (("plain", plain), ("run_states", with_runs), ("forward", forward)):
+                    seconds[key].append(value)
+                emit(dict(leg="run_states", thresholds=len(thresholds), round=rnd, plain_s=plain, run_states_s=with_runs, forward_s=forward))
+        stats = {key: spread(v) for key, v in seconds.items()}
+        added = stats["run_states"]["median_s"] - stats["plain"]["median_s"]
+        emit(dict(summary=True, leg="run_states", thresholds=len(thresholds), edges=list(edges), reads=resident.n_reads, stretch=STRETCH,
+                  rounds=rounds, samples_per_round=resident.n_reads * (STRETCH // 35 * 35), legs=stats, added_s=added,
+                  forward_share_of_round=stats["forward"]["median_s"] / stats["plain"]["median_s"],
+                  added_over_forward=added / stats["forward"]["median_s"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -69,6 +113,8 @@ def main():
     ap.add_argument("--commit", default=None, help="stamp of the lines (default: git rev-parse HEAD)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "validation_round_bench.jsonl"))
     ap.add_argument("--trace-rounds", type=int, default=0, help="route (c) alone for this many rounds, then exit")
+    ap.add_argument("--resident-rounds", type=int, default=0, help="route (c) alone, timed for this many rounds, then exit")
+    ap.add_argument("--run-states", action="store_true", help="the run-state leg alone, then exit")
     args = ap.parse_args()
     rounds = max(5, args.rounds)
     commit = args.commit or commit_id()
@@ -116,6 +162,17 @@ def main():
                 out.write(line + "\n")
                 out.flush()
 
+            if args.resident_rounds or args.run_states:
+                if args.resident_rounds:
+                    routes[2][1](-1)
+                    took = [routes[2][1](rnd)[0] for rnd in range(args.resident_rounds)]
+                    emit(dict(summary=True, leg="resident_only", reads=args.reads, read_len=args.read_len, stretch=STRETCH,
+                              rounds=args.resident_rounds, seconds=took, **spread(took)))
+                if args.run_states:
+                    run_states_leg(net, resident, rounds, emit)
+                os.chdir(ROOT)
+                net.engine.close()
+                return
             for name, run in routes:                       # warm-up: allocator, page cache, the set's upload, lazy initialisation
                 run(-1)
             seconds = {name: [] for name, _ in routes}
