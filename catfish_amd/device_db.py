@@ -25,7 +25,9 @@ device's are one number -- whichever side drew last writes it through.
 ``centre_tables`` states in numpy which windows the tables hold -- the reference's selection (``TrainingRead.get_pos`` / ``get_neg``,
 networks/trainingDB/TrainingRead.py:226-257; ``ExampleDb.add_training_read`` draws as many negatives as the read has positives),
 with the random subset of negatives drawn by the keyed bijection above, so that it is reproducible and a kernel could repeat it.
-It is a host database and feeds the per-step loop; building the tables and gathering on the card is not implemented.
+It is a host database and feeds the per-step loop.  Building the tables and gathering on the card is not in the tree; the index rules
+such kernels would follow are (csrc/read_tables_plan.hpp, pieces of ``TABLE_PIECE`` window starts), replayed on the CPU against
+``centre_tables`` and ``DeviceReadDb.gather`` (tests/test_read_tables_replay.py).
 """
 from __future__ import annotations
 
@@ -33,6 +35,7 @@ import numpy as np
 
 WINDOW = 35
 ROUNDS = 4
+TABLE_PIECE = 1024                       # window starts per piece of a read's walk (RT_PIECE, csrc/read_tables_plan.hpp)
 _U = np.uint32
 
 
