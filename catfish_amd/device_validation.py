@@ -13,7 +13,9 @@ Every random draw stays on the host, on Python's global generator and in the ref
 This module states both device steps in numpy and those statements are normative: ``DeviceValidationSet.pack`` is what the
 gather kernel writes (bit for bit), ``score_host`` what the scoring kernel returns (counts exactly; the double sums up to the
 summation order), ``run_states_host`` what the run-state step returns (``cf_validation_run_states``, csrc/validation_runs.hpp:
-how many homopolymers a round found, bit for bit).  The object is host-only until ``device_arrays`` is called and usable without a GPU.
+how many homopolymers a round found, bit for bit), ``curve_host`` what the curve step returns (``cf_validation_curve``,
+csrc/validation_curve.hpp: the round's probabilities binned at every threshold step, bit for bit; ``curves_from_histogram`` turns
+that table into the whole ROC and precision-recall curves, their areas and the best F1).  The object is host-only until ``device_arrays`` is called and usable without a GPU.
 """
 from __future__ import annotations
 
@@ -156,6 +158,109 @@ def run_state_rates(table):
             int(called[2]) / n_called if n_called else 0)
 
 
+CURVE_ONE_BITS = 0x3F800000                                # float32 1.0 (VC_ONE_BITS, csrc/validation_curve_bin.hpp)
+CURVE_SHIFT_MIN, CURVE_SHIFT_MAX, CURVE_SHIFT = 10, 22, 14
+
+
+def curve_bins(shift=CURVE_SHIFT):
+    """Bins of a curve histogram: ``(0x3F800000 >> shift) + 1`` -- 65 025 at shift 14.  ``shift`` is an int in 10 .. 22."""
+    if isinstance(shift, bool) or not isinstance(shift, (int, np.integer)) or not CURVE_SHIFT_MIN <= shift <= CURVE_SHIFT_MAX:
+        raise ValueError("curve shift must be an int in %d .. %d, got %r" % (CURVE_SHIFT_MIN, CURVE_SHIFT_MAX, shift))
+    return (CURVE_ONE_BITS >> int(shift)) + 1
+
+
+def curve_bin(bits, shift=CURVE_SHIFT):
+    """The bin of float32 probabilities given by their bit patterns (any integer array or scalar; only the low 32 bits count): read
+    as signed int32, negatives clamped to 0, shifted right, clamped to the top bin -> int64.  Non-negative floats order as their
+    bits do, so for every p in [0, 1]: ``p >= curve_thresholds(shift)[b]``  <=>  ``curve_bin(p) >= b``.  The top bin holds exactly
+    p == 1.0 plus what is clamped into it (1 + ulp, +inf, positive NaN); -0.0, negative values and negative NaN go to bin 0."""
+    top = curve_bins(shift) - 1
+    signed = (np.asarray(bits).astype(np.int64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32).astype(np.int64)
+    return np.minimum(np.maximum(signed, 0) >> int(shift), top)
+
+
+def curve_thresholds(shift=CURVE_SHIFT):
+    """float32 [NB]: the lower edge of every bin, the float whose bits are ``b << shift`` (0.0 first, exactly 1.0 last)."""
+    return (np.arange(curve_bins(shift), dtype=np.uint32) << np.uint32(shift)).view(np.float32)
+
+
+def curve_host(probs, y, bounds, lengths, shift=CURVE_SHIFT):
+    """What ``cf_validation_curve`` returns, in numpy: int64 [3, NB] -- how many samples of label 1 (row 0), label 0 (row 1) and
+    any other label (row 2) fall into every bin of ``curve_bin``.  Only the ``lengths[r]`` real samples from ``bounds[r]`` are
+    counted; the zero tails are not part of it, as in ``run_states_host``."""
+    nb = curve_bins(shift)
+    p = np.ascontiguousarray(np.asarray(probs, dtype=np.float32).reshape(-1))
+    y = np.asarray(y).reshape(-1)
+    bounds = np.asarray(bounds, dtype=np.int64)
+    lengths = np.asarray(lengths, dtype=np.int64)
+    hist = np.zeros((3, nb), dtype=np.int64)
+    for b0, size, n in zip(bounds[:len(lengths)].tolist(), np.diff(bounds)[:len(lengths)].tolist(), lengths.tolist()):
+        n = min(n, size, p.size - b0)
+        if n <= 0:
+            continue
+        bins = curve_bin(p[b0:b0 + n].view(np.uint32), shift)
+        label = y[b0:b0 + n]
+        rows = np.where(label == 1, 0, np.where(label == 0, 1, 2))
+        hist += np.bincount(rows * nb + bins, minlength=3 * nb).reshape(3, nb)
+    return hist
+
+
+def curves_from_histogram(hist, shift=CURVE_SHIFT):
+    """The whole ROC and precision-recall curves of a ``curve_host`` histogram (the reference computes them offline from dumps of
+    every score: networks/metrics.py:66-94, networks/precision_recall_ROC.py:14-82).  Entry b of every array belongs to the
+    threshold ``curve_thresholds(shift)[b]``; a sample is called there when its bin is >= b.  -> dict:
+
+    ``tp``, ``fp``, ``tn``, ``fn`` int64 [NB]: ``score_host``'s rules without the tails -- called & label 1, called & any other
+    label, not called & label 0, not called & any label but 0 (so they equal ``score_host`` + ``finish`` wherever no tail sample is
+    called and no probability is NaN).  ``n_pos``, ``n_neg``, ``n_other``: samples of label 1, 0 and neither.
+    ``tpr``, ``fpr`` float64 [NB]: called label-1 samples / n_pos and called label-0 samples / n_neg (nan for an empty class).
+    ``precision``, ``recall`` float64 [NB]: ``metrics.precision_recall(tp, fp, fn)``, 0 for an empty denominator.
+    ``roc_auc``: the trapezoid under (fpr, tpr) over the bins, = sum_b neg_b (2 tp_above_b + pos_b) / (2 P N): the AUC of the
+    scores quantised to their bin edge (sklearn's ``roc_auc_score`` of them, ties counted one half).
+    ``roc_auc_slack`` = sum_b pos_b neg_b / (2 P N): only pairs that share a bin can order differently before quantisation, and
+    each is counted one half, so the AUC of the unquantised scores lies within ``roc_auc`` +- ``roc_auc_slack``.
+    ``pr_auc``: ``sklearn.metrics.auc(recall, precision)`` in ``precision_recall_curve``'s convention -- one point per OCCUPIED bin
+    (precision = tp / (tp + fp), recall = tp / n_pos there) and the final point (recall 0, precision 1), trapezoids between.
+    ``best_f1``: {threshold, f1, precision, recall} of the first bin with the largest ``metrics.f1(precision, recall)``.
+    ``roc_auc``, ``roc_auc_slack`` and ``pr_auc`` are nan when n_pos or n_neg is 0."""
+    nb = curve_bins(shift)
+    hist = np.asarray(hist, dtype=np.int64)
+    if hist.shape != (3, nb):
+        raise ValueError("a curve histogram at shift %d is int64 [3, %d], got %s" % (shift, nb, hist.shape))
+    pos, neg, other = hist[0], hist[1], hist[2]
+    n_pos, n_neg, n_other = int(pos.sum()), int(neg.sum()), int(other.sum())
+    from_top = lambda row: np.cumsum(row[::-1])[::-1]                                # noqa: E731   bins >= b
+    below = lambda row: np.concatenate(([0], np.cumsum(row)[:-1]))                   # noqa: E731   bins < b
+    tp, called_neg = from_top(pos), from_top(neg)
+    fp = called_neg + from_top(other)
+    tn, fn = below(neg), below(pos + other)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        tpr = tp / np.float64(n_pos) if n_pos else np.full(nb, np.nan)
+        fpr = called_neg / np.float64(n_neg) if n_neg else np.full(nb, np.nan)
+        precision = np.where(tp + fp > 0, tp / np.maximum(tp + fp, 1), 0.0)          # int / int in double, as Python divides them
+        recall = np.where(tp + fn > 0, tp / np.maximum(tp + fn, 1), 0.0)
+        f1 = np.where(precision + recall > 0, 2 * (precision * recall) / (precision + recall), 0.0)
+    roc_auc = roc_auc_slack = pr_auc = float("nan")
+    if n_pos and n_neg:
+        at = np.flatnonzero(neg)
+        above = tp[at] - pos[at]                                                     # label-1 samples in the bins above b
+        if 2 * n_pos * n_neg < 2 ** 62:                                              # exact in int64
+            area, shared = int(np.sum(neg[at] * (2 * above + pos[at]))), int(np.sum(neg[at] * pos[at]))
+        else:
+            area = float(np.sum(neg[at].astype(np.float64) * (2.0 * above + pos[at])))
+            shared = float(np.sum(neg[at].astype(np.float64) * pos[at]))
+        roc_auc, roc_auc_slack = area / (2 * n_pos * n_neg), shared / (2 * n_pos * n_neg)
+        occupied = np.flatnonzero(pos + neg + other)
+        r = np.concatenate((tp[occupied] / np.float64(n_pos), [0.0]))
+        p = np.concatenate((tp[occupied] / (tp[occupied] + fp[occupied]).astype(np.float64), [1.0]))
+        pr_auc = float(np.sum((r[:-1] - r[1:]) * (p[:-1] + p[1:]) / 2.0))
+    best = int(np.argmax(f1))
+    return {"tp": tp, "fp": fp, "tn": tn, "fn": fn, "n_pos": n_pos, "n_neg": n_neg, "n_other": n_other, "tpr": tpr, "fpr": fpr,
+            "precision": precision, "recall": recall, "roc_auc": roc_auc, "roc_auc_slack": roc_auc_slack, "pr_auc": pr_auc,
+            "best_f1": {"threshold": float(curve_thresholds(shift)[best]), "f1": float(f1[best]), "precision": float(precision[best]),
+                        "recall": float(recall[best])}}
+
+
 def finish(right, ce_sum, counts_k, bounds, tails):
     """The divisions of ``train_validate.score_validation_batch`` on the raw results: (acc float32 [n], loss float32 [n],
     (tp, fp, tn, fn)).  ``acc`` = count as float32 / size as float32; ``loss`` = ``ce_sum / size`` in double, then float32;
@@ -268,6 +373,7 @@ class DeviceValidationSet(object):
 
     score_host = staticmethod(score_host)
     run_states_host = staticmethod(run_states_host)
+    curve_host = staticmethod(curve_host)
     finish = staticmethod(finish)
     layout = staticmethod(layout)
 

@@ -361,6 +361,29 @@ class HipEngine(object):
                                                    len(edges), int(min_run), C.c_void_p(counts_out.data_ptr()),
                                                    C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
 
+    def curve_validation(self, probs, y, bounds, length, total, longest, shift, hist_out, stream=None):
+        """``cf_validation_curve``: how many samples of label 1 / label 0 / any other label fall into every bin of
+        ``device_validation.curve_bin`` at ``shift`` (10 .. 22) -- ``device_validation.curve_host`` -- into ``hist_out`` (int64 CUDA,
+        at least ``3 * curve_bins(shift)`` elements, zeroed and written by the call).  ``bounds`` [n + 1] and ``length`` [n] are
+        int64 CUDA tensors; the zero tails are not counted.  Asynchronous on the stream; equal inputs give equal bits."""
+        import torch
+        self._check_validation_tensors("curve_validation", [
+            ("probs", probs, torch.float32), ("y", y, torch.uint8), ("bounds", bounds, torch.int64), ("length", length, torch.int64),
+            ("hist_out", hist_out, torch.int64)])
+        n, total, longest = int(length.numel()), int(total), int(longest)
+        if int(bounds.numel()) != n + 1:
+            raise ValueError("curve_validation: length needs n entries, bounds n + 1")
+        if total < 0 or min(int(probs.numel()), int(y.numel())) < total:
+            raise ValueError("curve_validation: probs and y need %d elements" % total)
+        if isinstance(shift, bool) or int(shift) != shift:
+            raise ValueError("curve_validation: shift must be an int, got %r" % (shift,))
+        if stream is None:
+            stream = torch.cuda.current_stream(probs.device)
+        # n, the shift and the room in hist_out are refused by the library (CF_ERR_INVALID -> ValueError)
+        N.check(self._lib.cf_validation_curve(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()),
+                                              C.c_void_p(bounds.data_ptr()), C.c_void_p(length.data_ptr()), n, total, longest, int(shift),
+                                              C.c_void_p(hist_out.data_ptr()), int(hist_out.numel()), C.c_void_p(stream.cuda_stream)))
+
     # ------------------------------------------------------------------ profiling / debug
     def profile_enable(self, on=True, every=1):
         """Per-kernel HIP-event timing of every ``every``-th call (events cost ~1.6 % when on every call)."""

@@ -209,14 +209,18 @@ class RNN(object):
         self._require_engine()
         return self.engine.infer_host(np.asarray(windows), return_logits=True)
 
-    def score_validation_device(self, vset, selection, thresholds=(0.5,), run_edges=None):
+    def score_validation_device(self, vset, selection, thresholds=(0.5,), run_edges=None, curve_shift=None):
         """One validation round on the card: the stretches ``selection`` (``vset.select``) of a
         ``device_validation.DeviceValidationSet`` -> what ``device_validation.score_host`` returns for them, (right int64 [n],
         ce_sum float64 [n], counts int64 [K, 4]).  With ``run_edges`` (a tuple of up to 7 ascending run lengths, possibly empty)
         a fourth result follows: what ``device_validation.run_states_host`` returns for the round's probabilities, int64
         [K, 2, len(run_edges) + 1, 3] -- how many true homopolymers were found completely, partly or not at all and how many
         called stretches hold one, per length bin (``cf_validation_run_states`` after the same gather and forward pass, in the
-        same copy back; its label work space and the larger result buffer follow the grow-only rule below).
+        same copy back; its label work space and the larger result buffer follow the grow-only rule below).  With ``curve_shift``
+        (an int in 10 .. 22) the LAST result -- after the run states when both are asked for -- is what
+        ``device_validation.curve_host`` returns for the round's probabilities, int64 [3, curve_bins(curve_shift)]: the histogram
+        ``device_validation.curves_from_histogram`` turns into the whole ROC and precision-recall curves (``cf_validation_curve``,
+        same forward pass, same copy back; its room in the result buffer is ``validation_buffers["capacity"]["curve_cells"]``).
 
         The selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes
         probabilities and logits (the weights just trained, as ``score_windows`` uses them), ``cf_validation_score`` reduces them
@@ -231,6 +235,7 @@ class RNN(object):
             raise ValueError("score_validation_device: no threshold given")
         if run_edges is not None:
             run_edges = dv.check_run_edges(run_edges)
+        curve_cells = 0 if curve_shift is None else 3 * dv.curve_bins(curve_shift)
         read_index, first, length = vset.check_selection(selection)
         n = int(read_index.size)
         if n == 0:
@@ -248,6 +253,8 @@ class RNN(object):
             run_cells = k_all * 2 * (len(run_edges) + 1) * 3
             need.update({"run_cells": run_cells,
                          "run_work": max(self.engine.run_states_work_bytes(total, min(k_all, dv.MAX_THRESHOLDS)), 1)})
+        if curve_shift is not None:
+            need["curve_cells"] = curve_cells
         if any(book["capacity"].get(key, 0) < value for key, value in need.items()):
             cap = {key: max(book["capacity"].get(key, 0), value) for key, value in need.items()}
             f32 = lambda count: torch.empty(count, dtype=torch.float32, device=device)     # noqa: E731
@@ -255,9 +262,10 @@ class RNN(object):
                                "y": torch.empty(cap["samples"], dtype=torch.uint8, device=device),
                                "table": torch.empty(3 * (cap["reads"] + 1), dtype=torch.int64, device=device),
                                "partials": torch.empty(cap["slots"], dtype=torch.float64, device=device),
-                               # right [reads] | ce_sum [reads], double bits | counts [4 per threshold] | run states: one copy back
-                               "out": torch.empty(2 * cap["reads"] + 4 * cap["thresholds"] + cap.get("run_cells", 0), dtype=torch.int64,
-                                                  device=device)}
+                               # right [reads] | ce_sum [reads], double bits | counts [4 per threshold] | run states | curve
+                               # histogram: one copy back
+                               "out": torch.empty(2 * cap["reads"] + 4 * cap["thresholds"] + cap.get("run_cells", 0)
+                                                  + cap.get("curve_cells", 0), dtype=torch.int64, device=device)}
             if "run_work" in cap:                                                    # corrected labels, one array per threshold of a group
                 book["tensors"]["run_work"] = torch.empty(cap["run_work"], dtype=torch.uint8, device=device)
             book["capacity"] = cap
@@ -274,8 +282,9 @@ class RNN(object):
         book["selection_uploads"] += 1
         src_d, len_d, bounds_d = (t["table"][i * (n + 1):i * (n + 1) + count] for i, count in ((0, n), (1, n), (2, n + 1)))
         x, y, probs, logits = t["x"][:total], t["y"][:total], t["probs"][:total], t["logits"][:total]
-        out = t["out"][:2 * n + 4 * k_all + run_cells]
-        right_d, ce_d, counts_d, runs_d = out[:n], out[n:2 * n].view(torch.float64), out[2 * n:2 * n + 4 * k_all], out[2 * n + 4 * k_all:]
+        out = t["out"][:2 * n + 4 * k_all + run_cells + curve_cells]
+        right_d, ce_d, counts_d = out[:n], out[n:2 * n].view(torch.float64), out[2 * n:2 * n + 4 * k_all]
+        runs_d, curve_d = out[2 * n + 4 * k_all:2 * n + 4 * k_all + run_cells], out[2 * n + 4 * k_all + run_cells:]
         self.engine.gather_validation(signal, labels, src_d, len_d, bounds_d, total, longest, x, y)
         self.engine.infer_device(x.view(-1, self.window), out=probs, logits=logits)
         for k0 in range(0, k_all, dv.MAX_THRESHOLDS):
@@ -286,12 +295,16 @@ class RNN(object):
                 per_k = run_cells // k_all
                 self.engine.run_states_validation(probs, y, bounds_d, len_d, total, longest, thresholds[k0:k1], run_edges,
                                                   runs_d[per_k * k0:per_k * k1], t["run_work"])
+        if curve_shift is not None:
+            self.engine.curve_validation(probs, y, bounds_d, len_d, total, longest, curve_shift, curve_d)
         back = out.cpu().numpy()                                                     # synchronises the stream
         self.engine.check_error()
-        three = (back[:n].copy(), back[n:2 * n].view(np.float64).copy(), back[2 * n:2 * n + 4 * k_all].reshape(k_all, 4).copy())
-        if run_edges is None:
-            return three
-        return three + (back[2 * n + 4 * k_all:].reshape(k_all, 2, len(run_edges) + 1, 3).copy(),)
+        results = (back[:n].copy(), back[n:2 * n].view(np.float64).copy(), back[2 * n:2 * n + 4 * k_all].reshape(k_all, 4).copy())
+        if run_edges is not None:
+            results += (back[2 * n + 4 * k_all:2 * n + 4 * k_all + run_cells].reshape(k_all, 2, len(run_edges) + 1, 3).copy(),)
+        if curve_shift is not None:
+            results += (back[2 * n + 4 * k_all + run_cells:].reshape(3, -1).copy(),)
+        return results
 
     @property
     def validation_buffers(self):

@@ -22,7 +22,7 @@ import random
 import numpy as np
 
 from . import metrics
-from .device_validation import RUN_STATES, run_state_rates
+from .device_validation import RUN_STATES, curve_thresholds, curves_from_histogram, run_state_rates
 from .neural_network import build_model as _build_model
 
 
@@ -193,6 +193,17 @@ def _append(path, text):
         fh.write(text)
 
 
+def _json_line(record):
+    """One JSON line; nan (an AUC without one of the classes) is written as null, at any depth."""
+    def clean(value):
+        if isinstance(value, dict):
+            return {key: clean(v) for key, v in value.items()}
+        if isinstance(value, float) and value != value:
+            return None
+        return value
+    return json.dumps(clean(record), allow_nan=False) + "\n"
+
+
 def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     """What the reference does at a checkpoint step (networks/train_validate.py:154-175): save, score the batch just
     trained on, run one round of validation; the report lines go to ``report`` in that order."""
@@ -208,17 +219,25 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     _append(report, "\nTraining accuracy: {}\nTraining loss: {}\n".format(batch_acc, batch_loss))
     clock = datetime.datetime.now()
     run_edges = getattr(network, "validation_run_edges", None)
+    curve_shift = getattr(network, "validation_curve_shift", None)
+    extra = {} if curve_shift is None else {"curve_shift": curve_shift}
     if run_edges is None:
-        _acc, precision, recall = validate(network, *validation)
+        _acc, precision, recall = validate(network, *validation, **extra)
     else:
         # the homopolymers the round found, next to the report (which stays the reference's): one JSON line per round
-        _acc, precision, recall = validate(network, *validation, run_edges=run_edges)
+        _acc, precision, recall = validate(network, *validation, run_edges=run_edges, **extra)
         table = np.asarray(network.validation_run_states)
         complete, found, called_absent = run_state_rates(table)
         _append(report[:-len(".txt")] + "_hp_states.jsonl", json.dumps({
             "step": int(step), "threshold": 0.5, "edges": list(run_edges), "states": list(RUN_STATES),
             "hp_states": table[0].tolist(), "called_states": table[1].tolist(), "hp_complete": complete, "hp_found": found,
             "called_absent": called_absent}) + "\n")
+    if curve_shift is not None:
+        # the round's whole ROC and precision-recall curves, reduced to their areas and the best F1: one JSON line per round
+        curves = curves_from_histogram(network.validation_curve, curve_shift)
+        line = {"step": int(step), "shift": int(curve_shift)}
+        line.update({key: curves[key] for key in ("roc_auc", "roc_auc_slack", "pr_auc", "best_f1", "n_pos", "n_neg", "n_other")})
+        _append(report[:-len(".txt")] + "_curves.jsonl", _json_line(line))
     print("Validated in {}".format(datetime.datetime.now() - clock))
     _append(report, "Validation precision: {}\nValidation recall: {}\n".format(precision, recall))
     return batch_acc
@@ -358,7 +377,7 @@ def score_validation_batch(probs32, logits32, y, bounds, tails, threshold=0.5):
     return acc, loss.astype(np.float32), counts
 
 
-def validate(network, squiggles, max_seq_length, file_path, validation_start="random", max_number=856, run_edges=None):
+def validate(network, squiggles, max_seq_length, file_path, validation_start="random", max_number=856, run_edges=None, curve_shift=None):
     """networks/train_validate.py:188-295 as one packed launch.
 
     The reference pushes every read through ``test_network`` (one ``sess.run`` each, up to 856 per round); windows are
@@ -374,6 +393,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
 
     ``run_edges`` (a ``DeviceValidationSet`` only): the round also counts the homopolymers found at threshold 0.5
     (``device_validation.run_states_host``, on the card); the [2, B, 3] table is left in ``network.validation_run_states``.
+    ``curve_shift`` (a ``DeviceValidationSet`` only; an int in 10 .. 22): the round also bins its probabilities
+    (``device_validation.curve_host``, on the card); the [3, NB] histogram is left in ``network.validation_curve``.
     Report, prints and return value stay as they are."""
     print("Max length is {}".format(max_seq_length))
     print("Validation start is {}".format(validation_start))
@@ -385,15 +406,21 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
         n_samples = int(selection[2].sum())
         if n_reads == 0:
             raise ZeroDivisionError("validation selected no read")
-        if run_edges is None:
+        if run_edges is None and curve_shift is None:
             right, ce_sum, counts_k = network.score_validation_device(squiggles, selection)
         else:
-            right, ce_sum, counts_k, run_states = network.score_validation_device(squiggles, selection, (0.5,), run_edges=run_edges)
-            network.validation_run_states = run_states[0]
+            got = network.score_validation_device(squiggles, selection, (0.5,), run_edges=run_edges, curve_shift=curve_shift)
+            right, ce_sum, counts_k = got[:3]
+            if run_edges is not None:
+                network.validation_run_states = got[3][0]
+            if curve_shift is not None:
+                network.validation_curve = got[-1]
         acc, loss, counts = squiggles.finish(right, ce_sum, counts_k[0], *squiggles.layout(selection[2], network.window))
     else:
         if run_edges is not None:
             raise ValueError("validate: run_edges needs a DeviceValidationSet (the run states are counted on the card)")
+        if curve_shift is not None:
+            raise ValueError("validate: curve_shift needs a DeviceValidationSet (the probabilities are binned on the card)")
         signals, labels = select_validation_stretches(squiggles, network.window, max_seq_length, validation_start,
                                                       max_number)
         n_reads = len(signals)
@@ -458,7 +485,26 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     return rows
 
 
+def validation_curves(network, vset, max_seq_length, validation_start="complete", max_number=856, shift=14):
+    """The reference's whole-curve evaluation (``roc_curve``, ``precision_recall_curve`` and ``auc``, networks/metrics.py:66-94;
+    ``roc_auc_score`` and the marks on the curve, networks/precision_recall_ROC.py:14-82 -- offline there, from text dumps of every
+    score) over a ``DeviceValidationSet``: ONE forward pass, the probabilities binned on the card at every ``1 << shift`` step of
+    their float32 bits (``device_validation.curve_host``; 65 025 thresholds at shift 14), the curves drawn from that table on the
+    host.  The stretches are ``threshold_sweep``'s (same selection; the zero tails are not counted).  ->
+    ``device_validation.curves_from_histogram``'s dict (tp / fp / tn / fn, tpr / fpr, precision / recall per threshold, roc_auc
+    with its quantisation slack, pr_auc, best_f1, n_pos / n_neg / n_other) plus ``shift`` and ``thresholds`` (float32 [NB])."""
+    selection = vset.select(network.window, max_seq_length, validation_start, max_number)
+    if len(selection[0]) == 0:
+        raise ZeroDivisionError("validation selected no read")
+    hist = network.score_validation_device(vset, selection, (0.5,), curve_shift=shift)[-1]
+    curves = curves_from_histogram(hist, shift)
+    curves.update({"shift": int(shift), "thresholds": curve_thresholds(shift)})
+    return curves
+
+
 VALIDATION_RUN_EDGES = (35, 70, 140)        # length bins of the per-round homopolymer table: one, two and four windows
+
+VALIDATION_CURVE_SHIFT = 14                  # 65 025 threshold steps for the per-round curve line
 
 _USAGE = ("The following arguments should be provided in this order:\n"
           "\t-network type\n\t-path to training db"
@@ -507,7 +553,11 @@ def main(argv):
     once): a checkpoint round gathers and scores its stretches there instead of re-opening the files.
     CATFISH_VALIDATION_RUNS=1 (with CATFISH_DEVICE_VALIDATION=1) also counts, per round, the homopolymers found at threshold 0.5
     in the length bins ``VALIDATION_RUN_EDGES`` and appends them as one JSON line to ``<model path>_hp_states.jsonl``; the
-    ``.txt`` report is unchanged."""
+    ``.txt`` report is unchanged.
+    CATFISH_VALIDATION_CURVE=1 (with CATFISH_DEVICE_VALIDATION=1) also bins every round's probabilities on the card
+    (``validation_curves``' histogram at shift ``VALIDATION_CURVE_SHIFT``) and appends step, shift, roc_auc, roc_auc_slack, pr_auc,
+    best_f1, n_pos, n_neg and n_other as one JSON line to ``<model path>_curves.jsonl`` (nan as null); the ``.txt`` reports and the
+    ``_hp_states.jsonl`` lines are unchanged."""
     args = list(argv[1:])
     if len(args) < 5:
         raise ValueError(_USAGE)
@@ -539,6 +589,8 @@ def main(argv):
         squiggles = DeviceValidationSet.from_npz(squiggles)
         if os.environ.get("CATFISH_VALIDATION_RUNS") == "1":     # ... and the homopolymers found, one JSON line per round
             network.validation_run_edges = VALIDATION_RUN_EDGES
+        if os.environ.get("CATFISH_VALIDATION_CURVE") == "1":    # ... and the round's ROC / PR areas and best F1, one JSON line per round
+            network.validation_curve_shift = VALIDATION_CURVE_SHIFT
     began = datetime.datetime.now()
     train_and_validate(network, db_train, n_train, squiggles, stretch, network.model_path, start, most)
     print("Trained and validated network in {}".format(datetime.datetime.now() - began))

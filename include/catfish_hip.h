@@ -565,6 +565,20 @@ int cf_validation_run_states(cf_model* m, const float* probs, const uint8_t* y, 
                              int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds, const int64_t* edges,
                              int32_t n_edges, int32_t min_run, int64_t* counts_out, void* work, int64_t work_bytes, void* stream);
 
+/* Validation curves (csrc/validation_curve.hpp; device_validation.curve_host is its definition): the histogram of a round's
+ * probabilities from which the host draws the whole ROC and precision-recall curves (device_validation.curves_from_histogram).
+ * With NB = (0x3F800000 >> shift) + 1 bins, a probability with float32 bits u falls into bin min(max((int32_t)u, 0) >> shift, NB - 1)
+ * (csrc/validation_curve_bin.hpp), so for p in [0, 1]: p >= the float with bits b << shift  <=>  bin(p) >= b.
+ *   hist_out     device int64 [3][NB] (rows: label == 1, label == 0, any other label), zeroed and written by the call; only the
+ *                first length[r] samples from bounds[r] of every stretch are counted (the zero tails are not)
+ *   shift        10 .. 22 (14: NB = 65 025);  hist_capacity  entries of hist_out, >= 3 NB
+ * One workgroup per cf_validation_score_chunk() samples sorts its cells in LDS and issues one 64-bit integer atomic per DISTINCT
+ * cell; integers only, so equal inputs give equal results whatever `longest` (a hint, as above).  Asynchronous on `stream`; m may be
+ * NULL.  CF_ERR_INVALID before anything is written for a null pointer, n outside [1, 2^31), a shift outside 10 .. 22, a bad size or
+ * hist_capacity < 3 NB. */
+int cf_validation_curve(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length, int64_t n,
+                        int64_t total, int64_t longest, int32_t shift, int64_t* hist_out, int64_t hist_capacity, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream) for bench.py's
  * roofline report.  cf_profile_enable(m, N) makes every N-th cf_infer call
  * (N = 1: every call; 0 = off) record events around each of its kernels; cf_profile_read synchronises and returns, for

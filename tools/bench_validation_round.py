@@ -16,11 +16,18 @@ and range of seconds per round, and whether (c)'s range lies below (a)'s and bel
     python tools/bench_validation_round.py --resident-rounds 15  # route (c) alone, timed: one summary line (to compare two builds,
                                                                  # run them alternately and compare against the spread of each)
     python tools/bench_validation_round.py --run-states          # the run-state leg, see below
+    python tools/bench_validation_round.py --curve               # the curve leg, see below
+    python tools/bench_validation_round.py --trace-curve 3       # rounds with the curve at shift 14 and shift 10, for rocprofv3
 
 The run-state leg (``--run-states``) times the device-resident round itself (``RNN.score_validation_device`` on a seeded selection,
 ending in its copy back), alternating per round: without run states, with ``run_edges=(35, 70, 140)``, and the forward pass of
 that round alone -- at 1 and at 16 thresholds.  Its summary line gives the medians, the time the run-state step adds to the round
 and the forward pass's share of the round.
+
+The curve leg (``--curve``) times the same round, alternating per round: without the curve, with ``curve_shift=14``, with
+``curve_shift=10``, and ``HipEngine.curve_validation`` alone (launch to synchronise, no copy back) at both shifts on the round's
+own probabilities and on an all-equal input (every probability 0.5, every label 1: all samples on one cell).  Its summary line
+gives the medians and the milliseconds the curve adds to the round.
 """
 import argparse
 import contextlib
@@ -105,6 +112,44 @@ def run_states_leg(net, resident, rounds, emit, edges=(35, 70, 140)):
                   added_over_forward=added / stats["forward"]["median_s"]))
 
 
+def curve_leg(net, resident, rounds, emit, shifts=(14, 10)):
+    from catfish_amd import device_validation as dv
+    thresholds = (0.5,)
+    names = ["plain"] + ["curve_%d" % s for s in shifts] + ["kernel_%d" % s for s in shifts] + ["kernel_equal_%d" % s for s in shifts]
+    seconds = {name: [] for name in names}
+    hist = {s: torch.empty(3 * dv.curve_bins(s), dtype=torch.int64, device="cuda:%d" % net.device) for s in shifts}
+    equal = None
+    for rnd in range(-1, rounds):                          # round -1 warms up (buffers grow once per shift)
+        random.seed(rnd)
+        selection = resident.select(net.window, STRETCH, START, MOST)
+        took = {"plain": timed(lambda: net.score_validation_device(resident, selection, thresholds))}
+        for s in shifts:
+            took["curve_%d" % s] = timed(lambda: net.score_validation_device(resident, selection, thresholds, curve_shift=s))
+        t = net.validation_buffers["tensors"]
+        bounds, _tails = dv.layout(selection[2], net.window)
+        n, total, longest = len(selection[2]), int(bounds[-1]), int(np.diff(bounds).max())
+        len_d, bounds_d = t["table"][n + 1:2 * n + 1], t["table"][2 * (n + 1):3 * (n + 1)]
+        if equal is None or equal[0].numel() < total:
+            equal = (torch.full((total,), 0.5, dtype=torch.float32, device=hist[shifts[0]].device),
+                     torch.ones(total, dtype=torch.uint8, device=hist[shifts[0]].device))
+        for s in shifts:
+            took["kernel_%d" % s] = timed(lambda: net.engine.curve_validation(t["probs"][:total], t["y"][:total], bounds_d, len_d, total,
+                                                                              longest, s, hist[s]))
+            took["kernel_equal_%d" % s] = timed(lambda: net.engine.curve_validation(equal[0][:total], equal[1][:total], bounds_d, len_d,
+                                                                                    total, longest, s, hist[s]))
+        if rnd >= 0:
+            for name in names:
+                seconds[name].append(took[name])
+            emit(dict(leg="curve", round=rnd, **{name + "_s": took[name] for name in names}))
+    stats = {name: spread(v) for name, v in seconds.items()}
+    emit(dict(summary=True, leg="curve", shifts=list(shifts), reads=resident.n_reads, stretch=STRETCH, rounds=rounds,
+              samples_per_round=resident.n_reads * (STRETCH // 35 * 35), legs=stats,
+              added_ms={str(s): 1e3 * (stats["curve_%d" % s]["median_s"] - stats["plain"]["median_s"]) for s in shifts},
+              kernel_ms={str(s): 1e3 * stats["kernel_%d" % s]["median_s"] for s in shifts},
+              kernel_equal_ms={str(s): 1e3 * stats["kernel_equal_%d" % s]["median_s"] for s in shifts},
+              histogram_bytes={str(s): 24 * dv.curve_bins(s) for s in shifts}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=5)
@@ -115,6 +160,8 @@ def main():
     ap.add_argument("--trace-rounds", type=int, default=0, help="route (c) alone for this many rounds, then exit")
     ap.add_argument("--resident-rounds", type=int, default=0, help="route (c) alone, timed for this many rounds, then exit")
     ap.add_argument("--run-states", action="store_true", help="the run-state leg alone, then exit")
+    ap.add_argument("--curve", action="store_true", help="the curve leg alone, then exit")
+    ap.add_argument("--trace-curve", type=int, default=0, help="this many rounds with the curve at shift 14 and at shift 10, then exit")
     args = ap.parse_args()
     rounds = max(5, args.rounds)
     commit = args.commit or commit_id()
@@ -154,6 +201,15 @@ def main():
             print(json.dumps(dict(traced="c_resident", rounds=args.trace_rounds)))
             os.chdir(ROOT)
             return
+        if args.trace_curve:
+            for rnd in range(args.trace_curve):
+                random.seed(rnd)
+                selection = resident.select(net.window, STRETCH, START, MOST)
+                for shift in (14, 10):
+                    net.score_validation_device(resident, selection, (0.5,), curve_shift=shift)
+            print(json.dumps(dict(traced="curve", rounds=args.trace_curve, shifts=[14, 10])))
+            os.chdir(ROOT)
+            return
         os.makedirs(os.path.dirname(out_path), exist_ok=True)
         with open(out_path, "a") as out:
             def emit(rec):
@@ -162,7 +218,7 @@ def main():
                 out.write(line + "\n")
                 out.flush()
 
-            if args.resident_rounds or args.run_states:
+            if args.resident_rounds or args.run_states or args.curve:
                 if args.resident_rounds:
                     routes[2][1](-1)
                     took = [routes[2][1](rnd)[0] for rnd in range(args.resident_rounds)]
@@ -170,6 +226,8 @@ def main():
                               rounds=args.resident_rounds, seconds=took, **spread(took)))
                 if args.run_states:
                     run_states_leg(net, resident, rounds, emit)
+                if args.curve:
+                    curve_leg(net, resident, rounds, emit)
                 os.chdir(ROOT)
                 net.engine.close()
                 return
