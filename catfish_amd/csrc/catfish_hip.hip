@@ -2567,6 +2567,7 @@ extern "C" int cf_opt_step(cf_model* m, int32_t kind, float* params, const float
 #include "sample_batch.hpp"   // device-resident training set: cf_sample_batch draws and gathers a training step's next batch on the card
 #include "validation.hpp"     // device-resident validation set: cf_validation_gather packs a round's stretches, cf_validation_score scores them
 #include "validation_runs.hpp" // ... and cf_validation_run_states counts the homopolymers found: run states per threshold and length bin
+#include "validation_borders.hpp" // ... cf_validation_run_borders the rest of check_hp: how far called borders miss, and the interruptions
 #include "validation_curve.hpp" // ... and cf_validation_curve bins the probabilities at every threshold step: whole ROC / PR curves and AUC
 
 // ---- profiling ---------------------------------------------------------------------------

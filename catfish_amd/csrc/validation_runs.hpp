@@ -203,6 +203,31 @@ extern "C" int64_t cf_validation_run_work_bytes(int64_t total, int32_t n_thresho
     return (int64_t)n_thresholds * ((total + 63) / 64 * 64);
 }
 
+// The corrected labels of the whole packed batch, one array per threshold at lab + k * stride (threshold + correct_short inside every
+// stretch): what cf_validation_run_states and cf_validation_run_borders count on.
+static int validation_label_passes(const float* probs, const int64_t* bounds, const int64_t* length, int64_t n, int64_t total,
+                                   const double* thresholds, int32_t n_thresholds, int32_t min_run, uint8_t* lab, int64_t stride,
+                                   hipStream_t s) {
+    // the bit-mask kernel covers runs of up to 64 samples and stores labels 16 bytes at a time (cf_postprocess's rule)
+    const bool bits = min_run <= 64 && (reinterpret_cast<uintptr_t>(lab) & 15u) == 0;
+    for (int k = 0; k < n_thresholds; ++k) {
+        // (double)p >= t  <=>  p >= tf with tf the smallest float not below t
+        float tf = (float)thresholds[k];
+        if ((double)tf < thresholds[k]) tf = std::nextafterf(tf, INFINITY);
+        if (bits) {
+            const int64_t n_words = (total + 63) / 64, n_chunks = (n_words + CF_POST_WORDS - 1) / CF_POST_WORDS;
+            hipLaunchKernelGGL(postprocess_bits_kernel<false>, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, s, probs, bounds, length, n,
+                               total, tf, (int)min_run, lab + k * stride, (int64_t)0, (int64_t*)nullptr, (int64_t*)nullptr,
+                               (unsigned long long*)nullptr);
+        } else {
+            hipLaunchKernelGGL(postprocess_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, probs, bounds, length, n, total, tf,
+                               (int)min_run, lab + k * stride);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return CF_OK;
+}
+
 extern "C" int cf_validation_run_states(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length,
                                         int64_t n, int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds,
                                         const int64_t* edges, int32_t n_edges, int32_t min_run, int64_t* counts_out, void* work,
@@ -232,23 +257,7 @@ extern "C" int cf_validation_run_states(cf_model* m, const float* probs, const u
     HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_thresholds * 2 * n_bins * 3 * sizeof(int64_t), s));
     if (total == 0) return CF_OK;                              // stretches without a sample: the zeroed table
     uint8_t* lab = static_cast<uint8_t*>(work);
-    // the bit-mask kernel covers runs of up to 64 samples and stores labels 16 bytes at a time (cf_postprocess's rule)
-    const bool bits = min_run <= 64 && (reinterpret_cast<uintptr_t>(work) & 15u) == 0;
-    for (int k = 0; k < n_thresholds; ++k) {
-        // (double)p >= t  <=>  p >= tf with tf the smallest float not below t
-        float tf = (float)thresholds[k];
-        if ((double)tf < thresholds[k]) tf = std::nextafterf(tf, INFINITY);
-        if (bits) {
-            const int64_t n_words = (total + 63) / 64, n_chunks = (n_words + CF_POST_WORDS - 1) / CF_POST_WORDS;
-            hipLaunchKernelGGL(postprocess_bits_kernel<false>, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, s, probs, bounds, length, n,
-                               total, tf, (int)min_run, lab + k * stride, (int64_t)0, (int64_t*)nullptr, (int64_t*)nullptr,
-                               (unsigned long long*)nullptr);
-        } else {
-            hipLaunchKernelGGL(postprocess_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, probs, bounds, length, n, total, tf,
-                               (int)min_run, lab + k * stride);
-        }
-        HIP_TRY(hipGetLastError());
-    }
+    if (const int rc = validation_label_passes(probs, bounds, length, n, total, thresholds, n_thresholds, min_run, lab, stride, s)) return rc;
     hipLaunchKernelGGL(validation_run_states_kernel, dim3((unsigned)std::min<int64_t>(n, 1 << 20), (unsigned)n_thresholds), dim3(CF_RUN_THREADS),
                        0, s, lab, stride, y, bounds, length, n, total, (int)n_thresholds, e, n_bins,
                        reinterpret_cast<unsigned long long*>(counts_out));

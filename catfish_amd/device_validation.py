@@ -13,7 +13,8 @@ Every random draw stays on the host, on Python's global generator and in the ref
 This module states both device steps in numpy and those statements are normative: ``DeviceValidationSet.pack`` is what the
 gather kernel writes (bit for bit), ``score_host`` what the scoring kernel returns (counts exactly; the double sums up to the
 summation order), ``run_states_host`` what the run-state step returns (``cf_validation_run_states``, csrc/validation_runs.hpp:
-how many homopolymers a round found, bit for bit), ``curve_host`` what the curve step returns (``cf_validation_curve``,
+how many homopolymers a round found, bit for bit), ``run_borders_host`` what the border step returns
+(``cf_validation_run_borders``, csrc/validation_borders.hpp: how far the called borders miss and the interruptions, bit for bit), ``curve_host`` what the curve step returns (``cf_validation_curve``,
 csrc/validation_curve.hpp: the round's probabilities binned at every threshold step, bit for bit; ``curves_from_histogram`` turns
 that table into the whole ROC and precision-recall curves, their areas and the best F1).  The object is host-only until ``device_arrays`` is called and usable without a GPU.
 """
@@ -158,6 +159,132 @@ def run_state_rates(table):
             int(called[2]) / n_called if n_called else 0)
 
 
+MAX_BORDER_REACH = 128      # the widest offset / interruption histogram (VB_MAX_REACH, csrc/validation_borders_word.hpp)
+BORDER_REACH = 64
+
+
+def check_border_reach(reach):
+    """``reach`` as an int in 1 .. 128 (ValueError otherwise; no bool, no fraction)."""
+    if isinstance(reach, bool) or not isinstance(reach, (int, np.integer)) or not 1 <= reach <= MAX_BORDER_REACH:
+        raise ValueError("border reach must be an int in 1 .. %d, got %r" % (MAX_BORDER_REACH, reach))
+    return int(reach)
+
+
+def border_cells(reach):
+    """Cells of one (threshold, kind) row of a border table: ``5 * reach + 3``."""
+    return 5 * check_border_reach(reach) + 3
+
+
+def _streak(mask):
+    """How many consecutive True values end at every index (inclusive), int64."""
+    at = np.arange(1, mask.size + 1, dtype=np.int64)
+    return at - np.maximum.accumulate(np.where(mask, 0, at))
+
+
+def _borders_of(mask, other, reach, row):
+    """Add the non-absent runs of ``mask`` (bool), judged against ``other`` (bool: the other array is 1), to one row."""
+    starts, ends = _runs_of(mask)
+    if not starts.size:
+        return
+    ones = np.concatenate(([0], np.cumsum(other)))
+    judged = ones[ends + 1] - ones[starts] > 0
+    starts, ends = starts[judged], ends[judged]
+    inner = other.copy()
+    inner[0] = False                                       # check_hp: `not position <= 0` -- position 0 never counts
+    ones_to = np.concatenate(([0], _streak(inner)))        # [i]: ones ending at i - 1, position 0 left out
+    zeros_to, zeros_from = _streak(~other), _streak(~other[::-1])[::-1]
+    ones_from = np.concatenate((_streak(other[::-1])[::-1], [0]))
+    left = np.where(other[starts], -ones_to[starts], zeros_from[starts])
+    right = np.where(other[ends], ones_from[ends + 1], -zeros_to[ends])
+    np.add.at(row, np.clip(left, -reach, reach) + reach, 1)
+    np.add.at(row, 2 * reach + 1 + np.clip(right, -reach, reach) + reach, 1)
+    step = np.diff(np.concatenate(([0], (~other).astype(np.int8), [0])))
+    hole_starts, hole_ends = np.flatnonzero(step == 1), np.flatnonzero(step == -1) - 1
+    run = np.searchsorted(starts, hole_starts, side="right") - 1          # the judged run a hole could lie in
+    inside = run >= 0
+    inside[inside] = (hole_starts[inside] > starts[run[inside]]) & (hole_ends[inside] < ends[run[inside]])
+    np.add.at(row, 4 * reach + 2 + np.minimum(hole_ends[inside] - hole_starts[inside] + 1, reach) - 1, 1)
+    row[5 * reach + 2] += np.unique(run[inside]).size
+
+
+def run_borders_host(probs, y, bounds, lengths, thresholds, reach=BORDER_REACH, min_run=15):
+    """What ``cf_validation_run_borders`` returns, in numpy: int64 [K, 2, 5 * reach + 3] -- the rest of what the reference's
+    ``check_hp`` says about a run (networks/process_output.py:814-895): how far the other array's ones reach beyond its borders
+    or fall short of them, and the interruptions inside it.
+
+    Stretches, prediction, runs (``_runs_of``, the last-sample rule included) and kinds are ``run_states_host``'s; labels must be 0
+    or 1 inside every stretch (ValueError).  Per run [s, e] that is not absent, with ``o`` the other array and n the stretch length:
+    left ``l`` = minus the ones of ``o`` immediately before s, position 0 never counted (``check_hp`` tests ``not position <= 0``),
+    when ``o[s] == 1``, else the zeros of ``o`` from s to its first one; right ``r`` = the ones of ``o`` after e (up to n - 1) when
+    ``o[e] == 1``, else minus the zeros of ``o`` from e down to its last one; interruptions = the maximal runs of zeros of ``o``
+    inside [s, e] that touch neither end.  ``l < 0`` / ``r > 0``: the other array's ones reach beyond the run; ``l > 0`` /
+    ``r < 0``: they start late / stop early.  Cells of a row, R = reach: [0, 2R+1) histogram of ``clip(l, -R, R) + R``; [2R+1, 4R+2)
+    of ``clip(r, -R, R) + R``; [4R+2, 5R+2) of ``min(g, R) - 1`` over the interruption lengths g; [5R+2] runs with an interruption."""
+    from .infer import correct_short
+    reach = check_border_reach(reach)
+    if int(min_run) < 1:
+        raise ValueError("min_run must be >= 1")
+    p = np.asarray(probs, dtype=np.float64).reshape(-1)
+    y = np.asarray(y).reshape(-1)
+    bounds = np.asarray(bounds, dtype=np.int64)
+    lengths = np.asarray(lengths, dtype=np.int64)
+    out = np.zeros((len(thresholds), 2, 5 * reach + 3), dtype=np.int64)
+    for b0, n in zip(bounds[:len(lengths)].tolist(), lengths.tolist()):
+        if n <= 0:
+            continue
+        truth = y[b0:b0 + n]
+        if np.any((truth != 0) & (truth != 1)):
+            raise ValueError("run borders need labels of 0 or 1, got %r" % (truth[(truth != 0) & (truth != 1)][0],))
+        truth = truth == 1
+        for k, t in enumerate(thresholds):
+            pred = np.asarray(correct_short((p[b0:b0 + n] >= float(t)).astype(np.int64), int(min_run))) == 1
+            _borders_of(truth, pred, reach, out[k, 0])
+            _borders_of(pred, truth, reach, out[k, 1])
+    return out
+
+
+def split_run_borders(table, reach):
+    """The four parts of a border table ``[..., 5 * reach + 3]`` as views: {"left": [..., 2R+1], "right": [..., 2R+1],
+    "gaps": [..., R], "interrupted": [...]}."""
+    r = check_border_reach(reach)
+    table = np.asarray(table)
+    if table.shape[-1] != 5 * r + 3:
+        raise ValueError("a border table at reach %d has %d cells per row, got %d" % (r, 5 * r + 3, table.shape[-1]))
+    return {"left": table[..., :2 * r + 1], "right": table[..., 2 * r + 1:4 * r + 2], "gaps": table[..., 4 * r + 2:5 * r + 2],
+            "interrupted": table[..., 5 * r + 2]}
+
+
+def _lower_median(hist, reach):
+    """The lower median offset of a ``clip(v, -R, R) + R`` histogram; None when it is empty or the median lies in a clip bin."""
+    total = int(hist.sum())
+    if not total:
+        return None
+    at = int(np.searchsorted(np.cumsum(hist), (total + 1) // 2))
+    return None if at in (0, 2 * reach) else at - reach
+
+
+def run_border_summary(row, reach):
+    """One threshold's ``[2, 5 * reach + 3]`` row -> per kind a dict: ``judged`` (runs that are not absent), ``exact_left`` /
+    ``exact_right`` (share at offset 0), ``median_left`` / ``median_right`` (lower median from the histogram; None in a clip bin
+    or without runs), ``clipped`` (share of runs in the four end bins), ``interrupted`` (share of judged runs), ``gaps`` (number of
+    interruptions).  A share over nothing is 0 (``metrics.precision_recall``)."""
+    r = check_border_reach(reach)
+    row = np.asarray(row)
+    if row.shape != (2, 5 * r + 3):
+        raise ValueError("one threshold's border row at reach %d is [2, %d], got %s" % (r, 5 * r + 3, row.shape))
+    out = []
+    for kind in range(2):
+        part = split_run_borders(row[kind], r)
+        left, right = part["left"], part["right"]
+        judged = int(left.sum())
+        share = lambda count: int(count) / judged if judged else 0            # noqa: E731
+        out.append({"judged": judged, "exact_left": share(left[r]), "exact_right": share(right[r]),
+                    "median_left": _lower_median(left, r), "median_right": _lower_median(right, r),
+                    "clipped": share(left[0] + left[2 * r] + right[0] + right[2 * r]), "interrupted": share(part["interrupted"]),
+                    "gaps": int(part["gaps"].sum())})
+    return out
+
+
 CURVE_ONE_BITS = 0x3F800000                                # float32 1.0 (VC_ONE_BITS, csrc/validation_curve_bin.hpp)
 CURVE_SHIFT_MIN, CURVE_SHIFT_MAX, CURVE_SHIFT = 10, 22, 14
 
@@ -286,6 +413,7 @@ class DeviceValidationSet(object):
         self.device = device
         self._dev = None                 # {"device", "signal", "labels"} on the card, uploaded once
         self.uploads = 0                 # how often the reads went to a card
+        self._binary = None              # every label is 0 or 1 (looked at once)
 
     @classmethod
     def from_arrays(cls, signals, labels, device=None):
@@ -320,6 +448,13 @@ class DeviceValidationSet(object):
     @property
     def n_reads(self):
         return len(self.lengths)
+
+    @property
+    def labels_binary(self):
+        """Whether every label of the set is 0 or 1 (what the border step needs); computed once and kept."""
+        if self._binary is None:
+            self._binary = not bool(np.any(np.asarray(self.labels) > 1))
+        return self._binary
 
     # ------------------------------------------------------------------ one round on the host
     def select(self, window, max_seq_length, validation_start, max_number):
@@ -373,6 +508,7 @@ class DeviceValidationSet(object):
 
     score_host = staticmethod(score_host)
     run_states_host = staticmethod(run_states_host)
+    run_borders_host = staticmethod(run_borders_host)
     curve_host = staticmethod(curve_host)
     finish = staticmethod(finish)
     layout = staticmethod(layout)

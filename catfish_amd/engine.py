@@ -361,6 +361,41 @@ class HipEngine(object):
                                                    len(edges), int(min_run), C.c_void_p(counts_out.data_ptr()),
                                                    C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
 
+    def run_borders_work_bytes(self, total, n_thresholds):
+        """Bytes of work space ``run_borders_validation`` needs (``run_states_work_bytes``' rule: the two can share a buffer)."""
+        return int(self._lib.cf_validation_run_borders_work_bytes(int(total), int(n_thresholds)))
+
+    def run_borders_validation(self, probs, y, bounds, length, total, longest, thresholds, reach, counts_out, work, min_run=15, stream=None):
+        """``cf_validation_run_borders``: per threshold (``thresholds``: 1..16 host floats) and kind the histograms of how far the
+        other array reaches beyond a run's left and right border or falls short of it (clipped at ``reach``, an int in 1 .. 128),
+        of the interruptions inside the runs, and the number of interrupted runs -- ``device_validation.run_borders_host`` -- into
+        ``counts_out`` (int64 CUDA, ``K * 2 * (5 * reach + 3)`` elements).  ``bounds`` [n + 1] and ``length`` [n] are int64 CUDA
+        tensors; ``work`` is a uint8 CUDA tensor of at least ``run_borders_work_bytes(total, K)`` bytes.  A label other than 1
+        counts as 0 here (``RNN.score_validation_device`` refuses such sets).  Asynchronous on the stream; equal inputs give equal
+        bits."""
+        import torch
+        from .device_validation import check_border_reach
+        self._check_validation_tensors("run_borders_validation", [
+            ("probs", probs, torch.float32), ("y", y, torch.uint8), ("bounds", bounds, torch.int64), ("length", length, torch.int64),
+            ("counts_out", counts_out, torch.int64), ("work", work, torch.uint8)])
+        thresholds = [float(t) for t in thresholds]
+        reach = check_border_reach(reach)
+        n, k, total, longest = int(length.numel()), len(thresholds), int(total), int(longest)
+        if int(bounds.numel()) != n + 1:
+            raise ValueError("run_borders_validation: length needs n entries, bounds n + 1")
+        if total < 0 or min(int(probs.numel()), int(y.numel())) < total:
+            raise ValueError("run_borders_validation: probs and y need %d elements" % total)
+        if int(counts_out.numel()) < k * 2 * (5 * reach + 3):
+            raise ValueError("run_borders_validation: counts_out needs 2 * (5 * reach + 3) entries per threshold")
+        if stream is None:
+            stream = torch.cuda.current_stream(probs.device)
+        # n, K, min_run and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
+        N.check(self._lib.cf_validation_run_borders(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()),
+                                                    C.c_void_p(bounds.data_ptr()), C.c_void_p(length.data_ptr()), n, total, longest,
+                                                    (C.c_double * max(k, 1))(*thresholds), k, reach, int(min_run),
+                                                    C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()),
+                                                    C.c_void_p(stream.cuda_stream)))
+
     def curve_validation(self, probs, y, bounds, length, total, longest, shift, hist_out, stream=None):
         """``cf_validation_curve``: how many samples of label 1 / label 0 / any other label fall into every bin of
         ``device_validation.curve_bin`` at ``shift`` (10 .. 22) -- ``device_validation.curve_host`` -- into ``hist_out`` (int64 CUDA,

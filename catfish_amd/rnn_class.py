@@ -209,7 +209,7 @@ class RNN(object):
         self._require_engine()
         return self.engine.infer_host(np.asarray(windows), return_logits=True)
 
-    def score_validation_device(self, vset, selection, thresholds=(0.5,), run_edges=None, curve_shift=None):
+    def score_validation_device(self, vset, selection, thresholds=(0.5,), run_edges=None, curve_shift=None, border_reach=None):
         """One validation round on the card: the stretches ``selection`` (``vset.select``) of a
         ``device_validation.DeviceValidationSet`` -> what ``device_validation.score_host`` returns for them, (right int64 [n],
         ce_sum float64 [n], counts int64 [K, 4]).  With ``run_edges`` (a tuple of up to 7 ascending run lengths, possibly empty)
@@ -221,6 +221,11 @@ class RNN(object):
         ``device_validation.curve_host`` returns for the round's probabilities, int64 [3, curve_bins(curve_shift)]: the histogram
         ``device_validation.curves_from_histogram`` turns into the whole ROC and precision-recall curves (``cf_validation_curve``,
         same forward pass, same copy back; its room in the result buffer is ``validation_buffers["capacity"]["curve_cells"]``).
+        With ``border_reach`` (an int in 1 .. 128) one more result sits after the run states and before the curve histogram: what
+        ``device_validation.run_borders_host`` returns for the round's probabilities, int64 [K, 2, 5 * border_reach + 3] -- how far
+        the called borders miss the true ones and how often a homopolymer is called in pieces (``cf_validation_run_borders``, same
+        forward pass, same copy back; room ``capacity["border_cells"]``, label work space shared with the run states).  The set's
+        labels must all be 0 or 1 then (ValueError).
 
         The selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes
         probabilities and logits (the weights just trained, as ``score_windows`` uses them), ``cf_validation_score`` reduces them
@@ -236,6 +241,10 @@ class RNN(object):
         if run_edges is not None:
             run_edges = dv.check_run_edges(run_edges)
         curve_cells = 0 if curve_shift is None else 3 * dv.curve_bins(curve_shift)
+        if border_reach is not None:
+            border_reach = dv.check_border_reach(border_reach)
+            if not vset.labels_binary:
+                raise ValueError("score_validation_device: border_reach needs a set whose labels are all 0 or 1")
         read_index, first, length = vset.check_selection(selection)
         n = int(read_index.size)
         if n == 0:
@@ -253,6 +262,11 @@ class RNN(object):
             run_cells = k_all * 2 * (len(run_edges) + 1) * 3
             need.update({"run_cells": run_cells,
                          "run_work": max(self.engine.run_states_work_bytes(total, min(k_all, dv.MAX_THRESHOLDS)), 1)})
+        border_cells = 0
+        if border_reach is not None:
+            border_cells = k_all * 2 * dv.border_cells(border_reach)
+            need.update({"border_cells": border_cells,
+                         "run_work": max(self.engine.run_borders_work_bytes(total, min(k_all, dv.MAX_THRESHOLDS)), 1)})
         if curve_shift is not None:
             need["curve_cells"] = curve_cells
         if any(book["capacity"].get(key, 0) < value for key, value in need.items()):
@@ -262,10 +276,10 @@ class RNN(object):
                                "y": torch.empty(cap["samples"], dtype=torch.uint8, device=device),
                                "table": torch.empty(3 * (cap["reads"] + 1), dtype=torch.int64, device=device),
                                "partials": torch.empty(cap["slots"], dtype=torch.float64, device=device),
-                               # right [reads] | ce_sum [reads], double bits | counts [4 per threshold] | run states | curve
-                               # histogram: one copy back
+                               # right [reads] | ce_sum [reads], double bits | counts [4 per threshold] | run states | borders |
+                               # curve histogram: one copy back
                                "out": torch.empty(2 * cap["reads"] + 4 * cap["thresholds"] + cap.get("run_cells", 0)
-                                                  + cap.get("curve_cells", 0), dtype=torch.int64, device=device)}
+                                                  + cap.get("border_cells", 0) + cap.get("curve_cells", 0), dtype=torch.int64, device=device)}
             if "run_work" in cap:                                                    # corrected labels, one array per threshold of a group
                 book["tensors"]["run_work"] = torch.empty(cap["run_work"], dtype=torch.uint8, device=device)
             book["capacity"] = cap
@@ -282,9 +296,11 @@ class RNN(object):
         book["selection_uploads"] += 1
         src_d, len_d, bounds_d = (t["table"][i * (n + 1):i * (n + 1) + count] for i, count in ((0, n), (1, n), (2, n + 1)))
         x, y, probs, logits = t["x"][:total], t["y"][:total], t["probs"][:total], t["logits"][:total]
-        out = t["out"][:2 * n + 4 * k_all + run_cells + curve_cells]
+        out = t["out"][:2 * n + 4 * k_all + run_cells + border_cells + curve_cells]
         right_d, ce_d, counts_d = out[:n], out[n:2 * n].view(torch.float64), out[2 * n:2 * n + 4 * k_all]
-        runs_d, curve_d = out[2 * n + 4 * k_all:2 * n + 4 * k_all + run_cells], out[2 * n + 4 * k_all + run_cells:]
+        runs_at = 2 * n + 4 * k_all
+        borders_at, curve_at = runs_at + run_cells, runs_at + run_cells + border_cells
+        runs_d, borders_d, curve_d = out[runs_at:borders_at], out[borders_at:curve_at], out[curve_at:]
         self.engine.gather_validation(signal, labels, src_d, len_d, bounds_d, total, longest, x, y)
         self.engine.infer_device(x.view(-1, self.window), out=probs, logits=logits)
         for k0 in range(0, k_all, dv.MAX_THRESHOLDS):
@@ -295,15 +311,21 @@ class RNN(object):
                 per_k = run_cells // k_all
                 self.engine.run_states_validation(probs, y, bounds_d, len_d, total, longest, thresholds[k0:k1], run_edges,
                                                   runs_d[per_k * k0:per_k * k1], t["run_work"])
+            if border_reach is not None:
+                per_k = border_cells // k_all
+                self.engine.run_borders_validation(probs, y, bounds_d, len_d, total, longest, thresholds[k0:k1], border_reach,
+                                                   borders_d[per_k * k0:per_k * k1], t["run_work"])
         if curve_shift is not None:
             self.engine.curve_validation(probs, y, bounds_d, len_d, total, longest, curve_shift, curve_d)
         back = out.cpu().numpy()                                                     # synchronises the stream
         self.engine.check_error()
         results = (back[:n].copy(), back[n:2 * n].view(np.float64).copy(), back[2 * n:2 * n + 4 * k_all].reshape(k_all, 4).copy())
         if run_edges is not None:
-            results += (back[2 * n + 4 * k_all:2 * n + 4 * k_all + run_cells].reshape(k_all, 2, len(run_edges) + 1, 3).copy(),)
+            results += (back[runs_at:borders_at].reshape(k_all, 2, len(run_edges) + 1, 3).copy(),)
+        if border_reach is not None:
+            results += (back[borders_at:curve_at].reshape(k_all, 2, -1).copy(),)
         if curve_shift is not None:
-            results += (back[2 * n + 4 * k_all + run_cells:].reshape(3, -1).copy(),)
+            results += (back[curve_at:].reshape(3, -1).copy(),)
         return results
 
     @property

@@ -22,7 +22,8 @@ import random
 import numpy as np
 
 from . import metrics
-from .device_validation import RUN_STATES, curve_thresholds, curves_from_histogram, run_state_rates
+from .device_validation import (BORDER_REACH, RUN_STATES, check_border_reach, curve_thresholds, curves_from_histogram,
+                                run_border_summary, run_state_rates, split_run_borders)
 from .neural_network import build_model as _build_model
 
 
@@ -204,6 +205,17 @@ def _json_line(record):
     return json.dumps(clean(record), allow_nan=False) + "\n"
 
 
+def border_report(row, reach):
+    """One threshold's [2, 5 * reach + 3] border row -> (hp_borders, called_borders): ``device_validation.run_border_summary``'s two
+    dicts, each with the four parts of its row as lists (``left``, ``right``, ``gaps``) and a number (``interrupted_runs``)."""
+    out = []
+    for kind, summary in enumerate(run_border_summary(row, reach)):
+        part = split_run_borders(np.asarray(row)[kind], reach)
+        out.append(dict(summary, left=part["left"].tolist(), right=part["right"].tolist(), gaps_by_length=part["gaps"].tolist(),
+                        interrupted_runs=int(part["interrupted"])))
+    return tuple(out)
+
+
 def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     """What the reference does at a checkpoint step (networks/train_validate.py:154-175): save, score the batch just
     trained on, run one round of validation; the report lines go to ``report`` in that order."""
@@ -220,7 +232,10 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     clock = datetime.datetime.now()
     run_edges = getattr(network, "validation_run_edges", None)
     curve_shift = getattr(network, "validation_curve_shift", None)
+    border_reach = getattr(network, "validation_border_reach", None)
     extra = {} if curve_shift is None else {"curve_shift": curve_shift}
+    if border_reach is not None:
+        extra["border_reach"] = border_reach
     if run_edges is None:
         _acc, precision, recall = validate(network, *validation, **extra)
     else:
@@ -232,6 +247,12 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
             "step": int(step), "threshold": 0.5, "edges": list(run_edges), "states": list(RUN_STATES),
             "hp_states": table[0].tolist(), "called_states": table[1].tolist(), "hp_complete": complete, "hp_found": found,
             "called_absent": called_absent}) + "\n")
+    if border_reach is not None:
+        # how far the round's called borders miss the true ones, and how often a homopolymer comes in pieces: one JSON line per round
+        hp_borders, called_borders = border_report(network.validation_run_borders, border_reach)
+        _append(report[:-len(".txt")] + "_hp_borders.jsonl", json.dumps({
+            "step": int(step), "threshold": 0.5, "reach": int(border_reach), "hp_borders": hp_borders,
+            "called_borders": called_borders}) + "\n")
     if curve_shift is not None:
         # the round's whole ROC and precision-recall curves, reduced to their areas and the best F1: one JSON line per round
         curves = curves_from_histogram(network.validation_curve, curve_shift)
@@ -377,7 +398,8 @@ def score_validation_batch(probs32, logits32, y, bounds, tails, threshold=0.5):
     return acc, loss.astype(np.float32), counts
 
 
-def validate(network, squiggles, max_seq_length, file_path, validation_start="random", max_number=856, run_edges=None, curve_shift=None):
+def validate(network, squiggles, max_seq_length, file_path, validation_start="random", max_number=856, run_edges=None, curve_shift=None,
+             border_reach=None):
     """networks/train_validate.py:188-295 as one packed launch.
 
     The reference pushes every read through ``test_network`` (one ``sess.run`` each, up to 856 per round); windows are
@@ -395,6 +417,9 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     (``device_validation.run_states_host``, on the card); the [2, B, 3] table is left in ``network.validation_run_states``.
     ``curve_shift`` (a ``DeviceValidationSet`` only; an int in 10 .. 22): the round also bins its probabilities
     (``device_validation.curve_host``, on the card); the [3, NB] histogram is left in ``network.validation_curve``.
+    ``border_reach`` (a ``DeviceValidationSet`` only; an int in 1 .. 128): the round also counts how far the called borders miss
+    the true ones and the interruptions at threshold 0.5 (``device_validation.run_borders_host``, on the card); the
+    [2, 5 * border_reach + 3] table is left in ``network.validation_run_borders``.
     Report, prints and return value stay as they are."""
     print("Max length is {}".format(max_seq_length))
     print("Validation start is {}".format(validation_start))
@@ -406,13 +431,16 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
         n_samples = int(selection[2].sum())
         if n_reads == 0:
             raise ZeroDivisionError("validation selected no read")
-        if run_edges is None and curve_shift is None:
+        if run_edges is None and curve_shift is None and border_reach is None:
             right, ce_sum, counts_k = network.score_validation_device(squiggles, selection)
         else:
-            got = network.score_validation_device(squiggles, selection, (0.5,), run_edges=run_edges, curve_shift=curve_shift)
+            extra = {} if border_reach is None else {"border_reach": border_reach}
+            got = network.score_validation_device(squiggles, selection, (0.5,), run_edges=run_edges, curve_shift=curve_shift, **extra)
             right, ce_sum, counts_k = got[:3]
             if run_edges is not None:
                 network.validation_run_states = got[3][0]
+            if border_reach is not None:
+                network.validation_run_borders = got[3 + (run_edges is not None)][0]
             if curve_shift is not None:
                 network.validation_curve = got[-1]
         acc, loss, counts = squiggles.finish(right, ce_sum, counts_k[0], *squiggles.layout(selection[2], network.window))
@@ -421,6 +449,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
             raise ValueError("validate: run_edges needs a DeviceValidationSet (the run states are counted on the card)")
         if curve_shift is not None:
             raise ValueError("validate: curve_shift needs a DeviceValidationSet (the probabilities are binned on the card)")
+        if border_reach is not None:
+            raise ValueError("validate: border_reach needs a DeviceValidationSet (the borders are compared on the card)")
         signals, labels = select_validation_stretches(squiggles, network.window, max_seq_length, validation_start,
                                                       max_number)
         n_reads = len(signals)
@@ -452,7 +482,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     return whole_acc, precision, recall
 
 
-def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start="complete", max_number=856, run_edges=None):
+def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start="complete", max_number=856, run_edges=None,
+                    border_reach=None):
     """The reference's precision / recall sweep (networks/precision_recall_ROC.py:85-100: ``class_from_threshold`` --
     ``p >= t`` -- then ``compute_f1`` per threshold) over a ``DeviceValidationSet``: ONE forward pass, every threshold counted
     from its probabilities on the card.  The stretches are ``validate``'s (same selection, same tail rule for the true
@@ -462,16 +493,24 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     finds (``device_validation.run_states_host``; the reference's offline networks/process_output.py:235-273): ``hp_states`` and
     ``called_states`` -- per length bin [complete, incomplete, absent] of the true runs against the corrected prediction and of
     the called runs against the truth --, ``hp_complete`` and ``hp_found`` (complete, complete + incomplete over all true runs)
-    and ``called_absent`` (called runs that hold no homopolymer sample over all called runs); 0 for an empty denominator."""
+    and ``called_absent`` (called runs that hold no homopolymer sample over all called runs); 0 for an empty denominator.
+
+    With ``border_reach`` (an int in 1 .. 128) every row also says how far that threshold's borders miss
+    (``device_validation.run_borders_host``; the rest of the reference's ``check_hp``): ``hp_borders`` -- the true runs against
+    the corrected prediction -- and ``called_borders`` -- the called runs against the truth --, each ``border_report``'s dict."""
     thresholds = [float(t) for t in thresholds]
     selection = vset.select(network.window, max_seq_length, validation_start, max_number)
     if len(selection[0]) == 0:
         raise ZeroDivisionError("validation selected no read")
-    run_states = None
-    if run_edges is None:
+    run_states = borders = None
+    if run_edges is None and border_reach is None:
         _right, _ce_sum, counts = network.score_validation_device(vset, selection, thresholds)
-    else:
+    elif border_reach is None:
         _right, _ce_sum, counts, run_states = network.score_validation_device(vset, selection, thresholds, run_edges=run_edges)
+    else:
+        got = network.score_validation_device(vset, selection, thresholds, run_edges=run_edges, border_reach=border_reach)
+        counts, borders = got[2], got[-1]
+        run_states = None if run_edges is None else got[3]
     tail = int(vset.layout(selection[2], network.window)[1].sum())
     rows = []
     for k, (t, (tp, fp, tn_raw, fn)) in enumerate(zip(thresholds, np.asarray(counts).tolist())):
@@ -482,6 +521,8 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
             complete, found, called_absent = run_state_rates(run_states[k])
             rows[-1].update({"hp_states": run_states[k][0].tolist(), "called_states": run_states[k][1].tolist(),
                              "hp_complete": complete, "hp_found": found, "called_absent": called_absent})
+        if borders is not None:
+            rows[-1]["hp_borders"], rows[-1]["called_borders"] = border_report(borders[k], border_reach)
     return rows
 
 
@@ -557,7 +598,11 @@ def main(argv):
     CATFISH_VALIDATION_CURVE=1 (with CATFISH_DEVICE_VALIDATION=1) also bins every round's probabilities on the card
     (``validation_curves``' histogram at shift ``VALIDATION_CURVE_SHIFT``) and appends step, shift, roc_auc, roc_auc_slack, pr_auc,
     best_f1, n_pos, n_neg and n_other as one JSON line to ``<model path>_curves.jsonl`` (nan as null); the ``.txt`` reports and the
-    ``_hp_states.jsonl`` lines are unchanged."""
+    ``_hp_states.jsonl`` lines are unchanged.
+    CATFISH_VALIDATION_BORDERS=1 (reach 64) or =<int> (that reach, 1 .. 128; with CATFISH_DEVICE_VALIDATION=1) also counts, per
+    round, how far the called borders miss the true ones and the interruptions at threshold 0.5 and appends step, threshold,
+    reach, ``hp_borders`` and ``called_borders`` (``border_report``; None as null) as one JSON line to
+    ``<model path>_hp_borders.jsonl``; the ``.txt`` reports and the other ``.jsonl`` files are unchanged."""
     args = list(argv[1:])
     if len(args) < 5:
         raise ValueError(_USAGE)
@@ -591,6 +636,9 @@ def main(argv):
             network.validation_run_edges = VALIDATION_RUN_EDGES
         if os.environ.get("CATFISH_VALIDATION_CURVE") == "1":    # ... and the round's ROC / PR areas and best F1, one JSON line per round
             network.validation_curve_shift = VALIDATION_CURVE_SHIFT
+        borders = os.environ.get("CATFISH_VALIDATION_BORDERS") or "0"
+        if borders != "0":                                       # ... and how far the called borders miss, one JSON line per round
+            network.validation_border_reach = BORDER_REACH if borders == "1" else check_border_reach(int(borders))
     began = datetime.datetime.now()
     train_and_validate(network, db_train, n_train, squiggles, stretch, network.model_path, start, most)
     print("Trained and validated network in {}".format(datetime.datetime.now() - began))

@@ -565,6 +565,27 @@ int cf_validation_run_states(cf_model* m, const float* probs, const uint8_t* y, 
                              int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds, const int64_t* edges,
                              int32_t n_edges, int32_t min_run, int64_t* counts_out, void* work, int64_t work_bytes, void* stream);
 
+/* Border-level validation (csrc/validation_borders.hpp, csrc/validation_borders_word.hpp; device_validation.run_borders_host is its
+ * definition): the rest of what the reference's check_hp (networks/process_output.py:814-895) returns for a run.  Stretches,
+ * prediction, runs and kinds as for cf_validation_run_states; a label other than 1 counts as 0.  For every run [s, e] that is not
+ * absent, with o the other array: l = -(ones of o right before s, position 0 never counted) when o[s] == 1, else the zeros of o from s
+ * to its first one; r = the ones of o right after e when o[e] == 1, else -(the zeros of o from e down to its last one); an
+ * interruption is a maximal run of zeros of o inside [s, e] that touches neither end.  With R = reach a (threshold, kind) row is
+ * 5 R + 3 cells: [0, 2R+1) histogram of clip(l, -R, R) + R; [2R+1, 4R+2) of clip(r, -R, R) + R; [4R+2, 5R+2) of min(g, R) - 1 over
+ * the interruption lengths g; [5R+2] runs with at least one interruption.
+ *   counts_out   device int64 [n_thresholds][2][5 * reach + 3], zeroed and written by the call
+ *   thresholds   HOST double [n_thresholds], 1..16 of them;  reach  1 .. 128
+ *   work         device bytes, >= cf_validation_run_borders_work_bytes(total, n_thresholds) (= cf_validation_run_work_bytes: the two
+ *                calls can share one buffer); 16-byte aligned for the bit-mask post-processing kernel
+ * A workgroup walks a stretch twice, forward and mirrored, in pieces of cf_validation_run_piece() samples; integer arithmetic only,
+ * so equal inputs give equal results whatever `longest` (a hint) or the grid.  Asynchronous on `stream`; m may be NULL.
+ * CF_ERR_INVALID before any launch for a null pointer, n outside [1, 2^31), total >= 2^31, n_thresholds outside 1..16, reach outside
+ * 1..128, min_run < 1 or too small a work buffer. */
+int64_t cf_validation_run_borders_work_bytes(int64_t total, int32_t n_thresholds);
+int cf_validation_run_borders(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length, int64_t n,
+                              int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds, int32_t reach,
+                              int32_t min_run, int64_t* counts_out, void* work, int64_t work_bytes, void* stream);
+
 /* Validation curves (csrc/validation_curve.hpp; device_validation.curve_host is its definition): the histogram of a round's
  * probabilities from which the host draws the whole ROC and precision-recall curves (device_validation.curves_from_histogram).
  * With NB = (0x3F800000 >> shift) + 1 bins, a probability with float32 bits u falls into bin min(max((int32_t)u, 0) >> shift, NB - 1)

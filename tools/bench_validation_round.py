@@ -18,6 +18,8 @@ and range of seconds per round, and whether (c)'s range lies below (a)'s and bel
     python tools/bench_validation_round.py --run-states          # the run-state leg, see below
     python tools/bench_validation_round.py --curve               # the curve leg, see below
     python tools/bench_validation_round.py --trace-curve 3       # rounds with the curve at shift 14 and shift 10, for rocprofv3
+    python tools/bench_validation_round.py --borders --rounds 7  # the border leg, see below
+    python tools/bench_validation_round.py --trace-borders 3     # rounds with border_reach=64, for rocprofv3 --kernel-trace --stats
 
 The run-state leg (``--run-states``) times the device-resident round itself (``RNN.score_validation_device`` on a seeded selection,
 ending in its copy back), alternating per round: without run states, with ``run_edges=(35, 70, 140)``, and the forward pass of
@@ -28,6 +30,11 @@ The curve leg (``--curve``) times the same round, alternating per round: without
 ``curve_shift=10``, and ``HipEngine.curve_validation`` alone (launch to synchronise, no copy back) at both shifts on the round's
 own probabilities and on an all-equal input (every probability 0.5, every label 1: all samples on one cell).  Its summary line
 gives the medians and the milliseconds the curve adds to the round.
+
+The border leg (``--borders``) times the same round, alternating per round: without borders, with ``run_edges=(35, 70, 140)`` (the
+yardstick, in the same process), with ``border_reach=64`` -- at 1 and at 16 thresholds -- and ``HipEngine.run_borders_validation``
+and ``run_states_validation`` alone (launch to synchronise, no copy back) on the round's own probabilities.  Its summary line gives
+the medians, what either step adds to the round and the microseconds per threshold of either call alone.
 """
 import argparse
 import contextlib
@@ -112,6 +119,40 @@ def run_states_leg(net, resident, rounds, emit, edges=(35, 70, 140)):
                   added_over_forward=added / stats["forward"]["median_s"]))
 
 
+def borders_leg(net, resident, rounds, emit, reach=64, edges=(35, 70, 140)):
+    from catfish_amd import device_validation as dv
+    device = "cuda:%d" % net.device
+    for thresholds in ((0.5,), tuple(float(t) for t in np.linspace(0.2, 0.95, 16))):
+        k = len(thresholds)
+        names = ("plain", "run_states", "borders", "states_call", "borders_call")
+        seconds = {name: [] for name in names}
+        counts = torch.empty(k * 2 * max(dv.border_cells(reach), (len(edges) + 1) * 3), dtype=torch.int64, device=device)
+        for rnd in range(-1, rounds):                      # round -1 warms up (buffers grow once)
+            random.seed(rnd)
+            selection = resident.select(net.window, STRETCH, START, MOST)
+            took = {"plain": timed(lambda: net.score_validation_device(resident, selection, thresholds)),
+                    "run_states": timed(lambda: net.score_validation_device(resident, selection, thresholds, run_edges=edges)),
+                    "borders": timed(lambda: net.score_validation_device(resident, selection, thresholds, border_reach=reach))}
+            t = net.validation_buffers["tensors"]
+            bounds, _tails = dv.layout(selection[2], net.window)
+            n, total, longest = len(selection[2]), int(bounds[-1]), int(np.diff(bounds).max())
+            len_d, bounds_d = t["table"][n + 1:2 * n + 1], t["table"][2 * (n + 1):3 * (n + 1)]
+            took["states_call"] = timed(lambda: net.engine.run_states_validation(t["probs"][:total], t["y"][:total], bounds_d, len_d, total,
+                                                                                 longest, thresholds, edges, counts, t["run_work"]))
+            took["borders_call"] = timed(lambda: net.engine.run_borders_validation(t["probs"][:total], t["y"][:total], bounds_d, len_d, total,
+                                                                                   longest, thresholds, reach, counts, t["run_work"]))
+            if rnd >= 0:
+                for name in names:
+                    seconds[name].append(took[name])
+                emit(dict(leg="borders", thresholds=k, round=rnd, **{name + "_s": took[name] for name in names}))
+        stats = {name: spread(v) for name, v in seconds.items()}
+        emit(dict(summary=True, leg="borders", thresholds=k, reach=reach, edges=list(edges), reads=resident.n_reads, stretch=STRETCH,
+                  rounds=rounds, samples_per_round=resident.n_reads * (STRETCH // 35 * 35), legs=stats,
+                  added_ms={name: 1e3 * (stats[name]["median_s"] - stats["plain"]["median_s"]) for name in ("run_states", "borders")},
+                  call_us_per_threshold={name: 1e6 * stats[name]["median_s"] / k for name in ("states_call", "borders_call")},
+                  borders_over_states_call=stats["borders_call"]["median_s"] / stats["states_call"]["median_s"]))
+
+
 def curve_leg(net, resident, rounds, emit, shifts=(14, 10)):
     from catfish_amd import device_validation as dv
     thresholds = (0.5,)
@@ -162,6 +203,8 @@ def main():
     ap.add_argument("--run-states", action="store_true", help="the run-state leg alone, then exit")
     ap.add_argument("--curve", action="store_true", help="the curve leg alone, then exit")
     ap.add_argument("--trace-curve", type=int, default=0, help="this many rounds with the curve at shift 14 and at shift 10, then exit")
+    ap.add_argument("--borders", action="store_true", help="the border leg alone, then exit")
+    ap.add_argument("--trace-borders", type=int, default=0, help="this many rounds with border_reach=64 at 16 thresholds, then exit")
     args = ap.parse_args()
     rounds = max(5, args.rounds)
     commit = args.commit or commit_id()
@@ -210,6 +253,15 @@ def main():
             print(json.dumps(dict(traced="curve", rounds=args.trace_curve, shifts=[14, 10])))
             os.chdir(ROOT)
             return
+        if args.trace_borders:
+            for rnd in range(args.trace_borders):
+                random.seed(rnd)
+                selection = resident.select(net.window, STRETCH, START, MOST)
+                net.score_validation_device(resident, selection, tuple(float(t) for t in np.linspace(0.2, 0.95, 16)), run_edges=(35, 70, 140),
+                                            border_reach=64)
+            print(json.dumps(dict(traced="borders", rounds=args.trace_borders, reach=64, thresholds=16)))
+            os.chdir(ROOT)
+            return
         os.makedirs(os.path.dirname(out_path), exist_ok=True)
         with open(out_path, "a") as out:
             def emit(rec):
@@ -218,7 +270,7 @@ def main():
                 out.write(line + "\n")
                 out.flush()
 
-            if args.resident_rounds or args.run_states or args.curve:
+            if args.resident_rounds or args.run_states or args.curve or args.borders:
                 if args.resident_rounds:
                     routes[2][1](-1)
                     took = [routes[2][1](rnd)[0] for rnd in range(args.resident_rounds)]
@@ -228,6 +280,8 @@ def main():
                     run_states_leg(net, resident, rounds, emit)
                 if args.curve:
                     curve_leg(net, resident, rounds, emit)
+                if args.borders:
+                    borders_leg(net, resident, rounds, emit)
                 os.chdir(ROOT)
                 net.engine.close()
                 return
