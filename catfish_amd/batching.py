@@ -133,6 +133,16 @@ def spans_from_runs(starts, ends, sample_offsets, n_reads, ext_left=EXT_LEFT, ex
     return [pairs[bounds[r]:bounds[r + 1]] for r in range(n_reads)]
 
 
+def scores_from_runs(scores, n_reads):
+    """The flat score dict (``span_scores.span_scores_host`` or the device's, sorted by start) -> one float64 array
+    [n_spans, 6] per read, columns n, mean_p, min_p, max_p, level, spread, in the order of ``spans_from_runs``' spans."""
+    from .span_scores import span_score_summary, summary_rows
+    rows = summary_rows(span_score_summary(scores))
+    read_of = np.asarray(scores["read"], dtype=np.int64)
+    bounds = np.concatenate(([0], np.cumsum(np.bincount(read_of, minlength=n_reads)[:n_reads]))).tolist()
+    return [rows[bounds[r]:bounds[r + 1]] for r in range(n_reads)]
+
+
 def infer_packed(engine, packed, threshold=0.5, min_run=15, return_probs=False):
     """PackedReads -> list of (spans, read length) per read, optionally with per-read probabilities."""
     import torch

@@ -1067,6 +1067,7 @@ __global__ __launch_bounds__(256) void normalize_kernel(const int16_t* __restric
 }
 
 #include "ingest_post.hpp"      // round 5: normalize_regs_kernel, postprocess_bits_kernel (same results, see there)
+#include "span_scores.hpp"      // span_scores_kernel: per-call scores of the runs postprocess_bits_kernel<true> reports
 
 // ==========================================================================================
 // Host side
@@ -2086,6 +2087,27 @@ extern "C" int cf_postprocess_spans(cf_model* m, const float* probs, const int64
                        reinterpret_cast<unsigned long long*>(counts));
     HIP_TRY(hipGetLastError());
     return prof_end(m, s, pi);
+}
+
+// Per-call scores (csrc/span_scores.hpp): row k belongs to starts[k]; rows at and above min(counts[0], max_runs) are left untouched.
+extern "C" int cf_span_scores(cf_model* m, const float* probs, const float* signal, const int64_t* read_offsets,
+                              const int64_t* read_lengths, int64_t n_reads, int64_t total_samples, float threshold, const int64_t* starts,
+                              const uint64_t* counts, int64_t max_runs, int64_t* ends_paired, double* sums, float* extremes, void* stream) {
+    if (!m) return fail(CF_ERR_INVALID, "cf_span_scores: null model");
+    if (n_reads < 0 || total_samples < 0 || max_runs < 0) return fail(CF_ERR_INVALID, "cf_span_scores: negative size");
+    if (!counts) return fail(CF_ERR_INVALID, "cf_span_scores: null counts");
+    if (max_runs == 0) return CF_OK;
+    if (!starts || !ends_paired || !sums || !extremes) return fail(CF_ERR_INVALID, "cf_span_scores: null buffer");
+    if (n_reads > 0 && total_samples > 0 && (!probs || !read_offsets || !read_lengths)) return fail(CF_ERR_INVALID, "cf_span_scores: null buffer");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    // (with no read or no sample every start is outside every read: the kernel writes empty rows without a load)
+    const int64_t blocks = (max_runs + CF_SCORE_WAVES - 1) / CF_SCORE_WAVES;
+    hipLaunchKernelGGL(span_scores_kernel, dim3((unsigned)(blocks < CF_SCORE_MAX_BLOCKS ? blocks : CF_SCORE_MAX_BLOCKS)), dim3(64 * CF_SCORE_WAVES),
+                       0, s, probs, signal, read_offsets, read_lengths, n_reads, total_samples, threshold, starts,
+                       reinterpret_cast<const unsigned long long*>(counts), max_runs, ends_paired, sums, extremes);
+    HIP_TRY(hipGetLastError());
+    return CF_OK;
 }
 
 extern "C" int cf_spans(cf_model* m, const uint8_t* labels, int64_t total_samples, int64_t max_runs, int64_t* starts,

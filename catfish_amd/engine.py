@@ -187,9 +187,13 @@ class HipEngine(object):
         return out
 
     def postprocess_spans_device(self, probs, read_offsets, read_lengths, threshold=0.5, min_run=15, max_runs=None, labels=False,
-                                 stream=None):
+                                 stream=None, scores=False, signal=None):
         """``postprocess_device`` + ``spans_device`` as ONE launch (``cf_postprocess_spans``) -> (starts, ends) numpy int64, sorted
-        ascending (packed positions; ends exclusive), and the uint8 CUDA labels as a third value when ``labels=True``."""
+        ascending (packed positions; ends exclusive), and the uint8 CUDA labels as a third value when ``labels=True``.
+
+        ``scores=True`` appends the per-run score dict of ``span_scores.span_scores_host`` (``cf_span_scores`` on the same stream, its
+        rows carried through the argsort of the starts; ``signal``: the float32 CUDA samples the network saw, None: ``sum_x`` and
+        ``sum_x2`` are NaN)."""
         import torch
         if not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
             raise ValueError("probs must be a contiguous float32 CUDA tensor")
@@ -213,14 +217,62 @@ class HipEngine(object):
                                                C.c_void_p(lab.data_ptr()) if lab is not None else None, int(max_runs),
                                                C.c_void_p(starts.data_ptr()), C.c_void_p(ends.data_ptr()), C.c_void_p(counts.data_ptr()),
                                                C.c_void_p(stream.cuda_stream)))
+        rows = self.span_scores_device(probs, signal, read_offsets, read_lengths, starts, counts, threshold, stream) if scores else None
         n_s, n_e = (int(v) for v in counts.cpu().tolist())      # synchronises the stream
         self.check_error()
         if n_s != n_e:
             raise RuntimeError("cf_postprocess_spans: %d run starts but %d run ends" % (n_s, n_e))
         if n_s > max_runs:
-            return self.postprocess_spans_device(probs, read_offsets, read_lengths, threshold, min_run, n_s, labels, stream)
+            return self.postprocess_spans_device(probs, read_offsets, read_lengths, threshold, min_run, n_s, labels, stream, scores, signal)
         out = (np.sort(starts[:n_s].cpu().numpy()), np.sort(ends[:n_e].cpu().numpy()))
-        return out + (lab,) if labels else out
+        if labels:
+            out = out + (lab,)
+        if scores:
+            from .span_scores import scores_from_device_rows
+            flat, _order = scores_from_device_rows(starts[:n_s].cpu().numpy(), rows[0][:n_s].cpu().numpy(), rows[1][:n_s].cpu().numpy(),
+                                                   rows[2][:n_s].cpu().numpy(), read_offsets.cpu().numpy(), n_reads, signal is not None)
+            if not np.array_equal(flat["end"], out[1]):
+                raise RuntimeError("cf_span_scores: the paired ends differ from the sorted ends of cf_postprocess_spans")
+            out = out + (flat,)
+        return out
+
+    def span_scores_device(self, probs, signal, read_offsets, read_lengths, starts, counts, threshold=0.5, stream=None, out=None):
+        """``cf_span_scores``: for every run k < min(counts[0], len(starts)) of the start list ``cf_postprocess_spans`` wrote ->
+        CUDA tensors (ends_paired int64 [max_runs], sums float64 [max_runs, 3] = sum p, sum x, sum x * x, extremes float32
+        [max_runs, 2] = min p, max p); rows at and above the count are left as they were (``out``: the three tensors to write into).
+        ``signal`` None: columns 1 and 2 of sums are not written.  Asynchronous on the stream: the count is read on the card."""
+        import torch
+        if not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
+            raise ValueError("probs must be a contiguous float32 CUDA tensor")
+        total = int(probs.numel())
+        if signal is not None and (not signal.is_cuda or signal.dtype != torch.float32 or not signal.is_contiguous()
+                                   or int(signal.numel()) != total):
+            raise ValueError("signal must be a contiguous float32 CUDA tensor with as many samples as probs")
+        for t in (read_offsets, read_lengths, starts, counts):
+            if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("read_offsets, read_lengths, starts and counts must be contiguous int64 CUDA tensors")
+        n_reads, max_runs = int(read_lengths.numel()), int(starts.numel())
+        if int(read_offsets.numel()) != n_reads + 1:
+            raise ValueError("read_offsets must have n_reads + 1 entries")
+        if int(counts.numel()) < 1:
+            raise ValueError("counts must hold the number of starts")
+        dev = probs.device
+        if out is None:
+            out = (torch.empty(max_runs, dtype=torch.int64, device=dev), torch.empty(max_runs, 3, dtype=torch.float64, device=dev),
+                   torch.empty(max_runs, 2, dtype=torch.float32, device=dev))
+        ends_paired, sums, extremes = out
+        if (ends_paired.dtype != torch.int64 or sums.dtype != torch.float64 or extremes.dtype != torch.float32
+                or ends_paired.numel() < max_runs or sums.numel() < 3 * max_runs or extremes.numel() < 2 * max_runs
+                or not all(t.is_cuda and t.is_contiguous() for t in out)):
+            raise ValueError("out must be contiguous CUDA tensors int64 [max_runs], float64 [max_runs, 3], float32 [max_runs, 2]")
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        N.check(self._lib.cf_span_scores(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(signal.data_ptr()) if signal is not None else None,
+                                         C.c_void_p(read_offsets.data_ptr()), C.c_void_p(read_lengths.data_ptr()), n_reads, total,
+                                         float(threshold), C.c_void_p(starts.data_ptr()), C.c_void_p(counts.data_ptr()), max_runs,
+                                         C.c_void_p(ends_paired.data_ptr()), C.c_void_p(sums.data_ptr()), C.c_void_p(extremes.data_ptr()),
+                                         C.c_void_p(stream.cuda_stream)))
+        return out
 
     def spans_device(self, labels, max_runs=None, stream=None):
         """Device run-length pass over corrected labels -> (starts, ends) numpy int64, sorted ascending

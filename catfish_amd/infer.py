@@ -166,12 +166,49 @@ def hp_in_pred(predictions, extension_left=11, extension_right=16, label=1):
 
 
 # --------------------------------------------------------------------------- inference
-def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE):
-    """Body of infer_class_from_signal (infer.py:31-51) for an already normalised signal."""
+def _scores_of_read(raw_in, model, length):
+    """Spans and score rows of one padded, windowed read: on the card when the model has an engine (``cf_postprocess_spans`` +
+    ``cf_span_scores``; the probabilities never come down), else ``span_scores.span_scores_host`` over ``model.infer``."""
+    from .span_scores import scores_of_runs, span_score_summary, span_scores_host, summary_rows
+    x = np.ascontiguousarray(np.asarray(raw_in, dtype=np.float32).reshape(-1))
+    off, lengths = np.array([0, x.shape[0]], dtype=np.int64), np.array([length], dtype=np.int64)
+    if hasattr(model, "_require_engine"):
+        model._require_engine()
+    engine = getattr(model, "engine", None)
+    if engine is not None:
+        import torch
+        dev = torch.device("cuda", engine.device)
+        d_x = torch.from_numpy(x).to(dev)
+        probs = engine.infer_device(d_x.view(-1, WINDOW_SIZE))
+        starts, ends, flat = engine.postprocess_spans_device(probs, torch.from_numpy(off).to(dev), torch.from_numpy(lengths).to(dev),
+                                                             scores=True, signal=d_x)
+        spans = [[int(s) - 11, int(e) + 16] for s, e in zip(starts.tolist(), ends.tolist())]
+        return spans, summary_rows(span_score_summary(flat))
+    scores = np.asarray(model.infer(raw_in)).reshape(-1)
+    labels = correct_short(class_from_threshold(scores[:length]))
+    spans = hp_in_pred(labels)
+    p32 = scores.astype(np.float32)
+    flat = span_scores_host(p32, x, off, lengths)
+    runs = [[s + 11, e - 16] for s, e in spans]
+    if [list(r) for r in zip(flat["start"].tolist(), flat["end"].tolist())] != runs:
+        # a probability that rounds across the threshold on its way to float32: the rows describe the spans that are returned
+        flat = scores_of_runs(p32, x, [r[0] for r in runs], [r[1] for r in runs], off, 1)
+    return spans, summary_rows(span_score_summary(flat))
+
+
+def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE, scores=False):
+    """Body of infer_class_from_signal (infer.py:31-51) for an already normalised signal.
+
+    ``scores=True`` returns a third value: a float64 array [n_spans, 6], one row per span in span order, columns n, mean_p,
+    min_p, max_p, level, spread (``span_scores.SCORE_COLUMNS``)."""
     raw = np.asarray(raw)
     padding_size = padding_size_for(len(raw), window_size)
+    length = len(raw)
     raw = np.hstack((raw, np.array(padding_size * [0])))
     raw_in = reshape_input(raw, window_size, 1)
+    if scores:
+        predicted_hps, rows = _scores_of_read(raw_in, model, length)
+        return predicted_hps, length, rows
     scores = model.infer(raw_in)
     scores = scores[:-padding_size]
     labels = correct_short(class_from_threshold(scores))
@@ -179,10 +216,11 @@ def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE):
     return predicted_hps, len(labels)
 
 
-def infer_class_from_signal(fast5_file, model, label=1, window_size=WINDOW_SIZE):
-    """infer.py:12-51.  Returns (list of [start, end] homopolymer spans, length of the read)."""
+def infer_class_from_signal(fast5_file, model, label=1, window_size=WINDOW_SIZE, scores=False):
+    """infer.py:12-51.  Returns (list of [start, end] homopolymer spans, length of the read), and the score rows of
+    ``infer_class_from_raw`` as a third value with ``scores=True``."""
     raw = load_raw(fast5_file)
-    return infer_class_from_raw(raw, model, label=label, window_size=window_size)
+    return infer_class_from_raw(raw, model, label=label, window_size=window_size, scores=scores)
 
 
 def infer_class_from_npz(npz_file, model, label=1, window_size=WINDOW_SIZE):

@@ -16,23 +16,27 @@ import os
 import numpy as np
 
 from . import _native as N
-from .batching import spans_from_runs
+from .batching import scores_from_runs, spans_from_runs
 from .infer import WINDOW_SIZE
 
 
 class _Ticket(object):
     __slots__ = ("lengths", "s_off", "starts", "ends", "counts", "starts_h", "ends_h", "counts_h", "done", "max_runs", "labels",
-                 "keep")
+                 "keep", "rows", "rows_h")
 
 
 class ReadPipeline(object):
-    def __init__(self, engine, max_samples_per_batch, threshold=0.5, min_run=15, depth=2, overlap_kernels=None):
+    def __init__(self, engine, max_samples_per_batch, threshold=0.5, min_run=15, depth=2, overlap_kernels=None, scores=False):
         import torch
         self.torch = torch
         self.eng = engine
         self.dev = torch.device("cuda", engine.device)
         self.threshold = float(threshold)
         self.min_run = int(min_run)
+        # per-call scores (span_scores.py): one more launch per batch (cf_span_scores, right behind cf_postprocess_spans) and 40 B
+        # per run more on the way down; off, nothing is launched, allocated or copied that was not before
+        self.scores = bool(scores)
+        self.out_scores = [None] * max(2, int(depth))           # pinned (ends_paired, sums, extremes) per in-flight slot
         # (All three streams at one priority: raising the forward pass's -- tried in round 5 -- starves the next batch's ingest until
         # the running biGRU launch ends and serialises the two; the CLI's 131 072-window batches lost 8 %,
         # profiles/r05_ab_pipeline_knobs.log.)
@@ -260,6 +264,10 @@ class ReadPipeline(object):
                 float(self.threshold), int(self.min_run), C.c_void_p(labels.data_ptr()) if labels is not None else None, max_runs,
                 C.c_void_p(t.starts.data_ptr()), C.c_void_p(t.ends.data_ptr()), C.c_void_p(t.counts.data_ptr()),
                 C.c_void_p(k_post.cuda_stream)))
+            t.rows = None
+            if self.scores:
+                # x and probs stay resident until the batch is collected (t.keep): the scores cost no transfer upwards
+                t.rows = self.eng.span_scores_device(probs, x.view(-1), d_soff, d_len, t.starts, t.counts, self.threshold, stream=k_post)
             spans_done = torch.cuda.Event()
             spans_done.record(k_post)
         if self.out[slot] is None or self.out[slot][0].numel() < max_runs:
@@ -267,11 +275,21 @@ class ReadPipeline(object):
                               torch.empty(max_runs, dtype=torch.int64, pin_memory=True),
                               torch.empty(2, dtype=torch.int64, pin_memory=True))
         t.starts_h, t.ends_h, t.counts_h = self.out[slot]
+        t.rows_h = None
+        if self.scores:
+            if self.out_scores[slot] is None or self.out_scores[slot][0].numel() < max_runs:
+                self.out_scores[slot] = (torch.empty(max_runs, dtype=torch.int64, pin_memory=True),
+                                         torch.empty(max_runs, 3, dtype=torch.float64, pin_memory=True),
+                                         torch.empty(max_runs, 2, dtype=torch.float32, pin_memory=True))
+            t.rows_h = self.out_scores[slot]
         with torch.cuda.stream(self.down):                       # D2H of the (unsorted) run lists, whole capacity: ~1 MB
             self.down.wait_event(spans_done)
             t.starts_h[:max_runs].copy_(t.starts, non_blocking=True)
             t.ends_h[:max_runs].copy_(t.ends, non_blocking=True)
             t.counts_h.copy_(t.counts, non_blocking=True)
+            if self.scores:
+                for h, d in zip(t.rows_h, t.rows):
+                    h[:max_runs].copy_(d, non_blocking=True)
             t.done = torch.cuda.Event()
             t.done.record(self.down)
         t.lengths, t.s_off, t.max_runs, t.labels = lengths, win_off * WINDOW_SIZE, max_runs, labels
@@ -283,7 +301,11 @@ class ReadPipeline(object):
         """Wait for a batch and assemble [(spans, read length)] in input order.
 
         ``as_lists=False`` skips the per-read Python lists and returns the span table as arrays
-        ``(read_index, start - 11, end + 16, read_lengths)`` (what a high-rate consumer wants)."""
+        ``(read_index, start - 11, end + 16, read_lengths)`` (what a high-rate consumer wants).
+
+        A pipeline built with ``scores=True`` yields ``(spans, read length, scores)`` per read -- ``scores`` a float64 array
+        [n_spans, 6], columns n, mean_p, min_p, max_p, level, spread -- and with ``as_lists=False`` appends the flat summary dict
+        (``span_scores.span_score_summary``, one entry per row of the span table) to the tuple."""
         t.done.synchronize()
         try:
             self.eng.check_error()                               # asynchronous launches of this batch (a device-side error is
@@ -292,17 +314,31 @@ class ReadPipeline(object):
                 raise RuntimeError("cf_spans returned %d starts / %d ends (capacity %d)" % (n_s, n_e, t.max_runs))
             starts = np.sort(t.starts_h[:n_s].numpy())           # np.sort copies out of the pinned slot
             ends = np.sort(t.ends_h[:n_e].numpy())
+            flat = None
+            if t.rows_h is not None:
+                from .span_scores import scores_from_device_rows
+                flat, _order = scores_from_device_rows(t.starts_h[:n_s].numpy(), t.rows_h[0][:n_s].numpy(), t.rows_h[1][:n_s].numpy(),
+                                                       t.rows_h[2][:n_s].numpy(), t.s_off, len(t.lengths))
+                if not np.array_equal(flat["end"], ends):
+                    raise RuntimeError("cf_span_scores: the paired ends differ from the sorted ends of cf_postprocess_spans")
         finally:
             # the slot is free again and the batch's device buffers are released whether or not its results were good: a
             # failed batch must not leave the pipeline claiming "too many batches in flight" on the next submit
             self.inflight[t.keep[-1]] = None
             t.keep = None
-            t.starts = t.ends = t.counts = None
+            t.starts = t.ends = t.counts = t.rows = None
         if not as_lists:
             read_of = np.searchsorted(t.s_off, starts, side="right") - 1
             base = t.s_off[read_of]
-            return read_of, starts - base - 11, ends - base + 16, t.lengths
+            out = (read_of, starts - base - 11, ends - base + 16, t.lengths)
+            if flat is not None:
+                from .span_scores import span_score_summary
+                out = out + (span_score_summary(flat),)
+            return out
         spans = spans_from_runs(starts, ends, t.s_off, len(t.lengths))
+        if flat is not None:
+            rows = scores_from_runs(flat, len(t.lengths))
+            return [(spans[i], int(t.lengths[i]), rows[i]) for i in range(len(t.lengths))]
         return [(spans[i], int(t.lengths[i])) for i in range(len(t.lengths))]
 
     def run(self, batches, as_lists=True):
@@ -319,3 +355,6 @@ class ReadPipeline(object):
                     yield self.collect(pending.popleft(), as_lists)
             while pending:
                 yield self.collect(pending.popleft(), as_lists)
+
+
+StreamingPipeline = ReadPipeline      # the name the documents use for it

@@ -199,6 +199,24 @@ int cf_postprocess_spans(cf_model* m, const float* probs, const int64_t* read_of
                          int64_t total_samples, float threshold, int32_t min_run, uint8_t* labels, int64_t max_runs,
                          int64_t* starts, int64_t* ends, uint64_t* counts, void* stream);
 
+/* Per-call scores of the runs cf_postprocess_spans reports (csrc/span_scores.hpp; span_scores.span_scores_host is the definition).
+ * starts / counts: what that call wrote (device; counts[0] = number of starts, read on the card, so the call stays asynchronous).
+ * For every k < min(counts[0], max_runs), row k describes the run that begins at starts[k] -- the maximal streak of
+ * probs >= threshold (float32 compare, NaN is false) from there inside the real part of its read:
+ *   ends_paired  device int64 [max_runs]      one past the run's last sample
+ *   sums         device double [max_runs][3]  sum of p, of x and of x * x over the run (float32 values widened to double); signal,
+ *                the normalised samples the network saw (device float32 [total_samples]), may be NULL: then columns 1 and 2 are
+ *                not written
+ *   extremes     device float [max_runs][2]   smallest and largest p of the run
+ * Rows at and above min(counts[0], max_runs) are left untouched.  A start that is negative, >= total_samples or outside the real
+ * part of its read gets an empty row (end = start, zero sums, min = +inf, max = -inf) and is never dereferenced: the call is
+ * memory-safe for any contents of starts.  One wave per run, a fixed reduction order: equal inputs give equal bits. */
+int cf_span_scores(cf_model* m, const float* probs, const float* signal /* NULL: no level sums */,
+                   const int64_t* read_offsets, const int64_t* read_lengths, int64_t n_reads, int64_t total_samples,
+                   float threshold, const int64_t* starts, const uint64_t* counts, int64_t max_runs,
+                   int64_t* ends_paired, double* sums /* [max_runs][3]: sum p, sum x, sum x * x */, float* extremes /* [max_runs][2] */,
+                   void* stream);
+
 /* Signal ingest on device, replacing normalize_raw_signal + the padding / reshape of
  * infer_class_from_signal (catfish/infer.py:96-105, 31-43) for many reads at once.
  * dac: device int16, the reads' raw DAC samples back to back (after the leader trim of
