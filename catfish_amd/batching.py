@@ -143,16 +143,28 @@ def scores_from_runs(scores, n_reads):
     return [rows[bounds[r]:bounds[r + 1]] for r in range(n_reads)]
 
 
-def infer_packed(engine, packed, threshold=0.5, min_run=15, return_probs=False):
-    """PackedReads -> list of (spans, read length) per read, optionally with per-read probabilities."""
+def _device_runs(engine, probs, offs, lens, threshold, min_run, max_gap):
+    """Sorted packed run boundaries of the corrected labels; ``max_gap > 0``: gaps bridged first (``infer.bridge_gaps``), in the one
+    launch of ``cf_postprocess_spans_bridged``; 0: the two launches of before."""
+    if max_gap > 0:
+        return engine.postprocess_spans_device(probs, offs, lens, threshold=threshold, min_run=min_run, max_gap=max_gap)
+    labels = engine.postprocess_device(probs, offs, lens, threshold=threshold, min_run=min_run)
+    return engine.spans_device(labels)
+
+
+def infer_packed(engine, packed, threshold=0.5, min_run=15, return_probs=False, max_gap=0):
+    """PackedReads -> list of (spans, read length) per read, optionally with per-read probabilities.  ``max_gap``: gaps of at most
+    that many samples between two called stretches of a read are bridged before ``correct_short`` (0: none; ValueError for
+    ``min_run + max_gap > 64``)."""
     import torch
+    from .infer import check_bridge
+    max_gap = check_bridge(max_gap, min_run)
     dev = torch.device("cuda", engine.device)
     x = torch.from_numpy(packed.x).to(dev, non_blocking=True)
     offs = torch.from_numpy(packed.sample_offsets).to(dev)
     lens = torch.from_numpy(packed.lengths).to(dev)
     probs = engine.infer_device(x)
-    labels = engine.postprocess_device(probs, offs, lens, threshold=threshold, min_run=min_run)
-    starts, ends = engine.spans_device(labels)
+    starts, ends = _device_runs(engine, probs, offs, lens, threshold, min_run, max_gap)
     spans = spans_from_runs(starts, ends, packed.sample_offsets, packed.n_reads)
     result = [(spans[i], int(packed.lengths[i])) for i in range(packed.n_reads)]
     if return_probs:
@@ -162,11 +174,14 @@ def infer_packed(engine, packed, threshold=0.5, min_run=15, return_probs=False):
     return result
 
 
-def infer_reads(model, signals, max_windows=None, threshold=0.5, min_run=15):
-    """Many normalised reads -> [(spans, length)] in input order, length-bucketed packed launches."""
+def infer_reads(model, signals, max_windows=None, threshold=0.5, min_run=15, max_gap=0):
+    """Many normalised reads -> [(spans, length)] in input order, length-bucketed packed launches; ``max_gap`` as in
+    ``infer_packed``."""
+    from .infer import check_bridge
     engine = model.engine if hasattr(model, "engine") else model
     if engine is None:
         raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
+    max_gap = check_bridge(max_gap, min_run)
     signals = [np.asarray(s).reshape(-1) for s in signals]
     if max_windows is None:
         max_windows = 32768
@@ -174,22 +189,24 @@ def infer_reads(model, signals, max_windows=None, threshold=0.5, min_run=15):
     with quiet_gc():
         for bucket in length_buckets([len(s) for s in signals], max_windows):
             packed = pack_reads([signals[i] for i in bucket])
-            for i, res in zip(bucket, infer_packed(engine, packed, threshold, min_run)):
+            for i, res in zip(bucket, infer_packed(engine, packed, threshold, min_run, max_gap=max_gap)):
                 out[i] = res
     return out
 
 
-def infer_reads_dac(model, dac_reads, max_windows=None, threshold=0.5, min_run=15, return_probs=False):
+def infer_reads_dac(model, dac_reads, max_windows=None, threshold=0.5, min_run=15, return_probs=False, max_gap=0):
     """Raw int16 DAC reads (leader already trimmed) -> [(spans, length)] with normalisation ON DEVICE.
 
     Uploads 2 B per sample; median/MAD normalisation, padding and window packing run in
     ``cf_normalize`` (bit-identical to infer.normalize_raw_signal cast to float32), then the
-    forward pass and the device post-processing as in ``infer_packed``.
+    forward pass and the device post-processing as in ``infer_packed`` (``max_gap`` included).
     """
     import torch
+    from .infer import check_bridge
     engine = model.engine if hasattr(model, "engine") else model
     if engine is None:
         raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
+    max_gap = check_bridge(max_gap, min_run)
     dac_reads = [np.ascontiguousarray(np.asarray(r).reshape(-1), dtype=np.int16) for r in dac_reads]
     if max_windows is None:
         max_windows = 32768
@@ -211,9 +228,8 @@ def infer_reads_dac(model, dac_reads, max_windows=None, threshold=0.5, min_run=1
         engine.normalize_device(d_dac, d_doff, d_woff, out=x)
         probs = engine.infer_device(x)
         s_off = win_off * WINDOW_SIZE
-        labels = engine.postprocess_device(probs, torch.from_numpy(s_off).to(dev), torch.from_numpy(lengths).to(dev),
-                                           threshold=threshold, min_run=min_run)
-        starts, ends = engine.spans_device(labels)
+        starts, ends = _device_runs(engine, probs, torch.from_numpy(s_off).to(dev), torch.from_numpy(lengths).to(dev), threshold, min_run,
+                                    max_gap)
         spans = spans_from_runs(starts, ends, s_off, len(bucket))
         p_host = probs.cpu().numpy() if return_probs else None
         for k, i in enumerate(bucket):

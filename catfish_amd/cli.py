@@ -75,7 +75,7 @@ def chunks_of_read(hp_positions, len_read, chunk_size=1000):
 
 
 def run_pipeline(input_dir, split_dir, chunk_size=1000, network_path="ResNetRNN", network_type="ResNetRNN",
-                 checkpoint=30000, device=None, precision="fp32", timings=None, gather_table=False, bind=False):
+                 checkpoint=30000, device=None, precision="fp32", timings=None, gather_table=False, bind=False, bridge_gap=0):
     """Body of the reference's ``main`` (catfish/catfish:23-94), split step included.
 
     Under ``torch.distributed.run`` (RANK / WORLD_SIZE / LOCAL_RANK in the environment) the per-file loop of
@@ -97,10 +97,13 @@ def run_pipeline(input_dir, split_dir, chunk_size=1000, network_path="ResNetRNN"
     (the CPUs the rank is bound to, ``placement.summary``).  ``bind=True``: bind this PROCESS to the CPUs next to the rank's GPU before
     the first GPU call (``catfish_amd/placement.py``; process-wide and permanent, like a ``taskset`` around the job).  The command line
     (``main``) does that; a library caller keeps its affinity unless it asks (the default), and a binding the process took earlier
-    (``placement.bind`` at start-up, as bench.py does) is reported as it is.
+    (``placement.bind`` at start-up, as bench.py does) is reported as it is.  ``bridge_gap`` (the command line reads it from ``CATFISH_BRIDGE_GAP``): gaps of at most that
+    many samples between two called stretches of a read are bridged before ``correct_short`` (``infer.bridge_gaps``); 0, the default,
+    changes nothing, more than 49 is refused (ValueError: ``min_run`` 15 + gap must stay within 64).
     """
     import time
     from . import chunks, placement, sharding, split
+    bridge_gap = infer.check_bridge(bridge_gap, 15)
     rank, world, local_rank = sharding.dist_env()
     # before the first GPU call and the first pinned allocation: this rank, its loader thread and the library's file pool run
     # on the CPUs next to its MI355X (a no-op when the caller -- bench.py -- bound the process already; CATFISH_BIND=0 turns it off)
@@ -157,8 +160,9 @@ def run_pipeline(input_dir, split_dir, chunk_size=1000, network_path="ResNetRNN"
         mine = table = shard_error = None
         try:
             # path strings are built for this rank's block only (sharding.ListingPaths): 100 000 of them on each of 8 ranks was 15 ms
+            runner = sharding.EngineBatchRunner(model, max_windows * infer.WINDOW_SIZE, max_gap=bridge_gap) if bridge_gap else None
             mine, table = sharding.chunk_files_local(model, sharding.ListingPaths(listing), chunk_size,
-                                                     max_samples_per_batch=max_windows * infer.WINDOW_SIZE, rank=rank,
+                                                     max_samples_per_batch=max_windows * infer.WINDOW_SIZE, batch_runner=runner, rank=rank,
                                                      world_size=world, timings=timings, file_sizes=file_sizes)
         except Exception as exc:                          # noqa: BLE001 -- a bad file on one rank fails the whole job, at once
             shard_error = exc
@@ -205,6 +209,16 @@ def run_pipeline(input_dir, split_dir, chunk_size=1000, network_path="ResNetRNN"
             dist.destroy_process_group()
 
 
+def bridge_gap_from_env():
+    """``CATFISH_BRIDGE_GAP=N`` (0 .. 49; unset or empty: 0; the ranks of a multi-GPU job inherit it): the command line's
+    ``bridge_gap``.  Anything but such an integer is a ValueError that names the variable."""
+    text = os.environ.get("CATFISH_BRIDGE_GAP") or "0"
+    try:
+        return infer.check_bridge(int(text), 15)
+    except ValueError as exc:
+        raise ValueError("CATFISH_BRIDGE_GAP must be an integer in 0 .. 49, got %r (%s)" % (text, exc))
+
+
 def _pick_device(local_rank):
     """One process per GPU: rank r of the node drives device r.  ``CATFISH_DEVICE`` pins every rank to one device
     instead (rehearsing the multi-rank path on a box with fewer GPUs than ranks)."""
@@ -249,12 +263,14 @@ def _build_click_main():
         A tool with a neural network as basis to predict the presence of
         homopolymers in the raw signal from a MinION sequencer.
         """
+        bridge_gap_from_env()                       # a bad value ends the job here, before any rank is started
         if gpus > 1 and "WORLD_SIZE" not in os.environ:
             import sys
             argv = ["-i", input_dir, "-s", split_dir, "-c", str(chunk_size), "--network-path", network_path,
                     "--precision", precision]
             sys.exit(launch_ranks(gpus, argv))
-        run_pipeline(input_dir, split_dir, chunk_size, network_path=network_path, precision=precision, bind=True)
+        run_pipeline(input_dir, split_dir, chunk_size, network_path=network_path, precision=precision, bind=True,
+                     bridge_gap=bridge_gap_from_env())
 
     return main
 

@@ -2089,6 +2089,39 @@ extern "C" int cf_postprocess_spans(cf_model* m, const float* probs, const int64
     return prof_end(m, s, pi);
 }
 
+// cf_postprocess_spans with gaps of at most max_gap samples between two stretches of one read bridged before correct_short
+// (csrc/post_bridge_rule.hpp; infer.bridge_gaps is the definition).  max_gap == 0 IS cf_postprocess_spans; any other pair must lie in
+// the bit-mask kernel's domain -- there is no slower route to fall back to.
+extern "C" int cf_postprocess_spans_bridged(cf_model* m, const float* probs, const int64_t* read_offsets, const int64_t* read_lengths,
+                                            int64_t n_reads, int64_t total_samples, float threshold, int32_t max_gap, int32_t min_run,
+                                            uint8_t* labels, int64_t max_runs, int64_t* starts, int64_t* ends, uint64_t* counts,
+                                            void* stream) {
+    if (max_gap == 0)
+        return cf_postprocess_spans(m, probs, read_offsets, read_lengths, n_reads, total_samples, threshold, min_run, labels, max_runs, starts,
+                                    ends, counts, stream);
+    if (!m) return fail(CF_ERR_INVALID, "cf_postprocess_spans_bridged: null model");
+    if (n_reads < 0 || total_samples < 0 || max_runs < 0) return fail(CF_ERR_INVALID, "cf_postprocess_spans_bridged: negative size");
+    if (!counts) return fail(CF_ERR_INVALID, "cf_postprocess_spans_bridged: null counts");
+    if (!pb_domain(min_run, max_gap))
+        return fail(CF_ERR_INVALID, "cf_postprocess_spans_bridged: needs min_run >= 1, max_gap >= 0 and min_run + max_gap <= 64");
+    if ((reinterpret_cast<uintptr_t>(labels) & 15u) != 0) return fail(CF_ERR_INVALID, "cf_postprocess_spans_bridged: labels must be 16-byte aligned");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIP_TRY(hipMemsetAsync(counts, 0, 2 * sizeof(uint64_t), s));
+    if (n_reads == 0 || total_samples == 0) return CF_OK;
+    if (!probs || !read_offsets || !read_lengths || (max_runs > 0 && (!starts || !ends)))
+        return fail(CF_ERR_INVALID, "cf_postprocess_spans_bridged: null buffer");
+    size_t pi = 0;
+    int rc = prof_begin(m, SLOT_POST, s, &pi);
+    if (rc != CF_OK) return rc;
+    const int64_t n_words = (total_samples + 63) / 64, n_chunks = (n_words + CF_POST_WORDS - 1) / CF_POST_WORDS;
+    hipLaunchKernelGGL(postprocess_bridged_kernel<true>, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, s, probs, read_offsets,
+                       read_lengths, n_reads, total_samples, threshold, (int)max_gap, (int)min_run, labels, max_runs, starts, ends,
+                       reinterpret_cast<unsigned long long*>(counts));
+    HIP_TRY(hipGetLastError());
+    return prof_end(m, s, pi);
+}
+
 // Per-call scores (csrc/span_scores.hpp): row k belongs to starts[k]; rows at and above min(counts[0], max_runs) are left untouched.
 extern "C" int cf_span_scores(cf_model* m, const float* probs, const float* signal, const int64_t* read_offsets,
                               const int64_t* read_lengths, int64_t n_reads, int64_t total_samples, float threshold, const int64_t* starts,
@@ -2105,6 +2138,29 @@ extern "C" int cf_span_scores(cf_model* m, const float* probs, const float* sign
     const int64_t blocks = (max_runs + CF_SCORE_WAVES - 1) / CF_SCORE_WAVES;
     hipLaunchKernelGGL(span_scores_kernel, dim3((unsigned)(blocks < CF_SCORE_MAX_BLOCKS ? blocks : CF_SCORE_MAX_BLOCKS)), dim3(64 * CF_SCORE_WAVES),
                        0, s, probs, signal, read_offsets, read_lengths, n_reads, total_samples, threshold, starts,
+                       reinterpret_cast<const unsigned long long*>(counts), max_runs, ends_paired, sums, extremes);
+    HIP_TRY(hipGetLastError());
+    return CF_OK;
+}
+
+// cf_span_scores over runs that are given by LABELS (what cf_postprocess_spans_bridged wrote): a bridged run holds samples below the
+// threshold, and they belong to its sums and extremes.
+extern "C" int cf_span_scores_labels(cf_model* m, const float* probs, const float* signal, const uint8_t* labels, const int64_t* read_offsets,
+                                     const int64_t* read_lengths, int64_t n_reads, int64_t total_samples, const int64_t* starts,
+                                     const uint64_t* counts, int64_t max_runs, int64_t* ends_paired, double* sums, float* extremes,
+                                     void* stream) {
+    if (!m) return fail(CF_ERR_INVALID, "cf_span_scores_labels: null model");
+    if (n_reads < 0 || total_samples < 0 || max_runs < 0) return fail(CF_ERR_INVALID, "cf_span_scores_labels: negative size");
+    if (!counts) return fail(CF_ERR_INVALID, "cf_span_scores_labels: null counts");
+    if (max_runs == 0) return CF_OK;
+    if (!starts || !ends_paired || !sums || !extremes) return fail(CF_ERR_INVALID, "cf_span_scores_labels: null buffer");
+    if (n_reads > 0 && total_samples > 0 && (!probs || !labels || !read_offsets || !read_lengths))
+        return fail(CF_ERR_INVALID, "cf_span_scores_labels: null buffer");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int64_t blocks = (max_runs + CF_SCORE_WAVES - 1) / CF_SCORE_WAVES;
+    hipLaunchKernelGGL(span_scores_labels_kernel, dim3((unsigned)(blocks < CF_SCORE_MAX_BLOCKS ? blocks : CF_SCORE_MAX_BLOCKS)),
+                       dim3(64 * CF_SCORE_WAVES), 0, s, probs, signal, labels, read_offsets, read_lengths, n_reads, total_samples, starts,
                        reinterpret_cast<const unsigned long long*>(counts), max_runs, ends_paired, sums, extremes);
     HIP_TRY(hipGetLastError());
     return CF_OK;

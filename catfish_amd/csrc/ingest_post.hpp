@@ -3,6 +3,8 @@
 //                            packing (infer.py:31-43)
 //   postprocess_bits_kernel  threshold + correct_short (catfish/infer.py:128-138, 174-198): labels[i] = 1 iff probs[i] >= threshold
 //                            and i lies in a positive run of >= min_run samples inside the real part of its read
+//   postprocess_bridged_kernel  the same with gaps of at most max_gap samples between two stretches of a read bridged first
+//                            (infer.bridge_gaps; the bit logic is csrc/post_bridge_rule.hpp)
 // Same results, bit for bit, as normalize_kernel / postprocess_kernel in catfish_hip.hip (which stay: longer reads and unusual
 // min_run values fall back to them, and CATFISH_INGEST_V1=1 behind the debug switch selects them for A/B tests).  Included by
 // catfish_hip.hip after those kernels.
@@ -14,6 +16,7 @@
 // bins eight times per read; postprocess_kernel ran a binary search over the read table and a 14-sample walk to either side for
 // every positive sample.
 #pragma once
+#include "post_bridge_rule.hpp"
 
 // --------------------------------------------------------------------------------------------------------------------------
 // Ingest.  One workgroup of 256 threads per read of up to 256 * E samples, which live in REGISTERS (E per thread) from the first
@@ -175,12 +178,16 @@ __device__ __forceinline__ cf_w192 w192_shl(const cf_w192& x, int s) {     // to
 // the neighbours across the word's edges are the final bits 63 / 0 of the window's outer words, which are exact (see above: what is
 // incomplete there never comes within min_run - 1 bits of the middle word).  A wave reserves room for all its boundaries with one
 // global atomic per list (prefix sums of the lanes' popcounts), like spans_kernel; labels may then be NULL (not written at all).
-template <bool SPANS>
-__global__ __launch_bounds__(256) void postprocess_bits_kernel(const float* __restrict__ probs, const int64_t* __restrict__ read_offsets,
-                                                               const int64_t* __restrict__ read_lengths, int64_t n_reads, int64_t total,
-                                                               float threshold, int min_run, uint8_t* __restrict__ labels, int64_t max_runs,
-                                                               int64_t* __restrict__ starts, int64_t* __restrict__ ends,
-                                                               unsigned long long* __restrict__ counts) {
+//
+// BRIDGE (postprocess_bridged_kernel, cf_postprocess_spans_bridged): step 2 1/2 fills the gaps of at most max_gap samples between two
+// stretches of ones of one read before the erosion (post_bridge_rule.hpp: the rule, and why min_run + max_gap <= 64 keeps the middle
+// word and its two neighbour bits exact).  Everything else is the same code.
+template <bool SPANS, bool BRIDGE>
+__device__ __forceinline__ void postprocess_bits_body(const float* __restrict__ probs, const int64_t* __restrict__ read_offsets,
+                                                      const int64_t* __restrict__ read_lengths, int64_t n_reads, int64_t total,
+                                                      float threshold, int max_gap, int min_run, uint8_t* __restrict__ labels,
+                                                      int64_t max_runs, int64_t* __restrict__ starts, int64_t* __restrict__ ends,
+                                                      unsigned long long* __restrict__ counts) {
     const int lane = threadIdx.x & 63;
     const int64_t chunk = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int64_t n_words = (total + 63) >> 6;
@@ -229,25 +236,39 @@ __global__ __launch_bounds__(256) void postprocess_bits_kernel(const float* __re
     cut.m = ~first;
     cut.p = ~(unsigned long long)__shfl_up((long long)first, 1);
     cut.n = ~(unsigned long long)__shfl_down((long long)first, 1);
-    int have = 1;                                                          // x marks positions where `have` ones of one read begin
-    while (2 * have <= min_run) {
-        const cf_w192 s = w192_shr({x.p & cut.p, x.m & cut.m, x.n & cut.n}, have);
-        x = {x.p & s.p, x.m & s.m, x.n & s.n};
-        have *= 2;
-    }
-    if (have < min_run) {
-        const cf_w192 s = w192_shr(x, min_run - have);
-        x = {x.p & s.p, x.m & s.m, x.n & s.n};
-    }
-    have = 1;                                                              // x marks the first `have` samples of every qualifying run
-    while (2 * have <= min_run) {
-        const cf_w192 s = w192_shl(x, have);
-        x = {x.p | s.p, x.m | s.m, x.n | s.n};
-        have *= 2;
-    }
-    if (have < min_run) {
-        const cf_w192 s = w192_shl(x, min_run - have);
-        x = {x.p | s.p, x.m | s.m, x.n | s.n};
+    if constexpr (BRIDGE) {
+        // 2 1/2. short gaps inside one read become ones (valid of the halo lanes' outer words is 0, like their bits), then the
+        // same opening, both as post_bridge_rule.hpp states them
+        pb_w192 v;
+        v.m = valid;
+        v.p = (unsigned long long)__shfl_up((long long)valid, 1);          // (every lane takes part in a shuffle: no lane-dependent branch around it)
+        v.n = (unsigned long long)__shfl_down((long long)valid, 1);
+        if (lane == 0) v.p = 0;
+        if (lane == 63) v.n = 0;
+        const pb_w192 c = {cut.p, cut.m, cut.n};
+        const pb_w192 f = pb_open(pb_fill({x.p, x.m, x.n}, v, pb_not(c), max_gap), c, min_run);
+        x = {f.p, f.m, f.n};
+    } else {
+        int have = 1;                                                          // x marks positions where `have` ones of one read begin
+        while (2 * have <= min_run) {
+            const cf_w192 s = w192_shr({x.p & cut.p, x.m & cut.m, x.n & cut.n}, have);
+            x = {x.p & s.p, x.m & s.m, x.n & s.n};
+            have *= 2;
+        }
+        if (have < min_run) {
+            const cf_w192 s = w192_shr(x, min_run - have);
+            x = {x.p & s.p, x.m & s.m, x.n & s.n};
+        }
+        have = 1;                                                              // x marks the first `have` samples of every qualifying run
+        while (2 * have <= min_run) {
+            const cf_w192 s = w192_shl(x, have);
+            x = {x.p | s.p, x.m | s.m, x.n | s.n};
+            have *= 2;
+        }
+        if (have < min_run) {
+            const cf_w192 s = w192_shl(x, min_run - have);
+            x = {x.p | s.p, x.m | s.m, x.n | s.n};
+        }
     }
     const bool payload = lane != 0 && lane != 63 && base < total;
     if constexpr (SPANS) {
@@ -305,4 +326,25 @@ __global__ __launch_bounds__(256) void postprocess_bits_kernel(const float* __re
     } else {
         for (int b = 0; base + b < total; ++b) labels[base + b] = (uint8_t)((bits >> b) & 1ull);
     }
+}
+
+template <bool SPANS>
+__global__ __launch_bounds__(256) void postprocess_bits_kernel(const float* __restrict__ probs, const int64_t* __restrict__ read_offsets,
+                                                               const int64_t* __restrict__ read_lengths, int64_t n_reads, int64_t total,
+                                                               float threshold, int min_run, uint8_t* __restrict__ labels, int64_t max_runs,
+                                                               int64_t* __restrict__ starts, int64_t* __restrict__ ends,
+                                                               unsigned long long* __restrict__ counts) {
+    postprocess_bits_body<SPANS, false>(probs, read_offsets, read_lengths, n_reads, total, threshold, 0, min_run, labels, max_runs, starts,
+                                        ends, counts);
+}
+
+// ... with gaps of up to max_gap samples bridged first: 1 <= max_gap, min_run + max_gap <= 64 (the host checks)
+template <bool SPANS>
+__global__ __launch_bounds__(256) void postprocess_bridged_kernel(const float* __restrict__ probs, const int64_t* __restrict__ read_offsets,
+                                                                  const int64_t* __restrict__ read_lengths, int64_t n_reads, int64_t total,
+                                                                  float threshold, int max_gap, int min_run, uint8_t* __restrict__ labels,
+                                                                  int64_t max_runs, int64_t* __restrict__ starts, int64_t* __restrict__ ends,
+                                                                  unsigned long long* __restrict__ counts) {
+    postprocess_bits_body<SPANS, true>(probs, read_offsets, read_lengths, n_reads, total, threshold, max_gap, min_run, labels, max_runs,
+                                       starts, ends, counts);
 }

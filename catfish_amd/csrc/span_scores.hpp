@@ -18,11 +18,14 @@
 #define CF_SCORE_WAVES 4           // waves (runs in flight) per workgroup
 #define CF_SCORE_MAX_BLOCKS 2048   // grid-stride beyond: 8192 runs in flight fill the chip's wave slots
 
-__global__ __launch_bounds__(64 * CF_SCORE_WAVES) void span_scores_kernel(
-    const float* __restrict__ probs, const float* __restrict__ signal, const int64_t* __restrict__ read_offsets,
-    const int64_t* __restrict__ read_lengths, int64_t n_reads, int64_t total, float threshold, const int64_t* __restrict__ starts,
-    const unsigned long long* __restrict__ counts, int64_t max_runs, int64_t* __restrict__ ends_paired, double* __restrict__ sums,
-    float* __restrict__ extremes) {
+// LABELS (span_scores_labels_kernel, cf_span_scores_labels): "the run continues" is labels[i] != 0 instead of p >= threshold -- a run
+// that cf_postprocess_spans_bridged reports holds samples below the threshold, and they count.  Everything else is the same code.
+template <bool LABELS>
+__device__ __forceinline__ void span_scores_body(
+    const float* __restrict__ probs, const float* __restrict__ signal, const uint8_t* __restrict__ labels,
+    const int64_t* __restrict__ read_offsets, const int64_t* __restrict__ read_lengths, int64_t n_reads, int64_t total, float threshold,
+    const int64_t* __restrict__ starts, const unsigned long long* __restrict__ counts, int64_t max_runs, int64_t* __restrict__ ends_paired,
+    double* __restrict__ sums, float* __restrict__ extremes) {
     const int lane = threadIdx.x & 63;
     const int64_t n_rows = ss_rows((uint64_t)counts[0], max_runs);
     const int64_t n_waves = (int64_t)gridDim.x * CF_SCORE_WAVES;
@@ -39,7 +42,9 @@ __global__ __launch_bounds__(64 * CF_SCORE_WAVES) void span_scores_kernel(
             const int64_t i = pos + lane;                                   // in: start <= i < w.end <= total
             const float p = in ? probs[i] : 0.f;
             const float x = (in && signal != nullptr) ? signal[i] : 0.f;
-            const ss_taken t = ss_step(__ballot(in && p >= threshold), left);
+            bool hit = in && p >= threshold;
+            if constexpr (LABELS) hit = in && labels[i] != 0;
+            const ss_taken t = ss_step(__ballot(hit), left);
             if (lane < t.take) {
                 sp += (double)p;
                 sx += (double)x;
@@ -69,4 +74,22 @@ __global__ __launch_bounds__(64 * CF_SCORE_WAVES) void span_scores_kernel(
             extremes[ss_extreme_index(k, 1)] = hi;
         }
     }
+}
+
+__global__ __launch_bounds__(64 * CF_SCORE_WAVES) void span_scores_kernel(
+    const float* __restrict__ probs, const float* __restrict__ signal, const int64_t* __restrict__ read_offsets,
+    const int64_t* __restrict__ read_lengths, int64_t n_reads, int64_t total, float threshold, const int64_t* __restrict__ starts,
+    const unsigned long long* __restrict__ counts, int64_t max_runs, int64_t* __restrict__ ends_paired, double* __restrict__ sums,
+    float* __restrict__ extremes) {
+    span_scores_body<false>(probs, signal, nullptr, read_offsets, read_lengths, n_reads, total, threshold, starts, counts, max_runs,
+                            ends_paired, sums, extremes);
+}
+
+__global__ __launch_bounds__(64 * CF_SCORE_WAVES) void span_scores_labels_kernel(
+    const float* __restrict__ probs, const float* __restrict__ signal, const uint8_t* __restrict__ labels,
+    const int64_t* __restrict__ read_offsets, const int64_t* __restrict__ read_lengths, int64_t n_reads, int64_t total,
+    const int64_t* __restrict__ starts, const unsigned long long* __restrict__ counts, int64_t max_runs, int64_t* __restrict__ ends_paired,
+    double* __restrict__ sums, float* __restrict__ extremes) {
+    span_scores_body<true>(probs, signal, labels, read_offsets, read_lengths, n_reads, total, 0.f, starts, counts, max_runs, ends_paired,
+                           sums, extremes);
 }

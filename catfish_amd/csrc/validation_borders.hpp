@@ -126,30 +126,49 @@ extern "C" int64_t cf_validation_run_borders_work_bytes(int64_t total, int32_t n
     return cf_validation_run_work_bytes(total, n_thresholds);
 }
 
-extern "C" int cf_validation_run_borders(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length,
-                                         int64_t n, int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds,
-                                         int32_t reach, int32_t min_run, int64_t* counts_out, void* work, int64_t work_bytes, void* stream) {
+static int validation_run_borders_impl(const std::string& fn, cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds,
+                                       const int64_t* length, int64_t n, int64_t total, int64_t longest, const double* thresholds,
+                                       int32_t n_thresholds, int32_t reach, int32_t max_gap, int32_t min_run, int64_t* counts_out, void* work,
+                                       int64_t work_bytes, void* stream) {
     if (!probs || !y || !bounds || !length || !thresholds || !counts_out || !work)
-        return fail(CF_ERR_INVALID, "cf_validation_run_borders: null argument");
-    if (n <= 0 || n > 0x7fffffff) return fail(CF_ERR_INVALID, "cf_validation_run_borders: n must be in [1, 2^31)");
+        return fail(CF_ERR_INVALID, fn + ": null argument");
+    if (n <= 0 || n > 0x7fffffff) return fail(CF_ERR_INVALID, fn + ": n must be in [1, 2^31)");
     if (n_thresholds < 1 || n_thresholds > CF_SCORE_MAX_K)
-        return fail(CF_ERR_INVALID, "cf_validation_run_borders: between 1 and " + std::to_string(CF_SCORE_MAX_K) + " thresholds per call");
-    if (total < 0 || total > 0x7fffffff || longest < 0 || longest > total) return fail(CF_ERR_INVALID, "cf_validation_run_borders: bad size");
+        return fail(CF_ERR_INVALID, fn + ": between 1 and " + std::to_string(CF_SCORE_MAX_K) + " thresholds per call");
+    if (total < 0 || total > 0x7fffffff || longest < 0 || longest > total) return fail(CF_ERR_INVALID, fn + ": bad size");
     if (reach < 1 || reach > VB_MAX_REACH)
-        return fail(CF_ERR_INVALID, "cf_validation_run_borders: reach must be in 1 .. " + std::to_string(VB_MAX_REACH));
-    if (min_run < 1) return fail(CF_ERR_INVALID, "cf_validation_run_borders: min_run must be >= 1");
+        return fail(CF_ERR_INVALID, fn + ": reach must be in 1 .. " + std::to_string(VB_MAX_REACH));
+    if (min_run < 1) return fail(CF_ERR_INVALID, fn + ": min_run must be >= 1");
+    if (!validation_bridge_ok(min_run, max_gap, work))
+        return fail(CF_ERR_INVALID, fn + ": bridging needs max_gap >= 0, min_run + max_gap <= 64 and a 16-byte aligned work buffer");
     const int64_t stride = (total + 63) / 64 * 64;
     if (work_bytes < cf_validation_run_borders_work_bytes(total, n_thresholds))
-        return fail(CF_ERR_INVALID, "cf_validation_run_borders: work needs cf_validation_run_borders_work_bytes(total, n_thresholds) bytes");
+        return fail(CF_ERR_INVALID, fn + ": work needs cf_validation_run_borders_work_bytes(total, n_thresholds) bytes");
     if (m) HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_thresholds * 2 * vb_cells(reach) * sizeof(int64_t), s));
     if (total == 0) return CF_OK;                              // stretches without a sample: the zeroed table
     uint8_t* lab = static_cast<uint8_t*>(work);
-    if (const int rc = validation_label_passes(probs, bounds, length, n, total, thresholds, n_thresholds, min_run, lab, stride, s)) return rc;
+    if (const int rc = validation_label_passes(probs, bounds, length, n, total, thresholds, n_thresholds, max_gap, min_run, lab, stride, s)) return rc;
     hipLaunchKernelGGL(validation_run_borders_kernel, dim3((unsigned)std::min<int64_t>(n, 1 << 20), (unsigned)n_thresholds), dim3(CF_RUN_THREADS),
                        0, s, lab, stride, y, bounds, length, n, total, (int)n_thresholds, (int)reach,
                        reinterpret_cast<unsigned long long*>(counts_out));
     HIP_TRY(hipGetLastError());
     return CF_OK;
+}
+
+extern "C" int cf_validation_run_borders(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length,
+                                         int64_t n, int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds,
+                                         int32_t reach, int32_t min_run, int64_t* counts_out, void* work, int64_t work_bytes, void* stream) {
+    return validation_run_borders_impl("cf_validation_run_borders", m, probs, y, bounds, length, n, total, longest, thresholds, n_thresholds,
+                                       reach, 0, min_run, counts_out, work, work_bytes, stream);
+}
+
+// ... with gaps of at most max_gap samples bridged in every stretch before correct_short (device_validation.run_borders_host(max_gap=))
+extern "C" int cf_validation_run_borders_bridged(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds,
+                                                 const int64_t* length, int64_t n, int64_t total, int64_t longest, const double* thresholds,
+                                                 int32_t n_thresholds, int32_t reach, int32_t max_gap, int32_t min_run, int64_t* counts_out,
+                                                 void* work, int64_t work_bytes, void* stream) {
+    return validation_run_borders_impl("cf_validation_run_borders_bridged", m, probs, y, bounds, length, n, total, longest, thresholds,
+                                       n_thresholds, reach, max_gap, min_run, counts_out, work, work_bytes, stream);
 }

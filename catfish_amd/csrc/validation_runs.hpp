@@ -203,18 +203,30 @@ extern "C" int64_t cf_validation_run_work_bytes(int64_t total, int32_t n_thresho
     return (int64_t)n_thresholds * ((total + 63) / 64 * 64);
 }
 
+// what a bridged label pass needs: the bit-mask kernel's domain and a work buffer it can store 16 bytes at a time into
+static bool validation_bridge_ok(int32_t min_run, int32_t max_gap, const void* work) {
+    return max_gap == 0 || (pb_domain(min_run, max_gap) && (reinterpret_cast<uintptr_t>(work) & 15u) == 0);
+}
+
 // The corrected labels of the whole packed batch, one array per threshold at lab + k * stride (threshold + correct_short inside every
 // stretch): what cf_validation_run_states and cf_validation_run_borders count on.
+// max_gap > 0: gaps of at most max_gap samples inside a stretch are bridged first (postprocess_bridged_kernel; the callers have checked
+// validation_bridge_ok).
 static int validation_label_passes(const float* probs, const int64_t* bounds, const int64_t* length, int64_t n, int64_t total,
-                                   const double* thresholds, int32_t n_thresholds, int32_t min_run, uint8_t* lab, int64_t stride,
-                                   hipStream_t s) {
+                                   const double* thresholds, int32_t n_thresholds, int32_t max_gap, int32_t min_run, uint8_t* lab,
+                                   int64_t stride, hipStream_t s) {
     // the bit-mask kernel covers runs of up to 64 samples and stores labels 16 bytes at a time (cf_postprocess's rule)
     const bool bits = min_run <= 64 && (reinterpret_cast<uintptr_t>(lab) & 15u) == 0;
     for (int k = 0; k < n_thresholds; ++k) {
         // (double)p >= t  <=>  p >= tf with tf the smallest float not below t
         float tf = (float)thresholds[k];
         if ((double)tf < thresholds[k]) tf = std::nextafterf(tf, INFINITY);
-        if (bits) {
+        if (max_gap > 0) {
+            const int64_t n_words = (total + 63) / 64, n_chunks = (n_words + CF_POST_WORDS - 1) / CF_POST_WORDS;
+            hipLaunchKernelGGL(postprocess_bridged_kernel<false>, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, s, probs, bounds, length,
+                               n, total, tf, (int)max_gap, (int)min_run, lab + k * stride, (int64_t)0, (int64_t*)nullptr, (int64_t*)nullptr,
+                               (unsigned long long*)nullptr);
+        } else if (bits) {
             const int64_t n_words = (total + 63) / 64, n_chunks = (n_words + CF_POST_WORDS - 1) / CF_POST_WORDS;
             hipLaunchKernelGGL(postprocess_bits_kernel<false>, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, s, probs, bounds, length, n,
                                total, tf, (int)min_run, lab + k * stride, (int64_t)0, (int64_t*)nullptr, (int64_t*)nullptr,
@@ -228,39 +240,58 @@ static int validation_label_passes(const float* probs, const int64_t* bounds, co
     return CF_OK;
 }
 
-extern "C" int cf_validation_run_states(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length,
-                                        int64_t n, int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds,
-                                        const int64_t* edges, int32_t n_edges, int32_t min_run, int64_t* counts_out, void* work,
-                                        int64_t work_bytes, void* stream) {
+static int validation_run_states_impl(const std::string& fn, cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds,
+                                      const int64_t* length, int64_t n, int64_t total, int64_t longest, const double* thresholds,
+                                      int32_t n_thresholds, const int64_t* edges, int32_t n_edges, int32_t max_gap, int32_t min_run,
+                                      int64_t* counts_out, void* work, int64_t work_bytes, void* stream) {
     if (!probs || !y || !bounds || !length || !thresholds || !counts_out || !work || (n_edges > 0 && !edges))
-        return fail(CF_ERR_INVALID, "cf_validation_run_states: null argument");
-    if (n <= 0 || n > 0x7fffffff) return fail(CF_ERR_INVALID, "cf_validation_run_states: n must be in [1, 2^31)");
+        return fail(CF_ERR_INVALID, fn + ": null argument");
+    if (n <= 0 || n > 0x7fffffff) return fail(CF_ERR_INVALID, fn + ": n must be in [1, 2^31)");
     if (n_thresholds < 1 || n_thresholds > CF_SCORE_MAX_K)
-        return fail(CF_ERR_INVALID, "cf_validation_run_states: between 1 and " + std::to_string(CF_SCORE_MAX_K) + " thresholds per call");
-    if (total < 0 || total > 0x7fffffff || longest < 0 || longest > total) return fail(CF_ERR_INVALID, "cf_validation_run_states: bad size");
+        return fail(CF_ERR_INVALID, fn + ": between 1 and " + std::to_string(CF_SCORE_MAX_K) + " thresholds per call");
+    if (total < 0 || total > 0x7fffffff || longest < 0 || longest > total) return fail(CF_ERR_INVALID, fn + ": bad size");
     if (n_edges < 0 || n_edges > CF_RUN_MAX_EDGES)
-        return fail(CF_ERR_INVALID, "cf_validation_run_states: at most " + std::to_string(CF_RUN_MAX_EDGES) + " edges");
+        return fail(CF_ERR_INVALID, fn + ": at most " + std::to_string(CF_RUN_MAX_EDGES) + " edges");
     cf_run_edges e;
     for (int j = 0; j < CF_RUN_MAX_EDGES; ++j) e.e[j] = 0xffffffffu;
     for (int j = 0; j < n_edges; ++j) {
         if (edges[j] < 1 || (j > 0 && edges[j] <= edges[j - 1]))
-            return fail(CF_ERR_INVALID, "cf_validation_run_states: edges must be positive and ascending");
+            return fail(CF_ERR_INVALID, fn + ": edges must be positive and ascending");
         e.e[j] = (unsigned)std::min<int64_t>(edges[j], 0xffffffffll);
     }
-    if (min_run < 1) return fail(CF_ERR_INVALID, "cf_validation_run_states: min_run must be >= 1");
+    if (min_run < 1) return fail(CF_ERR_INVALID, fn + ": min_run must be >= 1");
+    if (!validation_bridge_ok(min_run, max_gap, work))
+        return fail(CF_ERR_INVALID, fn + ": bridging needs max_gap >= 0, min_run + max_gap <= 64 and a 16-byte aligned work buffer");
     const int64_t stride = (total + 63) / 64 * 64;
     if (work_bytes < cf_validation_run_work_bytes(total, n_thresholds))
-        return fail(CF_ERR_INVALID, "cf_validation_run_states: work needs cf_validation_run_work_bytes(total, n_thresholds) bytes");
+        return fail(CF_ERR_INVALID, fn + ": work needs cf_validation_run_work_bytes(total, n_thresholds) bytes");
     if (m) HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int n_bins = n_edges + 1;
     HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_thresholds * 2 * n_bins * 3 * sizeof(int64_t), s));
     if (total == 0) return CF_OK;                              // stretches without a sample: the zeroed table
     uint8_t* lab = static_cast<uint8_t*>(work);
-    if (const int rc = validation_label_passes(probs, bounds, length, n, total, thresholds, n_thresholds, min_run, lab, stride, s)) return rc;
+    if (const int rc = validation_label_passes(probs, bounds, length, n, total, thresholds, n_thresholds, max_gap, min_run, lab, stride, s)) return rc;
     hipLaunchKernelGGL(validation_run_states_kernel, dim3((unsigned)std::min<int64_t>(n, 1 << 20), (unsigned)n_thresholds), dim3(CF_RUN_THREADS),
                        0, s, lab, stride, y, bounds, length, n, total, (int)n_thresholds, e, n_bins,
                        reinterpret_cast<unsigned long long*>(counts_out));
     HIP_TRY(hipGetLastError());
     return CF_OK;
+}
+
+extern "C" int cf_validation_run_states(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length,
+                                        int64_t n, int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds,
+                                        const int64_t* edges, int32_t n_edges, int32_t min_run, int64_t* counts_out, void* work,
+                                        int64_t work_bytes, void* stream) {
+    return validation_run_states_impl("cf_validation_run_states", m, probs, y, bounds, length, n, total, longest, thresholds, n_thresholds,
+                                      edges, n_edges, 0, min_run, counts_out, work, work_bytes, stream);
+}
+
+// ... with gaps of at most max_gap samples bridged in every stretch before correct_short (device_validation.run_states_host(max_gap=))
+extern "C" int cf_validation_run_states_bridged(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds,
+                                                const int64_t* length, int64_t n, int64_t total, int64_t longest, const double* thresholds,
+                                                int32_t n_thresholds, const int64_t* edges, int32_t n_edges, int32_t max_gap,
+                                                int32_t min_run, int64_t* counts_out, void* work, int64_t work_bytes, void* stream) {
+    return validation_run_states_impl("cf_validation_run_states_bridged", m, probs, y, bounds, length, n, total, longest, thresholds,
+                                      n_thresholds, edges, n_edges, max_gap, min_run, counts_out, work, work_bytes, stream);
 }

@@ -117,7 +117,7 @@ def _states_of(starts, ends, other):
     return np.where(ones[ends + 1] - ones[starts] == size, 0, np.where(zeros[ends + 1] - zeros[starts] == size, 2, 1))
 
 
-def run_states_host(probs, y, bounds, lengths, thresholds, edges=(), min_run=15):
+def run_states_host(probs, y, bounds, lengths, thresholds, edges=(), min_run=15, max_gap=0):
     """What ``cf_validation_run_states`` returns, in numpy: int64 [K, 2, B, 3] -- per threshold, kind, length bin and state how
     many runs (the reference's offline networks/process_output.py:235-273).
 
@@ -127,11 +127,15 @@ def run_states_host(probs, y, bounds, lengths, thresholds, edges=(), min_run=15)
     judged against).  Kind 0: the runs of ``y == 1`` judged against the prediction; kind 1: the runs of the prediction judged
     against ``y``.  State (``check_hp``) 0 = complete, the other array is 1 over the whole run; 2 = absent, it is 0 over the whole
     run; 1 = incomplete, anything else (so a label other than 0 / 1 inside a run makes it incomplete).  A run of L samples falls
-    into bin ``searchsorted(edges, L, side="right")``; B = len(edges) + 1."""
-    from .infer import correct_short
+    into bin ``searchsorted(edges, L, side="right")``; B = len(edges) + 1.
+
+    ``max_gap > 0`` (``cf_validation_run_states_bridged``): the prediction is ``correct_short(infer.bridge_gaps((double)p >= t,
+    max_gap), min_run)`` over the stretch alone; ValueError for ``min_run + max_gap > 64``."""
+    from .infer import bridge_gaps, check_bridge, correct_short
     edges = np.asarray(check_run_edges(edges), dtype=np.int64)
     if int(min_run) < 1:
         raise ValueError("min_run must be >= 1")
+    max_gap = check_bridge(max_gap, min_run)
     p = np.asarray(probs, dtype=np.float64).reshape(-1)
     y = np.asarray(y).reshape(-1)
     bounds = np.asarray(bounds, dtype=np.int64)
@@ -142,7 +146,7 @@ def run_states_host(probs, y, bounds, lengths, thresholds, edges=(), min_run=15)
             continue
         truth = y[b0:b0 + n]
         for k, t in enumerate(thresholds):
-            pred = np.asarray(correct_short((p[b0:b0 + n] >= float(t)).astype(np.int64), int(min_run)))
+            pred = np.asarray(correct_short(bridge_gaps((p[b0:b0 + n] >= float(t)).astype(np.int64), max_gap), int(min_run)))
             for kind, (mask, other) in enumerate(((truth == 1, pred), (pred == 1, truth))):
                 starts, ends = _runs_of(mask)
                 bins = np.searchsorted(edges, ends - starts + 1, side="right")
@@ -207,7 +211,7 @@ def _borders_of(mask, other, reach, row):
     row[5 * reach + 2] += np.unique(run[inside]).size
 
 
-def run_borders_host(probs, y, bounds, lengths, thresholds, reach=BORDER_REACH, min_run=15):
+def run_borders_host(probs, y, bounds, lengths, thresholds, reach=BORDER_REACH, min_run=15, max_gap=0):
     """What ``cf_validation_run_borders`` returns, in numpy: int64 [K, 2, 5 * reach + 3] -- the rest of what the reference's
     ``check_hp`` says about a run (networks/process_output.py:814-895): how far the other array's ones reach beyond its borders
     or fall short of them, and the interruptions inside it.
@@ -219,11 +223,14 @@ def run_borders_host(probs, y, bounds, lengths, thresholds, reach=BORDER_REACH, 
     ``o[e] == 1``, else minus the zeros of ``o`` from e down to its last one; interruptions = the maximal runs of zeros of ``o``
     inside [s, e] that touch neither end.  ``l < 0`` / ``r > 0``: the other array's ones reach beyond the run; ``l > 0`` /
     ``r < 0``: they start late / stop early.  Cells of a row, R = reach: [0, 2R+1) histogram of ``clip(l, -R, R) + R``; [2R+1, 4R+2)
-    of ``clip(r, -R, R) + R``; [4R+2, 5R+2) of ``min(g, R) - 1`` over the interruption lengths g; [5R+2] runs with an interruption."""
-    from .infer import correct_short
+    of ``clip(r, -R, R) + R``; [4R+2, 5R+2) of ``min(g, R) - 1`` over the interruption lengths g; [5R+2] runs with an interruption.
+
+    ``max_gap > 0`` (``cf_validation_run_borders_bridged``): the bridged prediction of ``run_states_host``."""
+    from .infer import bridge_gaps, check_bridge, correct_short
     reach = check_border_reach(reach)
     if int(min_run) < 1:
         raise ValueError("min_run must be >= 1")
+    max_gap = check_bridge(max_gap, min_run)
     p = np.asarray(probs, dtype=np.float64).reshape(-1)
     y = np.asarray(y).reshape(-1)
     bounds = np.asarray(bounds, dtype=np.int64)
@@ -237,7 +244,7 @@ def run_borders_host(probs, y, bounds, lengths, thresholds, reach=BORDER_REACH, 
             raise ValueError("run borders need labels of 0 or 1, got %r" % (truth[(truth != 0) & (truth != 1)][0],))
         truth = truth == 1
         for k, t in enumerate(thresholds):
-            pred = np.asarray(correct_short((p[b0:b0 + n] >= float(t)).astype(np.int64), int(min_run))) == 1
+            pred = np.asarray(correct_short(bridge_gaps((p[b0:b0 + n] >= float(t)).astype(np.int64), max_gap), int(min_run))) == 1
             _borders_of(truth, pred, reach, out[k, 0])
             _borders_of(pred, truth, reach, out[k, 1])
     return out

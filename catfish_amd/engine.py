@@ -187,14 +187,20 @@ class HipEngine(object):
         return out
 
     def postprocess_spans_device(self, probs, read_offsets, read_lengths, threshold=0.5, min_run=15, max_runs=None, labels=False,
-                                 stream=None, scores=False, signal=None):
+                                 stream=None, scores=False, signal=None, max_gap=0):
         """``postprocess_device`` + ``spans_device`` as ONE launch (``cf_postprocess_spans``) -> (starts, ends) numpy int64, sorted
         ascending (packed positions; ends exclusive), and the uint8 CUDA labels as a third value when ``labels=True``.
 
         ``scores=True`` appends the per-run score dict of ``span_scores.span_scores_host`` (``cf_span_scores`` on the same stream, its
         rows carried through the argsort of the starts; ``signal``: the float32 CUDA samples the network saw, None: ``sum_x`` and
-        ``sum_x2`` are NaN)."""
+        ``sum_x2`` are NaN).
+
+        ``max_gap > 0`` bridges gaps of at most that many samples first (``cf_postprocess_spans_bridged``; ``infer.bridge_gaps`` is
+        the definition); the score rows then come from ``cf_span_scores_labels`` over the labels of the same launch, so that they
+        cover the samples of the bridged gaps.  A pair with ``min_run + max_gap > 64`` raises ValueError."""
         import torch
+        from .infer import check_bridge
+        max_gap = check_bridge(max_gap, min_run)
         if not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
             raise ValueError("probs must be a contiguous float32 CUDA tensor")
         for t in (read_offsets, read_lengths):
@@ -206,24 +212,35 @@ class HipEngine(object):
         if max_runs is None:
             max_runs = total // max(1, int(min_run)) + 16
         dev = probs.device
-        lab = torch.empty(total, dtype=torch.uint8, device=dev) if labels else None      # NULL: the library never writes labels
+        by_labels = scores and max_gap > 0                                                # the score walk follows the labels
+        lab = torch.empty(total, dtype=torch.uint8, device=dev) if labels or by_labels else None      # NULL: the library never writes labels
         starts = torch.empty(max_runs, dtype=torch.int64, device=dev)
         ends = torch.empty(max_runs, dtype=torch.int64, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
         if stream is None:
             stream = torch.cuda.current_stream(dev)
-        N.check(self._lib.cf_postprocess_spans(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(read_offsets.data_ptr()),
-                                               C.c_void_p(read_lengths.data_ptr()), n_reads, total, float(threshold), int(min_run),
-                                               C.c_void_p(lab.data_ptr()) if lab is not None else None, int(max_runs),
-                                               C.c_void_p(starts.data_ptr()), C.c_void_p(ends.data_ptr()), C.c_void_p(counts.data_ptr()),
-                                               C.c_void_p(stream.cuda_stream)))
-        rows = self.span_scores_device(probs, signal, read_offsets, read_lengths, starts, counts, threshold, stream) if scores else None
+        if max_gap > 0:
+            N.check(self._lib.cf_postprocess_spans_bridged(
+                self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(read_offsets.data_ptr()), C.c_void_p(read_lengths.data_ptr()), n_reads,
+                total, float(threshold), max_gap, int(min_run), C.c_void_p(lab.data_ptr()) if lab is not None else None, int(max_runs),
+                C.c_void_p(starts.data_ptr()), C.c_void_p(ends.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(stream.cuda_stream)))
+        else:
+            N.check(self._lib.cf_postprocess_spans(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(read_offsets.data_ptr()),
+                                                   C.c_void_p(read_lengths.data_ptr()), n_reads, total, float(threshold), int(min_run),
+                                                   C.c_void_p(lab.data_ptr()) if lab is not None else None, int(max_runs),
+                                                   C.c_void_p(starts.data_ptr()), C.c_void_p(ends.data_ptr()), C.c_void_p(counts.data_ptr()),
+                                                   C.c_void_p(stream.cuda_stream)))
+        rows = None
+        if scores:
+            rows = self.span_scores_device(probs, signal, read_offsets, read_lengths, starts, counts, threshold, stream,
+                                           labels=lab if by_labels else None)
         n_s, n_e = (int(v) for v in counts.cpu().tolist())      # synchronises the stream
         self.check_error()
         if n_s != n_e:
             raise RuntimeError("cf_postprocess_spans: %d run starts but %d run ends" % (n_s, n_e))
         if n_s > max_runs:
-            return self.postprocess_spans_device(probs, read_offsets, read_lengths, threshold, min_run, n_s, labels, stream, scores, signal)
+            return self.postprocess_spans_device(probs, read_offsets, read_lengths, threshold, min_run, n_s, labels, stream, scores, signal,
+                                                 max_gap)
         out = (np.sort(starts[:n_s].cpu().numpy()), np.sort(ends[:n_e].cpu().numpy()))
         if labels:
             out = out + (lab,)
@@ -236,11 +253,14 @@ class HipEngine(object):
             out = out + (flat,)
         return out
 
-    def span_scores_device(self, probs, signal, read_offsets, read_lengths, starts, counts, threshold=0.5, stream=None, out=None):
+    def span_scores_device(self, probs, signal, read_offsets, read_lengths, starts, counts, threshold=0.5, stream=None, out=None,
+                           labels=None):
         """``cf_span_scores``: for every run k < min(counts[0], len(starts)) of the start list ``cf_postprocess_spans`` wrote ->
         CUDA tensors (ends_paired int64 [max_runs], sums float64 [max_runs, 3] = sum p, sum x, sum x * x, extremes float32
         [max_runs, 2] = min p, max p); rows at and above the count are left as they were (``out``: the three tensors to write into).
-        ``signal`` None: columns 1 and 2 of sums are not written.  Asynchronous on the stream: the count is read on the card."""
+        ``signal`` None: columns 1 and 2 of sums are not written.  Asynchronous on the stream: the count is read on the card.
+        ``labels`` (uint8 CUDA [total], what ``cf_postprocess_spans_bridged`` wrote): a run lasts while its labels are non-zero
+        instead of while ``p >= threshold`` (``cf_span_scores_labels``) -- bridged runs hold samples below the threshold."""
         import torch
         if not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
             raise ValueError("probs must be a contiguous float32 CUDA tensor")
@@ -267,6 +287,15 @@ class HipEngine(object):
             raise ValueError("out must be contiguous CUDA tensors int64 [max_runs], float64 [max_runs, 3], float32 [max_runs, 2]")
         if stream is None:
             stream = torch.cuda.current_stream(dev)
+        if labels is not None:
+            if labels.dtype != torch.uint8 or not labels.is_cuda or not labels.is_contiguous() or int(labels.numel()) != total:
+                raise ValueError("labels must be a contiguous uint8 CUDA tensor with as many samples as probs")
+            N.check(self._lib.cf_span_scores_labels(
+                self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(signal.data_ptr()) if signal is not None else None,
+                C.c_void_p(labels.data_ptr()), C.c_void_p(read_offsets.data_ptr()), C.c_void_p(read_lengths.data_ptr()), n_reads, total,
+                C.c_void_p(starts.data_ptr()), C.c_void_p(counts.data_ptr()), max_runs, C.c_void_p(ends_paired.data_ptr()),
+                C.c_void_p(sums.data_ptr()), C.c_void_p(extremes.data_ptr()), C.c_void_p(stream.cuda_stream)))
+            return out
         N.check(self._lib.cf_span_scores(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(signal.data_ptr()) if signal is not None else None,
                                          C.c_void_p(read_offsets.data_ptr()), C.c_void_p(read_lengths.data_ptr()), n_reads, total,
                                          float(threshold), C.c_void_p(starts.data_ptr()), C.c_void_p(counts.data_ptr()), max_runs,
@@ -384,7 +413,8 @@ class HipEngine(object):
         """Bytes of work space ``run_states_validation`` needs for ``total`` packed samples and ``n_thresholds`` thresholds."""
         return int(self._lib.cf_validation_run_work_bytes(int(total), int(n_thresholds)))
 
-    def run_states_validation(self, probs, y, bounds, length, total, longest, thresholds, edges, counts_out, work, min_run=15, stream=None):
+    def run_states_validation(self, probs, y, bounds, length, total, longest, thresholds, edges, counts_out, work, min_run=15, stream=None,
+                              max_gap=0):
         """``cf_validation_run_states``: per threshold (``thresholds``: 1..16 host floats), kind (0 = true runs judged against the
         corrected prediction, 1 = predicted runs judged against ``y``), length bin (``edges``: up to 7 ascending host ints) and
         state (complete / incomplete / absent) how many runs -- ``device_validation.run_states_host`` -- into ``counts_out``
@@ -407,6 +437,13 @@ class HipEngine(object):
         if stream is None:
             stream = torch.cuda.current_stream(probs.device)
         # n, K, the edges, min_run and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
+        if max_gap:            # (``max_gap``: the prediction is bridged first, ``cf_validation_run_states_bridged``; a pair it refuses raises)
+            N.check(self._lib.cf_validation_run_states_bridged(
+                self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
+                C.c_void_p(length.data_ptr()), n, total, longest, (C.c_double * max(k, 1))(*thresholds), k,
+                (C.c_int64 * max(len(edges), 1))(*edges), len(edges), int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()),
+                C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
+            return
         N.check(self._lib.cf_validation_run_states(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()),
                                                    C.c_void_p(bounds.data_ptr()), C.c_void_p(length.data_ptr()), n, total, longest,
                                                    (C.c_double * max(k, 1))(*thresholds), k, (C.c_int64 * max(len(edges), 1))(*edges),
@@ -417,7 +454,8 @@ class HipEngine(object):
         """Bytes of work space ``run_borders_validation`` needs (``run_states_work_bytes``' rule: the two can share a buffer)."""
         return int(self._lib.cf_validation_run_borders_work_bytes(int(total), int(n_thresholds)))
 
-    def run_borders_validation(self, probs, y, bounds, length, total, longest, thresholds, reach, counts_out, work, min_run=15, stream=None):
+    def run_borders_validation(self, probs, y, bounds, length, total, longest, thresholds, reach, counts_out, work, min_run=15, stream=None,
+                               max_gap=0):
         """``cf_validation_run_borders``: per threshold (``thresholds``: 1..16 host floats) and kind the histograms of how far the
         other array reaches beyond a run's left and right border or falls short of it (clipped at ``reach``, an int in 1 .. 128),
         of the interruptions inside the runs, and the number of interrupted runs -- ``device_validation.run_borders_host`` -- into
@@ -442,6 +480,13 @@ class HipEngine(object):
         if stream is None:
             stream = torch.cuda.current_stream(probs.device)
         # n, K, min_run and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
+        if max_gap:            # (the prediction is bridged first: ``cf_validation_run_borders_bridged``)
+            N.check(self._lib.cf_validation_run_borders_bridged(
+                self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
+                C.c_void_p(length.data_ptr()), n, total, longest, (C.c_double * max(k, 1))(*thresholds), k, reach, int(max_gap),
+                int(min_run), C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()),
+                C.c_void_p(stream.cuda_stream)))
+            return
         N.check(self._lib.cf_validation_run_borders(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()),
                                                     C.c_void_p(bounds.data_ptr()), C.c_void_p(length.data_ptr()), n, total, longest,
                                                     (C.c_double * max(k, 1))(*thresholds), k, reach, int(min_run),

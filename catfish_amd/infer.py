@@ -156,6 +156,38 @@ def correct_short(predictions, threshold=15):
     return np.repeat(vals, lengths)
 
 
+def check_bridge(max_gap, min_run=15):
+    """``max_gap`` as an int, after checking the pair against what the on-card post-processing takes: ``min_run >= 1``,
+    ``max_gap >= 0`` and, when bridging is on, ``min_run + max_gap <= 64`` (its window has one 64-sample word of halo).  The same
+    rule holds on the host route, so that a pair never gives results on one route and an error on the other."""
+    if max_gap is None:
+        return 0
+    if isinstance(max_gap, bool) or int(max_gap) != max_gap:
+        raise ValueError("max_gap must be an int, got %r" % (max_gap,))
+    max_gap, min_run = int(max_gap), int(min_run)
+    if max_gap < 0:
+        raise ValueError("max_gap must be >= 0, got %d" % max_gap)
+    if max_gap > 0 and (min_run < 1 or min_run + max_gap > 64):
+        raise ValueError("bridging needs min_run >= 1 and min_run + max_gap <= 64, got min_run %d, max_gap %d" % (min_run, max_gap))
+    return max_gap
+
+
+def bridge_gaps(bits, max_gap):
+    """The definition of bridging, over ONE read's real samples (``bits`` = float32 p >= float32 threshold, NaN is false): a maximal
+    run of zeros of at most ``max_gap`` samples with a one directly before it and a one directly after it becomes ones.  Zeros that
+    touch the read's first or last sample are never filled.  ``max_gap <= 0`` is the identity.  The labels of a read are
+    ``correct_short(bridge_gaps(bits, max_gap), min_run)``; ``cf_postprocess_spans_bridged`` computes them on the card."""
+    b = np.asarray(bits).astype(np.int64).copy()
+    n = len(b)
+    if max_gap <= 0 or n == 0:
+        return b
+    e = np.flatnonzero(np.diff(b)) + 1
+    for s, t in zip(np.concatenate([[0], e]), np.concatenate([e, [n]])):
+        if b[s] == 0 and s > 0 and t < n and t - s <= max_gap:
+            b[s:t] = 1
+    return b
+
+
 def hp_in_pred(predictions, extension_left=11, extension_right=16, label=1):
     """infer.py:141-162: each run of ``label`` -> [start - 11, start + length + 16] (end exclusive;
     spans may start below 0 or end beyond the read, exactly like the reference)."""
@@ -166,9 +198,10 @@ def hp_in_pred(predictions, extension_left=11, extension_right=16, label=1):
 
 
 # --------------------------------------------------------------------------- inference
-def _scores_of_read(raw_in, model, length):
+def _scores_of_read(raw_in, model, length, max_gap=0):
     """Spans and score rows of one padded, windowed read: on the card when the model has an engine (``cf_postprocess_spans`` +
-    ``cf_span_scores``; the probabilities never come down), else ``span_scores.span_scores_host`` over ``model.infer``."""
+    ``cf_span_scores``; the probabilities never come down), else ``span_scores.span_scores_host`` over ``model.infer``.  With
+    ``max_gap > 0`` the runs are the bridged ones and a row covers every sample of its run, those below the threshold included."""
     from .span_scores import scores_of_runs, span_score_summary, span_scores_host, summary_rows
     x = np.ascontiguousarray(np.asarray(raw_in, dtype=np.float32).reshape(-1))
     off, lengths = np.array([0, x.shape[0]], dtype=np.int64), np.array([length], dtype=np.int64)
@@ -181,23 +214,45 @@ def _scores_of_read(raw_in, model, length):
         d_x = torch.from_numpy(x).to(dev)
         probs = engine.infer_device(d_x.view(-1, WINDOW_SIZE))
         starts, ends, flat = engine.postprocess_spans_device(probs, torch.from_numpy(off).to(dev), torch.from_numpy(lengths).to(dev),
-                                                             scores=True, signal=d_x)
+                                                             scores=True, signal=d_x, max_gap=max_gap)
         spans = [[int(s) - 11, int(e) + 16] for s, e in zip(starts.tolist(), ends.tolist())]
         return spans, summary_rows(span_score_summary(flat))
     scores = np.asarray(model.infer(raw_in)).reshape(-1)
-    labels = correct_short(class_from_threshold(scores[:length]))
+    labels = correct_short(bridge_gaps(class_from_threshold(scores[:length]), max_gap))
     spans = hp_in_pred(labels)
     p32 = scores.astype(np.float32)
-    flat = span_scores_host(p32, x, off, lengths)
     runs = [[s + 11, e - 16] for s, e in spans]
-    if [list(r) for r in zip(flat["start"].tolist(), flat["end"].tolist())] != runs:
+    flat = span_scores_host(p32, x, off, lengths) if max_gap == 0 else None
+    if flat is None or [list(r) for r in zip(flat["start"].tolist(), flat["end"].tolist())] != runs:
+        # bridged runs hold samples below the threshold; or
         # a probability that rounds across the threshold on its way to float32: the rows describe the spans that are returned
         flat = scores_of_runs(p32, x, [r[0] for r in runs], [r[1] for r in runs], off, 1)
     return spans, summary_rows(span_score_summary(flat))
 
 
-def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE, scores=False):
+def _bridged_spans_of_read(raw_in, model, length, max_gap):
+    """Spans of one padded, windowed read with gaps bridged: ``cf_postprocess_spans_bridged`` when the model has an engine, else the
+    host definition over ``model.infer``."""
+    if hasattr(model, "_require_engine"):
+        model._require_engine()
+    engine = getattr(model, "engine", None)
+    if engine is None:
+        scores = np.asarray(model.infer(raw_in)).reshape(-1)[:length]
+        return hp_in_pred(correct_short(bridge_gaps(class_from_threshold(scores), max_gap)))
+    import torch
+    dev = torch.device("cuda", engine.device)
+    x = np.ascontiguousarray(np.asarray(raw_in, dtype=np.float32).reshape(-1))
+    probs = engine.infer_device(torch.from_numpy(x).to(dev).view(-1, WINDOW_SIZE))
+    off, lengths = torch.tensor([0, x.shape[0]], dtype=torch.int64, device=dev), torch.tensor([length], dtype=torch.int64, device=dev)
+    starts, ends = engine.postprocess_spans_device(probs, off, lengths, max_gap=max_gap)
+    return [[int(s) - 11, int(e) + 16] for s, e in zip(starts.tolist(), ends.tolist())]
+
+
+def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE, scores=False, max_gap=0):
     """Body of infer_class_from_signal (infer.py:31-51) for an already normalised signal.
+
+    ``max_gap > 0`` bridges gaps of at most that many samples between two called stretches before ``correct_short``
+    (``bridge_gaps``); 0 changes nothing.
 
     ``scores=True`` returns a third value: a float64 array [n_spans, 6], one row per span in span order, columns n, mean_p,
     min_p, max_p, level, spread (``span_scores.SCORE_COLUMNS``)."""
@@ -206,9 +261,12 @@ def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE, scores=Fa
     length = len(raw)
     raw = np.hstack((raw, np.array(padding_size * [0])))
     raw_in = reshape_input(raw, window_size, 1)
+    max_gap = check_bridge(max_gap)
     if scores:
-        predicted_hps, rows = _scores_of_read(raw_in, model, length)
+        predicted_hps, rows = _scores_of_read(raw_in, model, length, max_gap)
         return predicted_hps, length, rows
+    if max_gap > 0:
+        return _bridged_spans_of_read(raw_in, model, length, max_gap), length
     scores = model.infer(raw_in)
     scores = scores[:-padding_size]
     labels = correct_short(class_from_threshold(scores))
@@ -216,11 +274,11 @@ def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE, scores=Fa
     return predicted_hps, len(labels)
 
 
-def infer_class_from_signal(fast5_file, model, label=1, window_size=WINDOW_SIZE, scores=False):
+def infer_class_from_signal(fast5_file, model, label=1, window_size=WINDOW_SIZE, scores=False, max_gap=0):
     """infer.py:12-51.  Returns (list of [start, end] homopolymer spans, length of the read), and the score rows of
-    ``infer_class_from_raw`` as a third value with ``scores=True``."""
+    ``infer_class_from_raw`` as a third value with ``scores=True``; ``max_gap`` as there."""
     raw = load_raw(fast5_file)
-    return infer_class_from_raw(raw, model, label=label, window_size=window_size, scores=scores)
+    return infer_class_from_raw(raw, model, label=label, window_size=window_size, scores=scores, max_gap=max_gap)
 
 
 def infer_class_from_npz(npz_file, model, label=1, window_size=WINDOW_SIZE):

@@ -26,13 +26,18 @@ class _Ticket(object):
 
 
 class ReadPipeline(object):
-    def __init__(self, engine, max_samples_per_batch, threshold=0.5, min_run=15, depth=2, overlap_kernels=None, scores=False):
+    def __init__(self, engine, max_samples_per_batch, threshold=0.5, min_run=15, depth=2, overlap_kernels=None, scores=False, max_gap=0):
         import torch
+        from .infer import check_bridge
         self.torch = torch
         self.eng = engine
         self.dev = torch.device("cuda", engine.device)
         self.threshold = float(threshold)
         self.min_run = int(min_run)
+        # bridging (infer.bridge_gaps): gaps of at most max_gap samples between two called stretches of a read are closed before
+        # correct_short, in the same single launch (cf_postprocess_spans_bridged); 0: the launches of before.  ValueError for a
+        # pair the kernel's window does not cover (min_run + max_gap > 64)
+        self.max_gap = check_bridge(max_gap, self.min_run)
         # per-call scores (span_scores.py): one more launch per batch (cf_span_scores, right behind cf_postprocess_spans) and 40 B
         # per run more on the way down; off, nothing is launched, allocated or copied that was not before
         self.scores = bool(scores)
@@ -255,19 +260,29 @@ class ReadPipeline(object):
             # never written (cf_postprocess_spans with labels = NULL) -- except for min_run > 64, which takes the two older kernels
             max_runs = n_windows * WINDOW_SIZE // self.min_run + 16
             total = n_windows * WINDOW_SIZE
-            labels = torch.empty(total, dtype=torch.uint8, device=self.dev) if self.min_run > 64 else None
+            # bridged runs hold samples below the threshold: their scores follow the labels, which are written only then
+            by_labels = self.max_gap > 0 and self.scores
+            labels = torch.empty(total, dtype=torch.uint8, device=self.dev) if self.min_run > 64 or by_labels else None
             t.starts = torch.empty(max_runs, dtype=torch.int64, device=self.dev)
             t.ends = torch.empty(max_runs, dtype=torch.int64, device=self.dev)
             t.counts = torch.empty(2, dtype=torch.int64, device=self.dev)
-            N.check(self.eng._lib.cf_postprocess_spans(
-                self.eng._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(d_soff.data_ptr()), C.c_void_p(d_len.data_ptr()), n_reads, total,
-                float(self.threshold), int(self.min_run), C.c_void_p(labels.data_ptr()) if labels is not None else None, max_runs,
-                C.c_void_p(t.starts.data_ptr()), C.c_void_p(t.ends.data_ptr()), C.c_void_p(t.counts.data_ptr()),
-                C.c_void_p(k_post.cuda_stream)))
+            if self.max_gap > 0:
+                N.check(self.eng._lib.cf_postprocess_spans_bridged(
+                    self.eng._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(d_soff.data_ptr()), C.c_void_p(d_len.data_ptr()), n_reads,
+                    total, float(self.threshold), self.max_gap, int(self.min_run),
+                    C.c_void_p(labels.data_ptr()) if labels is not None else None, max_runs, C.c_void_p(t.starts.data_ptr()),
+                    C.c_void_p(t.ends.data_ptr()), C.c_void_p(t.counts.data_ptr()), C.c_void_p(k_post.cuda_stream)))
+            else:
+                N.check(self.eng._lib.cf_postprocess_spans(
+                    self.eng._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(d_soff.data_ptr()), C.c_void_p(d_len.data_ptr()), n_reads, total,
+                    float(self.threshold), int(self.min_run), C.c_void_p(labels.data_ptr()) if labels is not None else None, max_runs,
+                    C.c_void_p(t.starts.data_ptr()), C.c_void_p(t.ends.data_ptr()), C.c_void_p(t.counts.data_ptr()),
+                    C.c_void_p(k_post.cuda_stream)))
             t.rows = None
             if self.scores:
                 # x and probs stay resident until the batch is collected (t.keep): the scores cost no transfer upwards
-                t.rows = self.eng.span_scores_device(probs, x.view(-1), d_soff, d_len, t.starts, t.counts, self.threshold, stream=k_post)
+                t.rows = self.eng.span_scores_device(probs, x.view(-1), d_soff, d_len, t.starts, t.counts, self.threshold, stream=k_post,
+                                                     labels=labels if by_labels else None)
             spans_done = torch.cuda.Event()
             spans_done.record(k_post)
         if self.out[slot] is None or self.out[slot][0].numel() < max_runs:

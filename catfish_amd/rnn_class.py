@@ -209,7 +209,8 @@ class RNN(object):
         self._require_engine()
         return self.engine.infer_host(np.asarray(windows), return_logits=True)
 
-    def score_validation_device(self, vset, selection, thresholds=(0.5,), run_edges=None, curve_shift=None, border_reach=None):
+    def score_validation_device(self, vset, selection, thresholds=(0.5,), run_edges=None, curve_shift=None, border_reach=None,
+                                bridge_gap=0):
         """One validation round on the card: the stretches ``selection`` (``vset.select``) of a
         ``device_validation.DeviceValidationSet`` -> what ``device_validation.score_host`` returns for them, (right int64 [n],
         ce_sum float64 [n], counts int64 [K, 4]).  With ``run_edges`` (a tuple of up to 7 ascending run lengths, possibly empty)
@@ -225,7 +226,9 @@ class RNN(object):
         ``device_validation.run_borders_host`` returns for the round's probabilities, int64 [K, 2, 5 * border_reach + 3] -- how far
         the called borders miss the true ones and how often a homopolymer is called in pieces (``cf_validation_run_borders``, same
         forward pass, same copy back; room ``capacity["border_cells"]``, label work space shared with the run states).  The set's
-        labels must all be 0 or 1 then (ValueError).
+        labels must all be 0 or 1 then (ValueError).  ``bridge_gap`` (0 .. 49): the prediction the run states and the borders are
+        counted on has its gaps of at most that many samples bridged first (``infer.bridge_gaps``; ``cf_validation_run_states_bridged``
+        and ``cf_validation_run_borders_bridged``); the per-sample counts are not touched.
 
         The selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes
         probabilities and logits (the weights just trained, as ``score_windows`` uses them), ``cf_validation_score`` reduces them
@@ -235,6 +238,8 @@ class RNN(object):
         import torch
         from . import device_validation as dv
         self._require_engine()
+        from .infer import check_bridge
+        bridge_gap = check_bridge(bridge_gap, 15)
         thresholds = tuple(float(t) for t in thresholds)
         if not thresholds:
             raise ValueError("score_validation_device: no threshold given")
@@ -310,11 +315,11 @@ class RNN(object):
             if run_edges is not None:
                 per_k = run_cells // k_all
                 self.engine.run_states_validation(probs, y, bounds_d, len_d, total, longest, thresholds[k0:k1], run_edges,
-                                                  runs_d[per_k * k0:per_k * k1], t["run_work"])
+                                                  runs_d[per_k * k0:per_k * k1], t["run_work"], max_gap=bridge_gap)
             if border_reach is not None:
                 per_k = border_cells // k_all
                 self.engine.run_borders_validation(probs, y, bounds_d, len_d, total, longest, thresholds[k0:k1], border_reach,
-                                                   borders_d[per_k * k0:per_k * k1], t["run_work"])
+                                                   borders_d[per_k * k0:per_k * k1], t["run_work"], max_gap=bridge_gap)
         if curve_shift is not None:
             self.engine.curve_validation(probs, y, bounds_d, len_d, total, longest, curve_shift, curve_d)
         back = out.cpu().numpy()                                                     # synchronises the stream

@@ -236,6 +236,9 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     extra = {} if curve_shift is None else {"curve_shift": curve_shift}
     if border_reach is not None:
         extra["border_reach"] = border_reach
+    bridge_gap = int(getattr(network, "validation_bridge_gap", 0) or 0)
+    if bridge_gap:
+        extra["bridge_gap"] = bridge_gap
     if run_edges is None:
         _acc, precision, recall = validate(network, *validation, **extra)
     else:
@@ -246,13 +249,13 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
         _append(report[:-len(".txt")] + "_hp_states.jsonl", json.dumps({
             "step": int(step), "threshold": 0.5, "edges": list(run_edges), "states": list(RUN_STATES),
             "hp_states": table[0].tolist(), "called_states": table[1].tolist(), "hp_complete": complete, "hp_found": found,
-            "called_absent": called_absent}) + "\n")
+            "called_absent": called_absent, **({"bridge_gap": bridge_gap} if bridge_gap else {})}) + "\n")
     if border_reach is not None:
         # how far the round's called borders miss the true ones, and how often a homopolymer comes in pieces: one JSON line per round
         hp_borders, called_borders = border_report(network.validation_run_borders, border_reach)
         _append(report[:-len(".txt")] + "_hp_borders.jsonl", json.dumps({
             "step": int(step), "threshold": 0.5, "reach": int(border_reach), "hp_borders": hp_borders,
-            "called_borders": called_borders}) + "\n")
+            "called_borders": called_borders, **({"bridge_gap": bridge_gap} if bridge_gap else {})}) + "\n")
     if curve_shift is not None:
         # the round's whole ROC and precision-recall curves, reduced to their areas and the best F1: one JSON line per round
         curves = curves_from_histogram(network.validation_curve, curve_shift)
@@ -399,7 +402,7 @@ def score_validation_batch(probs32, logits32, y, bounds, tails, threshold=0.5):
 
 
 def validate(network, squiggles, max_seq_length, file_path, validation_start="random", max_number=856, run_edges=None, curve_shift=None,
-             border_reach=None):
+             border_reach=None, bridge_gap=0):
     """networks/train_validate.py:188-295 as one packed launch.
 
     The reference pushes every read through ``test_network`` (one ``sess.run`` each, up to 856 per round); windows are
@@ -420,7 +423,13 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     ``border_reach`` (a ``DeviceValidationSet`` only; an int in 1 .. 128): the round also counts how far the called borders miss
     the true ones and the interruptions at threshold 0.5 (``device_validation.run_borders_host``, on the card); the
     [2, 5 * border_reach + 3] table is left in ``network.validation_run_borders``.
+    ``bridge_gap`` (with ``run_edges`` or ``border_reach``; 0 .. 49): those two tables are counted on the prediction with its gaps of
+    at most that many samples bridged (``infer.bridge_gaps``).
     Report, prints and return value stay as they are."""
+    from .infer import check_bridge
+    bridge_gap = check_bridge(bridge_gap, 15)
+    if bridge_gap and run_edges is None and border_reach is None:
+        raise ValueError("validate: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
     print("Max length is {}".format(max_seq_length))
     print("Validation start is {}".format(validation_start))
     from .device_validation import DeviceValidationSet
@@ -435,6 +444,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
             right, ce_sum, counts_k = network.score_validation_device(squiggles, selection)
         else:
             extra = {} if border_reach is None else {"border_reach": border_reach}
+            if bridge_gap:
+                extra["bridge_gap"] = bridge_gap
             got = network.score_validation_device(squiggles, selection, (0.5,), run_edges=run_edges, curve_shift=curve_shift, **extra)
             right, ce_sum, counts_k = got[:3]
             if run_edges is not None:
@@ -483,7 +494,7 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
 
 
 def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start="complete", max_number=856, run_edges=None,
-                    border_reach=None):
+                    border_reach=None, bridge_gap=0):
     """The reference's precision / recall sweep (networks/precision_recall_ROC.py:85-100: ``class_from_threshold`` --
     ``p >= t`` -- then ``compute_f1`` per threshold) over a ``DeviceValidationSet``: ONE forward pass, every threshold counted
     from its probabilities on the card.  The stretches are ``validate``'s (same selection, same tail rule for the true
@@ -497,7 +508,15 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
 
     With ``border_reach`` (an int in 1 .. 128) every row also says how far that threshold's borders miss
     (``device_validation.run_borders_host``; the rest of the reference's ``check_hp``): ``hp_borders`` -- the true runs against
-    the corrected prediction -- and ``called_borders`` -- the called runs against the truth --, each ``border_report``'s dict."""
+    the corrected prediction -- and ``called_borders`` -- the called runs against the truth --, each ``border_report``'s dict.
+
+    ``bridge_gap`` (with ``run_edges`` or ``border_reach``; 0 .. 49): the run states and the borders are those of the prediction
+    with its gaps of at most that many samples bridged (``infer.bridge_gaps``); tp / fp / tn / fn stay per-sample counts."""
+    from .infer import check_bridge
+    bridge_gap = check_bridge(bridge_gap, 15)
+    if bridge_gap and run_edges is None and border_reach is None:
+        raise ValueError("threshold_sweep: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
+    bridged = {"bridge_gap": bridge_gap} if bridge_gap else {}
     thresholds = [float(t) for t in thresholds]
     selection = vset.select(network.window, max_seq_length, validation_start, max_number)
     if len(selection[0]) == 0:
@@ -506,9 +525,9 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     if run_edges is None and border_reach is None:
         _right, _ce_sum, counts = network.score_validation_device(vset, selection, thresholds)
     elif border_reach is None:
-        _right, _ce_sum, counts, run_states = network.score_validation_device(vset, selection, thresholds, run_edges=run_edges)
+        _right, _ce_sum, counts, run_states = network.score_validation_device(vset, selection, thresholds, run_edges=run_edges, **bridged)
     else:
-        got = network.score_validation_device(vset, selection, thresholds, run_edges=run_edges, border_reach=border_reach)
+        got = network.score_validation_device(vset, selection, thresholds, run_edges=run_edges, border_reach=border_reach, **bridged)
         counts, borders = got[2], got[-1]
         run_states = None if run_edges is None else got[3]
     tail = int(vset.layout(selection[2], network.window)[1].sum())
@@ -523,6 +542,26 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
                              "hp_complete": complete, "hp_found": found, "called_absent": called_absent})
         if borders is not None:
             rows[-1]["hp_borders"], rows[-1]["called_borders"] = border_report(borders[k], border_reach)
+    return rows
+
+
+def bridge_sweep(network, vset, gaps, max_seq_length, threshold=0.5, validation_start="complete", max_number=856, run_edges=(),
+                 border_reach=BORDER_REACH):
+    """What bridging gaps of up to g samples does to the homopolymers a round finds, for every g of ``gaps`` (ints in 0 .. 49), over
+    a ``DeviceValidationSet`` at one threshold: one ``threshold_sweep`` round per gap (same stretches; ``validation_start`` should
+    not be "random").  -> a list of dicts {bridge_gap, hp_complete, hp_found, called_absent (``run_state_rates``), hp_states,
+    called_states, hp_interrupted, called_interrupted}: the last two are the share of the true (called) runs that are not absent
+    and have at least one interruption in the other array -- homopolymers found in pieces."""
+    rows = []
+    for gap in gaps:
+        row = threshold_sweep(network, vset, [threshold], max_seq_length, validation_start, max_number, run_edges=run_edges,
+                              border_reach=border_reach, bridge_gap=gap)[0]
+        out = {"bridge_gap": int(gap)}
+        out.update({key: row[key] for key in ("hp_complete", "hp_found", "called_absent", "hp_states", "called_states")})
+        for name, part in (("hp_interrupted", row["hp_borders"]), ("called_interrupted", row["called_borders"])):
+            judged = int(np.sum(part["left"]))
+            out[name] = part["interrupted_runs"] / judged if judged else 0
+        rows.append(out)
     return rows
 
 
@@ -602,7 +641,10 @@ def main(argv):
     CATFISH_VALIDATION_BORDERS=1 (reach 64) or =<int> (that reach, 1 .. 128; with CATFISH_DEVICE_VALIDATION=1) also counts, per
     round, how far the called borders miss the true ones and the interruptions at threshold 0.5 and appends step, threshold,
     reach, ``hp_borders`` and ``called_borders`` (``border_report``; None as null) as one JSON line to
-    ``<model path>_hp_borders.jsonl``; the ``.txt`` reports and the other ``.jsonl`` files are unchanged."""
+    ``<model path>_hp_borders.jsonl``; the ``.txt`` reports and the other ``.jsonl`` files are unchanged.
+    CATFISH_VALIDATION_BRIDGE=<int> (1 .. 49; with CATFISH_VALIDATION_RUNS or CATFISH_VALIDATION_BORDERS) counts those two on the
+    prediction with its gaps of at most that many samples bridged (``infer.bridge_gaps``); their JSON lines then carry
+    ``bridge_gap``."""
     args = list(argv[1:])
     if len(args) < 5:
         raise ValueError(_USAGE)
@@ -639,6 +681,12 @@ def main(argv):
         borders = os.environ.get("CATFISH_VALIDATION_BORDERS") or "0"
         if borders != "0":                                       # ... and how far the called borders miss, one JSON line per round
             network.validation_border_reach = BORDER_REACH if borders == "1" else check_border_reach(int(borders))
+        bridge = int(os.environ.get("CATFISH_VALIDATION_BRIDGE") or "0")
+        if bridge:                                               # ... both counted on the bridged prediction
+            from .infer import check_bridge
+            network.validation_bridge_gap = check_bridge(bridge, 15)
+            if getattr(network, "validation_run_edges", None) is None and getattr(network, "validation_border_reach", None) is None:
+                raise ValueError("CATFISH_VALIDATION_BRIDGE needs CATFISH_VALIDATION_RUNS=1 or CATFISH_VALIDATION_BORDERS")
     began = datetime.datetime.now()
     train_and_validate(network, db_train, n_train, squiggles, stretch, network.model_path, start, most)
     print("Trained and validated network in {}".format(datetime.datetime.now() - began))

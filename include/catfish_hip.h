@@ -217,6 +217,26 @@ int cf_span_scores(cf_model* m, const float* probs, const float* signal /* NULL:
                    int64_t* ends_paired, double* sums /* [max_runs][3]: sum p, sum x, sum x * x */, float* extremes /* [max_runs][2] */,
                    void* stream);
 
+/* Bridging (csrc/post_bridge_rule.hpp; infer.bridge_gaps is the definition): cf_postprocess_spans with one step more.  Inside the real
+ * part of ONE read, a maximal run of samples below the threshold of at most max_gap samples, with a sample at or above the threshold
+ * directly before it and directly after it, counts as above the threshold; then correct_short and the run lists as in
+ * cf_postprocess_spans.  Samples that touch a read's first or last real sample are never filled, padding is never read as a one, and
+ * nothing is bridged from one read into the next, also when reads are packed without padding.  max_gap == 0 is cf_postprocess_spans
+ * itself (same launches).  Otherwise the pair must satisfy min_run >= 1, max_gap >= 0, min_run + max_gap <= 64 and labels (NULL is
+ * fine) must be 16-byte aligned: anything else is CF_ERR_INVALID before any launch -- there is no slower route. */
+int cf_postprocess_spans_bridged(cf_model* m, const float* probs, const int64_t* read_offsets, const int64_t* read_lengths,
+                                 int64_t n_reads, int64_t total_samples, float threshold, int32_t max_gap, int32_t min_run,
+                                 uint8_t* labels /* NULL ok */, int64_t max_runs /* 0: labels and counts only */, int64_t* starts,
+                                 int64_t* ends, uint64_t* counts, void* stream);
+
+/* cf_span_scores for runs given by labels: "the run continues" is labels[i] != 0 (device uint8 [total_samples], what
+ * cf_postprocess_spans_bridged wrote) instead of probs[i] >= threshold, so the samples of a bridged gap belong to the run's sums and
+ * extremes.  Same rows, same empty-row rule, same memory safety for any contents of starts, same fixed reduction order. */
+int cf_span_scores_labels(cf_model* m, const float* probs, const float* signal /* NULL: no level sums */, const uint8_t* labels,
+                          const int64_t* read_offsets, const int64_t* read_lengths, int64_t n_reads, int64_t total_samples,
+                          const int64_t* starts, const uint64_t* counts, int64_t max_runs, int64_t* ends_paired, double* sums,
+                          float* extremes, void* stream);
+
 /* Signal ingest on device, replacing normalize_raw_signal + the padding / reshape of
  * infer_class_from_signal (catfish/infer.py:96-105, 31-43) for many reads at once.
  * dac: device int16, the reads' raw DAC samples back to back (after the leader trim of
@@ -583,6 +603,14 @@ int cf_validation_run_states(cf_model* m, const float* probs, const uint8_t* y, 
                              int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds, const int64_t* edges,
                              int32_t n_edges, int32_t min_run, int64_t* counts_out, void* work, int64_t work_bytes, void* stream);
 
+/* ... with pred = correct_short(bridge_gaps((double)p >= t, max_gap), min_run) inside every stretch (cf_postprocess_spans_bridged's
+ * rule and domain: max_gap == 0 is cf_validation_run_states; otherwise min_run + max_gap <= 64 and a 16-byte aligned work buffer, else
+ * CF_ERR_INVALID before any launch).  The work size is the same. */
+int cf_validation_run_states_bridged(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length,
+                                     int64_t n, int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds,
+                                     const int64_t* edges, int32_t n_edges, int32_t max_gap, int32_t min_run, int64_t* counts_out,
+                                     void* work, int64_t work_bytes, void* stream);
+
 /* Border-level validation (csrc/validation_borders.hpp, csrc/validation_borders_word.hpp; device_validation.run_borders_host is its
  * definition): the rest of what the reference's check_hp (networks/process_output.py:814-895) returns for a run.  Stretches,
  * prediction, runs and kinds as for cf_validation_run_states; a label other than 1 counts as 0.  For every run [s, e] that is not
@@ -603,6 +631,12 @@ int64_t cf_validation_run_borders_work_bytes(int64_t total, int32_t n_thresholds
 int cf_validation_run_borders(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length, int64_t n,
                               int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds, int32_t reach,
                               int32_t min_run, int64_t* counts_out, void* work, int64_t work_bytes, void* stream);
+
+/* ... with the bridged prediction of cf_validation_run_states_bridged (same rule, same domain, same work size). */
+int cf_validation_run_borders_bridged(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length,
+                                      int64_t n, int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds,
+                                      int32_t reach, int32_t max_gap, int32_t min_run, int64_t* counts_out, void* work,
+                                      int64_t work_bytes, void* stream);
 
 /* Validation curves (csrc/validation_curve.hpp; device_validation.curve_host is its definition): the histogram of a round's
  * probabilities from which the host draws the whole ROC and precision-recall curves (device_validation.curves_from_histogram).
