@@ -152,18 +152,36 @@ def _device_runs(engine, probs, offs, lens, threshold, min_run, max_gap):
     return engine.spans_device(labels)
 
 
-def infer_packed(engine, packed, threshold=0.5, min_run=15, return_probs=False, max_gap=0):
+def _voted_probs(engine, x, offs, lens, n_reads, phases, vote_weight):
+    """The probabilities of the base layout ``x`` ([n_windows, 35] CUDA), voted over the tilings of ``phases``
+    (``tilings.vote_host``): ``cf_retile_windows``, ONE forward pass over all tilings, ``cf_vote_tilings``.  One phase: the forward
+    pass alone, as before."""
+    import torch
+    if len(phases) == 1:
+        return engine.infer_device(x)
+    from .tilings import tiling_size
+    total = int(x.numel())
+    x_all = torch.empty(tiling_size(total, n_reads, len(phases)) // WINDOW_SIZE, WINDOW_SIZE, dtype=torch.float32, device=x.device)
+    x_all[:total // WINDOW_SIZE].copy_(x.view(-1, WINDOW_SIZE))
+    engine.retile_device(x_all, offs, lens, total, phases)
+    return engine.vote_device(engine.infer_device(x_all), offs, lens, total, phases, vote_weight)
+
+
+def infer_packed(engine, packed, threshold=0.5, min_run=15, return_probs=False, max_gap=0, phases=(0,), vote_weight="mean"):
     """PackedReads -> list of (spans, read length) per read, optionally with per-read probabilities.  ``max_gap``: gaps of at most
     that many samples between two called stretches of a read are bridged before ``correct_short`` (0: none; ValueError for
-    ``min_run + max_gap > 64``)."""
+    ``min_run + max_gap > 64``).  ``phases`` / ``vote_weight``: shifted-window voting (``infer.check_phases``, ``tilings.py``);
+    the probabilities that are thresholded -- and returned -- are then the voted ones."""
     import torch
-    from .infer import check_bridge
+    from .infer import check_bridge, check_phases, check_weight
     max_gap = check_bridge(max_gap, min_run)
+    phases = check_phases(phases)
+    check_weight(vote_weight)
     dev = torch.device("cuda", engine.device)
     x = torch.from_numpy(packed.x).to(dev, non_blocking=True)
     offs = torch.from_numpy(packed.sample_offsets).to(dev)
     lens = torch.from_numpy(packed.lengths).to(dev)
-    probs = engine.infer_device(x)
+    probs = _voted_probs(engine, x, offs, lens, packed.n_reads, phases, vote_weight)
     starts, ends = _device_runs(engine, probs, offs, lens, threshold, min_run, max_gap)
     spans = spans_from_runs(starts, ends, packed.sample_offsets, packed.n_reads)
     result = [(spans[i], int(packed.lengths[i])) for i in range(packed.n_reads)]
@@ -174,14 +192,17 @@ def infer_packed(engine, packed, threshold=0.5, min_run=15, return_probs=False, 
     return result
 
 
-def infer_reads(model, signals, max_windows=None, threshold=0.5, min_run=15, max_gap=0):
-    """Many normalised reads -> [(spans, length)] in input order, length-bucketed packed launches; ``max_gap`` as in
-    ``infer_packed``."""
-    from .infer import check_bridge
+def infer_reads(model, signals, max_windows=None, threshold=0.5, min_run=15, max_gap=0, phases=(0,), vote_weight="mean"):
+    """Many normalised reads -> [(spans, length)] in input order, length-bucketed packed launches; ``max_gap``, ``phases`` and
+    ``vote_weight`` as in ``infer_packed`` (``max_windows`` bounds the base layout of a launch: K tilings make it about K times as
+    large)."""
+    from .infer import check_bridge, check_phases, check_weight
     engine = model.engine if hasattr(model, "engine") else model
     if engine is None:
         raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
     max_gap = check_bridge(max_gap, min_run)
+    phases = check_phases(phases)
+    check_weight(vote_weight)
     signals = [np.asarray(s).reshape(-1) for s in signals]
     if max_windows is None:
         max_windows = 32768
@@ -189,24 +210,28 @@ def infer_reads(model, signals, max_windows=None, threshold=0.5, min_run=15, max
     with quiet_gc():
         for bucket in length_buckets([len(s) for s in signals], max_windows):
             packed = pack_reads([signals[i] for i in bucket])
-            for i, res in zip(bucket, infer_packed(engine, packed, threshold, min_run, max_gap=max_gap)):
+            for i, res in zip(bucket, infer_packed(engine, packed, threshold, min_run, max_gap=max_gap, phases=phases,
+                                                    vote_weight=vote_weight)):
                 out[i] = res
     return out
 
 
-def infer_reads_dac(model, dac_reads, max_windows=None, threshold=0.5, min_run=15, return_probs=False, max_gap=0):
+def infer_reads_dac(model, dac_reads, max_windows=None, threshold=0.5, min_run=15, return_probs=False, max_gap=0, phases=(0,),
+                    vote_weight="mean"):
     """Raw int16 DAC reads (leader already trimmed) -> [(spans, length)] with normalisation ON DEVICE.
 
     Uploads 2 B per sample; median/MAD normalisation, padding and window packing run in
     ``cf_normalize`` (bit-identical to infer.normalize_raw_signal cast to float32), then the
-    forward pass and the device post-processing as in ``infer_packed`` (``max_gap`` included).
+    forward pass and the device post-processing as in ``infer_packed`` (``max_gap``, ``phases`` and ``vote_weight`` included).
     """
     import torch
-    from .infer import check_bridge
+    from .infer import check_bridge, check_phases, check_weight
     engine = model.engine if hasattr(model, "engine") else model
     if engine is None:
         raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
     max_gap = check_bridge(max_gap, min_run)
+    phases = check_phases(phases)
+    check_weight(vote_weight)
     dac_reads = [np.ascontiguousarray(np.asarray(r).reshape(-1), dtype=np.int16) for r in dac_reads]
     if max_windows is None:
         max_windows = 32768
@@ -226,10 +251,10 @@ def infer_reads_dac(model, dac_reads, max_windows=None, threshold=0.5, min_run=1
         d_woff = torch.from_numpy(win_off).to(dev)
         x = torch.empty(int(win_off[-1]), WINDOW_SIZE, dtype=torch.float32, device=dev)
         engine.normalize_device(d_dac, d_doff, d_woff, out=x)
-        probs = engine.infer_device(x)
         s_off = win_off * WINDOW_SIZE
-        starts, ends = _device_runs(engine, probs, torch.from_numpy(s_off).to(dev), torch.from_numpy(lengths).to(dev), threshold, min_run,
-                                    max_gap)
+        d_soff, d_len = torch.from_numpy(s_off).to(dev), torch.from_numpy(lengths).to(dev)
+        probs = _voted_probs(engine, x, d_soff, d_len, len(bucket), phases, vote_weight)
+        starts, ends = _device_runs(engine, probs, d_soff, d_len, threshold, min_run, max_gap)
         spans = spans_from_runs(starts, ends, s_off, len(bucket))
         p_host = probs.cpu().numpy() if return_probs else None
         for k, i in enumerate(bucket):

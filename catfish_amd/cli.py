@@ -75,7 +75,8 @@ def chunks_of_read(hp_positions, len_read, chunk_size=1000):
 
 
 def run_pipeline(input_dir, split_dir, chunk_size=1000, network_path="ResNetRNN", network_type="ResNetRNN",
-                 checkpoint=30000, device=None, precision="fp32", timings=None, gather_table=False, bind=False, bridge_gap=0):
+                 checkpoint=30000, device=None, precision="fp32", timings=None, gather_table=False, bind=False, bridge_gap=0,
+                 phases=(0,), vote_weight="mean"):
     """Body of the reference's ``main`` (catfish/catfish:23-94), split step included.
 
     Under ``torch.distributed.run`` (RANK / WORLD_SIZE / LOCAL_RANK in the environment) the per-file loop of
@@ -99,11 +100,16 @@ def run_pipeline(input_dir, split_dir, chunk_size=1000, network_path="ResNetRNN"
     (``main``) does that; a library caller keeps its affinity unless it asks (the default), and a binding the process took earlier
     (``placement.bind`` at start-up, as bench.py does) is reported as it is.  ``bridge_gap`` (the command line reads it from ``CATFISH_BRIDGE_GAP``): gaps of at most that
     many samples between two called stretches of a read are bridged before ``correct_short`` (``infer.bridge_gaps``); 0, the default,
-    changes nothing, more than 49 is refused (ValueError: ``min_run`` 15 + gap must stay within 64).
+    changes nothing, more than 49 is refused (ValueError: ``min_run`` 15 + gap must stay within 64).  ``phases`` / ``vote_weight``
+    (the command line reads them from ``CATFISH_TILINGS`` and ``CATFISH_TILING_WEIGHT``): shifted-window voting -- every read goes
+    through the network once per phase and the per-sample probabilities are merged before the threshold (``tilings.py``); ``(0,)``,
+    the default, changes nothing.
     """
     import time
     from . import chunks, placement, sharding, split
     bridge_gap = infer.check_bridge(bridge_gap, 15)
+    phases = infer.check_phases(phases)
+    infer.check_weight(vote_weight)
     rank, world, local_rank = sharding.dist_env()
     # before the first GPU call and the first pinned allocation: this rank, its loader thread and the library's file pool run
     # on the CPUs next to its MI355X (a no-op when the caller -- bench.py -- bound the process already; CATFISH_BIND=0 turns it off)
@@ -160,7 +166,8 @@ def run_pipeline(input_dir, split_dir, chunk_size=1000, network_path="ResNetRNN"
         mine = table = shard_error = None
         try:
             # path strings are built for this rank's block only (sharding.ListingPaths): 100 000 of them on each of 8 ranks was 15 ms
-            runner = sharding.EngineBatchRunner(model, max_windows * infer.WINDOW_SIZE, max_gap=bridge_gap) if bridge_gap else None
+            runner = sharding.EngineBatchRunner(model, max_windows * infer.WINDOW_SIZE, max_gap=bridge_gap, phases=phases,
+                                                vote_weight=vote_weight) if bridge_gap or len(phases) > 1 else None
             mine, table = sharding.chunk_files_local(model, sharding.ListingPaths(listing), chunk_size,
                                                      max_samples_per_batch=max_windows * infer.WINDOW_SIZE, batch_runner=runner, rank=rank,
                                                      world_size=world, timings=timings, file_sizes=file_sizes)
@@ -219,6 +226,22 @@ def bridge_gap_from_env():
         raise ValueError("CATFISH_BRIDGE_GAP must be an integer in 0 .. 49, got %r (%s)" % (text, exc))
 
 
+def tilings_from_env():
+    """``CATFISH_TILINGS=0,12,23`` (unset or empty: ``(0,)``) and ``CATFISH_TILING_WEIGHT=mean|centre`` (unset or empty: ``mean``; the
+    ranks of a multi-GPU job inherit both): the command line's ``phases`` and ``vote_weight``.  A value that breaks
+    ``infer.check_phases`` or names no weight is a ValueError that names the variable."""
+    from . import tilings
+    try:
+        phases = tilings.phases_from_env(os.environ.get("CATFISH_TILINGS"))
+    except ValueError as exc:
+        raise ValueError("CATFISH_TILINGS must be phases such as 0,12,23, got %r (%s)" % (os.environ.get("CATFISH_TILINGS"), exc))
+    try:
+        weight = tilings.weight_from_env(os.environ.get("CATFISH_TILING_WEIGHT"))
+    except ValueError as exc:
+        raise ValueError("CATFISH_TILING_WEIGHT must be mean or centre, got %r (%s)" % (os.environ.get("CATFISH_TILING_WEIGHT"), exc))
+    return phases, weight
+
+
 def _pick_device(local_rank):
     """One process per GPU: rank r of the node drives device r.  ``CATFISH_DEVICE`` pins every rank to one device
     instead (rehearsing the multi-rank path on a box with fewer GPUs than ranks)."""
@@ -264,13 +287,14 @@ def _build_click_main():
         homopolymers in the raw signal from a MinION sequencer.
         """
         bridge_gap_from_env()                       # a bad value ends the job here, before any rank is started
+        phases, vote_weight = tilings_from_env()    # ... and so does a bad CATFISH_TILINGS / CATFISH_TILING_WEIGHT
         if gpus > 1 and "WORLD_SIZE" not in os.environ:
             import sys
             argv = ["-i", input_dir, "-s", split_dir, "-c", str(chunk_size), "--network-path", network_path,
                     "--precision", precision]
             sys.exit(launch_ranks(gpus, argv))
         run_pipeline(input_dir, split_dir, chunk_size, network_path=network_path, precision=precision, bind=True,
-                     bridge_gap=bridge_gap_from_env())
+                     bridge_gap=bridge_gap_from_env(), phases=phases, vote_weight=vote_weight)
 
     return main
 

@@ -353,6 +353,77 @@ class HipEngine(object):
                                        C.c_void_p(stream.cuda_stream)))
         return out
 
+    # ------------------------------------------------------------------ shifted-window voting (csrc/tilings.hpp)
+    def _check_tiling_tables(self, what, offsets, lengths, total, phases):
+        import torch
+        from .tilings import check_phases, tiling_size
+        phases = check_phases(phases)
+        for name, t in (("offsets", offsets), ("lengths", lengths)):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s: %s must be a contiguous int64 CUDA tensor" % (what, name))
+        n, total = int(lengths.numel()), int(total)
+        if int(offsets.numel()) != n + 1:
+            raise ValueError("%s: offsets must have n_reads + 1 entries" % what)
+        if total < 0:
+            raise ValueError("%s: negative total" % what)
+        return phases, n, total, tiling_size(total, n, len(phases)), (C.c_int32 * len(phases))(*phases)
+
+    def retile_device(self, x_all, offsets, lengths, total, phases, stream=None):
+        """``cf_retile_windows``: ``x_all`` (float32 CUDA, at least ``tilings.tiling_size(total, n, K)`` samples) holds the base
+        layout in its first ``total`` samples; the call fills the K - 1 tiling regions behind it, zeros included
+        (``tilings.retile_host`` is the definition).  ``offsets`` [n + 1] / ``lengths`` [n]: int64 CUDA tensors of the base layout.
+        Asynchronous on the stream; one phase launches nothing.  Returns ``x_all``."""
+        import torch
+        phases, n, total, size, c_phases = self._check_tiling_tables("retile_device", offsets, lengths, total, phases)
+        if not isinstance(x_all, torch.Tensor) or not x_all.is_cuda or x_all.dtype != torch.float32 or not x_all.is_contiguous():
+            raise ValueError("retile_device: x_all must be a contiguous float32 CUDA tensor")
+        if int(x_all.numel()) < size:
+            raise ValueError("retile_device: x_all needs %d samples for %d tilings, has %d" % (size, len(phases), int(x_all.numel())))
+        if stream is None:
+            stream = torch.cuda.current_stream(x_all.device)
+        N.check(self._lib.cf_retile_windows(self._handle, C.c_void_p(x_all.data_ptr()), C.c_void_p(offsets.data_ptr()),
+                                            C.c_void_p(lengths.data_ptr()), n, total, c_phases, len(phases), C.c_void_p(stream.cuda_stream)))
+        return x_all
+
+    def vote_device(self, probs_all, offsets, lengths, total, phases, weight="mean", logits_all=None, out=None, logits_out=None, stream=None):
+        """``cf_vote_tilings``: the per-sample weighted mean over the K tilings of ``probs_all`` (float32 CUDA, at least
+        ``tilings.tiling_size(total, n, K)`` samples: what the forward pass made of a retiled buffer) -> float32 CUDA [total]
+        (``tilings.vote_host`` is the definition; ``weight``: ``"mean"`` or ``"centre"``).  ``out`` may be ``probs_all`` itself.
+        ``logits_all`` (same size) is merged by the same formula on its own values -- the voted logit is the weighted mean of the
+        logits, not the logit of the voted probability -- and the call then returns ``(voted, voted_logits)``.  Asynchronous on the
+        stream; with one phase nothing is launched (the outputs are copies when they are other buffers)."""
+        import torch
+        from .tilings import check_weight
+        phases, n, total, size, c_phases = self._check_tiling_tables("vote_device", offsets, lengths, total, phases)
+        weight = check_weight(weight)
+
+        def checked(name, t, need):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError("vote_device: %s must be a contiguous float32 CUDA tensor" % name)
+            if int(t.numel()) < need:
+                raise ValueError("vote_device: %s needs %d samples, has %d" % (name, need, int(t.numel())))
+            return t
+        checked("probs_all", probs_all, size)
+        if out is None:
+            out = torch.empty(total, dtype=torch.float32, device=probs_all.device)
+        checked("out", out, total)
+        if logits_all is not None:
+            checked("logits_all", logits_all, size)
+            if logits_out is None:
+                logits_out = torch.empty(total, dtype=torch.float32, device=probs_all.device)
+            checked("logits_out", logits_out, total)
+        elif logits_out is not None:
+            raise ValueError("vote_device: logits_out without logits_all")
+        if stream is None:
+            stream = torch.cuda.current_stream(probs_all.device)
+        N.check(self._lib.cf_vote_tilings(self._handle, C.c_void_p(probs_all.data_ptr()),
+                                          C.c_void_p(logits_all.data_ptr()) if logits_all is not None else None,
+                                          C.c_void_p(offsets.data_ptr()), C.c_void_p(lengths.data_ptr()), n, total, c_phases, len(phases),
+                                          weight, C.c_void_p(out.data_ptr()),
+                                          C.c_void_p(logits_out.data_ptr()) if logits_all is not None else None,
+                                          C.c_void_p(stream.cuda_stream)))
+        return out if logits_all is None else (out, logits_out)
+
     # ------------------------------------------------------------------ validation rounds on the card (csrc/validation.hpp)
     def _check_validation_tensors(self, what, tensors):
         import torch

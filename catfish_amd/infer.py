@@ -12,6 +12,8 @@ import os
 
 import numpy as np
 
+from .tilings import check_phases, check_weight      # noqa: F401  (phases / vote_weight are accepted wherever max_gap is)
+
 WINDOW_SIZE = 35
 
 
@@ -248,20 +250,67 @@ def _bridged_spans_of_read(raw_in, model, length, max_gap):
     return [[int(s) - 11, int(e) + 16] for s, e in zip(starts.tolist(), ends.tolist())]
 
 
-def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE, scores=False, max_gap=0):
+def _voted_read(raw_in, model, length, phases, vote_weight, scores, max_gap):
+    """``infer_class_from_raw`` for more than one tiling: the read goes through the network once per phase and everything after the
+    forward pass sees the voted probabilities (``tilings.vote_host``).  With an engine: ``cf_retile_windows``, one forward pass over
+    all tilings, ``cf_vote_tilings``, and the on-card post-processing; else ``tilings.voted_probs_of_read`` over ``model.infer`` and
+    the host definitions."""
+    from .tilings import tiling_size, voted_probs_of_read
+    x = np.ascontiguousarray(np.asarray(raw_in, dtype=np.float32).reshape(-1))
+    total = x.shape[0]
+    if hasattr(model, "_require_engine"):
+        model._require_engine()
+    engine = getattr(model, "engine", None)
+    if engine is not None:
+        import torch
+        dev = torch.device("cuda", engine.device)
+        off = torch.tensor([0, total], dtype=torch.int64, device=dev)
+        lengths = torch.tensor([length], dtype=torch.int64, device=dev)
+        x_all = torch.empty(tiling_size(total, 1, len(phases)), dtype=torch.float32, device=dev)
+        x_all[:total].copy_(torch.from_numpy(x))
+        engine.retile_device(x_all, off, lengths, total, phases)
+        probs_all = engine.infer_device(x_all.view(-1, WINDOW_SIZE))
+        voted = engine.vote_device(probs_all, off, lengths, total, phases, vote_weight)
+        out = engine.postprocess_spans_device(voted, off, lengths, scores=scores, signal=x_all[:total] if scores else None, max_gap=max_gap)
+        spans = [[int(s) - 11, int(e) + 16] for s, e in zip(out[0].tolist(), out[1].tolist())]
+        if not scores:
+            return spans, length
+        from .span_scores import span_score_summary, summary_rows
+        return spans, length, summary_rows(span_score_summary(out[2]))
+    voted = voted_probs_of_read(raw_in, model.infer, length, phases, vote_weight)
+    spans = hp_in_pred(correct_short(bridge_gaps(class_from_threshold(voted[:length]), max_gap)))
+    if not scores:
+        return spans, length
+    from .span_scores import scores_of_runs, span_score_summary, summary_rows
+    off = np.array([0, total], dtype=np.int64)
+    flat = scores_of_runs(voted, x, [s + 11 for s, _e in spans], [e - 16 for _s, e in spans], off, 1)
+    return spans, length, summary_rows(span_score_summary(flat))
+
+
+def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE, scores=False, max_gap=0, phases=(0,), vote_weight="mean"):
     """Body of infer_class_from_signal (infer.py:31-51) for an already normalised signal.
 
     ``max_gap > 0`` bridges gaps of at most that many samples between two called stretches before ``correct_short``
     (``bridge_gaps``); 0 changes nothing.
 
     ``scores=True`` returns a third value: a float64 array [n_spans, 6], one row per span in span order, columns n, mean_p,
-    min_p, max_p, level, spread (``span_scores.SCORE_COLUMNS``)."""
+    min_p, max_p, level, spread (``span_scores.SCORE_COLUMNS``).
+
+    ``phases`` (``check_phases``; more than one needs the 35-sample window) asks the network once per tiling -- the read shifted
+    right by that many samples before it is cut into windows -- and merges the per-sample probabilities by ``vote_weight``
+    (``"mean"`` or ``"centre"``, ``tilings.vote_host``) before the threshold; ``(0,)`` changes nothing."""
     raw = np.asarray(raw)
     padding_size = padding_size_for(len(raw), window_size)
     length = len(raw)
     raw = np.hstack((raw, np.array(padding_size * [0])))
     raw_in = reshape_input(raw, window_size, 1)
     max_gap = check_bridge(max_gap)
+    phases = check_phases(phases)
+    check_weight(vote_weight)
+    if len(phases) > 1:
+        if window_size != WINDOW_SIZE:
+            raise ValueError("shifted-window voting needs window_size %d, got %r" % (WINDOW_SIZE, window_size))
+        return _voted_read(raw_in, model, length, phases, vote_weight, scores, max_gap)
     if scores:
         predicted_hps, rows = _scores_of_read(raw_in, model, length, max_gap)
         return predicted_hps, length, rows
@@ -274,11 +323,12 @@ def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE, scores=Fa
     return predicted_hps, len(labels)
 
 
-def infer_class_from_signal(fast5_file, model, label=1, window_size=WINDOW_SIZE, scores=False, max_gap=0):
+def infer_class_from_signal(fast5_file, model, label=1, window_size=WINDOW_SIZE, scores=False, max_gap=0, phases=(0,), vote_weight="mean"):
     """infer.py:12-51.  Returns (list of [start, end] homopolymer spans, length of the read), and the score rows of
-    ``infer_class_from_raw`` as a third value with ``scores=True``; ``max_gap`` as there."""
+    ``infer_class_from_raw`` as a third value with ``scores=True``; ``max_gap``, ``phases`` and ``vote_weight`` as there."""
     raw = load_raw(fast5_file)
-    return infer_class_from_raw(raw, model, label=label, window_size=window_size, scores=scores, max_gap=max_gap)
+    return infer_class_from_raw(raw, model, label=label, window_size=window_size, scores=scores, max_gap=max_gap, phases=phases,
+                                vote_weight=vote_weight)
 
 
 def infer_class_from_npz(npz_file, model, label=1, window_size=WINDOW_SIZE):

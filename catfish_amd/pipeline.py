@@ -22,13 +22,14 @@ from .infer import WINDOW_SIZE
 
 class _Ticket(object):
     __slots__ = ("lengths", "s_off", "starts", "ends", "counts", "starts_h", "ends_h", "counts_h", "done", "max_runs", "labels",
-                 "keep", "rows", "rows_h")
+                 "keep", "rows", "rows_h", "tilings")
 
 
 class ReadPipeline(object):
-    def __init__(self, engine, max_samples_per_batch, threshold=0.5, min_run=15, depth=2, overlap_kernels=None, scores=False, max_gap=0):
+    def __init__(self, engine, max_samples_per_batch, threshold=0.5, min_run=15, depth=2, overlap_kernels=None, scores=False, max_gap=0,
+                 phases=(0,), vote_weight="mean"):
         import torch
-        from .infer import check_bridge
+        from .infer import check_bridge, check_phases, check_weight
         self.torch = torch
         self.eng = engine
         self.dev = torch.device("cuda", engine.device)
@@ -38,6 +39,12 @@ class ReadPipeline(object):
         # correct_short, in the same single launch (cf_postprocess_spans_bridged); 0: the launches of before.  ValueError for a
         # pair the kernel's window does not cover (min_run + max_gap > 64)
         self.max_gap = check_bridge(max_gap, self.min_run)
+        # shifted-window voting (tilings.py): with K > 1 phases a batch goes through the forward pass in K tilings -- cf_retile_windows
+        # behind cf_normalize on the same stream, ONE forward call over everything, cf_vote_tilings ahead of the post-processing -- and
+        # all that follows sees the voted probabilities of the base layout.  (0,): nothing is allocated or launched that was not before
+        self.phases = check_phases(phases)
+        check_weight(vote_weight)
+        self.vote_weight = "mean" if vote_weight is None else vote_weight
         # per-call scores (span_scores.py): one more launch per batch (cf_span_scores, right behind cf_postprocess_spans) and 40 B
         # per run more on the way down; off, nothing is launched, allocated or copied that was not before
         self.scores = bool(scores)
@@ -244,14 +251,23 @@ class ReadPipeline(object):
             # overlap mode: normalisation rides on the copy stream and overlaps the previous batch's biGRU kernels (which leave
             # wave slots and 15 KiB of LDS free on every CU) instead of delaying this batch's
             k_norm.wait_event(h2d_done)
-            x = torch.empty(n_windows, WINDOW_SIZE, dtype=torch.float32, device=self.dev)
+            n_tilings = len(self.phases)
+            if n_tilings > 1:
+                from .tilings import tiling_size
+                x_all = torch.empty(tiling_size(n_windows * WINDOW_SIZE, n_reads, n_tilings) // WINDOW_SIZE, WINDOW_SIZE,
+                                    dtype=torch.float32, device=self.dev)
+                x = x_all[:n_windows]                            # the base layout: what cf_normalize fills and cf_span_scores reads
+            else:
+                x = x_all = torch.empty(n_windows, WINDOW_SIZE, dtype=torch.float32, device=self.dev)
             self.eng.normalize_device(d_dac, d_doff, d_woff, out=x, stream=k_norm)
+            if n_tilings > 1:
+                self.eng.retile_device(x_all, d_soff, d_len, n_windows * WINDOW_SIZE, self.phases, stream=k_norm)
             copied = torch.cuda.Event()
             copied.record(k_norm)
         t = _Ticket()
         with torch.cuda.stream(self.compute):                    # overlap mode: the compute stream only ever holds the forward pass
             self.compute.wait_event(copied)
-            probs = self.eng.infer_device(x, stream=self.compute)
+            probs = probs_all = self.eng.infer_device(x_all, stream=self.compute)
             infer_done = torch.cuda.Event()
             infer_done.record(self.compute)
         with torch.cuda.stream(k_post):                          # overlap mode: post-processing overlaps the next batch's forward pass
@@ -260,6 +276,8 @@ class ReadPipeline(object):
             # never written (cf_postprocess_spans with labels = NULL) -- except for min_run > 64, which takes the two older kernels
             max_runs = n_windows * WINDOW_SIZE // self.min_run + 16
             total = n_windows * WINDOW_SIZE
+            if n_tilings > 1:
+                probs = self.eng.vote_device(probs_all, d_soff, d_len, total, self.phases, self.vote_weight, stream=k_post)
             # bridged runs hold samples below the threshold: their scores follow the labels, which are written only then
             by_labels = self.max_gap > 0 and self.scores
             labels = torch.empty(total, dtype=torch.uint8, device=self.dev) if self.min_run > 64 or by_labels else None
@@ -309,6 +327,7 @@ class ReadPipeline(object):
             t.done.record(self.down)
         t.lengths, t.s_off, t.max_runs, t.labels = lengths, win_off * WINDOW_SIZE, max_runs, labels
         t.keep = (d_dac, d_tab, x, probs, slot)                  # keep device buffers alive until collected
+        t.tilings = (x_all, probs_all) if n_tilings > 1 else None   # every tiling's input and probabilities, alive until collected
         self.inflight[slot] = t
         return t
 
@@ -340,7 +359,7 @@ class ReadPipeline(object):
             # the slot is free again and the batch's device buffers are released whether or not its results were good: a
             # failed batch must not leave the pipeline claiming "too many batches in flight" on the next submit
             self.inflight[t.keep[-1]] = None
-            t.keep = None
+            t.keep = t.tilings = None
             t.starts = t.ends = t.counts = t.rows = None
         if not as_lists:
             read_of = np.searchsorted(t.s_off, starts, side="right") - 1

@@ -210,7 +210,7 @@ class RNN(object):
         return self.engine.infer_host(np.asarray(windows), return_logits=True)
 
     def score_validation_device(self, vset, selection, thresholds=(0.5,), run_edges=None, curve_shift=None, border_reach=None,
-                                bridge_gap=0):
+                                bridge_gap=0, phases=(0,), vote_weight="mean"):
         """One validation round on the card: the stretches ``selection`` (``vset.select``) of a
         ``device_validation.DeviceValidationSet`` -> what ``device_validation.score_host`` returns for them, (right int64 [n],
         ce_sum float64 [n], counts int64 [K, 4]).  With ``run_edges`` (a tuple of up to 7 ascending run lengths, possibly empty)
@@ -228,7 +228,12 @@ class RNN(object):
         forward pass, same copy back; room ``capacity["border_cells"]``, label work space shared with the run states).  The set's
         labels must all be 0 or 1 then (ValueError).  ``bridge_gap`` (0 .. 49): the prediction the run states and the borders are
         counted on has its gaps of at most that many samples bridged first (``infer.bridge_gaps``; ``cf_validation_run_states_bridged``
-        and ``cf_validation_run_borders_bridged``); the per-sample counts are not touched.
+        and ``cf_validation_run_borders_bridged``); the per-sample counts are not touched.  ``phases`` / ``vote_weight``
+        (``infer.check_phases``; shifted-window voting, ``tilings.py``): after the gather ``cf_retile_windows`` lays out the K tilings,
+        the forward pass writes probabilities and logits for all of them (``validation_buffers["tensors"]["tilings_probs"]`` /
+        ``["tilings_logits"]``, room ``capacity["tiling_samples"]``, the same grow-only rule), and ``cf_vote_tilings`` writes the voted
+        probabilities and logits (the weighted mean of the logits, not the logit of the voted probability) that everything after it
+        consumes; ``(0,)`` launches and allocates nothing that was not before.
 
         The selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes
         probabilities and logits (the weights just trained, as ``score_windows`` uses them), ``cf_validation_score`` reduces them
@@ -238,8 +243,11 @@ class RNN(object):
         import torch
         from . import device_validation as dv
         self._require_engine()
-        from .infer import check_bridge
+        from .infer import check_bridge, check_phases, check_weight
+        from .tilings import tiling_size
         bridge_gap = check_bridge(bridge_gap, 15)
+        phases = check_phases(phases)
+        check_weight(vote_weight)
         thresholds = tuple(float(t) for t in thresholds)
         if not thresholds:
             raise ValueError("score_validation_device: no threshold given")
@@ -274,6 +282,8 @@ class RNN(object):
                          "run_work": max(self.engine.run_borders_work_bytes(total, min(k_all, dv.MAX_THRESHOLDS)), 1)})
         if curve_shift is not None:
             need["curve_cells"] = curve_cells
+        if len(phases) > 1:
+            need["tiling_samples"] = tiling_size(total, n, len(phases))
         if any(book["capacity"].get(key, 0) < value for key, value in need.items()):
             cap = {key: max(book["capacity"].get(key, 0), value) for key, value in need.items()}
             f32 = lambda count: torch.empty(count, dtype=torch.float32, device=device)     # noqa: E731
@@ -287,6 +297,8 @@ class RNN(object):
                                                   + cap.get("border_cells", 0) + cap.get("curve_cells", 0), dtype=torch.int64, device=device)}
             if "run_work" in cap:                                                    # corrected labels, one array per threshold of a group
                 book["tensors"]["run_work"] = torch.empty(cap["run_work"], dtype=torch.uint8, device=device)
+            if "tiling_samples" in cap:                                              # every tiling's input, probabilities and logits
+                book["tensors"].update({key: f32(cap["tiling_samples"]) for key in ("tilings_x", "tilings_probs", "tilings_logits")})
             book["capacity"] = cap
             book["allocations"] += 1
         if book["thresholds"] is None or book["thresholds"][0] != thresholds or book["thresholds"][1].device != device:
@@ -306,8 +318,16 @@ class RNN(object):
         runs_at = 2 * n + 4 * k_all
         borders_at, curve_at = runs_at + run_cells, runs_at + run_cells + border_cells
         runs_d, borders_d, curve_d = out[runs_at:borders_at], out[borders_at:curve_at], out[curve_at:]
-        self.engine.gather_validation(signal, labels, src_d, len_d, bounds_d, total, longest, x, y)
-        self.engine.infer_device(x.view(-1, self.window), out=probs, logits=logits)
+        if len(phases) > 1:
+            size = need["tiling_samples"]
+            x_all, probs_all, logits_all = t["tilings_x"][:size], t["tilings_probs"][:size], t["tilings_logits"][:size]
+            self.engine.gather_validation(signal, labels, src_d, len_d, bounds_d, total, longest, x_all[:total], y)
+            self.engine.retile_device(x_all, bounds_d, len_d, total, phases)
+            self.engine.infer_device(x_all.view(-1, self.window), out=probs_all, logits=logits_all)
+            self.engine.vote_device(probs_all, bounds_d, len_d, total, phases, vote_weight, logits_all=logits_all, out=probs, logits_out=logits)
+        else:
+            self.engine.gather_validation(signal, labels, src_d, len_d, bounds_d, total, longest, x, y)
+            self.engine.infer_device(x.view(-1, self.window), out=probs, logits=logits)
         for k0 in range(0, k_all, dv.MAX_THRESHOLDS):
             k1 = min(k_all, k0 + dv.MAX_THRESHOLDS)
             self.engine.score_validation(probs, logits, y, bounds_d, total, longest, book["thresholds"][1][k0:k1], right_d, ce_d,

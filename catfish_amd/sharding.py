@@ -486,7 +486,7 @@ class EngineBatchRunner(object):
     host like ``infer.process_signal`` and goes through ``batching.infer_reads``.
     """
 
-    def __init__(self, model, max_samples_per_batch, threshold=0.5, min_run=15, max_gap=0):
+    def __init__(self, model, max_samples_per_batch, threshold=0.5, min_run=15, max_gap=0, phases=(0,), vote_weight="mean"):
         from .pipeline import ReadPipeline
         self.engine = model.engine if hasattr(model, "engine") else model
         if self.engine is None:
@@ -494,8 +494,11 @@ class EngineBatchRunner(object):
         self.max_samples = int(max_samples_per_batch)
         self.threshold, self.min_run = threshold, min_run
         # max_gap: gaps of at most that many samples between two called stretches are bridged (infer.bridge_gaps), on both routes
-        self.pipe = ReadPipeline(self.engine, self.max_samples, threshold=threshold, min_run=min_run, max_gap=max_gap)
+        # phases / vote_weight: shifted-window voting (tilings.py), on both routes too
+        self.pipe = ReadPipeline(self.engine, self.max_samples, threshold=threshold, min_run=min_run, max_gap=max_gap, phases=phases,
+                                 vote_weight=vote_weight)
         self.max_gap = self.pipe.max_gap
+        self.phases, self.vote_weight = self.pipe.phases, self.pipe.vote_weight
 
     def run(self, batches, compact=False):
         """``batches``: iterable of lists of raw reads -> yields per batch, in order, ``[(spans, length)]`` or (``compact``)
@@ -568,7 +571,8 @@ class EngineBatchRunner(object):
         normed = [normalize_raw_signal(np.asarray(r), "median") for r in reads]
         max_windows = max(1, self.max_samples // WINDOW_SIZE)
         return (None, batching.infer_reads(self.engine, normed, max_windows=max_windows,
-                                           threshold=self.threshold, min_run=self.min_run, max_gap=self.max_gap))
+                                           threshold=self.threshold, min_run=self.min_run, max_gap=self.max_gap,
+                                           phases=self.phases, vote_weight=self.vote_weight))
 
     def _drive(self, items):
         """Up to the pipeline's depth of batches in flight: ``items`` submits lazily (each element is (ticket, host-path results

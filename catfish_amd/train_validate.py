@@ -494,7 +494,7 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
 
 
 def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start="complete", max_number=856, run_edges=None,
-                    border_reach=None, bridge_gap=0):
+                    border_reach=None, bridge_gap=0, phases=(0,), vote_weight="mean"):
     """The reference's precision / recall sweep (networks/precision_recall_ROC.py:85-100: ``class_from_threshold`` --
     ``p >= t`` -- then ``compute_f1`` per threshold) over a ``DeviceValidationSet``: ONE forward pass, every threshold counted
     from its probabilities on the card.  The stretches are ``validate``'s (same selection, same tail rule for the true
@@ -511,19 +511,24 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     the corrected prediction -- and ``called_borders`` -- the called runs against the truth --, each ``border_report``'s dict.
 
     ``bridge_gap`` (with ``run_edges`` or ``border_reach``; 0 .. 49): the run states and the borders are those of the prediction
-    with its gaps of at most that many samples bridged (``infer.bridge_gaps``); tp / fp / tn / fn stay per-sample counts."""
-    from .infer import check_bridge
+    with its gaps of at most that many samples bridged (``infer.bridge_gaps``); tp / fp / tn / fn stay per-sample counts.
+
+    ``phases`` / ``vote_weight`` (``infer.check_phases``): shifted-window voting -- every count is taken from the probabilities voted
+    over those tilings (``tilings.vote_host``); ``(0,)`` changes nothing."""
+    from .infer import check_bridge, check_phases
     bridge_gap = check_bridge(bridge_gap, 15)
+    phases = check_phases(phases)
+    voted = {"phases": phases, "vote_weight": vote_weight} if len(phases) > 1 else {}      # (0,): the call of before
     if bridge_gap and run_edges is None and border_reach is None:
         raise ValueError("threshold_sweep: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
-    bridged = {"bridge_gap": bridge_gap} if bridge_gap else {}
+    bridged = dict(voted, bridge_gap=bridge_gap) if bridge_gap else voted
     thresholds = [float(t) for t in thresholds]
     selection = vset.select(network.window, max_seq_length, validation_start, max_number)
     if len(selection[0]) == 0:
         raise ZeroDivisionError("validation selected no read")
     run_states = borders = None
     if run_edges is None and border_reach is None:
-        _right, _ce_sum, counts = network.score_validation_device(vset, selection, thresholds)
+        _right, _ce_sum, counts = network.score_validation_device(vset, selection, thresholds, **voted)
     elif border_reach is None:
         _right, _ce_sum, counts, run_states = network.score_validation_device(vset, selection, thresholds, run_edges=run_edges, **bridged)
     else:
@@ -558,6 +563,31 @@ def bridge_sweep(network, vset, gaps, max_seq_length, threshold=0.5, validation_
                               border_reach=border_reach, bridge_gap=gap)[0]
         out = {"bridge_gap": int(gap)}
         out.update({key: row[key] for key in ("hp_complete", "hp_found", "called_absent", "hp_states", "called_states")})
+        for name, part in (("hp_interrupted", row["hp_borders"]), ("called_interrupted", row["called_borders"])):
+            judged = int(np.sum(part["left"]))
+            out[name] = part["interrupted_runs"] / judged if judged else 0
+        rows.append(out)
+    return rows
+
+
+def tiling_sweep(network, vset, phase_sets, max_seq_length, weight="mean", threshold=0.5, validation_start="complete", max_number=856,
+                 run_edges=(), border_reach=BORDER_REACH):
+    """What shifted-window voting does to a round, for every phase set of ``phase_sets`` (each ``infer.check_phases``'s; ``(0,)`` is
+    the network as it is), over a ``DeviceValidationSet`` at one threshold: one ``threshold_sweep`` round per phase set (same
+    stretches; ``validation_start`` should not be "random"), merged by ``weight``.  -> a list of dicts {phases, weight, tp, fp, tn,
+    fn, precision, recall, f1 (per sample), hp_complete, hp_found, called_absent (``run_state_rates``), hp_states, called_states,
+    hp_interrupted, called_interrupted}: the last two are the share of the true (called) runs that are not absent and have at
+    least one interruption in the other array -- homopolymers found in pieces.  Whether voting improves the calls on real reads
+    is what this function is there to find out."""
+    from .infer import check_phases
+    rows = []
+    for phases in phase_sets:
+        phases = check_phases(phases)
+        row = threshold_sweep(network, vset, [threshold], max_seq_length, validation_start, max_number, run_edges=run_edges,
+                              border_reach=border_reach, phases=phases, vote_weight=weight)[0]
+        out = {"phases": list(phases), "weight": weight}
+        out.update({key: row[key] for key in ("tp", "fp", "tn", "fn", "precision", "recall", "f1", "hp_complete", "hp_found",
+                                              "called_absent", "hp_states", "called_states")})
         for name, part in (("hp_interrupted", row["hp_borders"]), ("called_interrupted", row["called_borders"])):
             judged = int(np.sum(part["left"]))
             out[name] = part["interrupted_runs"] / judged if judged else 0

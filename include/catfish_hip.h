@@ -652,6 +652,37 @@ int cf_validation_run_borders_bridged(cf_model* m, const float* probs, const uin
 int cf_validation_curve(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length, int64_t n,
                         int64_t total, int64_t longest, int32_t shift, int64_t* hist_out, int64_t hist_capacity, void* stream);
 
+/* Shifted-window voting (csrc/tilings.hpp, index rules in csrc/tilings_rule.hpp; catfish_amd/tilings.py states both steps in numpy --
+ * retile_host and vote_host are their definitions).  A read is cut into 35-sample windows at one fixed phase; these two calls let the
+ * same reads go through the forward pass in K tilings whose window borders fall phi_j samples apart, and merge the per-sample
+ * results.  Base layout: offsets [n_reads + 1] / lengths [n_reads], device int64 -- read r owns packed samples offsets[r] ..
+ * offsets[r + 1] (multiples of 35), the first lengths[r] real, total = offsets[n_reads].  One buffer of
+ *   tiling size = total + (K - 1) * (total + 35 n_reads)
+ * samples holds the base region [0, total) and behind it tiling j >= 1 at T_j = total + (j - 1) * (total + 35 n_reads); read r of
+ * tiling j starts at T_j + offsets[r] + 35 r and is one window longer than in the base layout.
+ *   phases   HOST int32 [n_phases]: 1..8 strictly ascending ints in 0 .. 34, the first one 0; they travel by value in the kernel
+ *            arguments, so nothing is copied and both calls are asynchronous on `stream` and capturable.  m may be NULL (the
+ *            current device is used).
+ * cf_retile_windows: x[T_j + offsets[r] + 35 r + phi_j + i] = x[offsets[r] + i] for i < lengths[r], and every other sample of the
+ * tiling regions 0 -- one launch writes all K - 1 regions completely.  n_phases == 1 launches nothing.
+ * cf_vote_tilings: for i < lengths[r], with t_j = (i + phi_j) % 35, p_0 = probs[offsets[r] + i] and p_j the same sample in tiling j,
+ *   probs_out[offsets[r] + i] = float32((sum_j w(t_j) * double(p_j)) / (sum_j w(t_j))),  both sums in double in the order j = 0 .. K - 1,
+ * with w(t) = 1 (weight 0, "mean") or min(t + 1, 35 - t) (weight 1, "centre").  Samples of the zero tails keep the base value.
+ * logits (NULL ok; logits_out NULL exactly then) are merged by the same formula on their own values: the voted logit is the weighted
+ * mean of the logits, not the logit of the voted probability.  probs_out [total] may be probs itself (logits_out, logits).
+ * n_phases == 1 launches nothing, except that the outputs are copied when they are other buffers.
+ * A table entry that is not what the layout promises -- a length that is negative or longer than its region, an offset outside
+ * 0 .. total or not a multiple of 35, a descending pair of offsets -- makes that read's tiling regions zero and its vote the base
+ * value; where offsets descend, the reads beside the pair may come out so as well.  Whatever the tables hold, nothing is read or
+ * written outside [0, tiling size) of x / probs / logits and [0, total) of the outputs.
+ * CF_ERR_INVALID before any launch for a null pointer, a negative size, more than 2^31 - 1 reads or 2^40 samples, total % 35 != 0,
+ * phases that break the rule above, or an unknown weight. */
+int cf_retile_windows(cf_model* m, float* x, const int64_t* offsets, const int64_t* lengths, int64_t n_reads, int64_t total,
+                      const int32_t* phases, int32_t n_phases, void* stream);
+int cf_vote_tilings(cf_model* m, const float* probs, const float* logits, const int64_t* offsets, const int64_t* lengths,
+                    int64_t n_reads, int64_t total, const int32_t* phases, int32_t n_phases, int32_t weight, float* probs_out,
+                    float* logits_out, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream) for bench.py's
  * roofline report.  cf_profile_enable(m, N) makes every N-th cf_infer call
  * (N = 1: every call; 0 = off) record events around each of its kernels; cf_profile_read synchronises and returns, for
