@@ -143,48 +143,20 @@ def scores_from_runs(scores, n_reads):
     return [rows[bounds[r]:bounds[r + 1]] for r in range(n_reads)]
 
 
-def _device_runs(engine, probs, offs, lens, threshold, min_run, max_gap):
-    """Sorted packed run boundaries of the corrected labels; ``max_gap > 0``: gaps bridged first (``infer.bridge_gaps``), in the one
-    launch of ``cf_postprocess_spans_bridged``; 0: the two launches of before."""
-    if max_gap > 0:
-        return engine.postprocess_spans_device(probs, offs, lens, threshold=threshold, min_run=min_run, max_gap=max_gap)
-    labels = engine.postprocess_device(probs, offs, lens, threshold=threshold, min_run=min_run)
-    return engine.spans_device(labels)
-
-
-def _voted_probs(engine, x, offs, lens, n_reads, phases, vote_weight):
-    """The probabilities of the base layout ``x`` ([n_windows, 35] CUDA), voted over the tilings of ``phases``
-    (``tilings.vote_host``): ``cf_retile_windows``, ONE forward pass over all tilings, ``cf_vote_tilings``.  One phase: the forward
-    pass alone, as before."""
-    import torch
-    if len(phases) == 1:
-        return engine.infer_device(x)
-    from .tilings import tiling_size
-    total = int(x.numel())
-    x_all = torch.empty(tiling_size(total, n_reads, len(phases)) // WINDOW_SIZE, WINDOW_SIZE, dtype=torch.float32, device=x.device)
-    x_all[:total // WINDOW_SIZE].copy_(x.view(-1, WINDOW_SIZE))
-    engine.retile_device(x_all, offs, lens, total, phases)
-    return engine.vote_device(engine.infer_device(x_all), offs, lens, total, phases, vote_weight)
-
-
 def infer_packed(engine, packed, threshold=0.5, min_run=15, return_probs=False, max_gap=0, phases=(0,), vote_weight="mean"):
     """PackedReads -> list of (spans, read length) per read, optionally with per-read probabilities.  ``max_gap``: gaps of at most
     that many samples between two called stretches of a read are bridged before ``correct_short`` (0: none; ValueError for
     ``min_run + max_gap > 64``).  ``phases`` / ``vote_weight``: shifted-window voting (``infer.check_phases``, ``tilings.py``);
     the probabilities that are thresholded -- and returned -- are then the voted ones."""
     import torch
-    from .infer import check_bridge, check_phases, check_weight
-    max_gap = check_bridge(max_gap, min_run)
-    phases = check_phases(phases)
-    check_weight(vote_weight)
+    from . import calling
+    rule = calling.CallRule.of(threshold, min_run, max_gap, phases, vote_weight)
     dev = torch.device("cuda", engine.device)
-    x = torch.from_numpy(packed.x).to(dev, non_blocking=True)
+    x_all, x = calling.tiling_buffer(rule, packed.n_windows, packed.n_reads, dev)
+    x.copy_(torch.from_numpy(packed.x), non_blocking=True)
     offs = torch.from_numpy(packed.sample_offsets).to(dev)
     lens = torch.from_numpy(packed.lengths).to(dev)
-    probs = _voted_probs(engine, x, offs, lens, packed.n_reads, phases, vote_weight)
-    starts, ends = _device_runs(engine, probs, offs, lens, threshold, min_run, max_gap)
-    spans = spans_from_runs(starts, ends, packed.sample_offsets, packed.n_reads)
-    result = [(spans[i], int(packed.lengths[i])) for i in range(packed.n_reads)]
+    result, probs = calling.spans_of_batch(engine, rule, x_all, offs, lens, packed.sample_offsets, packed.lengths)
     if return_probs:
         p = probs.cpu().numpy()
         so = packed.sample_offsets
@@ -196,13 +168,11 @@ def infer_reads(model, signals, max_windows=None, threshold=0.5, min_run=15, max
     """Many normalised reads -> [(spans, length)] in input order, length-bucketed packed launches; ``max_gap``, ``phases`` and
     ``vote_weight`` as in ``infer_packed`` (``max_windows`` bounds the base layout of a launch: K tilings make it about K times as
     large)."""
-    from .infer import check_bridge, check_phases, check_weight
+    from .calling import CallRule
     engine = model.engine if hasattr(model, "engine") else model
     if engine is None:
         raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
-    max_gap = check_bridge(max_gap, min_run)
-    phases = check_phases(phases)
-    check_weight(vote_weight)
+    rule = CallRule.of(threshold, min_run, max_gap, phases, vote_weight)
     signals = [np.asarray(s).reshape(-1) for s in signals]
     if max_windows is None:
         max_windows = 32768
@@ -210,8 +180,8 @@ def infer_reads(model, signals, max_windows=None, threshold=0.5, min_run=15, max
     with quiet_gc():
         for bucket in length_buckets([len(s) for s in signals], max_windows):
             packed = pack_reads([signals[i] for i in bucket])
-            for i, res in zip(bucket, infer_packed(engine, packed, threshold, min_run, max_gap=max_gap, phases=phases,
-                                                    vote_weight=vote_weight)):
+            for i, res in zip(bucket, infer_packed(engine, packed, rule.threshold, rule.min_run, max_gap=rule.max_gap, phases=rule.phases,
+                                                    vote_weight=rule.vote_weight)):
                 out[i] = res
     return out
 
@@ -225,13 +195,11 @@ def infer_reads_dac(model, dac_reads, max_windows=None, threshold=0.5, min_run=1
     forward pass and the device post-processing as in ``infer_packed`` (``max_gap``, ``phases`` and ``vote_weight`` included).
     """
     import torch
-    from .infer import check_bridge, check_phases, check_weight
+    from . import calling
     engine = model.engine if hasattr(model, "engine") else model
     if engine is None:
         raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
-    max_gap = check_bridge(max_gap, min_run)
-    phases = check_phases(phases)
-    check_weight(vote_weight)
+    rule = calling.CallRule.of(threshold, min_run, max_gap, phases, vote_weight)
     dac_reads = [np.ascontiguousarray(np.asarray(r).reshape(-1), dtype=np.int16) for r in dac_reads]
     if max_windows is None:
         max_windows = 32768
@@ -249,16 +217,14 @@ def infer_reads_dac(model, dac_reads, max_windows=None, threshold=0.5, min_run=1
         d_dac = torch.from_numpy(flat).to(dev)
         d_doff = torch.from_numpy(dac_off).to(dev)
         d_woff = torch.from_numpy(win_off).to(dev)
-        x = torch.empty(int(win_off[-1]), WINDOW_SIZE, dtype=torch.float32, device=dev)
+        x_all, x = calling.tiling_buffer(rule, int(win_off[-1]), len(bucket), dev)
         engine.normalize_device(d_dac, d_doff, d_woff, out=x)
         s_off = win_off * WINDOW_SIZE
         d_soff, d_len = torch.from_numpy(s_off).to(dev), torch.from_numpy(lengths).to(dev)
-        probs = _voted_probs(engine, x, d_soff, d_len, len(bucket), phases, vote_weight)
-        starts, ends = _device_runs(engine, probs, d_soff, d_len, threshold, min_run, max_gap)
-        spans = spans_from_runs(starts, ends, s_off, len(bucket))
+        result, probs = calling.spans_of_batch(engine, rule, x_all, d_soff, d_len, s_off, lengths)
         p_host = probs.cpu().numpy() if return_probs else None
         for k, i in enumerate(bucket):
-            out[i] = (spans[k], int(lengths[k]))
+            out[i] = result[k]
             if return_probs:
                 probs_out[i] = p_host[s_off[k]:s_off[k] + lengths[k]]
     return (out, probs_out) if return_probs else out

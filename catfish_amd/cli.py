@@ -107,9 +107,8 @@ def run_pipeline(input_dir, split_dir, chunk_size=1000, network_path="ResNetRNN"
     """
     import time
     from . import chunks, placement, sharding, split
-    bridge_gap = infer.check_bridge(bridge_gap, 15)
-    phases = infer.check_phases(phases)
-    infer.check_weight(vote_weight)
+    from .calling import CallRule
+    rule = CallRule.of(max_gap=bridge_gap, phases=phases, vote_weight=vote_weight)
     rank, world, local_rank = sharding.dist_env()
     # before the first GPU call and the first pinned allocation: this rank, its loader thread and the library's file pool run
     # on the CPUs next to its MI355X (a no-op when the caller -- bench.py -- bound the process already; CATFISH_BIND=0 turns it off)
@@ -166,8 +165,8 @@ def run_pipeline(input_dir, split_dir, chunk_size=1000, network_path="ResNetRNN"
         mine = table = shard_error = None
         try:
             # path strings are built for this rank's block only (sharding.ListingPaths): 100 000 of them on each of 8 ranks was 15 ms
-            runner = sharding.EngineBatchRunner(model, max_windows * infer.WINDOW_SIZE, max_gap=bridge_gap, phases=phases,
-                                                vote_weight=vote_weight) if bridge_gap or len(phases) > 1 else None
+            runner = sharding.EngineBatchRunner(model, max_windows * infer.WINDOW_SIZE, max_gap=rule.max_gap, phases=rule.phases,
+                                                vote_weight=rule.vote_weight) if rule.bridged or rule.voted else None
             mine, table = sharding.chunk_files_local(model, sharding.ListingPaths(listing), chunk_size,
                                                      max_samples_per_batch=max_windows * infer.WINDOW_SIZE, batch_runner=runner, rank=rank,
                                                      world_size=world, timings=timings, file_sizes=file_sizes)

@@ -160,6 +160,22 @@ class HipEngine(object):
                                    C.c_void_p(stream.cuda_stream)))
         return out
 
+    @staticmethod
+    def _check_packed(probs, read_offsets, read_lengths, run_tables=()):
+        """The packed layout every post-processing call takes: contiguous float32 CUDA ``probs``, contiguous int64 CUDA tables,
+        ``n_reads + 1`` offsets -> (n_reads, total)."""
+        import torch
+        if not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
+            raise ValueError("probs must be a contiguous float32 CUDA tensor")
+        for t in (read_offsets, read_lengths) + tuple(run_tables):
+            if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("read_offsets, read_lengths, starts and counts must be contiguous int64 CUDA tensors" if run_tables
+                                 else "read_offsets/read_lengths must be contiguous int64 CUDA tensors")
+        n_reads = int(read_lengths.numel())
+        if int(read_offsets.numel()) != n_reads + 1:
+            raise ValueError("read_offsets must have n_reads + 1 entries")
+        return n_reads, int(probs.numel())
+
     def postprocess_device(self, probs, read_offsets, read_lengths, threshold=0.5, min_run=15, out=None, stream=None):
         """Device threshold + correct_short over packed padded reads.
 
@@ -167,15 +183,7 @@ class HipEngine(object):
         read_lengths: int64 CUDA [n_reads] (real lengths) -> uint8 CUDA labels [total] (padding = 0).
         """
         import torch
-        if not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
-            raise ValueError("probs must be a contiguous float32 CUDA tensor")
-        for t in (read_offsets, read_lengths):
-            if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("read_offsets/read_lengths must be contiguous int64 CUDA tensors")
-        n_reads = int(read_lengths.numel())
-        if int(read_offsets.numel()) != n_reads + 1:
-            raise ValueError("read_offsets must have n_reads + 1 entries")
-        total = int(probs.numel())
+        n_reads, total = self._check_packed(probs, read_offsets, read_lengths)
         if out is None:
             out = torch.empty(total, dtype=torch.uint8, device=probs.device)
         if stream is None:
@@ -185,6 +193,38 @@ class HipEngine(object):
                                          n_reads, total, float(threshold), int(min_run),
                                          C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)))
         return out
+
+    def postprocess_spans_launch(self, probs, read_offsets, read_lengths, rule, signal=None, stream=None, want_labels=False, max_runs=None):
+        """The asynchronous half of ``postprocess_spans_device``: threshold, bridging (``rule.bridged``), ``correct_short`` and the run
+        boundaries in ONE launch (``cf_postprocess_spans`` / ``cf_postprocess_spans_bridged``), then the score rows of those runs when
+        ``rule.scores`` (``span_scores_device``; by the labels when the runs are bridged).  ``rule``: a ``calling.CallRule``.  ->
+        (starts, ends, counts, labels, rows), all on the card and not waited for: int64 [max_runs] (unsorted; default room
+        ``rule.max_runs(total)``), int64 [2] = how many starts / ends there were (possibly more than the room), the uint8 labels
+        [total] -- written only when ``want_labels`` or the scores need them, else None: the library never writes labels -- and the
+        three score tensors or None."""
+        import torch
+        n_reads, total = self._check_packed(probs, read_offsets, read_lengths)
+        max_runs = rule.max_runs(total) if max_runs is None else int(max_runs)
+        dev = probs.device
+        labels = torch.empty(total, dtype=torch.uint8, device=dev) if want_labels or rule.scores_by_labels else None
+        starts = torch.empty(max_runs, dtype=torch.int64, device=dev)
+        ends = torch.empty(max_runs, dtype=torch.int64, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        head = (self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(read_offsets.data_ptr()), C.c_void_p(read_lengths.data_ptr()), n_reads,
+                total, rule.threshold)
+        tail = (rule.min_run, C.c_void_p(labels.data_ptr()) if labels is not None else None, max_runs, C.c_void_p(starts.data_ptr()),
+                C.c_void_p(ends.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(stream.cuda_stream))
+        if rule.bridged:
+            N.check(self._lib.cf_postprocess_spans_bridged(*head, rule.max_gap, *tail))
+        else:
+            N.check(self._lib.cf_postprocess_spans(*head, *tail))
+        rows = None
+        if rule.scores:
+            rows = self.span_scores_device(probs, signal, read_offsets, read_lengths, starts, counts, rule.threshold, stream,
+                                           labels=labels if rule.scores_by_labels else None)
+        return starts, ends, counts, labels, rows
 
     def postprocess_spans_device(self, probs, read_offsets, read_lengths, threshold=0.5, min_run=15, max_runs=None, labels=False,
                                  stream=None, scores=False, signal=None, max_gap=0):
@@ -197,48 +237,17 @@ class HipEngine(object):
 
         ``max_gap > 0`` bridges gaps of at most that many samples first (``cf_postprocess_spans_bridged``; ``infer.bridge_gaps`` is
         the definition); the score rows then come from ``cf_span_scores_labels`` over the labels of the same launch, so that they
-        cover the samples of the bridged gaps.  A pair with ``min_run + max_gap > 64`` raises ValueError."""
-        import torch
-        from .infer import check_bridge
-        max_gap = check_bridge(max_gap, min_run)
-        if not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
-            raise ValueError("probs must be a contiguous float32 CUDA tensor")
-        for t in (read_offsets, read_lengths):
-            if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("read_offsets/read_lengths must be contiguous int64 CUDA tensors")
-        n_reads, total = int(read_lengths.numel()), int(probs.numel())
-        if int(read_offsets.numel()) != n_reads + 1:
-            raise ValueError("read_offsets must have n_reads + 1 entries")
-        if max_runs is None:
-            max_runs = total // max(1, int(min_run)) + 16
-        dev = probs.device
-        by_labels = scores and max_gap > 0                                                # the score walk follows the labels
-        lab = torch.empty(total, dtype=torch.uint8, device=dev) if labels or by_labels else None      # NULL: the library never writes labels
-        starts = torch.empty(max_runs, dtype=torch.int64, device=dev)
-        ends = torch.empty(max_runs, dtype=torch.int64, device=dev)
-        counts = torch.empty(2, dtype=torch.int64, device=dev)
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        if max_gap > 0:
-            N.check(self._lib.cf_postprocess_spans_bridged(
-                self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(read_offsets.data_ptr()), C.c_void_p(read_lengths.data_ptr()), n_reads,
-                total, float(threshold), max_gap, int(min_run), C.c_void_p(lab.data_ptr()) if lab is not None else None, int(max_runs),
-                C.c_void_p(starts.data_ptr()), C.c_void_p(ends.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(stream.cuda_stream)))
-        else:
-            N.check(self._lib.cf_postprocess_spans(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(read_offsets.data_ptr()),
-                                                   C.c_void_p(read_lengths.data_ptr()), n_reads, total, float(threshold), int(min_run),
-                                                   C.c_void_p(lab.data_ptr()) if lab is not None else None, int(max_runs),
-                                                   C.c_void_p(starts.data_ptr()), C.c_void_p(ends.data_ptr()), C.c_void_p(counts.data_ptr()),
-                                                   C.c_void_p(stream.cuda_stream)))
-        rows = None
-        if scores:
-            rows = self.span_scores_device(probs, signal, read_offsets, read_lengths, starts, counts, threshold, stream,
-                                           labels=lab if by_labels else None)
+        cover the samples of the bridged gaps.  A pair with ``min_run + max_gap > 64`` raises ValueError.
+
+        ``postprocess_spans_launch`` and one wait; a run list that overflows is launched again with the true count."""
+        from .calling import CallRule
+        rule = CallRule.of(threshold, min_run, max_gap, scores=scores)
+        starts, ends, counts, lab, rows = self.postprocess_spans_launch(probs, read_offsets, read_lengths, rule, signal, stream, labels, max_runs)
         n_s, n_e = (int(v) for v in counts.cpu().tolist())      # synchronises the stream
         self.check_error()
         if n_s != n_e:
             raise RuntimeError("cf_postprocess_spans: %d run starts but %d run ends" % (n_s, n_e))
-        if n_s > max_runs:
+        if n_s > int(starts.numel()):
             return self.postprocess_spans_device(probs, read_offsets, read_lengths, threshold, min_run, n_s, labels, stream, scores, signal,
                                                  max_gap)
         out = (np.sort(starts[:n_s].cpu().numpy()), np.sort(ends[:n_e].cpu().numpy()))
@@ -247,7 +256,8 @@ class HipEngine(object):
         if scores:
             from .span_scores import scores_from_device_rows
             flat, _order = scores_from_device_rows(starts[:n_s].cpu().numpy(), rows[0][:n_s].cpu().numpy(), rows[1][:n_s].cpu().numpy(),
-                                                   rows[2][:n_s].cpu().numpy(), read_offsets.cpu().numpy(), n_reads, signal is not None)
+                                                   rows[2][:n_s].cpu().numpy(), read_offsets.cpu().numpy(), int(read_lengths.numel()),
+                                                   signal is not None)
             if not np.array_equal(flat["end"], out[1]):
                 raise RuntimeError("cf_span_scores: the paired ends differ from the sorted ends of cf_postprocess_spans")
             out = out + (flat,)
@@ -262,18 +272,11 @@ class HipEngine(object):
         ``labels`` (uint8 CUDA [total], what ``cf_postprocess_spans_bridged`` wrote): a run lasts while its labels are non-zero
         instead of while ``p >= threshold`` (``cf_span_scores_labels``) -- bridged runs hold samples below the threshold."""
         import torch
-        if not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
-            raise ValueError("probs must be a contiguous float32 CUDA tensor")
-        total = int(probs.numel())
+        n_reads, total = self._check_packed(probs, read_offsets, read_lengths, (starts, counts))
         if signal is not None and (not signal.is_cuda or signal.dtype != torch.float32 or not signal.is_contiguous()
                                    or int(signal.numel()) != total):
             raise ValueError("signal must be a contiguous float32 CUDA tensor with as many samples as probs")
-        for t in (read_offsets, read_lengths, starts, counts):
-            if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("read_offsets, read_lengths, starts and counts must be contiguous int64 CUDA tensors")
-        n_reads, max_runs = int(read_lengths.numel()), int(starts.numel())
-        if int(read_offsets.numel()) != n_reads + 1:
-            raise ValueError("read_offsets must have n_reads + 1 entries")
+        max_runs = int(starts.numel())
         if int(counts.numel()) < 1:
             raise ValueError("counts must hold the number of starts")
         dev = probs.device

@@ -200,91 +200,42 @@ def hp_in_pred(predictions, extension_left=11, extension_right=16, label=1):
 
 
 # --------------------------------------------------------------------------- inference
-def _scores_of_read(raw_in, model, length, max_gap=0):
-    """Spans and score rows of one padded, windowed read: on the card when the model has an engine (``cf_postprocess_spans`` +
-    ``cf_span_scores``; the probabilities never come down), else ``span_scores.span_scores_host`` over ``model.infer``.  With
-    ``max_gap > 0`` the runs are the bridged ones and a row covers every sample of its run, those below the threshold included."""
-    from .span_scores import scores_of_runs, span_score_summary, span_scores_host, summary_rows
-    x = np.ascontiguousarray(np.asarray(raw_in, dtype=np.float32).reshape(-1))
-    off, lengths = np.array([0, x.shape[0]], dtype=np.int64), np.array([length], dtype=np.int64)
-    if hasattr(model, "_require_engine"):
-        model._require_engine()
-    engine = getattr(model, "engine", None)
-    if engine is not None:
-        import torch
-        dev = torch.device("cuda", engine.device)
-        d_x = torch.from_numpy(x).to(dev)
-        probs = engine.infer_device(d_x.view(-1, WINDOW_SIZE))
-        starts, ends, flat = engine.postprocess_spans_device(probs, torch.from_numpy(off).to(dev), torch.from_numpy(lengths).to(dev),
-                                                             scores=True, signal=d_x, max_gap=max_gap)
-        spans = [[int(s) - 11, int(e) + 16] for s, e in zip(starts.tolist(), ends.tolist())]
-        return spans, summary_rows(span_score_summary(flat))
-    scores = np.asarray(model.infer(raw_in)).reshape(-1)
-    labels = correct_short(bridge_gaps(class_from_threshold(scores[:length]), max_gap))
-    spans = hp_in_pred(labels)
-    p32 = scores.astype(np.float32)
-    runs = [[s + 11, e - 16] for s, e in spans]
-    flat = span_scores_host(p32, x, off, lengths) if max_gap == 0 else None
-    if flat is None or [list(r) for r in zip(flat["start"].tolist(), flat["end"].tolist())] != runs:
-        # bridged runs hold samples below the threshold; or
-        # a probability that rounds across the threshold on its way to float32: the rows describe the spans that are returned
-        flat = scores_of_runs(p32, x, [r[0] for r in runs], [r[1] for r in runs], off, 1)
-    return spans, summary_rows(span_score_summary(flat))
-
-
-def _bridged_spans_of_read(raw_in, model, length, max_gap):
-    """Spans of one padded, windowed read with gaps bridged: ``cf_postprocess_spans_bridged`` when the model has an engine, else the
-    host definition over ``model.infer``."""
-    if hasattr(model, "_require_engine"):
-        model._require_engine()
-    engine = getattr(model, "engine", None)
-    if engine is None:
-        scores = np.asarray(model.infer(raw_in)).reshape(-1)[:length]
-        return hp_in_pred(correct_short(bridge_gaps(class_from_threshold(scores), max_gap)))
+def _engine_read(raw_in, engine, length, rule):
+    """One padded, windowed read on the card: the shared chain of ``calling.py`` and the one-launch post-processing; neither the
+    probabilities nor (with ``rule.scores``) the signal come down.  -> ``calling.results_of_runs``' entry of the read."""
     import torch
+    from . import calling
+    x_host = np.ascontiguousarray(np.asarray(raw_in, dtype=np.float32).reshape(-1, WINDOW_SIZE))
+    total = x_host.size
     dev = torch.device("cuda", engine.device)
-    x = np.ascontiguousarray(np.asarray(raw_in, dtype=np.float32).reshape(-1))
-    probs = engine.infer_device(torch.from_numpy(x).to(dev).view(-1, WINDOW_SIZE))
-    off, lengths = torch.tensor([0, x.shape[0]], dtype=torch.int64, device=dev), torch.tensor([length], dtype=torch.int64, device=dev)
-    starts, ends = engine.postprocess_spans_device(probs, off, lengths, max_gap=max_gap)
-    return [[int(s) - 11, int(e) + 16] for s, e in zip(starts.tolist(), ends.tolist())]
+    x_all, x = calling.tiling_buffer(rule, x_host.shape[0], 1, dev)
+    x.copy_(torch.from_numpy(x_host))
+    s_off, lengths = np.array([0, total], dtype=np.int64), np.array([length], dtype=np.int64)
+    off, lens = torch.from_numpy(s_off).to(dev), torch.from_numpy(lengths).to(dev)
+    probs, _probs_all = calling.forward_voted(engine, rule, x_all, off, lens, total)
+    out = engine.postprocess_spans_device(probs, off, lens, scores=rule.scores, signal=x.view(-1) if rule.scores else None,
+                                          max_gap=rule.max_gap)
+    return calling.results_of_runs(out[0], out[1], s_off, lengths, out[2] if rule.scores else None)[0]
 
 
-def _voted_read(raw_in, model, length, phases, vote_weight, scores, max_gap):
-    """``infer_class_from_raw`` for more than one tiling: the read goes through the network once per phase and everything after the
-    forward pass sees the voted probabilities (``tilings.vote_host``).  With an engine: ``cf_retile_windows``, one forward pass over
-    all tilings, ``cf_vote_tilings``, and the on-card post-processing; else ``tilings.voted_probs_of_read`` over ``model.infer`` and
-    the host definitions."""
-    from .tilings import tiling_size, voted_probs_of_read
+def _host_read(raw_in, model, length, rule):
+    """The same for a model without an engine, by the numpy definitions over ``model.infer``."""
+    from .calling import results_of_runs
+    from .span_scores import scores_of_runs
+    from .tilings import voted_probs_of_read
     x = np.ascontiguousarray(np.asarray(raw_in, dtype=np.float32).reshape(-1))
-    total = x.shape[0]
-    if hasattr(model, "_require_engine"):
-        model._require_engine()
-    engine = getattr(model, "engine", None)
-    if engine is not None:
-        import torch
-        dev = torch.device("cuda", engine.device)
-        off = torch.tensor([0, total], dtype=torch.int64, device=dev)
-        lengths = torch.tensor([length], dtype=torch.int64, device=dev)
-        x_all = torch.empty(tiling_size(total, 1, len(phases)), dtype=torch.float32, device=dev)
-        x_all[:total].copy_(torch.from_numpy(x))
-        engine.retile_device(x_all, off, lengths, total, phases)
-        probs_all = engine.infer_device(x_all.view(-1, WINDOW_SIZE))
-        voted = engine.vote_device(probs_all, off, lengths, total, phases, vote_weight)
-        out = engine.postprocess_spans_device(voted, off, lengths, scores=scores, signal=x_all[:total] if scores else None, max_gap=max_gap)
-        spans = [[int(s) - 11, int(e) + 16] for s, e in zip(out[0].tolist(), out[1].tolist())]
-        if not scores:
-            return spans, length
-        from .span_scores import span_score_summary, summary_rows
-        return spans, length, summary_rows(span_score_summary(out[2]))
-    voted = voted_probs_of_read(raw_in, model.infer, length, phases, vote_weight)
-    spans = hp_in_pred(correct_short(bridge_gaps(class_from_threshold(voted[:length]), max_gap)))
-    if not scores:
-        return spans, length
-    from .span_scores import scores_of_runs, span_score_summary, summary_rows
-    off = np.array([0, total], dtype=np.int64)
-    flat = scores_of_runs(voted, x, [s + 11 for s, _e in spans], [e - 16 for _s, e in spans], off, 1)
-    return spans, length, summary_rows(span_score_summary(flat))
+    if rule.voted:
+        probs = voted_probs_of_read(raw_in, model.infer, length, rule.phases, rule.vote_weight)
+    else:
+        probs = np.asarray(model.infer(raw_in)).reshape(-1)
+    labels = np.asarray(correct_short(bridge_gaps(class_from_threshold(probs[:length]), rule.max_gap)))
+    edges = np.diff(np.concatenate(([0], labels, [0])))
+    starts, ends = np.flatnonzero(edges == 1), np.flatnonzero(edges == -1)
+    s_off, lengths = np.array([0, x.shape[0]], dtype=np.int64), np.array([length], dtype=np.int64)
+    # the rows describe the runs that are returned: bridged runs hold samples below the threshold, and a probability may round across
+    # the threshold on its way to float32 (``span_scores_host`` would find other runs then)
+    flat = scores_of_runs(probs.astype(np.float32), x, starts, ends, s_off, 1) if rule.scores else None
+    return results_of_runs(starts, ends, s_off, lengths, flat)[0]
 
 
 def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE, scores=False, max_gap=0, phases=(0,), vote_weight="mean"):
@@ -304,18 +255,15 @@ def infer_class_from_raw(raw, model, label=1, window_size=WINDOW_SIZE, scores=Fa
     length = len(raw)
     raw = np.hstack((raw, np.array(padding_size * [0])))
     raw_in = reshape_input(raw, window_size, 1)
-    max_gap = check_bridge(max_gap)
-    phases = check_phases(phases)
-    check_weight(vote_weight)
-    if len(phases) > 1:
-        if window_size != WINDOW_SIZE:
-            raise ValueError("shifted-window voting needs window_size %d, got %r" % (WINDOW_SIZE, window_size))
-        return _voted_read(raw_in, model, length, phases, vote_weight, scores, max_gap)
-    if scores:
-        predicted_hps, rows = _scores_of_read(raw_in, model, length, max_gap)
-        return predicted_hps, length, rows
-    if max_gap > 0:
-        return _bridged_spans_of_read(raw_in, model, length, max_gap), length
+    from .calling import CallRule
+    rule = CallRule.of(max_gap=max_gap, phases=phases, vote_weight=vote_weight, scores=scores)
+    if rule.voted and window_size != WINDOW_SIZE:
+        raise ValueError("shifted-window voting needs window_size %d, got %r" % (WINDOW_SIZE, window_size))
+    if rule.voted or rule.bridged or rule.scores:
+        if hasattr(model, "_require_engine"):
+            model._require_engine()
+        engine = getattr(model, "engine", None)
+        return _engine_read(raw_in, engine, length, rule) if engine is not None else _host_read(raw_in, model, length, rule)
     scores = model.infer(raw_in)
     scores = scores[:-padding_size]
     labels = correct_short(class_from_threshold(scores))

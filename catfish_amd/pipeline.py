@@ -16,7 +16,8 @@ import os
 import numpy as np
 
 from . import _native as N
-from .batching import scores_from_runs, spans_from_runs
+from . import calling
+from .calling import CallRule
 from .infer import WINDOW_SIZE
 
 
@@ -29,25 +30,16 @@ class ReadPipeline(object):
     def __init__(self, engine, max_samples_per_batch, threshold=0.5, min_run=15, depth=2, overlap_kernels=None, scores=False, max_gap=0,
                  phases=(0,), vote_weight="mean"):
         import torch
-        from .infer import check_bridge, check_phases, check_weight
         self.torch = torch
         self.eng = engine
         self.dev = torch.device("cuda", engine.device)
-        self.threshold = float(threshold)
-        self.min_run = int(min_run)
-        # bridging (infer.bridge_gaps): gaps of at most max_gap samples between two called stretches of a read are closed before
-        # correct_short, in the same single launch (cf_postprocess_spans_bridged); 0: the launches of before.  ValueError for a
-        # pair the kernel's window does not cover (min_run + max_gap > 64)
-        self.max_gap = check_bridge(max_gap, self.min_run)
-        # shifted-window voting (tilings.py): with K > 1 phases a batch goes through the forward pass in K tilings -- cf_retile_windows
-        # behind cf_normalize on the same stream, ONE forward call over everything, cf_vote_tilings ahead of the post-processing -- and
-        # all that follows sees the voted probabilities of the base layout.  (0,): nothing is allocated or launched that was not before
-        self.phases = check_phases(phases)
-        check_weight(vote_weight)
-        self.vote_weight = "mean" if vote_weight is None else vote_weight
-        # per-call scores (span_scores.py): one more launch per batch (cf_span_scores, right behind cf_postprocess_spans) and 40 B
-        # per run more on the way down; off, nothing is launched, allocated or copied that was not before
-        self.scores = bool(scores)
+        # what is called (calling.CallRule; ValueError for a pair the kernel's window does not cover, min_run + max_gap > 64, or for
+        # phases / a weight that tilings.py refuses).  Every option off -- max_gap 0, phases (0,), scores False -- launches, allocates
+        # and copies nothing that the plain chain does not: bridging changes which ONE post-processing launch runs; K > 1 phases add
+        # cf_retile_windows behind cf_normalize and cf_vote_tilings ahead of the post-processing, around ONE forward call over
+        # everything; scores add one launch per batch (cf_span_scores) and 40 B per run on the way down
+        self.rule = CallRule.of(threshold, min_run, max_gap, phases, vote_weight, scores)
+        self.threshold, self.min_run, self.max_gap, self.phases, self.vote_weight, self.scores = self.rule
         self.out_scores = [None] * max(2, int(depth))           # pinned (ends_paired, sums, extremes) per in-flight slot
         # (All three streams at one priority: raising the forward pass's -- tried in round 5 -- starves the next batch's ingest until
         # the running biGRU launch ends and serialises the two; the CLI's 131 072-window batches lost 8 %,
@@ -218,7 +210,7 @@ class ReadPipeline(object):
 
     def _launch(self, slot, lengths, total):
         """Everything after staging: tables up, H2D, normalise, forward, post-process, run lists down."""
-        torch = self.torch
+        torch, rule = self.torch, self.rule
         n_reads = len(lengths)
         dac_off = np.zeros(n_reads + 1, dtype=np.int64)
         np.cumsum(lengths, out=dac_off[1:])
@@ -251,56 +243,28 @@ class ReadPipeline(object):
             # overlap mode: normalisation rides on the copy stream and overlaps the previous batch's biGRU kernels (which leave
             # wave slots and 15 KiB of LDS free on every CU) instead of delaying this batch's
             k_norm.wait_event(h2d_done)
-            n_tilings = len(self.phases)
-            if n_tilings > 1:
-                from .tilings import tiling_size
-                x_all = torch.empty(tiling_size(n_windows * WINDOW_SIZE, n_reads, n_tilings) // WINDOW_SIZE, WINDOW_SIZE,
-                                    dtype=torch.float32, device=self.dev)
-                x = x_all[:n_windows]                            # the base layout: what cf_normalize fills and cf_span_scores reads
-            else:
-                x = x_all = torch.empty(n_windows, WINDOW_SIZE, dtype=torch.float32, device=self.dev)
+            x_all, x = calling.tiling_buffer(rule, n_windows, n_reads, self.dev)
             self.eng.normalize_device(d_dac, d_doff, d_woff, out=x, stream=k_norm)
-            if n_tilings > 1:
-                self.eng.retile_device(x_all, d_soff, d_len, n_windows * WINDOW_SIZE, self.phases, stream=k_norm)
+            total = n_windows * WINDOW_SIZE
+            calling.retile_tilings(self.eng, rule, x_all, d_soff, d_len, total, stream=k_norm)
             copied = torch.cuda.Event()
             copied.record(k_norm)
         t = _Ticket()
         with torch.cuda.stream(self.compute):                    # overlap mode: the compute stream only ever holds the forward pass
             self.compute.wait_event(copied)
-            probs = probs_all = self.eng.infer_device(x_all, stream=self.compute)
+            probs_all = self.eng.infer_device(x_all, stream=self.compute)
             infer_done = torch.cuda.Event()
             infer_done.record(self.compute)
         with torch.cuda.stream(k_post):                          # overlap mode: post-processing overlaps the next batch's forward pass
             k_post.wait_event(infer_done)
+            probs = calling.vote_tilings(self.eng, rule, probs_all, d_soff, d_len, total, stream=k_post)
             # threshold + correct_short + run boundaries in ONE launch, straight from the probabilities; the labels themselves are
-            # never written (cf_postprocess_spans with labels = NULL) -- except for min_run > 64, which takes the two older kernels
-            max_runs = n_windows * WINDOW_SIZE // self.min_run + 16
-            total = n_windows * WINDOW_SIZE
-            if n_tilings > 1:
-                probs = self.eng.vote_device(probs_all, d_soff, d_len, total, self.phases, self.vote_weight, stream=k_post)
-            # bridged runs hold samples below the threshold: their scores follow the labels, which are written only then
-            by_labels = self.max_gap > 0 and self.scores
-            labels = torch.empty(total, dtype=torch.uint8, device=self.dev) if self.min_run > 64 or by_labels else None
-            t.starts = torch.empty(max_runs, dtype=torch.int64, device=self.dev)
-            t.ends = torch.empty(max_runs, dtype=torch.int64, device=self.dev)
-            t.counts = torch.empty(2, dtype=torch.int64, device=self.dev)
-            if self.max_gap > 0:
-                N.check(self.eng._lib.cf_postprocess_spans_bridged(
-                    self.eng._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(d_soff.data_ptr()), C.c_void_p(d_len.data_ptr()), n_reads,
-                    total, float(self.threshold), self.max_gap, int(self.min_run),
-                    C.c_void_p(labels.data_ptr()) if labels is not None else None, max_runs, C.c_void_p(t.starts.data_ptr()),
-                    C.c_void_p(t.ends.data_ptr()), C.c_void_p(t.counts.data_ptr()), C.c_void_p(k_post.cuda_stream)))
-            else:
-                N.check(self.eng._lib.cf_postprocess_spans(
-                    self.eng._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(d_soff.data_ptr()), C.c_void_p(d_len.data_ptr()), n_reads, total,
-                    float(self.threshold), int(self.min_run), C.c_void_p(labels.data_ptr()) if labels is not None else None, max_runs,
-                    C.c_void_p(t.starts.data_ptr()), C.c_void_p(t.ends.data_ptr()), C.c_void_p(t.counts.data_ptr()),
-                    C.c_void_p(k_post.cuda_stream)))
-            t.rows = None
-            if self.scores:
-                # x and probs stay resident until the batch is collected (t.keep): the scores cost no transfer upwards
-                t.rows = self.eng.span_scores_device(probs, x.view(-1), d_soff, d_len, t.starts, t.counts, self.threshold, stream=k_post,
-                                                     labels=labels if by_labels else None)
+            # never written -- except for min_run > 64, which takes the two older kernels, and for the scores of bridged runs.
+            # x and probs stay resident until the batch is collected (t.keep): the scores cost no transfer upwards
+            max_runs = rule.max_runs(total)
+            t.starts, t.ends, t.counts, labels, t.rows = self.eng.postprocess_spans_launch(
+                probs, d_soff, d_len, rule, signal=x.view(-1) if rule.scores else None, stream=k_post, want_labels=rule.min_run > 64,
+                max_runs=max_runs)
             spans_done = torch.cuda.Event()
             spans_done.record(k_post)
         if self.out[slot] is None or self.out[slot][0].numel() < max_runs:
@@ -327,7 +291,7 @@ class ReadPipeline(object):
             t.done.record(self.down)
         t.lengths, t.s_off, t.max_runs, t.labels = lengths, win_off * WINDOW_SIZE, max_runs, labels
         t.keep = (d_dac, d_tab, x, probs, slot)                  # keep device buffers alive until collected
-        t.tilings = (x_all, probs_all) if n_tilings > 1 else None   # every tiling's input and probabilities, alive until collected
+        t.tilings = (x_all, probs_all) if rule.voted else None   # every tiling's input and probabilities, alive until collected
         self.inflight[slot] = t
         return t
 
@@ -369,11 +333,7 @@ class ReadPipeline(object):
                 from .span_scores import span_score_summary
                 out = out + (span_score_summary(flat),)
             return out
-        spans = spans_from_runs(starts, ends, t.s_off, len(t.lengths))
-        if flat is not None:
-            rows = scores_from_runs(flat, len(t.lengths))
-            return [(spans[i], int(t.lengths[i]), rows[i]) for i in range(len(t.lengths))]
-        return [(spans[i], int(t.lengths[i])) for i in range(len(t.lengths))]
+        return calling.results_of_runs(starts, ends, t.s_off, t.lengths, flat)
 
     def run(self, batches, as_lists=True):
         """Iterate over batches (lists of int16 reads) with up to ``depth - 1`` batches in flight ahead; yields results in order."""

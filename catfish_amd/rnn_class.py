@@ -243,11 +243,10 @@ class RNN(object):
         import torch
         from . import device_validation as dv
         self._require_engine()
-        from .infer import check_bridge, check_phases, check_weight
+        from .calling import CallRule
         from .tilings import tiling_size
-        bridge_gap = check_bridge(bridge_gap, 15)
-        phases = check_phases(phases)
-        check_weight(vote_weight)
+        rule = CallRule.of(max_gap=bridge_gap, phases=phases, vote_weight=vote_weight)
+        bridge_gap, phases, vote_weight = rule.max_gap, rule.phases, rule.vote_weight
         thresholds = tuple(float(t) for t in thresholds)
         if not thresholds:
             raise ValueError("score_validation_device: no threshold given")
@@ -282,8 +281,8 @@ class RNN(object):
                          "run_work": max(self.engine.run_borders_work_bytes(total, min(k_all, dv.MAX_THRESHOLDS)), 1)})
         if curve_shift is not None:
             need["curve_cells"] = curve_cells
-        if len(phases) > 1:
-            need["tiling_samples"] = tiling_size(total, n, len(phases))
+        if rule.voted:
+            need["tiling_samples"] = tiling_size(total, n, rule.n_tilings)
         if any(book["capacity"].get(key, 0) < value for key, value in need.items()):
             cap = {key: max(book["capacity"].get(key, 0), value) for key, value in need.items()}
             f32 = lambda count: torch.empty(count, dtype=torch.float32, device=device)     # noqa: E731
@@ -318,7 +317,7 @@ class RNN(object):
         runs_at = 2 * n + 4 * k_all
         borders_at, curve_at = runs_at + run_cells, runs_at + run_cells + border_cells
         runs_d, borders_d, curve_d = out[runs_at:borders_at], out[borders_at:curve_at], out[curve_at:]
-        if len(phases) > 1:
+        if rule.voted:
             size = need["tiling_samples"]
             x_all, probs_all, logits_all = t["tilings_x"][:size], t["tilings_probs"][:size], t["tilings_logits"][:size]
             self.engine.gather_validation(signal, labels, src_d, len_d, bounds_d, total, longest, x_all[:total], y)

@@ -492,13 +492,10 @@ class EngineBatchRunner(object):
         if self.engine is None:
             raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
         self.max_samples = int(max_samples_per_batch)
-        self.threshold, self.min_run = threshold, min_run
-        # max_gap: gaps of at most that many samples between two called stretches are bridged (infer.bridge_gaps), on both routes
-        # phases / vote_weight: shifted-window voting (tilings.py), on both routes too
+        # one rule (calling.CallRule) for both routes: the pipeline checks it
         self.pipe = ReadPipeline(self.engine, self.max_samples, threshold=threshold, min_run=min_run, max_gap=max_gap, phases=phases,
                                  vote_weight=vote_weight)
-        self.max_gap = self.pipe.max_gap
-        self.phases, self.vote_weight = self.pipe.phases, self.pipe.vote_weight
+        self.threshold, self.min_run, self.max_gap, self.phases, self.vote_weight = self.pipe.rule[:5]
 
     def run(self, batches, compact=False):
         """``batches``: iterable of lists of raw reads -> yields per batch, in order, ``[(spans, length)]`` or (``compact``)

@@ -426,8 +426,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     ``bridge_gap`` (with ``run_edges`` or ``border_reach``; 0 .. 49): those two tables are counted on the prediction with its gaps of
     at most that many samples bridged (``infer.bridge_gaps``).
     Report, prints and return value stay as they are."""
-    from .infer import check_bridge
-    bridge_gap = check_bridge(bridge_gap, 15)
+    from .calling import CallRule
+    bridge_gap = CallRule.of(max_gap=bridge_gap).max_gap
     if bridge_gap and run_edges is None and border_reach is None:
         raise ValueError("validate: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
     print("Max length is {}".format(max_seq_length))
@@ -515,10 +515,10 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
 
     ``phases`` / ``vote_weight`` (``infer.check_phases``): shifted-window voting -- every count is taken from the probabilities voted
     over those tilings (``tilings.vote_host``); ``(0,)`` changes nothing."""
-    from .infer import check_bridge, check_phases
-    bridge_gap = check_bridge(bridge_gap, 15)
-    phases = check_phases(phases)
-    voted = {"phases": phases, "vote_weight": vote_weight} if len(phases) > 1 else {}      # (0,): the call of before
+    from .calling import CallRule
+    rule = CallRule.of(max_gap=bridge_gap, phases=phases, vote_weight=vote_weight)
+    bridge_gap = rule.max_gap
+    voted = {"phases": rule.phases, "vote_weight": rule.vote_weight} if rule.voted else {}      # (0,): the call of before
     if bridge_gap and run_edges is None and border_reach is None:
         raise ValueError("threshold_sweep: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
     bridged = dict(voted, bridge_gap=bridge_gap) if bridge_gap else voted
