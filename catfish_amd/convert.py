@@ -11,6 +11,10 @@ h5py live:
 
 ``read_x.fast5`` becomes ``read_x.npy`` (the name up to its first dot -- what the split step names its pieces after -- is kept).
 With h5py installed the CLI also takes FAST5 directly (``infer.load_dac``, one file at a time through the general loader).
+
+``--events`` converts Tombo-resquiggled reads for TRAINING instead: ``read_x.fast5`` becomes ``read_x.npz`` with the normalised
+signal and the corrected event table (``convert_events``), from which ``catfish_amd.labelling`` makes the per-sample labels for any
+k-mer size.
 """
 from __future__ import annotations
 
@@ -36,8 +40,56 @@ def convert_read(src, dst):
     return int(dac.shape[0])
 
 
-def convert_directory(input_dir, output_dir, keep_going=False):
-    """Every entry of ``input_dir`` (sorted) -> ``output_dir/<name without its last extension>.npy``.
+TOMBO_PATH = "Analyses/RawGenomeCorrected_000/"
+
+
+def _clipped_bases(fast5, end, default):
+    """``TrainingRead.clipped_bases_start`` / ``_end``: the Alignment's ``clipped_bases_<end>``, else its ``trimmed_obs_<end>``,
+    else the default (the reference's ``--clipped-bases``)."""
+    alignment = TOMBO_PATH + "BaseCalled_template/Alignment"
+    if alignment in fast5:
+        attrs = fast5[alignment].attrs
+        for name in ("clipped_bases_" + end, "trimmed_obs_" + end):
+            if name in attrs:
+                return int(attrs[name])
+    return int(default)
+
+
+def convert_events(src, dst_npz, clipped_bases=None):
+    """One Tombo-resquiggled read -> an event ``.npz`` (``labelling.load_event_npz`` reads it; ``CATFISH_LABEL_KMER`` trains from a
+    directory of them); -> its length in samples.  ``raw`` is the signal as ``TrainingRead.raw`` holds it --
+    ``Signal[read_start_rel_to_raw:]``, median / MAD normalised -- cut to ``final_signal``; ``event_base``, ``event_length`` and
+    ``event_start`` are the corrected Events table's columns; ``clipped_start`` / ``clipped_end`` come from the Alignment's
+    attributes with the reference's fall-backs (``clipped_bases``: its default of 10).  No k-mer size goes in: the labels are made
+    when the file is read.  ValueError for a wrong path or a table ``labelling.check_read`` refuses, ImportError without h5py."""
+    from . import labelling
+    if not os.path.exists(src):
+        raise ValueError("path to FAST5 is not correct: %s" % src)
+    try:
+        import h5py
+    except ImportError:
+        raise ImportError("reading %s needs h5py, which is not installed" % src)
+    default = labelling.DEFAULT_CLIPPED if clipped_bases is None else clipped_bases
+    with h5py.File(src, "r") as fast5:
+        events = fast5[TOMBO_PATH + "BaseCalled_template/Events"]
+        first_sample = int(events.attrs["read_start_rel_to_raw"])
+        lengths, bases, starts = np.asarray(events["length"]), np.asarray(events["base"]), np.asarray(events["start"])
+        clipped = (_clipped_bases(fast5, "start", default), _clipped_bases(fast5, "end", default))
+        read_name = fast5["Raw/Reads/"].visit(str)
+        signal = np.asarray(fast5["Raw/Reads/" + read_name + "/Signal"][()]).reshape(-1)
+    raw = infer.normalize_raw_signal(signal[first_sample:], "median")
+    bases, lengths, clipped, final = labelling.check_read(bases, lengths, clipped, starts, n_raw=len(raw))
+    tmp = dst_npz + ".part"
+    with open(tmp, "wb") as fh:
+        np.savez(fh, raw=raw[:final], event_base=bases.view("S1"), event_length=lengths, event_start=np.cumsum(lengths) - lengths,
+                 clipped_start=np.int64(clipped[0]), clipped_end=np.int64(clipped[1]))
+    os.replace(tmp, dst_npz)
+    return final
+
+
+def convert_directory(input_dir, output_dir, keep_going=False, events=False):
+    """Every entry of ``input_dir`` (sorted) -> ``output_dir/<name without its last extension>.npy`` (``events``: ``.npz``, through
+    ``convert_events``).
     -> dict(converted, samples, failed = [(name, error text)]); the first failure raises unless ``keep_going``."""
     os.makedirs(output_dir, exist_ok=True)
     done = {"converted": 0, "samples": 0, "failed": []}
@@ -46,6 +98,10 @@ def convert_directory(input_dir, output_dir, keep_going=False):
         if os.path.isdir(src):
             continue
         try:
+            if events:
+                done["samples"] += convert_events(src, os.path.join(output_dir, os.path.splitext(name)[0] + ".npz"))
+                done["converted"] += 1
+                continue
             done["samples"] += convert_read(src, os.path.join(output_dir, os.path.splitext(name)[0] + ".npy"))
             done["converted"] += 1
         except Exception as exc:                            # noqa: BLE001 -- reported per file; the reference aborts on the first (infer.py:25-29)
@@ -61,8 +117,10 @@ def main(argv=None):
     ap.add_argument("-i", "--input-dir", required=True)
     ap.add_argument("-o", "--output-dir", required=True)
     ap.add_argument("--keep-going", action="store_true", help="report unreadable files at the end instead of stopping at the first")
+    ap.add_argument("--events", action="store_true",
+                    help="Tombo-resquiggled reads -> event .npz files (normalised signal + the corrected event table) to label and train from")
     args = ap.parse_args(argv)
-    done = convert_directory(args.input_dir, args.output_dir, keep_going=args.keep_going)
+    done = convert_directory(args.input_dir, args.output_dir, keep_going=args.keep_going, **({"events": True} if args.events else {}))
     print("converted %d reads (%d samples) into %s" % (done["converted"], done["samples"], args.output_dir))
     for name, err in done["failed"]:
         print("FAILED %s: %s" % (name, err))

@@ -211,10 +211,10 @@ class DeviceExampleDb(DeviceFedDb):
         return self._dev["pos"], self._dev["neg"], self._dev["counter"]
 
 
-def device_db_from_npz(npz_files, width=34, lessen=1, max_neg_per_read=2000, seed=0, device=None):
-    """``train_validate.example_db_from_npz``'s windows (the same selection code) in a ``DeviceExampleDb``."""
+def device_db_from_npz(npz_files, width=34, lessen=1, max_neg_per_read=2000, seed=0, device=None, loader=None):
+    """``train_validate.example_db_from_npz``'s windows (the same selection code, the same ``loader``) in a ``DeviceExampleDb``."""
     from .train_validate import example_db_from_npz
-    return DeviceExampleDb.from_window_db(example_db_from_npz(npz_files, width, lessen, max_neg_per_read, seed), seed, device)
+    return DeviceExampleDb.from_window_db(example_db_from_npz(npz_files, width, lessen, max_neg_per_read, seed, loader), seed, device)
 
 
 def synthetic_device_db(n_reads=8, read_len=20000, seed=0, device=None):
@@ -329,6 +329,14 @@ class DeviceReadDb(DeviceFedDb):
         """The reads of ``paths`` (``raw`` + ``base_labels``, ``train_validate.load_npz``), in that order."""
         from .device_validation import DeviceValidationSet
         v = DeviceValidationSet.from_npz(paths, loader)
+        return cls(v.signal, v.labels, v.offsets, seed, lessen, neg_per_read)
+
+    @classmethod
+    def from_event_npz(cls, paths, kmer=5, seed=0, lessen=1, neg_per_read=None, device=None):
+        """The reads of ``paths`` (event ``.npz`` files: ``raw`` + an event table, ``labelling.load_event_npz``), in that order,
+        labelled with k-mer size ``kmer`` through ``DeviceValidationSet.from_event_npz`` (on the card where there is one)."""
+        from .device_validation import DeviceValidationSet
+        v = DeviceValidationSet.from_event_npz(paths, kmer, device)
         return cls(v.signal, v.labels, v.offsets, seed, lessen, neg_per_read)
 
     # ------------------------------------------------------------------ the tables

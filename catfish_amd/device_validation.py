@@ -407,6 +407,20 @@ def finish(right, ce_sum, counts_k, bounds, tails):
     return acc, loss.astype(np.float32), (tp, fp, tn - int(np.sum(tails)), fn)
 
 
+def _label_device(device):
+    """Where ``from_events`` makes the labels: the CUDA device to use, or None for the host.  An explicit CUDA device is taken at its
+    word (no GPU or no library is then an error of ``labelling.label_reads``); None means the card where there is one to use."""
+    if device is not None and str(device).split(":")[0] != "cuda":
+        return None
+    import torch
+    if device is None:
+        from . import _native
+        import os
+        if not torch.cuda.is_available() or not os.path.exists(_native.DEFAULT_LIB_PATH):
+            return None
+    return torch.device("cuda" if device is None else device)
+
+
 class DeviceValidationSet(object):
     """All validation reads of a run, concatenated: ``signal`` float32 [total] (cast once -- the values
     ``pack_validation_windows`` writes into its float32 batch), ``labels`` uint8 [total], ``offsets`` int64 [n_reads + 1],
@@ -451,6 +465,44 @@ class DeviceValidationSet(object):
             signals.append(raw)
             labels.append(lab)
         return cls.from_arrays(signals, labels, device)
+
+    @classmethod
+    def from_events(cls, signals, batch, kmer=5, device=None):
+        """Reads that come with their event tables instead of labels: ``signals[r]`` is read r's raw signal (its first
+        ``final_signal`` samples are kept, as the reference's collect_examples.py saves them) and ``batch`` a
+        ``labelling.EventBatch`` over the same reads.  On a GPU (``device`` a CUDA device, or None where one is there and the
+        native library is built) ``cf_label_events`` makes the labels: signal and labels are the set's device arrays from then on
+        (one upload) and the labels are copied back once for ``self.labels``.  Otherwise (``device="cpu"``, or no GPU)
+        ``batch.label_host`` makes them -- the same bytes."""
+        from . import labelling
+        kmer = labelling.check_kmer(kmer)
+        signals = [np.asarray(s).reshape(-1) for s in signals]
+        if len(signals) != batch.n_reads:
+            raise ValueError("%d signals but %d event tables" % (len(signals), batch.n_reads))
+        offsets = np.asarray(batch.sample_offsets, dtype=np.int64).copy()
+        signal = np.zeros(int(offsets[-1]), dtype=np.float32)
+        for r, s in enumerate(signals):
+            o, n = int(offsets[r]), int(offsets[r + 1] - offsets[r])
+            if len(s) < n:
+                raise ValueError("read %d: the events cover %d samples, the raw signal has %d" % (r, n, len(s)))
+            signal[o:o + n] = s[:n]
+        on_card = _label_device(device)
+        if on_card is None:
+            return cls(signal, batch.label_host(kmer), offsets, device)
+        import torch
+        labels_dev = labelling.label_reads(batch, kmer, on_card)
+        vset = cls(signal, labels_dev.cpu().numpy() if labels_dev.numel() else np.zeros(0, np.uint8), offsets, device)
+        if signal.size:
+            vset._dev = {"device": labels_dev.device, "signal": torch.from_numpy(signal).to(labels_dev.device), "labels": labels_dev}
+            vset.uploads = 1
+        return vset
+
+    @classmethod
+    def from_event_npz(cls, paths, kmer=5, device=None):
+        """The reads of ``paths`` (event ``.npz`` files, ``labelling.load_event_npz``), in that order, through ``from_events``."""
+        from . import labelling
+        reads = [labelling.load_event_npz(path) for path in paths]
+        return cls.from_events([read["raw"] for read in reads], labelling.EventBatch.from_reads(reads), kmer, device)
 
     @property
     def n_reads(self):

@@ -143,12 +143,23 @@ def load_npz(npz_file):
         return npz["raw"], npz["base_labels"]
 
 
-def example_db_from_npz(npz_files, width=34, lessen=1, max_neg_per_read=2000, seed=0):
-    """A training database over NPZ reads (raw = normalised signal, base_labels = 0/1 per sample)."""
+def npz_loader_from_env():
+    """The loader ``main`` reads its ``.npz`` directories with: ``load_npz``, or with ``CATFISH_LABEL_KMER=<odd k>`` set a loader
+    of event files (``raw`` + an event table, ``labelling.load_event_npz``) that labels each read with that k -- the same
+    ``(raw, labels)`` the ``raw`` + ``base_labels`` file made from it would give."""
+    from . import labelling
+    kmer = labelling.kmer_from_env(os.environ.get("CATFISH_LABEL_KMER"))
+    if kmer is None:
+        return load_npz
+    return lambda npz_file: labelling.load_labelled_event_npz(npz_file, kmer)
+
+
+def example_db_from_npz(npz_files, width=34, lessen=1, max_neg_per_read=2000, seed=0, loader=None):
+    """A training database over NPZ reads (raw = normalised signal, base_labels = 0/1 per sample; ``loader``: ``load_npz``)."""
     rng = np.random.default_rng(seed)
     pos, neg = [], []
     for f in npz_files:
-        raw, labels = load_npz(f)
+        raw, labels = (loader or load_npz)(f)
         p, n = windows_from_labelled_read(raw, labels, width, lessen, max_neg_per_read, rng)
         pos.extend(p)
         neg.extend(n)
@@ -239,6 +250,8 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     bridge_gap = int(getattr(network, "validation_bridge_gap", 0) or 0)
     if bridge_gap:
         extra["bridge_gap"] = bridge_gap
+    if getattr(network, "validation_loader", None) is not None:
+        extra["loader"] = network.validation_loader
     if run_edges is None:
         _acc, precision, recall = validate(network, *validation, **extra)
     else:
@@ -402,7 +415,7 @@ def score_validation_batch(probs32, logits32, y, bounds, tails, threshold=0.5):
 
 
 def validate(network, squiggles, max_seq_length, file_path, validation_start="random", max_number=856, run_edges=None, curve_shift=None,
-             border_reach=None, bridge_gap=0):
+             border_reach=None, bridge_gap=0, loader=None):
     """networks/train_validate.py:188-295 as one packed launch.
 
     The reference pushes every read through ``test_network`` (one ``sess.run`` each, up to 856 per round); windows are
@@ -425,6 +438,7 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     [2, 5 * border_reach + 3] table is left in ``network.validation_run_borders``.
     ``bridge_gap`` (with ``run_edges`` or ``border_reach``; 0 .. 49): those two tables are counted on the prediction with its gaps of
     at most that many samples bridged (``infer.bridge_gaps``).
+    ``loader`` (a list of paths only): what reads a path into ``(raw, labels)`` instead of ``load_npz``.
     Report, prints and return value stay as they are."""
     from .calling import CallRule
     bridge_gap = CallRule.of(max_gap=bridge_gap).max_gap
@@ -463,7 +477,7 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
         if border_reach is not None:
             raise ValueError("validate: border_reach needs a DeviceValidationSet (the borders are compared on the card)")
         signals, labels = select_validation_stretches(squiggles, network.window, max_seq_length, validation_start,
-                                                      max_number)
+                                                      max_number, **({} if loader is None else {"loader": loader}))
         n_reads = len(signals)
         n_samples = sum(len(s) for s in signals)
         if n_reads == 0:
@@ -636,12 +650,16 @@ def device_read_db_from_env(npz_files):
     read contributes: ``positives`` (the default: as many as it has positives, the reference's rule), an integer, or ``all``.
     A host database: it feeds the per-step loop (``get_training_set``)."""
     from .device_db import DeviceReadDb
+    from . import labelling
+    kmer = labelling.kmer_from_env(os.environ.get("CATFISH_LABEL_KMER"))
     rule = os.environ.get("CATFISH_DEVICE_NEG", "positives")
     if rule not in ("positives", "all"):
         try:
             rule = int(rule)
         except ValueError:
             raise ValueError("CATFISH_DEVICE_NEG must be 'positives', 'all' or an integer, got %r" % rule)
+    if kmer is not None:                                         # event files, labelled with that k (on the card where there is one)
+        return DeviceReadDb.from_event_npz(npz_files, kmer, seed=0, neg_per_read=None if rule == "all" else rule)
     return DeviceReadDb.from_npz(npz_files, seed=0, neg_per_read=None if rule == "all" else rule)
 
 
@@ -674,7 +692,12 @@ def main(argv):
     ``<model path>_hp_borders.jsonl``; the ``.txt`` reports and the other ``.jsonl`` files are unchanged.
     CATFISH_VALIDATION_BRIDGE=<int> (1 .. 49; with CATFISH_VALIDATION_RUNS or CATFISH_VALIDATION_BORDERS) counts those two on the
     prediction with its gaps of at most that many samples bridged (``infer.bridge_gaps``); their JSON lines then carry
-    ``bridge_gap``."""
+    ``bridge_gap``.
+    CATFISH_LABEL_KMER=<odd k in 1 .. 15>: both directories hold event files (``raw`` + ``event_base`` / ``event_length``,
+    ``labelling.load_event_npz``; ``python -m catfish_amd.convert --events`` writes them) and every read is labelled with that k-mer
+    size on the way in (``npz_loader_from_env``; with CATFISH_DEVICE_VALIDATION=1 or CATFISH_DEVICE_DB=reads on the card,
+    ``cf_label_events``) -- the labels a directory of ``raw`` + ``base_labels`` files made from them would hold.  Unset, nothing
+    changes."""
     args = list(argv[1:])
     if len(args) < 5:
         raise ValueError(_USAGE)
@@ -691,19 +714,28 @@ def main(argv):
         hparams["training_precision"] = os.environ["CATFISH_TRAINING_PRECISION"]
     network = build_model(kind, save=True, **hparams)
     network.initialize_network()
+    loader = npz_loader_from_env()                               # load_npz, or event files labelled on the way in (CATFISH_LABEL_KMER)
+    from_events = loader is not load_npz
+    with_loader = {"loader": loader} if from_events else {}
     print("Loading training database..")
     if os.environ.get("CATFISH_DEVICE_DB") == "1":               # the training set on the card, batches drawn by a HIP kernel
         from .device_db import device_db_from_npz
-        db_train = device_db_from_npz(_npz_files(train_dir))
+        db_train = device_db_from_npz(_npz_files(train_dir), **with_loader)
     elif os.environ.get("CATFISH_DEVICE_DB") == "reads":         # the labelled reads as they are, two tables of window starts: a HOST database
         db_train = device_read_db_from_env(_npz_files(train_dir))
     else:
-        db_train = example_db_from_npz(_npz_files(train_dir))
+        db_train = example_db_from_npz(_npz_files(train_dir), **with_loader)
+    if from_events:
+        network.validation_loader = loader
     print("Loading validation database..")
     squiggles = _npz_files(val_dir)
     if os.environ.get("CATFISH_DEVICE_VALIDATION") == "1":       # the validation reads on the card, rounds scored by HIP kernels
         from .device_validation import DeviceValidationSet
-        squiggles = DeviceValidationSet.from_npz(squiggles)
+        if from_events:
+            from . import labelling
+            squiggles = DeviceValidationSet.from_event_npz(squiggles, labelling.kmer_from_env(os.environ.get("CATFISH_LABEL_KMER")))
+        else:
+            squiggles = DeviceValidationSet.from_npz(squiggles)
         if os.environ.get("CATFISH_VALIDATION_RUNS") == "1":     # ... and the homopolymers found, one JSON line per round
             network.validation_run_edges = VALIDATION_RUN_EDGES
         if os.environ.get("CATFISH_VALIDATION_CURVE") == "1":    # ... and the round's ROC / PR areas and best F1, one JSON line per round

@@ -683,6 +683,29 @@ int cf_vote_tilings(cf_model* m, const float* probs, const float* logits, const 
                     int64_t n_reads, int64_t total, const int32_t* phases, int32_t n_phases, int32_t weight, float* probs_out,
                     float* logits_out, void* stream);
 
+/* Labels from event tables (csrc/label_events.hpp, index rules in csrc/label_events_rule.hpp; catfish_amd/labelling.py states the
+ * result in numpy -- event_classes_host, expand_events_host and base_map_host are the definitions).  A batch of resquiggled reads,
+ * packed, all device memory: read r owns events event_offsets[r] .. event_offsets[r + 1] (int64 [n_reads + 1]) of bases (uint8
+ * [n_events], the base byte, below 128) and lengths (int32 [n_events], samples, >= 1), clipped[2 r] / clipped[2 r + 1] (int32) are
+ * its clipped_start / clipped_end, and it owns samples sample_offsets[r] .. sample_offsets[r + 1] (int64 [n_reads + 1], the sum of
+ * its lengths apart) of the outputs; total = sample_offsets[n_reads].  With oh = kmer / 2 and E the read's events:
+ *   core[e]  = clipped_start <= e < E - clipped_end, e - oh >= 0, e + oh < E, and events e - oh .. e + oh are one byte that is not 'N'
+ *   cls[e]   = some core within two events of e (inside the read; the widening ignores clipping and 'N')
+ *   labels_out[first sample of e .. + length)  = cls[e]
+ *   basemap_out (NULL ok) there = the base byte, bit 7 set on the one sample first + length / 2
+ * work: device scratch of the work-bytes query below for n_events (the events' first samples, int32, and classes), 4-byte aligned.
+ * Two launches, asynchronous on `stream`, capturable; integers only and no atomics, so equal inputs give equal bytes.  m may be NULL
+ * (the current device is used).  The tables are not trusted: a length < 1 contributes nothing, a read whose event range leaves
+ * [0, n_events] has no events, samples that no event covers get label 0 and base 0, a read whose sample range leaves [0, total] is
+ * not written, and whatever the tables hold nothing is read or written outside the buffers.
+ * CF_ERR_INVALID before any launch for a null pointer, a negative size, 2^31 or more events or samples, an even kmer or one outside
+ * 1 .. 15, more than 2^23 workgroups (n_reads + total / 4096) or a work buffer that is too small; total == 0 is CF_OK with nothing
+ * launched. */
+int64_t cf_label_events_work_bytes(int64_t n_events);
+int cf_label_events(cf_model* m, const uint8_t* bases, const int32_t* lengths, const int64_t* event_offsets, const int32_t* clipped,
+                    const int64_t* sample_offsets, int64_t n_reads, int64_t n_events, int64_t total, int32_t kmer, uint8_t* labels_out,
+                    uint8_t* basemap_out, void* work, int64_t work_bytes, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream) for bench.py's
  * roofline report.  cf_profile_enable(m, N) makes every N-th cf_infer call
  * (N = 1: every call; 0 = off) record events around each of its kernels; cf_profile_read synchronises and returns, for
