@@ -2013,6 +2013,13 @@ extern "C" int cf_infer_host(cf_model* m, const float* x, int64_t n_windows, flo
     return cf_infer_host_logits(m, x, n_windows, probs, nullptr);
 }
 
+// grid of the bit-mask post-processing kernels over `total` packed samples: 64 samples a word, CF_POST_WORDS payload words a wave,
+// four waves a workgroup
+static dim3 post_bits_grid(int64_t total) {
+    const int64_t n_words = (total + 63) / 64, n_chunks = (n_words + CF_POST_WORDS - 1) / CF_POST_WORDS;
+    return dim3((unsigned)((n_chunks + 3) / 4));
+}
+
 extern "C" int cf_postprocess(cf_model* m, const float* probs, const int64_t* read_offsets, const int64_t* read_lengths,
                               int64_t n_reads, int64_t total_samples, float threshold, int32_t min_run, uint8_t* labels,
                               void* stream) {
@@ -2032,8 +2039,7 @@ extern "C" int cf_postprocess(cf_model* m, const float* probs, const int64_t* re
         hipLaunchKernelGGL(postprocess_kernel, dim3((unsigned)((total_samples + 255) / 256)), dim3(256), 0, s, probs, read_offsets,
                            read_lengths, n_reads, total_samples, threshold, (int)min_run, labels);
     } else {
-        const int64_t n_words = (total_samples + 63) / 64, n_chunks = (n_words + CF_POST_WORDS - 1) / CF_POST_WORDS;
-        hipLaunchKernelGGL(postprocess_bits_kernel<false>, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, s, probs, read_offsets,
+        hipLaunchKernelGGL(postprocess_bits_kernel<false>, post_bits_grid(total_samples), dim3(256), 0, s, probs, read_offsets,
                            read_lengths, n_reads, total_samples, threshold, (int)min_run, labels, (int64_t)0, (int64_t*)nullptr,
                            (int64_t*)nullptr, (unsigned long long*)nullptr);
     }
@@ -2081,8 +2087,7 @@ extern "C" int cf_postprocess_spans(cf_model* m, const float* probs, const int64
     size_t pi = 0;
     int rc = prof_begin(m, SLOT_POST, s, &pi);
     if (rc != CF_OK) return rc;
-    const int64_t n_words = (total_samples + 63) / 64, n_chunks = (n_words + CF_POST_WORDS - 1) / CF_POST_WORDS;
-    hipLaunchKernelGGL(postprocess_bits_kernel<true>, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, s, probs, read_offsets, read_lengths,
+    hipLaunchKernelGGL(postprocess_bits_kernel<true>, post_bits_grid(total_samples), dim3(256), 0, s, probs, read_offsets, read_lengths,
                        n_reads, total_samples, threshold, (int)min_run, labels, max_runs, starts, ends,
                        reinterpret_cast<unsigned long long*>(counts));
     HIP_TRY(hipGetLastError());
@@ -2114,8 +2119,7 @@ extern "C" int cf_postprocess_spans_bridged(cf_model* m, const float* probs, con
     size_t pi = 0;
     int rc = prof_begin(m, SLOT_POST, s, &pi);
     if (rc != CF_OK) return rc;
-    const int64_t n_words = (total_samples + 63) / 64, n_chunks = (n_words + CF_POST_WORDS - 1) / CF_POST_WORDS;
-    hipLaunchKernelGGL(postprocess_bridged_kernel<true>, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, s, probs, read_offsets,
+    hipLaunchKernelGGL(postprocess_bridged_kernel<true>, post_bits_grid(total_samples), dim3(256), 0, s, probs, read_offsets,
                        read_lengths, n_reads, total_samples, threshold, (int)max_gap, (int)min_run, labels, max_runs, starts, ends,
                        reinterpret_cast<unsigned long long*>(counts));
     HIP_TRY(hipGetLastError());

@@ -130,20 +130,11 @@ static int validation_run_borders_impl(const std::string& fn, cf_model* m, const
                                        const int64_t* length, int64_t n, int64_t total, int64_t longest, const double* thresholds,
                                        int32_t n_thresholds, int32_t reach, int32_t max_gap, int32_t min_run, int64_t* counts_out, void* work,
                                        int64_t work_bytes, void* stream) {
-    if (!probs || !y || !bounds || !length || !thresholds || !counts_out || !work)
-        return fail(CF_ERR_INVALID, fn + ": null argument");
-    if (n <= 0 || n > 0x7fffffff) return fail(CF_ERR_INVALID, fn + ": n must be in [1, 2^31)");
-    if (n_thresholds < 1 || n_thresholds > CF_SCORE_MAX_K)
-        return fail(CF_ERR_INVALID, fn + ": between 1 and " + std::to_string(CF_SCORE_MAX_K) + " thresholds per call");
-    if (total < 0 || total > 0x7fffffff || longest < 0 || longest > total) return fail(CF_ERR_INVALID, fn + ": bad size");
+    if (const int rc = validation_run_args_ok(fn, "cf_validation_run_borders_work_bytes", probs, y, bounds, length, n, total, longest,
+                                              thresholds, n_thresholds, max_gap, min_run, counts_out, work, work_bytes)) return rc;
     if (reach < 1 || reach > VB_MAX_REACH)
         return fail(CF_ERR_INVALID, fn + ": reach must be in 1 .. " + std::to_string(VB_MAX_REACH));
-    if (min_run < 1) return fail(CF_ERR_INVALID, fn + ": min_run must be >= 1");
-    if (!validation_bridge_ok(min_run, max_gap, work))
-        return fail(CF_ERR_INVALID, fn + ": bridging needs max_gap >= 0, min_run + max_gap <= 64 and a 16-byte aligned work buffer");
     const int64_t stride = (total + 63) / 64 * 64;
-    if (work_bytes < cf_validation_run_borders_work_bytes(total, n_thresholds))
-        return fail(CF_ERR_INVALID, fn + ": work needs cf_validation_run_borders_work_bytes(total, n_thresholds) bytes");
     if (m) HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(counts_out, 0, (size_t)n_thresholds * 2 * vb_cells(reach) * sizeof(int64_t), s));

@@ -222,13 +222,11 @@ static int validation_label_passes(const float* probs, const int64_t* bounds, co
         float tf = (float)thresholds[k];
         if ((double)tf < thresholds[k]) tf = std::nextafterf(tf, INFINITY);
         if (max_gap > 0) {
-            const int64_t n_words = (total + 63) / 64, n_chunks = (n_words + CF_POST_WORDS - 1) / CF_POST_WORDS;
-            hipLaunchKernelGGL(postprocess_bridged_kernel<false>, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, s, probs, bounds, length,
+            hipLaunchKernelGGL(postprocess_bridged_kernel<false>, post_bits_grid(total), dim3(256), 0, s, probs, bounds, length,
                                n, total, tf, (int)max_gap, (int)min_run, lab + k * stride, (int64_t)0, (int64_t*)nullptr, (int64_t*)nullptr,
                                (unsigned long long*)nullptr);
         } else if (bits) {
-            const int64_t n_words = (total + 63) / 64, n_chunks = (n_words + CF_POST_WORDS - 1) / CF_POST_WORDS;
-            hipLaunchKernelGGL(postprocess_bits_kernel<false>, dim3((unsigned)((n_chunks + 3) / 4)), dim3(256), 0, s, probs, bounds, length, n,
+            hipLaunchKernelGGL(postprocess_bits_kernel<false>, post_bits_grid(total), dim3(256), 0, s, probs, bounds, length, n,
                                total, tf, (int)min_run, lab + k * stride, (int64_t)0, (int64_t*)nullptr, (int64_t*)nullptr,
                                (unsigned long long*)nullptr);
         } else {
@@ -240,16 +238,32 @@ static int validation_label_passes(const float* probs, const int64_t* bounds, co
     return CF_OK;
 }
 
-static int validation_run_states_impl(const std::string& fn, cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds,
-                                      const int64_t* length, int64_t n, int64_t total, int64_t longest, const double* thresholds,
-                                      int32_t n_thresholds, const int64_t* edges, int32_t n_edges, int32_t max_gap, int32_t min_run,
-                                      int64_t* counts_out, void* work, int64_t work_bytes, void* stream) {
-    if (!probs || !y || !bounds || !length || !thresholds || !counts_out || !work || (n_edges > 0 && !edges))
-        return fail(CF_ERR_INVALID, fn + ": null argument");
+// The argument checks cf_validation_run_states and cf_validation_run_borders share (each keeps the ones of its own table);
+// `work_fn` is the function the message about too small a work buffer names (the two have one rule: cf_validation_run_work_bytes).
+static int validation_run_args_ok(const std::string& fn, const char* work_fn, const float* probs, const uint8_t* y, const int64_t* bounds,
+                                  const int64_t* length, int64_t n, int64_t total, int64_t longest, const double* thresholds,
+                                  int32_t n_thresholds, int32_t max_gap, int32_t min_run, const int64_t* counts_out, const void* work,
+                                  int64_t work_bytes) {
+    if (!probs || !y || !bounds || !length || !thresholds || !counts_out || !work) return fail(CF_ERR_INVALID, fn + ": null argument");
     if (n <= 0 || n > 0x7fffffff) return fail(CF_ERR_INVALID, fn + ": n must be in [1, 2^31)");
     if (n_thresholds < 1 || n_thresholds > CF_SCORE_MAX_K)
         return fail(CF_ERR_INVALID, fn + ": between 1 and " + std::to_string(CF_SCORE_MAX_K) + " thresholds per call");
     if (total < 0 || total > 0x7fffffff || longest < 0 || longest > total) return fail(CF_ERR_INVALID, fn + ": bad size");
+    if (min_run < 1) return fail(CF_ERR_INVALID, fn + ": min_run must be >= 1");
+    if (!validation_bridge_ok(min_run, max_gap, work))
+        return fail(CF_ERR_INVALID, fn + ": bridging needs max_gap >= 0, min_run + max_gap <= 64 and a 16-byte aligned work buffer");
+    if (work_bytes < cf_validation_run_work_bytes(total, n_thresholds))
+        return fail(CF_ERR_INVALID, fn + ": work needs " + work_fn + "(total, n_thresholds) bytes");
+    return CF_OK;
+}
+
+static int validation_run_states_impl(const std::string& fn, cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds,
+                                      const int64_t* length, int64_t n, int64_t total, int64_t longest, const double* thresholds,
+                                      int32_t n_thresholds, const int64_t* edges, int32_t n_edges, int32_t max_gap, int32_t min_run,
+                                      int64_t* counts_out, void* work, int64_t work_bytes, void* stream) {
+    if (n_edges > 0 && !edges) return fail(CF_ERR_INVALID, fn + ": null argument");
+    if (const int rc = validation_run_args_ok(fn, "cf_validation_run_work_bytes", probs, y, bounds, length, n, total, longest, thresholds,
+                                              n_thresholds, max_gap, min_run, counts_out, work, work_bytes)) return rc;
     if (n_edges < 0 || n_edges > CF_RUN_MAX_EDGES)
         return fail(CF_ERR_INVALID, fn + ": at most " + std::to_string(CF_RUN_MAX_EDGES) + " edges");
     cf_run_edges e;
@@ -259,12 +273,7 @@ static int validation_run_states_impl(const std::string& fn, cf_model* m, const 
             return fail(CF_ERR_INVALID, fn + ": edges must be positive and ascending");
         e.e[j] = (unsigned)std::min<int64_t>(edges[j], 0xffffffffll);
     }
-    if (min_run < 1) return fail(CF_ERR_INVALID, fn + ": min_run must be >= 1");
-    if (!validation_bridge_ok(min_run, max_gap, work))
-        return fail(CF_ERR_INVALID, fn + ": bridging needs max_gap >= 0, min_run + max_gap <= 64 and a 16-byte aligned work buffer");
     const int64_t stride = (total + 63) / 64 * 64;
-    if (work_bytes < cf_validation_run_work_bytes(total, n_thresholds))
-        return fail(CF_ERR_INVALID, fn + ": work needs cf_validation_run_work_bytes(total, n_thresholds) bytes");
     if (m) HIP_TRY(hipSetDevice(m->device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const int n_bins = n_edges + 1;

@@ -17,6 +17,8 @@ how many homopolymers a round found, bit for bit), ``run_borders_host`` what the
 (``cf_validation_run_borders``, csrc/validation_borders.hpp: how far the called borders miss and the interruptions, bit for bit), ``curve_host`` what the curve step returns (``cf_validation_curve``,
 csrc/validation_curve.hpp: the round's probabilities binned at every threshold step, bit for bit; ``curves_from_histogram`` turns
 that table into the whole ROC and precision-recall curves, their areas and the best F1).  The object is host-only until ``device_arrays`` is called and usable without a GPU.
+What a round on the card decides before its first launch -- the checked options, the buffer sizes, the layout of the result buffer and
+the named results -- is ``validation_round`` (host-only too).
 """
 from __future__ import annotations
 

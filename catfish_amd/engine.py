@@ -436,6 +436,16 @@ class HipEngine(object):
             if t.device.index != self.device:
                 raise ValueError("%s: %s lives on cuda:%s, model on cuda:%d" % (what, name, t.device.index, self.device))
 
+    @staticmethod
+    def _check_validation_sizes(what, probs, y, bounds, length, total, longest):
+        """What the run-state, border and curve steps ask of their tables: -> (n, total, longest) as ints."""
+        n, total, longest = int(length.numel()), int(total), int(longest)
+        if int(bounds.numel()) != n + 1:
+            raise ValueError("%s: length needs n entries, bounds n + 1" % what)
+        if total < 0 or min(int(probs.numel()), int(y.numel())) < total:
+            raise ValueError("%s: probs and y need %d elements" % (what, total))
+        return n, total, longest
+
     def gather_validation(self, signal, labels, src_first, length, bounds, total, longest, x_out, y_out, stream=None):
         """``cf_validation_gather``: packed sample ``bounds[r] + i`` of ``x_out`` / ``y_out`` (float32 / uint8, at least ``total``
         elements) becomes ``signal`` / ``labels`` ``[src_first[r] + i]`` for ``i < length[r]`` and 0 after it.  ``src_first``,
@@ -501,28 +511,19 @@ class HipEngine(object):
             ("counts_out", counts_out, torch.int64), ("work", work, torch.uint8)])
         thresholds = [float(t) for t in thresholds]
         edges = [int(e) for e in edges]
-        n, k, total, longest = int(length.numel()), len(thresholds), int(total), int(longest)
-        if int(bounds.numel()) != n + 1:
-            raise ValueError("run_states_validation: length needs n entries, bounds n + 1")
-        if total < 0 or min(int(probs.numel()), int(y.numel())) < total:
-            raise ValueError("run_states_validation: probs and y need %d elements" % total)
+        k = len(thresholds)
+        n, total, longest = self._check_validation_sizes("run_states_validation", probs, y, bounds, length, total, longest)
         if int(counts_out.numel()) < k * 2 * (len(edges) + 1) * 3:
             raise ValueError("run_states_validation: counts_out needs 2 * (edges + 1) * 3 entries per threshold")
         if stream is None:
             stream = torch.cuda.current_stream(probs.device)
-        # n, K, the edges, min_run and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
-        if max_gap:            # (``max_gap``: the prediction is bridged first, ``cf_validation_run_states_bridged``; a pair it refuses raises)
-            N.check(self._lib.cf_validation_run_states_bridged(
-                self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
-                C.c_void_p(length.data_ptr()), n, total, longest, (C.c_double * max(k, 1))(*thresholds), k,
-                (C.c_int64 * max(len(edges), 1))(*edges), len(edges), int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()),
-                C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
-            return
-        N.check(self._lib.cf_validation_run_states(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()),
-                                                   C.c_void_p(bounds.data_ptr()), C.c_void_p(length.data_ptr()), n, total, longest,
-                                                   (C.c_double * max(k, 1))(*thresholds), k, (C.c_int64 * max(len(edges), 1))(*edges),
-                                                   len(edges), int(min_run), C.c_void_p(counts_out.data_ptr()),
-                                                   C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
+        # n, K, the edges, min_run, the (min_run, max_gap) pair and the work space are refused by the library (CF_ERR_INVALID ->
+        # ValueError); ``max_gap`` 0 is ``cf_validation_run_states``, anything else bridges the prediction first
+        N.check(self._lib.cf_validation_run_states_bridged(
+            self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
+            C.c_void_p(length.data_ptr()), n, total, longest, (C.c_double * max(k, 1))(*thresholds), k,
+            (C.c_int64 * max(len(edges), 1))(*edges), len(edges), int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()),
+            C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
 
     def run_borders_work_bytes(self, total, n_thresholds):
         """Bytes of work space ``run_borders_validation`` needs (``run_states_work_bytes``' rule: the two can share a buffer)."""
@@ -544,28 +545,19 @@ class HipEngine(object):
             ("counts_out", counts_out, torch.int64), ("work", work, torch.uint8)])
         thresholds = [float(t) for t in thresholds]
         reach = check_border_reach(reach)
-        n, k, total, longest = int(length.numel()), len(thresholds), int(total), int(longest)
-        if int(bounds.numel()) != n + 1:
-            raise ValueError("run_borders_validation: length needs n entries, bounds n + 1")
-        if total < 0 or min(int(probs.numel()), int(y.numel())) < total:
-            raise ValueError("run_borders_validation: probs and y need %d elements" % total)
+        k = len(thresholds)
+        n, total, longest = self._check_validation_sizes("run_borders_validation", probs, y, bounds, length, total, longest)
         if int(counts_out.numel()) < k * 2 * (5 * reach + 3):
             raise ValueError("run_borders_validation: counts_out needs 2 * (5 * reach + 3) entries per threshold")
         if stream is None:
             stream = torch.cuda.current_stream(probs.device)
-        # n, K, min_run and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
-        if max_gap:            # (the prediction is bridged first: ``cf_validation_run_borders_bridged``)
-            N.check(self._lib.cf_validation_run_borders_bridged(
-                self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
-                C.c_void_p(length.data_ptr()), n, total, longest, (C.c_double * max(k, 1))(*thresholds), k, reach, int(max_gap),
-                int(min_run), C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()),
-                C.c_void_p(stream.cuda_stream)))
-            return
-        N.check(self._lib.cf_validation_run_borders(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()),
-                                                    C.c_void_p(bounds.data_ptr()), C.c_void_p(length.data_ptr()), n, total, longest,
-                                                    (C.c_double * max(k, 1))(*thresholds), k, reach, int(min_run),
-                                                    C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()),
-                                                    C.c_void_p(stream.cuda_stream)))
+        # n, K, min_run, the (min_run, max_gap) pair and the work space are refused by the library (CF_ERR_INVALID -> ValueError);
+        # ``max_gap`` 0 is ``cf_validation_run_borders``, anything else bridges the prediction first
+        N.check(self._lib.cf_validation_run_borders_bridged(
+            self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
+            C.c_void_p(length.data_ptr()), n, total, longest, (C.c_double * max(k, 1))(*thresholds), k, reach, int(max_gap),
+            int(min_run), C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()),
+            C.c_void_p(stream.cuda_stream)))
 
     def curve_validation(self, probs, y, bounds, length, total, longest, shift, hist_out, stream=None):
         """``cf_validation_curve``: how many samples of label 1 / label 0 / any other label fall into every bin of
@@ -576,11 +568,7 @@ class HipEngine(object):
         self._check_validation_tensors("curve_validation", [
             ("probs", probs, torch.float32), ("y", y, torch.uint8), ("bounds", bounds, torch.int64), ("length", length, torch.int64),
             ("hist_out", hist_out, torch.int64)])
-        n, total, longest = int(length.numel()), int(total), int(longest)
-        if int(bounds.numel()) != n + 1:
-            raise ValueError("curve_validation: length needs n entries, bounds n + 1")
-        if total < 0 or min(int(probs.numel()), int(y.numel())) < total:
-            raise ValueError("curve_validation: probs and y need %d elements" % total)
+        n, total, longest = self._check_validation_sizes("curve_validation", probs, y, bounds, length, total, longest)
         if isinstance(shift, bool) or int(shift) != shift:
             raise ValueError("curve_validation: shift must be an int, got %r" % (shift,))
         if stream is None:

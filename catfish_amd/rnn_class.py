@@ -235,122 +235,38 @@ class RNN(object):
         probabilities and logits (the weighted mean of the logits, not the logit of the voted probability) that everything after it
         consumes; ``(0,)`` launches and allocates nothing that was not before.
 
+        The tuple is a ``validation_round.RoundResult``: every result is also an attribute -- ``right``, ``ce_sum``, ``counts``,
+        ``run_states``, ``run_borders``, ``curve`` -- that is None when it was not asked for.  ``validation_round.RoundSpec`` checks the
+        options, ``RoundPlan`` holds the sizes and the layout of the result buffer (host-only, both).
+
         The selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes
         probabilities and logits (the weights just trained, as ``score_windows`` uses them), ``cf_validation_score`` reduces them
         -- more than 16 thresholds in groups of 16 over the same forward pass -- and ONE copy brings the results back; all on
         the current stream.  The work buffers stay on the object and grow only when a round is larger than every one before
         (``validation_buffers``: capacities and how often each was allocated or uploaded)."""
         import torch
-        from . import device_validation as dv
+        from .validation_round import RoundPlan, RoundSpec, grow, walk
         self._require_engine()
-        from .calling import CallRule
-        from .tilings import tiling_size
-        rule = CallRule.of(max_gap=bridge_gap, phases=phases, vote_weight=vote_weight)
-        bridge_gap, phases, vote_weight = rule.max_gap, rule.phases, rule.vote_weight
-        thresholds = tuple(float(t) for t in thresholds)
-        if not thresholds:
-            raise ValueError("score_validation_device: no threshold given")
-        if run_edges is not None:
-            run_edges = dv.check_run_edges(run_edges)
-        curve_cells = 0 if curve_shift is None else 3 * dv.curve_bins(curve_shift)
-        if border_reach is not None:
-            border_reach = dv.check_border_reach(border_reach)
-            if not vset.labels_binary:
-                raise ValueError("score_validation_device: border_reach needs a set whose labels are all 0 or 1")
+        spec = RoundSpec.of(thresholds, run_edges, border_reach, curve_shift, bridge_gap, phases, vote_weight)
+        if spec.border_reach is not None and not vset.labels_binary:
+            raise ValueError("score_validation_device: border_reach needs a set whose labels are all 0 or 1")
         read_index, first, length = vset.check_selection(selection)
-        n = int(read_index.size)
-        if n == 0:
+        if read_index.size == 0:
             raise ValueError("score_validation_device: no read selected")
-        bounds, _tails = dv.layout(length, self.window)
-        total, longest = int(bounds[-1]), int(np.diff(bounds).max())
+        plan = RoundPlan(spec, length, self.window)
         device = torch.device("cuda", self.device)
         signal, labels = vset.device_arrays(device)
         book = self.validation_buffers
-        k_all = len(thresholds)
-        slots = total // dv.SCORE_CHUNK + n
-        need = {"samples": max(total, 1), "reads": n, "slots": slots, "thresholds": k_all}
-        run_cells = 0
-        if run_edges is not None:
-            run_cells = k_all * 2 * (len(run_edges) + 1) * 3
-            need.update({"run_cells": run_cells,
-                         "run_work": max(self.engine.run_states_work_bytes(total, min(k_all, dv.MAX_THRESHOLDS)), 1)})
-        border_cells = 0
-        if border_reach is not None:
-            border_cells = k_all * 2 * dv.border_cells(border_reach)
-            need.update({"border_cells": border_cells,
-                         "run_work": max(self.engine.run_borders_work_bytes(total, min(k_all, dv.MAX_THRESHOLDS)), 1)})
-        if curve_shift is not None:
-            need["curve_cells"] = curve_cells
-        if rule.voted:
-            need["tiling_samples"] = tiling_size(total, n, rule.n_tilings)
-        if any(book["capacity"].get(key, 0) < value for key, value in need.items()):
-            cap = {key: max(book["capacity"].get(key, 0), value) for key, value in need.items()}
-            f32 = lambda count: torch.empty(count, dtype=torch.float32, device=device)     # noqa: E731
-            book["tensors"] = {"x": f32(cap["samples"]), "probs": f32(cap["samples"]), "logits": f32(cap["samples"]),
-                               "y": torch.empty(cap["samples"], dtype=torch.uint8, device=device),
-                               "table": torch.empty(3 * (cap["reads"] + 1), dtype=torch.int64, device=device),
-                               "partials": torch.empty(cap["slots"], dtype=torch.float64, device=device),
-                               # right [reads] | ce_sum [reads], double bits | counts [4 per threshold] | run states | borders |
-                               # curve histogram: one copy back
-                               "out": torch.empty(2 * cap["reads"] + 4 * cap["thresholds"] + cap.get("run_cells", 0)
-                                                  + cap.get("border_cells", 0) + cap.get("curve_cells", 0), dtype=torch.int64, device=device)}
-            if "run_work" in cap:                                                    # corrected labels, one array per threshold of a group
-                book["tensors"]["run_work"] = torch.empty(cap["run_work"], dtype=torch.uint8, device=device)
-            if "tiling_samples" in cap:                                              # every tiling's input, probabilities and logits
-                book["tensors"].update({key: f32(cap["tiling_samples"]) for key in ("tilings_x", "tilings_probs", "tilings_logits")})
-            book["capacity"] = cap
-            book["allocations"] += 1
-        if book["thresholds"] is None or book["thresholds"][0] != thresholds or book["thresholds"][1].device != device:
-            book["thresholds"] = (thresholds, torch.tensor(thresholds, dtype=torch.float64, device=device))
+        t = grow(book, plan.need, device)
+        if book["thresholds"] is None or book["thresholds"][0] != spec.thresholds or book["thresholds"][1].device != device:
+            book["thresholds"] = (spec.thresholds, torch.tensor(spec.thresholds, dtype=torch.float64, device=device))
             book["threshold_uploads"] += 1
-        t = book["tensors"]
-        table = np.zeros((3, n + 1), dtype=np.int64)
-        table[0, :n] = vset.offsets[read_index] + first
-        table[1, :n] = length
-        table[2] = bounds
-        t["table"][:3 * (n + 1)].copy_(torch.from_numpy(table.reshape(-1)))
+        t["table"][:3 * (plan.n + 1)].copy_(torch.from_numpy(plan.table(vset.offsets, read_index, first).reshape(-1)))
         book["selection_uploads"] += 1
-        src_d, len_d, bounds_d = (t["table"][i * (n + 1):i * (n + 1) + count] for i, count in ((0, n), (1, n), (2, n + 1)))
-        x, y, probs, logits = t["x"][:total], t["y"][:total], t["probs"][:total], t["logits"][:total]
-        out = t["out"][:2 * n + 4 * k_all + run_cells + border_cells + curve_cells]
-        right_d, ce_d, counts_d = out[:n], out[n:2 * n].view(torch.float64), out[2 * n:2 * n + 4 * k_all]
-        runs_at = 2 * n + 4 * k_all
-        borders_at, curve_at = runs_at + run_cells, runs_at + run_cells + border_cells
-        runs_d, borders_d, curve_d = out[runs_at:borders_at], out[borders_at:curve_at], out[curve_at:]
-        if rule.voted:
-            size = need["tiling_samples"]
-            x_all, probs_all, logits_all = t["tilings_x"][:size], t["tilings_probs"][:size], t["tilings_logits"][:size]
-            self.engine.gather_validation(signal, labels, src_d, len_d, bounds_d, total, longest, x_all[:total], y)
-            self.engine.retile_device(x_all, bounds_d, len_d, total, phases)
-            self.engine.infer_device(x_all.view(-1, self.window), out=probs_all, logits=logits_all)
-            self.engine.vote_device(probs_all, bounds_d, len_d, total, phases, vote_weight, logits_all=logits_all, out=probs, logits_out=logits)
-        else:
-            self.engine.gather_validation(signal, labels, src_d, len_d, bounds_d, total, longest, x, y)
-            self.engine.infer_device(x.view(-1, self.window), out=probs, logits=logits)
-        for k0 in range(0, k_all, dv.MAX_THRESHOLDS):
-            k1 = min(k_all, k0 + dv.MAX_THRESHOLDS)
-            self.engine.score_validation(probs, logits, y, bounds_d, total, longest, book["thresholds"][1][k0:k1], right_d, ce_d,
-                                         counts_d[4 * k0:4 * k1], t["partials"])
-            if run_edges is not None:
-                per_k = run_cells // k_all
-                self.engine.run_states_validation(probs, y, bounds_d, len_d, total, longest, thresholds[k0:k1], run_edges,
-                                                  runs_d[per_k * k0:per_k * k1], t["run_work"], max_gap=bridge_gap)
-            if border_reach is not None:
-                per_k = border_cells // k_all
-                self.engine.run_borders_validation(probs, y, bounds_d, len_d, total, longest, thresholds[k0:k1], border_reach,
-                                                   borders_d[per_k * k0:per_k * k1], t["run_work"], max_gap=bridge_gap)
-        if curve_shift is not None:
-            self.engine.curve_validation(probs, y, bounds_d, len_d, total, longest, curve_shift, curve_d)
+        out = walk(self.engine, plan, t, book["thresholds"][1], signal, labels, self.window)
         back = out.cpu().numpy()                                                     # synchronises the stream
         self.engine.check_error()
-        results = (back[:n].copy(), back[n:2 * n].view(np.float64).copy(), back[2 * n:2 * n + 4 * k_all].reshape(k_all, 4).copy())
-        if run_edges is not None:
-            results += (back[runs_at:borders_at].reshape(k_all, 2, len(run_edges) + 1, 3).copy(),)
-        if border_reach is not None:
-            results += (back[borders_at:curve_at].reshape(k_all, 2, -1).copy(),)
-        if curve_shift is not None:
-            results += (back[curve_at:].reshape(3, -1).copy(),)
-        return results
+        return plan.results(back)
 
     @property
     def validation_buffers(self):

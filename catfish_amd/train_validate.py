@@ -463,11 +463,11 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
             got = network.score_validation_device(squiggles, selection, (0.5,), run_edges=run_edges, curve_shift=curve_shift, **extra)
             right, ce_sum, counts_k = got[:3]
             if run_edges is not None:
-                network.validation_run_states = got[3][0]
+                network.validation_run_states = got.run_states[0]
             if border_reach is not None:
-                network.validation_run_borders = got[3 + (run_edges is not None)][0]
+                network.validation_run_borders = got.run_borders[0]
             if curve_shift is not None:
-                network.validation_curve = got[-1]
+                network.validation_curve = got.curve
         acc, loss, counts = squiggles.finish(right, ce_sum, counts_k[0], *squiggles.layout(selection[2], network.window))
     else:
         if run_edges is not None:
@@ -535,20 +535,16 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     voted = {"phases": rule.phases, "vote_weight": rule.vote_weight} if rule.voted else {}      # (0,): the call of before
     if bridge_gap and run_edges is None and border_reach is None:
         raise ValueError("threshold_sweep: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
-    bridged = dict(voted, bridge_gap=bridge_gap) if bridge_gap else voted
+    given = {"run_edges": run_edges, "border_reach": border_reach, "bridge_gap": bridge_gap or None}
+    given = {key: value for key, value in given.items() if value is not None}                  # nothing given: the call of before
     thresholds = [float(t) for t in thresholds]
     selection = vset.select(network.window, max_seq_length, validation_start, max_number)
     if len(selection[0]) == 0:
         raise ZeroDivisionError("validation selected no read")
-    run_states = borders = None
-    if run_edges is None and border_reach is None:
-        _right, _ce_sum, counts = network.score_validation_device(vset, selection, thresholds, **voted)
-    elif border_reach is None:
-        _right, _ce_sum, counts, run_states = network.score_validation_device(vset, selection, thresholds, run_edges=run_edges, **bridged)
-    else:
-        got = network.score_validation_device(vset, selection, thresholds, run_edges=run_edges, border_reach=border_reach, **bridged)
-        counts, borders = got[2], got[-1]
-        run_states = None if run_edges is None else got[3]
+    got = network.score_validation_device(vset, selection, thresholds, **given, **voted)
+    counts = got[2]
+    run_states = None if run_edges is None else got.run_states
+    borders = None if border_reach is None else got.run_borders
     tail = int(vset.layout(selection[2], network.window)[1].sum())
     rows = []
     for k, (t, (tp, fp, tn_raw, fn)) in enumerate(zip(thresholds, np.asarray(counts).tolist())):
@@ -620,7 +616,7 @@ def validation_curves(network, vset, max_seq_length, validation_start="complete"
     selection = vset.select(network.window, max_seq_length, validation_start, max_number)
     if len(selection[0]) == 0:
         raise ZeroDivisionError("validation selected no read")
-    hist = network.score_validation_device(vset, selection, (0.5,), curve_shift=shift)[-1]
+    hist = network.score_validation_device(vset, selection, (0.5,), curve_shift=shift).curve
     curves = curves_from_histogram(hist, shift)
     curves.update({"shift": int(shift), "thresholds": curve_thresholds(shift)})
     return curves

@@ -223,3 +223,53 @@ def test_rounds_score_the_weights_just_trained_and_keep_their_buffers(hp, tmp_pa
             assert (resident.uploads, book["allocations"], book["selection_uploads"]) == (1, 2, 5)
         net.engine.close()
     assert reports["device"] == reports["host"]
+
+
+def test_a_round_names_its_results_and_lays_them_out_as_before(hp):
+    """Every combination of the three optional results over three reads with a tail each and two thresholds: the named fields are
+    the items at the positions the docstring of ``score_validation_device`` states, the round with everything asked for holds the
+    bytes of the rounds that ask for one thing, and the buffers are allocated again only when a capacity grows."""
+    import itertools
+    from catfish_amd.resnet_class import ResNetRNN
+    reads = [tv.synthetic_labelled_read(3000 + 36 * i, seed=50 + i) for i in range(3)]
+    resident = DeviceValidationSet.from_arrays([raw for raw, _lab in reads], [lab for _raw, lab in reads])
+    selection = resident.select(35, 0, "complete", 856)
+    assert selection[2].tolist() == [3000, 3036, 3072] and all(dv.layout(selection[2], 35)[1] > 0)
+    net = ResNetRNN(**hp)
+    net.initialize_network(seed=5)
+    try:
+        book = net.validation_buffers
+        rounds = {}
+        for asked in itertools.product((False, True), repeat=3):
+            runs, borders, curve = asked
+            before, allocations = dict(book["capacity"]), book["allocations"]
+            got = net.score_validation_device(resident, selection, (0.3, 0.5), run_edges=(35,) if runs else None,
+                                              border_reach=32 if borders else None, curve_shift=14 if curve else None)
+            grown = [key for key, value in book["capacity"].items() if value > before.get(key, 0)]
+            assert book["allocations"] == allocations + bool(grown)
+            assert grown or book["capacity"] == before
+            assert isinstance(got, tuple) and len(got) == 3 + sum(asked)
+            assert got.right is got[0] and got.ce_sum is got[1] and got.counts is got[2]
+            assert got.right.shape == (3,) and got.ce_sum.dtype == np.float64 and got.counts.shape == (2, 4)
+            assert got.run_states is (got[3] if runs else None) and got.run_borders is (got[3 + runs] if borders else None)
+            assert got.curve is (got[-1] if curve else None)
+            if runs:
+                assert got.run_states.shape == (2, 2, 2, 3)
+            if borders:
+                assert got.run_borders.shape == (2, 2, 5 * 32 + 3)
+            if curve:
+                assert got.curve.shape == (3, dv.curve_bins(14)) and int(got.curve.sum()) == int(selection[2].sum())
+            assert got.counts.sum(axis=1).tolist() == [int(dv.layout(selection[2], 35)[0][-1])] * 2
+            rounds[asked] = got
+        assert book["selection_uploads"] == 8 and book["threshold_uploads"] == 1
+        everything, allocations = rounds[(True, True, True)], book["allocations"]
+        again = net.score_validation_device(resident, selection, (0.3, 0.5), run_edges=(35,), border_reach=32, curve_shift=14)
+        assert book["allocations"] == allocations and all(a.tobytes() == b.tobytes() for a, b in zip(again, everything))
+        for got in rounds.values():                            # the per-sample results do not depend on what else is asked for
+            assert all(a.tobytes() == b.tobytes() for a, b in zip(got[:3], everything[:3]))
+        assert everything.run_states.tobytes() == rounds[(True, False, False)].run_states.tobytes()
+        assert everything.run_borders.tobytes() == rounds[(False, True, False)].run_borders.tobytes()
+        assert everything.curve.tobytes() == rounds[(False, False, True)].curve.tobytes()
+        assert everything.run_states.sum() > 0 and everything.run_borders.sum() > 0
+    finally:
+        net.engine.close()
