@@ -137,6 +137,7 @@ SYMBOLS = {
     "cf_gru_anysize_train_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_int64, C.c_void_p]),
     "cf_gru_anysize_train_shape": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
+    "cf_anysize_infer_shape": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int64]),
     "cf_gru_anysize_x3_pack_floats": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     "cf_gen_repack_x3": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "cf_gru_anysize_train_forward_x3": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1072,6 +1072,7 @@ __global__ __launch_bounds__(256) void normalize_kernel(const int16_t* __restric
 // ==========================================================================================
 // Host side
 // ==========================================================================================
+#include "anysize_infer_launch.hpp"      // kernel, waves, grid and LDS bytes of the any-size inference recurrences: host-only, tested on the CPU
 #include "generic.hpp"
 
 // A/B and test knobs: environment variables (CATFISH_GENERIC, CATFISH_WAVES, CATFISH_BF16_PIPE, ... -- tools/README.md lists
@@ -2473,6 +2474,26 @@ extern "C" int cf_gru_anysize_train_shape(const cf_model* m, int32_t layer_size,
     const cf_anysize_shape f = cf_anysize_forward_shape(h16, n_tiles, m->n_cu), b = cf_anysize_backward_shape(h16, n_tiles, m->n_cu);
     out[0] = f.waves; out[1] = f.grid_x; out[2] = (int64_t)f.lds_bytes; out[3] = f.h_via_y;
     out[4] = b.waves; out[5] = b.grid_x; out[6] = (int64_t)b.lds_bytes; out[7] = b.max_waves;
+    return CF_OK;
+}
+
+// The launch shape of every biGRU layer of an any-size model in one pass of `n_windows` windows (what gen_run_pass takes from
+// csrc/anysize_infer_launch.hpp), for tests and tools: out = one row per layer of {kernel (0 tuned LDS-resident, 1 one tile per
+// wave, 2 two tiles per wave), waves per workgroup, grid x, dynamic LDS bytes, h_via_y}.  Nothing is launched.
+extern "C" int cf_anysize_infer_shape(const cf_model* m, int64_t n_windows, int64_t* out, int64_t capacity) {
+    if (!m || !out) return fail(CF_ERR_INVALID, "cf_anysize_infer_shape: null argument");
+    if (!m->gen) return fail(CF_ERR_INVALID, "cf_anysize_infer_shape: the model is not on the any-size path");
+    if (n_windows <= 0 || n_windows > m->cap_windows)
+        return fail(CF_ERR_INVALID, "cf_anysize_infer_shape: n_windows must be between 1 and the model's windows per pass");
+    const cf_generic* g = m->gen;
+    if (capacity < (int64_t)g->layers.size()) return fail(CF_ERR_INVALID, "cf_anysize_infer_shape: out needs one row of 5 values per biGRU layer");
+    const int n_tiles = (int)((n_windows + CF_TILE - 1) / CF_TILE);
+    for (size_t l = 0; l < g->layers.size(); ++l) {
+        const cf_generic::Layer& L = g->layers[l];
+        const cf_anysize_infer_launch sh = cf_anysize_infer_shape_for(g->cls, L.tuned != nullptr, L.kbx, n_tiles, m->n_cu);
+        int64_t* row = out + 5 * l;
+        row[0] = sh.kernel; row[1] = sh.waves; row[2] = sh.grid_x; row[3] = (int64_t)sh.lds_bytes; row[4] = sh.h_via_y;
+    }
     return CF_OK;
 }
 

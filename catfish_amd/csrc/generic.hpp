@@ -874,11 +874,7 @@ struct cf_generic {
     std::vector<void*> owned;                   // every device allocation above
     float* r[4] = {nullptr, nullptr, nullptr, nullptr};      // conv activations, C features
     float* g[2] = {nullptr, nullptr};                        // biGRU outputs, 2H features
-    int gru_waves = 8;
-    bool h_via_y = false;
-    int gru2_waves = 0;                         // gen_gru2_kernel (two tiles per wave): waves per workgroup, 0 = not used
-    size_t gru2_lds = 0;
-    size_t gru_lds = 0;
+    cf_anysize_infer_class cls;                 // biGRU launch class of this layer size (csrc/anysize_infer_launch.hpp)
 };
 
 // bf16x3 A pack (gen_dot_x3): K16 (a multiple of 4, padding included) -> per (mo, pair p) w_hi [lane][8] then w_lo [lane][8] in

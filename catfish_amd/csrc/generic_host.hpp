@@ -220,23 +220,16 @@ static int gen_build(cf_model* m, const cf_weights* w) {
         g->owned.push_back(g->g[i]);
     }
     m->ws_bytes = (int64_t)(n_r * r_bytes + 2 * g_bytes);
-    // biGRU launch shape: the state of a tile takes 3 H 64 B of LDS; as many waves per workgroup as fit (8 at most)
-    // (h, r.h and h'); when eight waves of that do not fit, h' goes through the output buffer instead (two arrays) and the
-    // workgroup is 8 or 4 waves, so that every SIMD carries the same number
-    size_t per_wave = (size_t)3 * g->H16 * 64 * sizeof(f32x4);
-    g->h_via_y = per_wave * 8 > (size_t)(160 * 1024);
-    if (g->h_via_y) per_wave = (size_t)2 * g->H16 * 64 * sizeof(f32x4);
-    g->gru_waves = per_wave * 8 <= (size_t)(160 * 1024) ? 8 : 4;
-    if (cf_knob("CATFISH_GEN_WAVES")) g->gru_waves = std::max(1, std::min(g->gru_waves, atoi(cf_knob("CATFISH_GEN_WAVES"))));    // A/B knob for tools/
-    g->gru_lds = per_wave * g->gru_waves;
-    // two tiles per wave (gen_gru2_kernel): two LDS arrays per tile; 8 or 4 waves per workgroup, else not used
-    const size_t per_wave2 = (size_t)2 * 2 * g->H16 * 64 * sizeof(f32x4);
-    g->gru2_waves = (g->H16 % 4) != 0 || g->x3 || cf_knob("CATFISH_GEN_ONE_TILE") ? 0 : (per_wave2 * 8 <= (size_t)(160 * 1024) ? 8 : (per_wave2 * 4 <= (size_t)(160 * 1024) ? 4 : 0));
-    g->gru2_lds = per_wave2 * g->gru2_waves;
-    if (g->gru2_waves)
-        HIP_TRY(hipFuncSetAttribute((const void*)gen_gru2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->gru2_lds));
+    // biGRU launch class (csrc/anysize_infer_launch.hpp): the state of a tile takes 3 H 64 B of LDS (h, r.h and h'); as many
+    // waves per workgroup as fit (8 at most); when eight waves of that do not fit, h' goes through the output buffer instead
+    // (two arrays) and the workgroup is 8 or 4 waves, so that every SIMD carries the same number.  Two tiles per wave
+    // (gen_gru2_kernel): two LDS arrays per tile; 8 or 4 waves per workgroup, else not used.  The two knobs are for tools/.
+    g->cls = cf_anysize_infer_class_for(g->H16, g->x3, cf_knob("CATFISH_GEN_ONE_TILE") != nullptr,
+                                        cf_knob("CATFISH_GEN_WAVES") ? std::max(1, atoi(cf_knob("CATFISH_GEN_WAVES"))) : 0);
+    if (g->cls.gru2_waves)
+        HIP_TRY(hipFuncSetAttribute((const void*)gen_gru2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->cls.gru2_lds));
     HIP_TRY(hipFuncSetAttribute(g->x3 ? (const void*)gen_gru_kernel<false, true> : (const void*)gen_gru_kernel<false, false>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->gru_lds));
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)g->cls.gru_lds));
     cf_optin tuned;              // the LDS-resident kernels of gen_layer_tuned layers: the same opt-in as a model on the tuned path
     optin_gru_layer(tuned);
     HIP_TRY(tuned.e);
@@ -291,7 +284,8 @@ static int gen_run_pass(cf_model* m, const float* x, int64_t n_windows, float* p
     for (size_t l = 0; l < g->layers.size(); ++l) {
         const cf_generic::Layer& L = g->layers[l];
         const int slot = l == 0 ? SLOT_GRU0 : (l + 1 == g->layers.size() ? SLOT_GRU_LAST : SLOT_GRU);
-        if (L.tuned) {               // a 64-unit layer with 16 / 32 / 128 inputs: the LDS-resident kernel (all its launch regimes)
+        const cf_anysize_infer_launch sh = cf_anysize_infer_shape_for(g->cls, L.tuned != nullptr, L.kbx, n_tiles, m->n_cu);
+        if (sh.kernel == CF_ANYSIZE_INFER_TUNED) {      // a 64-unit layer with 16 / 32 / 128 inputs: the LDS-resident kernel (all its launch regimes)
             const float* x_in = reinterpret_cast<const float*>(cur);
             float* y_out = reinterpret_cast<float*>(G[l & 1]);
             if ((rc = launch_gru(m, knobs, L.tuned_cin, false, L.tuned, x_in, y_out, nullptr, n_tiles, s, slot)) != CF_OK) return rc;
@@ -299,20 +293,16 @@ static int gen_run_pass(cf_model* m, const float* x, int64_t n_windows, float* p
             continue;
         }
         if ((rc = prof_begin(m, slot, s, &pi)) != CF_OK) return rc;
-        if (g->gru2_waves && (L.kbx % 4) == 0 && n_tiles >= 2 * m->n_cu) {          // enough tiles to fill the chip two per wave
-            const int pairs = (n_tiles + 1) / 2, gx = (pairs + g->gru2_waves - 1) / g->gru2_waves;
-            hipLaunchKernelGGL(gen_gru2_kernel, dim3((unsigned)gx, 2), dim3(g->gru2_waves * 64), g->gru2_lds, s,
+        if (sh.kernel == CF_ANYSIZE_INFER_TWO_TILE) {
+            hipLaunchKernelGGL(gen_gru2_kernel, dim3((unsigned)sh.grid_x, 2), dim3(sh.waves * 64), sh.lds_bytes, s,
                                L.w, L.b, cur, G[l & 1], g->H16, L.kbx);
             HIP_TRY(hipGetLastError());
             if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
             cur = G[l & 1];
             continue;
         }
-        // small calls (the reference's one-read-per-call pattern): fewer waves per workgroup, so that the tiles spread over the CUs
-        const int waves = std::max(1, std::min(g->gru_waves, (2 * n_tiles + m->n_cu - 1) / m->n_cu));
-        const int gx = (n_tiles + waves - 1) / waves;
-        hipLaunchKernelGGL((g->x3 ? gen_gru_kernel<false, true> : gen_gru_kernel<false, false>), dim3((unsigned)gx, 2), dim3(waves * 64),
-                           g->gru_lds / g->gru_waves * waves, s, L.w, L.b, cur, G[l & 1], g->H16, L.kbx, g->h_via_y ? 1 : 0, (f32x4*)nullptr, n_tiles);
+        hipLaunchKernelGGL((g->x3 ? gen_gru_kernel<false, true> : gen_gru_kernel<false, false>), dim3((unsigned)sh.grid_x, 2), dim3(sh.waves * 64),
+                           sh.lds_bytes, s, L.w, L.b, cur, G[l & 1], g->H16, L.kbx, sh.h_via_y, (f32x4*)nullptr, n_tiles);
         HIP_TRY(hipGetLastError());
         if ((rc = prof_end(m, s, pi)) != CF_OK) return rc;
         cur = G[l & 1];

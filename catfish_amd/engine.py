@@ -133,6 +133,15 @@ class HipEngine(object):
         N.check(self._lib.cf_launch_regimes(self._handle, out))
         return dict(n_cu=int(out[0]), hoist_max=int(out[1]), coop_max=int(out[2]), fuse_auto_min=int(out[3]))
 
+    def anysize_infer_shape(self, n_windows):
+        """The launch of every biGRU layer of an any-size model in one pass of ``n_windows`` windows (``cf_anysize_infer_shape``;
+        nothing is launched): a list of dict(kernel, waves, grid_x, lds_bytes, h_via_y), ``kernel`` one of "tuned" (the
+        LDS-resident kernel: see ``launch_regimes``), "one_tile", "two_tile".  ValueError on the tuned 64 / 32 path."""
+        out = (C.c_int64 * (5 * self.n_layers))()
+        N.check(self._lib.cf_anysize_infer_shape(self._handle, int(n_windows), out, self.n_layers))
+        return [dict(kernel=("tuned", "one_tile", "two_tile")[out[5 * l]], waves=int(out[5 * l + 1]), grid_x=int(out[5 * l + 2]),
+                     lds_bytes=int(out[5 * l + 3]), h_via_y=int(out[5 * l + 4])) for l in range(self.n_layers)]
+
     def infer_device(self, x, out=None, stream=None, logits=None):
         """torch CUDA float32 tensor [N,35(,1)] -> torch CUDA float32 [N*35], async on the stream.
 

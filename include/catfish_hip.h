@@ -378,6 +378,13 @@ int cf_gru_anysize_train_backward(cf_model* m, int32_t layer_size, const float* 
  * workgroup runs `waves` tiles of one direction, so grid x * waves >= tiles and the last workgroup may be partly empty.  For
  * tests and tools that must know which regime a size runs in; same argument checks as the two calls. */
 int cf_gru_anysize_train_shape(const cf_model* m, int32_t layer_size, int64_t n_windows, int64_t out[8]);
+/* The launch shape of the biGRU layers of an any-size model's forward pass (cf_infer* of a geometry other than 64 / 32, or of the
+ * plain RNN type in bf16x3) in one pass of n_windows windows, 1 <= n_windows <= the model's windows per pass, without launching
+ * anything (csrc/anysize_infer_launch.hpp): out receives one row of five values per biGRU layer, `capacity` >= n_layers rows of
+ * room: {kernel: 0 = the LDS-resident kernel of the tuned path (a 64-unit layer with 16 / 32 / 128 inputs in fp32), 1 = one tile
+ * per wave, 2 = two tiles per wave; waves per workgroup; grid x; dynamic LDS bytes; h_via_y}.  Waves, grid and LDS are 0 for
+ * kernel 0, whose regimes cf_launch_regimes reports.  For tests and tools that must know which launch a size runs in. */
+int cf_anysize_infer_shape(const cf_model* m, int64_t n_windows, int64_t* out, int64_t capacity);
 /* Training precision "bf16x3" for those two calls: only the matrix products on the serial chain -- forward [x | h] W_g and
  * [x | r.h] W_c, backward Wc_h^T da_c and Wg_h^T [da_r; da_u] -- are evaluated as a_hi w_hi + a_lo w_hi + a_hi w_lo on
  * v_mfma_f32_16x16x32_bf16 (hi = bf16(v), lo = bf16(v - hi)); state, gate activations, stash, da and all accumulation stay fp32,
