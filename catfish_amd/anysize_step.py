@@ -55,7 +55,7 @@ class AnySizeTrainStep(FlatTrainStep):
             self.walk.repack_x3(self.packed, self.packed_x3, stream)
 
     # ------------------------------------------------------------------ buffers per batch size
-    def _alloc(self, n):
+    def alloc(self, n):
         torch = self.torch
         npad = self._npad(n)
         f32 = dict(dtype=torch.float32, device=self.dev)

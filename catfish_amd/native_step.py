@@ -37,7 +37,7 @@ from .native_train import T, _stack_maps, dropout_scale_frag, frag_to_nat, nat_t
 
 class FlatTrainStep(object):
     """A training step over the flat buffers.  A subclass gives ``_layout`` (which calls ``_set_layout`` and sets ``pack_idx``,
-    ``pack_scale``, ``n_packed``: the gather map from the flat variables to its kernels' biGRU packs), ``_alloc`` and ``run``."""
+    ``pack_scale``, ``n_packed``: the gather map from the flat variables to its kernels' biGRU packs), ``alloc`` and ``run``."""
 
     def __init__(self, net, opt, engine, keep_prob, seed=None):
         import torch
@@ -150,7 +150,7 @@ class NativeTrainStep(FlatTrainStep):
         self.n_packed = int(self.pack_idx.numel())
 
     # ------------------------------------------------------------------ buffers per batch size
-    def _alloc(self, n):
+    def alloc(self, n):
         torch = self.torch
         dev = self.dev
         lib = self.lib

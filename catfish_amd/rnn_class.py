@@ -299,9 +299,9 @@ class RNN(object):
     def train_network(self, train_x, train_y, step):
         """rnn_class.py:201-210: one optimizer step on a batch (TF-1 update rules, dropout on the biGRU outputs).
 
-        On a GPU the whole step -- forward, loss, backward, optimizer, weight re-tiling -- runs on HIP kernels through
-        the C ABI (``training.Trainer`` -> ``native_step.py`` for the shipped 64 / 32 geometry, ``anysize_train.py``
-        for other sizes, ``anysize_step.py`` for other sizes with ``native_training=True``); the torch restatement is the CPU mode and the test reference.  The inference engine picks
+        ``training.Trainer`` takes the step; which path it trains through (the HIP kernels of the whole step at the shipped
+        64 / 32 geometry or, with ``native_training=True``, at any other; autograd around the any-size recurrences; the torch
+        restatement, which is the CPU mode and the test reference) is one row of the table in ``train_mode.py``.  The inference engine picks
         the updated weights up lazily, at the next ``infer``.  TensorBoard summaries (the reference's second forward,
         :206-208) are not written.
         """

@@ -1,0 +1,67 @@
+"""Which training path a ``training.Trainer`` takes, decided once, on the host: ints, strings and bools only (no torch, no library).
+
+``geometry(weights, n_layers_res)`` reads the two sizes; ``TrainMode.of`` maps them and the trainer's arguments to one row:
+
+    geometry   device  dtype    native      type       kind              engine keywords          step class        fed by card  captured
+    ---------  ------  -------  ----------  ---------  ----------------  -----------------------  ----------------  -----------  --------
+    64 / 32    cuda    float32  None, True  ResNetRNN  tuned_step        fuse_layers=False        NativeTrainStep   yes          yes
+    other      cuda    float32  True        either     anysize_step      layer_size, .._size_res  AnySizeTrainStep  yes          yes
+    other      cuda    float32  None        either     anysize_autograd  layer_size, .._size_res  AutogradStep      yes          yes
+    64 / 32    cuda    float32  True        RNN        tuned_autograd    fuse_layers=False        AutogradStep      yes          yes
+    64 / 32    cuda    other    None        ResNetRNN  tuned_autograd    fuse_layers=False        AutogradStep      no           yes
+    everything else (the CPU, native=False, ...)       torch             no engine                AutogradStep      cuda float32 cuda
+
+"ResNetRNN" is a model with a conv stack (``n_layers_res > 0``), "RNN" one without; an RNN's ``c`` counts as 32, so a 64-unit RNN is
+at the 64 / 32 geometry.  "fed by card" is ``Trainer.train_steps`` replaying the device-fed graph, "captured" is ``use_graph``.
+``native`` is True in the rows of ``tuned_step``, ``anysize_step`` and ``tuned_autograd`` and whenever ``native=True`` was passed;
+``anysize`` is True in the ``anysize_autograd`` row only.
+
+The two ``tuned_autograd`` rows are what the constructor has always admitted, kept as they are: autograd around
+``native_train.native_gru_stack`` through an engine that has no step.  No test trains through them; the GPU suite only constructs the
+first and checks its attributes against this table.
+
+``precision="bf16x3"`` exists in the two ``anysize_*`` rows.  Elsewhere it is refused, and so is ``native=True`` off the GPU or off
+float32, with one ``ValueError`` each, in the order of ``TrainMode.of``'s body.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+
+KINDS = ("tuned_step", "anysize_step", "anysize_autograd", "tuned_autograd", "torch")
+STEP_KINDS = KINDS[:2]                                       # the whole step on the HIP kernels, no autograd
+
+
+def geometry(weights, n_layers_res):
+    """(GRU units, conv channels, is it the shipped 64 / 32) of a {TF name: array or tensor}; without a conv stack ``c`` counts as 32."""
+    h = len(weights["stack_bidirectional_rnn/cell_0/bidirectional_rnn/fw/gru_cell/candidate/bias"])
+    c = len(weights["conv1d/bias"]) if n_layers_res > 0 else 32
+    return h, c, (h == 64 and c == 32)
+
+
+class TrainMode(namedtuple("TrainMode", "kind engine_kwargs native anysize")):
+    """One row of the module's table.  ``engine_kwargs``: None = no engine, else the keywords that size the trainer's ``HipEngine``."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, h, c, n_layers_res, device_type, float32, native, precision, dtype_name=""):
+        """``h``, ``c`` as ``geometry`` gives them; ``float32``: the variables' dtype is; ``native``: None | bool as passed to the
+        trainer; ``dtype_name`` only words the dtype refusal."""
+        shipped = (h == 64 and c == 32)
+        cuda, conv = device_type == "cuda", n_layers_res > 0
+        if precision == "bf16x3":
+            why = ("the tuned training kernels of the shipped 64 / 32 geometry are fp32" if shipped else
+                   "it runs on the HIP kernels: device='cpu' has none" if not cuda else
+                   "native=False is the pure-torch reference" if native is not None and not native else
+                   "the training kernels are float32 (dtype %s)" % dtype_name if not float32 else None)
+            if why:
+                raise ValueError("precision='bf16x3' is a mode of the any-size training recurrences; %s" % why)
+        if native and not (cuda and float32):
+            raise ValueError("native=True runs the fp32 HIP training kernels: it needs device='cuda' and dtype float32")
+        sizes = dict(layer_size=h, layer_size_res=c)
+        if native and not shipped:
+            return cls("anysize_step", sizes, True, False)
+        if native is None and cuda and float32 and not shipped:
+            return cls("anysize_autograd", sizes, False, True)
+        if native or (native is None and cuda and conv and shipped):
+            return cls("tuned_step" if conv and float32 else "tuned_autograd", dict(fuse_layers=False), True, False)
+        return cls("torch", None, False, False)

@@ -16,6 +16,8 @@ from __future__ import annotations
 
 import numpy as np
 
+from .train_mode import STEP_KINDS, TrainMode, geometry
+
 
 def _names(n_layers, n_layers_res):
     conv = lambda j: "conv1d" if j == 0 else "conv1d_%d" % j            # noqa: E731
@@ -69,10 +71,7 @@ class TorchResNetRNN(object):
         if x.dim() == 3:
             x = x[:, :, 0]
         a = x[:, None, :]                                # [N, C, T]
-        hsz0 = int(p["stack_bidirectional_rnn/cell_0/bidirectional_rnn/fw/gru_cell/candidate/bias"].shape[0])
-        csz0 = int(p["conv1d/bias"].shape[0]) if self.n_layers_res > 0 else 32
-        anysize = engine is not None and not (hsz0 == 64 and csz0 == 32)     # recurrence on the any-size HIP kernels
-        if anysize:
+        if engine is not None and not geometry(p, self.n_layers_res)[2]:     # recurrence on the any-size HIP kernels
             return self._logits_anysize(a, keep_prob, generator, engine, masks)
         native_res = engine is not None and self.n_layers_res > 0 and self.dtype == torch.float32
         if native_res:                                   # residual conv stack on the HIP training kernels
@@ -273,6 +272,56 @@ class TFOptimizer(object):
                     p.grad = None
 
 
+class AutogradStep(object):
+    """The step through torch autograd, behind the interface of ``native_step.FlatTrainStep`` (``alloc``, ``load_batch``, ``run``,
+    ``grads``): pure torch without an ``engine``, else with the biGRU recurrences on the HIP kernels.
+
+    A buffer set that the trainer marked ``captured`` runs inside a HIP graph: its dropout draws come from torch's default
+    (graph-safe) CUDA generator instead of ``gen``, the gradients stay where the replays rewrite them (``opt.keep_grads``), and the
+    loss, which autograd allocates, is also filed in the set's ``loss`` cell, where the device-fed graph's sampler looks for it."""
+
+    def __init__(self, net, opt, engine, keep_prob, gen):
+        self.net, self.opt, self.engine, self.gen = net, opt, engine, gen
+        self.keep_prob = float(keep_prob)
+        self._grads = {}
+
+    def alloc(self, n):
+        torch = self.net.torch
+        x = torch.zeros((n, 35), dtype=self.net.dtype, device=self.net.device)
+        return {"n": n, "x": x, "y": torch.zeros_like(x), "loss": torch.zeros(1, dtype=torch.float32, device=self.net.device)}
+
+    def load_batch(self, b, x, y):
+        torch = self.net.torch
+        for name, a in (("x", x), ("y", y)):
+            b[name].copy_(torch.as_tensor(np.asarray(a), dtype=self.net.dtype).reshape(b[name].shape), non_blocking=True)
+
+    def _clear(self):
+        for p in self.net.trainable().values():
+            p.grad = None
+
+    def run(self, b, keep_prob=None, masks=None, update=True):
+        kp = self.keep_prob if keep_prob is None else keep_prob
+        captured = b.get("captured", False)
+        if captured:
+            self.opt.keep_grads = True
+        if not update:
+            self._clear()                                   # whatever an earlier step kept would be added to
+        loss = self.net.loss(b["x"], b["y"], kp, None if captured else self.gen, self.engine, masks)
+        loss.backward()
+        if update:
+            self.opt.step()
+        else:
+            self._grads = {k: p.grad for k, p in self.net.trainable().items()}
+            self._clear()
+        if captured:
+            b["loss"].copy_(loss.detach().reshape(1))
+        return loss
+
+    def grads(self):
+        """{TF name: gradient} of the last update-free step."""
+        return self._grads
+
+
 class Trainer(object):
     """One training step = forward + backward + optimizer update.
 
@@ -280,7 +329,10 @@ class Trainer(object):
     (``catfish_amd/native_step.py``: conv stack, biGRU layers, dense head + loss, optimizer; no autograd), captured ONCE
     into a HIP graph (``torch.cuda.CUDAGraph``) and replayed per batch; batches are copied into static input buffers.
     Dropout masks inside the graph come from torch's default (graph-safe) CUDA generator.  ``native=False`` (and the CPU)
-    run the torch-autograd restatement of the same graph -- the reference the native step is tested against.
+    run the torch-autograd restatement of the same graph -- the reference the native step is tested against.  Which of the five
+    paths a trainer takes is one row of the table in ``catfish_amd/train_mode.py`` (``self.mode``); every path is one object
+    with ``alloc`` / ``load_batch`` / ``run`` / ``grads`` (``self.step``), run eagerly, captured (``_capture_step``) or captured
+    behind the on-card sampler (``_capture_fed``).  ``step_impl`` is that object where the whole step is native, else None.
 
     ``precision="bf16x3"`` (opt-in; the default "fp32" changes nothing) evaluates the matrix products on the serial chain of the
     any-size biGRU recurrences, forward and backward, as split bf16 products; everything else stays fp32.  It exists where those
@@ -310,107 +362,79 @@ class Trainer(object):
         if seed is not None:
             self.gen.manual_seed(int(seed))
         self.last_loss = None
-        # native = the whole step on the HIP training kernels, no autograd: the default on a GPU for the ResNetRNN type at
-        # the shipped geometry (64 GRU units, 32 conv channels), which is what those kernels are specialised for.  Other
-        # draws of train_validate.generate_random_hyperparameters train through torch autograd with the biGRU recurrence
-        # on the any-size HIP kernels (anysize_train.py); their inference runs on csrc/generic.hpp either way.
-        h = int(np.asarray(weights["stack_bidirectional_rnn/cell_0/bidirectional_rnn/fw/gru_cell/candidate/bias"]).shape[0])
-        c = int(np.asarray(weights["conv1d/bias"]).shape[0]) if n_layers_res > 0 else 32
-        shipped = (h == 64 and c == 32)
-        if self.precision == "bf16x3":
-            why = ("the tuned training kernels of the shipped 64 / 32 geometry are fp32" if shipped else
-                   "it runs on the HIP kernels: device='cpu' has none" if self.net.device.type != "cuda" else
-                   "native=False is the pure-torch reference" if native is not None and not native else
-                   "the training kernels are float32 (dtype %s)" % self.net.dtype if self.net.dtype != torch.float32 else None)
-            if why:
-                raise ValueError("precision='bf16x3' is a mode of the any-size training recurrences; %s" % why)
-        if native and (self.net.device.type != "cuda" or self.net.dtype != torch.float32):
-            raise ValueError("native=True runs the fp32 HIP training kernels: it needs device='cuda' and dtype float32")
-        # native=True at any other geometry (RNN or ResNetRNN type): the whole step on the run-time-sized kernels (anysize_step.py)
-        native_any = bool(native) and not shipped
-        self.native = (self.net.device.type == "cuda" and n_layers_res > 0 and shipped) if native is None else bool(native)
+        # the one decision of which path trains this model: train_mode's table
+        h, c, _ = geometry(weights, n_layers_res)
+        f32 = self.net.dtype == torch.float32
+        mode = TrainMode.of(h, c, n_layers_res, self.net.device.type, f32, native, self.precision, dtype_name=str(self.net.dtype))
+        self.mode, self.native, self.anysize = mode.kind, mode.native, mode.anysize
         self.engine = None
-        self.step_impl = None
-        # other geometries on a GPU: torch autograd around the any-size HIP recurrence kernels (anysize_train.py); the
-        # engine is only the C-ABI handle those launches go through.  native=False keeps pure torch (the test reference).
-        self.anysize = self.net.device.type == "cuda" and not shipped and native is None and self.net.dtype == torch.float32
-        if self.anysize or self.native:
+        if mode.engine_kwargs is not None:                   # for the autograd kinds only the C-ABI handle their recurrences launch through
             from .engine import HipEngine
-            # the tuned step's engine is the shipped geometry with per-layer launches; the other two carry their sizes
-            sizes = dict(layer_size=h, layer_size_res=c) if self.anysize or native_any else dict(fuse_layers=False)
             self.engine = HipEngine(weights, n_layers=n_layers, n_layers_res=n_layers_res, device=self.net.device.index or 0,
-                                    max_windows_per_pass=256, **sizes)
-        if native_any:
+                                    max_windows_per_pass=256, **mode.engine_kwargs)
+        if mode.kind == "anysize_step":
             from .anysize_step import AnySizeTrainStep
-            self.step_impl = AnySizeTrainStep(self.net, self.opt, self.engine, self.keep_prob, seed=seed, precision=self.precision)
-        elif self.native and n_layers_res > 0 and self.net.dtype == torch.float32:
+            self.step = AnySizeTrainStep(self.net, self.opt, self.engine, self.keep_prob, seed=seed, precision=self.precision)
+        elif mode.kind == "tuned_step":
             from .native_step import NativeTrainStep
-            self.step_impl = NativeTrainStep(self.net, self.opt, self.engine, self.keep_prob, seed=seed)
+            self.step = NativeTrainStep(self.net, self.opt, self.engine, self.keep_prob, seed=seed)
+        else:
+            self.step = AutogradStep(self.net, self.opt, self.engine, self.keep_prob, self.gen)
+        self.step_impl = self.step if mode.kind in STEP_KINDS else None      # the native step object, None in the autograd kinds
         self.use_graph = (self.net.device.type == "cuda") if use_graph is None else bool(use_graph)
-        self._graph = None
+        self._graph = None                                   # the host-fed capture (train_step) and its buffer set
         self._static = None
+        self._eager_bufs = None                              # the buffer set of the steps that run uncaptured
         if seed is not None and self.net.device.type == "cuda":
             torch.cuda.manual_seed(int(seed))
 
-    def _capture(self, x, y):
-        torch = self.torch_mod = __import__("torch")
-        shape = tuple(np.asarray(x).reshape(-1, 35).shape)
-        side = torch.cuda.Stream(self.net.device)
-        side.wait_stream(torch.cuda.current_stream(self.net.device))
-        if self.step_impl is not None:
-            # native step: every launch goes through the C ABI on the capture stream; buffers are static per batch size
-            b = self.step_impl._alloc(shape[0])
-            with torch.cuda.stream(side):                   # warm-up off the capture stream (allocator, lazy init); no update
-                for _ in range(2):
-                    self.step_impl.run(b, update=False)
-            torch.cuda.current_stream(self.net.device).wait_stream(side)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                sloss = self.step_impl.run(b)
-            self._graph, self._static = g, (b["x"], b, sloss)
-            return
-        sx = torch.zeros(shape, dtype=self.net.dtype, device=self.net.device)
-        sy = torch.zeros_like(sx)
-        self.opt.keep_grads = True
-        with torch.cuda.stream(side):                       # warm-up off the capture stream (allocator, lazy init)
+    def _capture_step(self, n, prologue=None, rewind=None):
+        """One step at batch ``n`` as a HIP graph -> (graph, its static buffer set).  ``prologue(b)`` is launched in front of the
+        step, in the graph and in the warm-ups; ``rewind()`` undoes on the warm-up stream what the warm-up prologues moved.
+        No warm-up result is kept: a live autograd loss would pin its gradient-accumulation nodes to the warm-up stream, and the
+        captured backward would hop over to it."""
+        import torch
+        dev = self.net.device
+        b = self.step.alloc(n)
+        b["captured"] = True
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):                       # warm-up off the capture stream (allocator, lazy init); no update
             for _ in range(2):
-                loss = self.net.loss(sx, sy, self.keep_prob, None, self.engine)
-                loss.backward()
-                for p in self.net.trainable().values():
-                    p.grad = None
-        torch.cuda.current_stream(self.net.device).wait_stream(side)
+                if prologue:
+                    prologue(b)
+                self.step.run(b, update=False)
+            if rewind:
+                rewind()
+        torch.cuda.current_stream(dev).wait_stream(side)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            sloss = self.net.loss(sx, sy, self.keep_prob, None, self.engine)
-            sloss.backward()
-            self.opt.step()
-        self._graph, self._static = g, (sx, sy, sloss)
+            if prologue:
+                prologue(b)
+            b["out"] = self.step.run(b)                     # the loss to read after a replay
+        return g, b
+
+    def _bufs(self, x, captured):
+        """The buffer set of ``x``'s batch size: the captured step's (captured first, or again at a new size) or the eager one."""
+        n = int(np.asarray(x).reshape(-1, 35).shape[0])
+        if captured:
+            if self._graph is None or self._static["n"] != n:
+                self._graph, self._static = self._capture_step(n)
+            return self._static
+        if self._eager_bufs is None or self._eager_bufs["n"] != n:
+            self._eager_bufs = self.step.alloc(n)
+        return self._eager_bufs
 
     def train_step(self, x, y, keep_prob=None, masks=None):
         kp = self.keep_prob if keep_prob is None else keep_prob
-        if self.use_graph and kp == self.keep_prob and masks is None:
-            torch = __import__("torch")
-            if self._graph is None or tuple(self._static[0].shape) != tuple(np.asarray(x).reshape(-1, 35).shape):
-                self._capture(x, y)          # first batch, or a new batch size: (re)capture the step
-            sx, sy, sloss = self._static
-            if self.step_impl is not None:
-                self.step_impl.load_batch(sy, x, y)
-            else:
-                sx.copy_(torch.as_tensor(np.asarray(x), dtype=self.net.dtype).reshape(sx.shape), non_blocking=True)
-                sy.copy_(torch.as_tensor(np.asarray(y), dtype=self.net.dtype).reshape(sy.shape), non_blocking=True)
+        captured = self.use_graph and kp == self.keep_prob and masks is None
+        b = self._bufs(x, captured)
+        self.step.load_batch(b, x, y)
+        if captured:
             self._graph.replay()
-            self.last_loss = float(sloss.detach())
-            return self.last_loss
-        if self.step_impl is not None:
-            n = int(np.asarray(x).reshape(-1, 35).shape[0])
-            if getattr(self, "_eager_bufs", None) is None or self._eager_bufs["n"] != n:
-                self._eager_bufs = self.step_impl._alloc(n)
-            self.step_impl.load_batch(self._eager_bufs, x, y)
-            self.last_loss = float(self.step_impl.run(self._eager_bufs, keep_prob=kp, masks=masks))
-            return self.last_loss
-        loss = self.net.loss(x, y, kp, self.gen, self.engine, masks)
-        loss.backward()
-        self.opt.step()
+            loss = b["out"]
+        else:
+            loss = self.step.run(b, keep_prob=kp, masks=masks)
         self.last_loss = float(loss.detach())
         return self.last_loss
 
@@ -420,59 +444,29 @@ class Trainer(object):
         one-thread launch then moves the draw counter on and files the previous step's loss in a device log) -> the step.
         Two launches more than the host-fed step.  A second capture next to ``train_step``'s: both work on the same variables,
         optimizer slots and ``opt.t``."""
-        import ctypes as C
         import torch
         from . import _native as N
+        from ._native import _p
         dev = self.net.device
         lib = N.lib()
         handle = self.engine._handle if self.engine is not None else None
         pos, neg, counter = db.device_pools(dev)
         log = torch.zeros(self.loss_log_capacity, dtype=torch.float32, device=dev)
         log_pos = torch.zeros(1, dtype=torch.int64, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())             # noqa: E731
-        cur = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)     # noqa: E731
 
-        def sample(x, y, loss):
-            # the call's one-thread launch moves the draw counter on and files the PREVIOUS step's loss (still in ``loss``)
-            N.check(lib.cf_sample_batch_logged(handle, ptr(pos), db.nb_pos, ptr(neg), db.nb_neg, n, ratio, db.seed, ptr(counter),
-                                               ptr(x), ptr(y), ptr(loss), ptr(log), self.loss_log_capacity, ptr(log_pos), cur()))
+        def sample(b):
+            # the call's one-thread launch moves the draw counter on and files the PREVIOUS step's loss (still in b["loss"])
+            N.check(lib.cf_sample_batch_logged(handle, _p(pos), db.nb_pos, _p(neg), db.nb_neg, n, ratio, db.seed, _p(counter),
+                                               _p(b["x"]), _p(b["y"]), _p(b["loss"]), _p(log), self.loss_log_capacity, _p(log_pos),
+                                               N.current_stream_ptr(torch, dev)))
 
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        if self.step_impl is not None:
-            b = self.step_impl._alloc(n)
-            sx, sy, sloss = b["x"], b["y"], b["loss"]        # the native steps write their loss into a static buffer
-
-            def step(update=True):
-                self.step_impl.run(b, update=update)
-        else:
-            sx = torch.zeros((n, 35), dtype=self.net.dtype, device=dev)
-            sy = torch.zeros_like(sx)
-            sloss = torch.zeros(1, dtype=torch.float32, device=dev)
-            self.opt.keep_grads = True
-
-            def step(update=True):
-                loss = self.net.loss(sx, sy, self.keep_prob, None, self.engine)
-                loss.backward()
-                if update:
-                    self.opt.step()
-                else:
-                    for p in self.net.trainable().values():
-                        p.grad = None
-                sloss.copy_(loss.detach().reshape(1))       # autograd allocates its loss: keep it where the next replay's sampler looks
-        with torch.cuda.stream(side):                       # warm-up off the capture stream; no update, and the counters go back
-            for _ in range(2):
-                sample(sx, sy, sloss)
-                step(update=False)
+        def rewind():                                        # the warm-ups leave no trace in the draw counter or the loss log
             counter.fill_(db.draw)
             db._dev_draw = db.draw
             log_pos.zero_()
-        torch.cuda.current_stream(dev).wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            sample(sx, sy, sloss)
-            step()
-        self._fed = {"key": (n, ratio), "db": db, "graph": g, "x": sx, "y": sy, "loss": sloss, "log": log, "log_pos": log_pos,
+
+        g, b = self._capture_step(n, sample, rewind)
+        self._fed = {"key": (n, ratio), "db": db, "graph": g, "x": b["x"], "y": b["y"], "loss": b["loss"], "log": log, "log_pos": log_pos,
                      "pools": (pos, neg, counter)}
 
     def train_steps(self, db, n_steps, batch_size, ratio=2):
@@ -487,7 +481,7 @@ class Trainer(object):
         out = np.zeros(max(n_steps, 0), dtype=np.float32)
         if n_steps <= 0:
             return out
-        torch = __import__("torch")
+        import torch
         on_card = hasattr(db, "device_pools")               # a database without a card side (DeviceReadDb) is fed by the host
         if not (on_card and self.use_graph and self.net.device.type == "cuda" and self.net.dtype == torch.float32):
             for i in range(n_steps):
@@ -517,17 +511,7 @@ class Trainer(object):
         """Loss and gradients of one batch WITHOUT an update: (loss, {TF name: ndarray}) -- what tests compare with the
         reference graph's gradient tensors."""
         kp = self.keep_prob if keep_prob is None else keep_prob
-        if self.step_impl is not None:
-            n = int(np.asarray(x).reshape(-1, 35).shape[0])
-            b = self.step_impl._alloc(n)
-            self.step_impl.load_batch(b, x, y)
-            loss = float(self.step_impl.run(b, keep_prob=kp, masks=masks, update=False))
-            return loss, {k: v.detach().cpu().numpy().copy() for k, v in self.step_impl.grads().items()}
-        for p in self.net.trainable().values():
-            p.grad = None
-        loss = self.net.loss(x, y, kp, self.gen, self.engine, masks)
-        loss.backward()
-        out = {k: p.grad.detach().cpu().numpy().copy() for k, p in self.net.trainable().items()}
-        for p in self.net.trainable().values():
-            p.grad = None
-        return float(loss.detach()), out
+        b = self._bufs(x, False)
+        self.step.load_batch(b, x, y)
+        loss = float(self.step.run(b, keep_prob=kp, masks=masks, update=False).detach())
+        return loss, {k: v.detach().cpu().numpy().copy() for k, v in self.step.grads().items()}

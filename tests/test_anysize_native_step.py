@@ -168,7 +168,7 @@ def test_native_step_on_the_shipped_geometry_draws_the_tuned_steps_masks(ckpt_we
     assert all(np.array_equal(ma[k], mb[k]) for k in mb)
     rng = np.random.default_rng(8)
     x, y = _batch(rng, 50)
-    b = st._alloc(50)
+    b = st.alloc(50)
     st.load_batch(b, x, y)
     la = float(st.run(b, update=False))
     ga = {k: v.detach().cpu().numpy() for k, v in st.grads().items()}

@@ -39,7 +39,8 @@ def profile_only(B, steps, overlap=True):
     torch.cuda.synchronize()
     wall = (time.perf_counter() - t0) / steps
     # the same step taken apart (untimed above): host copies, launch, device, read-back
-    sx, b, sloss = tr._static
+    b = tr._static
+    sloss = b["loss"]
     parts = {"load_batch_ms": 0.0, "replay_call_ms": 0.0, "graph_device_ms": 0.0, "loss_readback_ms": 0.0}
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for _ in range(steps):
