@@ -197,6 +197,9 @@ SYMBOLS = {
     "cf_validation_run_borders_bridged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                     C.c_int64, C.c_void_p]),
+    "cf_validation_run_bases": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "cf_validation_curve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
                                       C.c_void_p, C.c_int64, C.c_void_p]),
     "cf_retile_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -256,7 +259,10 @@ def lib():
             raise NativeLibraryMissing("%s was built for ABI %s, this binding needs %d: rebuild it "
                                        "(`python -m catfish_amd.build --force`)" % (path, built, CF_ABI_VERSION))
         for name, (res, args) in SYMBOLS.items():
-            fn = getattr(handle, name)
+            try:
+                fn = getattr(handle, name)
+            except AttributeError:                         # a library of the same ABI number from before the symbol was added
+                raise NativeLibraryMissing("%s has no %s: rebuild it (`python -m catfish_amd.build --force`)" % (path, name))
             fn.restype = res
             fn.argtypes = args
         _lib, LIB_PATH = handle, path

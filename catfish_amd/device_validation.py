@@ -14,7 +14,9 @@ This module states both device steps in numpy and those statements are normative
 gather kernel writes (bit for bit), ``score_host`` what the scoring kernel returns (counts exactly; the double sums up to the
 summation order), ``run_states_host`` what the run-state step returns (``cf_validation_run_states``, csrc/validation_runs.hpp:
 how many homopolymers a round found, bit for bit), ``run_borders_host`` what the border step returns
-(``cf_validation_run_borders``, csrc/validation_borders.hpp: how far the called borders miss and the interruptions, bit for bit), ``curve_host`` what the curve step returns (``cf_validation_curve``,
+(``cf_validation_run_borders``, csrc/validation_borders.hpp: how far the called borders miss and the interruptions, bit for bit),
+``run_bases_host`` what the base step returns (``cf_validation_run_bases``, csrc/validation_bases.hpp: the same runs by base and by
+length in bases, from the set's base map, bit for bit), ``curve_host`` what the curve step returns (``cf_validation_curve``,
 csrc/validation_curve.hpp: the round's probabilities binned at every threshold step, bit for bit; ``curves_from_histogram`` turns
 that table into the whole ROC and precision-recall curves, their areas and the best F1).  The object is host-only until ``device_arrays`` is called and usable without a GPU.
 What a round on the card decides before its first launch -- the checked options, the buffer sizes, the layout of the result buffer and
@@ -163,6 +165,85 @@ def run_state_rates(table):
     n_true, n_called = int(true_runs.sum()), int(called.sum())
     return (int(true_runs[0]) / n_true if n_true else 0, int(true_runs[0] + true_runs[1]) / n_true if n_true else 0,
             int(called[2]) / n_called if n_called else 0)
+
+
+MAX_BASES_LIMIT = 32        # the most length bins in bases (VBS_MAX_BASES, csrc/validation_bases_word.hpp)
+MAX_BASES = 16
+BASE_CLASSES = ("A", "C", "G", "T", "other")               # the fourth axis of a run-bases table
+BASE_MARK = 0x80            # the base map's "new base" bit (labelling.MARK)
+
+
+def check_max_bases(max_bases):
+    """``max_bases`` as an int in 1 .. 32 (ValueError otherwise; no bool, no fraction)."""
+    if isinstance(max_bases, (bool, np.bool_)) or not isinstance(max_bases, (int, np.integer)) or not 1 <= max_bases <= MAX_BASES_LIMIT:
+        raise ValueError("max_bases must be an int in 1 .. %d, got %r" % (MAX_BASES_LIMIT, max_bases))
+    return int(max_bases)
+
+
+def _bases_of(starts, ends, bmap, max_bases):
+    """(class, bin) of every run [s, e] over one stretch's base map: the marked samples inside the run are its bases
+    (``get_bases``); class 0..3 when there is one and all are that upper-case letter, else 4; bin = min(how many, max_bases)."""
+    marked = (bmap & BASE_MARK) != 0
+    count = np.concatenate(([0], np.cumsum(marked)))
+    nb = count[ends + 1] - count[starts]
+    cls = np.full(starts.size, 4, dtype=np.int64)
+    for c, letter in enumerate(b"ACGT"):
+        same = np.concatenate(([0], np.cumsum(marked & ((bmap & 0x7f) == letter))))
+        cls[(nb >= 1) & (same[ends + 1] - same[starts] == nb)] = c
+    return cls, np.minimum(nb, max_bases)
+
+
+def run_bases_host(probs, y, basemap, bounds, lengths, thresholds, max_bases=MAX_BASES, min_run=15, max_gap=0):
+    """What ``cf_validation_run_bases`` returns, in numpy: int64 [K, 2, 3, 5, max_bases + 1] -- per threshold, kind, state, base
+    class and length in BASES how many runs (the reference's offline networks/process_output.py: ``prediction_information`` ->
+    ``base_count_dict`` / ``get_bases`` / ``get_prevalence`` over the runs of ``hp_loc_dict`` and the states of ``check_hp``).
+
+    Stretches, thresholds, the corrected prediction, runs (``_runs_of``, the last-sample rule included), kinds and states are
+    ``run_states_host``'s.  ``basemap`` is packed like ``y`` (sample ``bounds[r] + i``; the zero tails are ignored): the event's
+    base byte with bit 7 on the event's centre sample (``labelling.base_map_host``).  The bases of a run [s, e] are
+    ``basemap[i] & 0x7f`` at the positions i in [s, e] with ``basemap[i] & 0x80``, in order; ``nb`` = how many -- the sample the
+    last-sample rule adds counts.  Class 0..3 (``BASE_CLASSES``): ``nb >= 1`` and every one of them is that upper-case letter (a byte
+    comparison); class 4, "other": anything else -- mixed, ``N``, lower case, or no base at all.  Bin = ``min(nb, max_bases)``.
+    Summed over class and bin the table is ``run_states_host(..., edges=())`` with its axes as [K, 2, 3]."""
+    from .infer import bridge_gaps, check_bridge, correct_short
+    max_bases = check_max_bases(max_bases)
+    if int(min_run) < 1:
+        raise ValueError("min_run must be >= 1")
+    max_gap = check_bridge(max_gap, min_run)
+    p = np.asarray(probs, dtype=np.float64).reshape(-1)
+    y = np.asarray(y).reshape(-1)
+    basemap = np.asarray(basemap, dtype=np.uint8).reshape(-1)
+    bounds = np.asarray(bounds, dtype=np.int64)
+    lengths = np.asarray(lengths, dtype=np.int64)
+    out = np.zeros((len(thresholds), 2, 3, len(BASE_CLASSES), max_bases + 1), dtype=np.int64)
+    for b0, n in zip(bounds[:len(lengths)].tolist(), lengths.tolist()):
+        if n <= 0:
+            continue
+        truth, bmap = y[b0:b0 + n], basemap[b0:b0 + n]
+        for k, t in enumerate(thresholds):
+            pred = np.asarray(correct_short(bridge_gaps((p[b0:b0 + n] >= float(t)).astype(np.int64), max_gap), int(min_run)))
+            for kind, (mask, other) in enumerate(((truth == 1, pred), (pred == 1, truth))):
+                starts, ends = _runs_of(mask)
+                cls, bins = _bases_of(starts, ends, bmap, max_bases)
+                np.add.at(out[k, kind], (_states_of(starts, ends, other), cls, bins), 1)
+    return out
+
+
+def run_base_rates(table_k):
+    """One threshold's [2, 3, 5, B] table -> dict: ``recall_by_base`` [5] and ``recall_by_length`` [B] = (complete + incomplete) /
+    all true runs of that class or bin; ``complete_by_base`` / ``complete_by_length`` = complete / all of them; ``called_pure`` =
+    the share of called runs with a class below 4.  A share over nothing is 0 (``run_state_rates``)."""
+    table = np.asarray(table_k)
+    if table.ndim != 4 or table.shape[:3] != (2, 3, len(BASE_CLASSES)):
+        raise ValueError("one threshold's run-bases table is [2, 3, 5, B], got %s" % (table.shape,))
+    share = lambda part, whole: [int(a) / int(b) if b else 0 for a, b in zip(part.tolist(), whole.tolist())]     # noqa: E731
+    by_base, by_length = table[0].sum(axis=2), table[0].sum(axis=1)               # [3, 5], [3, B]
+    n_called = int(table[1].sum())
+    return {"recall_by_base": share(by_base[0] + by_base[1], by_base.sum(axis=0)),
+            "recall_by_length": share(by_length[0] + by_length[1], by_length.sum(axis=0)),
+            "complete_by_base": share(by_base[0], by_base.sum(axis=0)),
+            "complete_by_length": share(by_length[0], by_length.sum(axis=0)),
+            "called_pure": int(table[1][:, :4].sum()) / n_called if n_called else 0}
 
 
 MAX_BORDER_REACH = 128      # the widest offset / interruption histogram (VB_MAX_REACH, csrc/validation_borders_word.hpp)
@@ -426,20 +507,26 @@ def _label_device(device):
 class DeviceValidationSet(object):
     """All validation reads of a run, concatenated: ``signal`` float32 [total] (cast once -- the values
     ``pack_validation_windows`` writes into its float32 batch), ``labels`` uint8 [total], ``offsets`` int64 [n_reads + 1],
-    ``lengths`` int64 [n_reads]."""
+    ``lengths`` int64 [n_reads]; ``basemap`` uint8 [total] or None -- the per-sample base map of reads that came with their
+    event tables (``labelling.base_map_host``), what ``run_bases_host`` counts bases on."""
 
-    def __init__(self, signal, labels, offsets, device=None):
+    def __init__(self, signal, labels, offsets, device=None, basemap=None):
         self.signal = signal
         self.labels = labels
         self.offsets = offsets
         self.lengths = np.diff(offsets)
         self.device = device
-        self._dev = None                 # {"device", "signal", "labels"} on the card, uploaded once
+        if basemap is not None:
+            basemap = np.asarray(basemap)
+            if basemap.dtype != np.uint8 or basemap.shape != (int(offsets[-1]),):
+                raise ValueError("basemap must be uint8 [%d], got %s %s" % (int(offsets[-1]), basemap.dtype, basemap.shape))
+        self.basemap = basemap
+        self._dev = None                 # {"device", "signal", "labels"[, "basemap"]} on the card, uploaded once
         self.uploads = 0                 # how often the reads went to a card
         self._binary = None              # every label is 0 or 1 (looked at once)
 
     @classmethod
-    def from_arrays(cls, signals, labels, device=None):
+    def from_arrays(cls, signals, labels, device=None, basemaps=None):
         signals = [np.asarray(s).reshape(-1) for s in signals]
         labels = [_as_labels(l) for l in labels]
         if len(signals) != len(labels):
@@ -447,6 +534,13 @@ class DeviceValidationSet(object):
         for i, (s, l) in enumerate(zip(signals, labels)):
             if len(s) != len(l):
                 raise ValueError("read %d: %d samples but %d labels" % (i, len(s), len(l)))
+        if basemaps is not None:
+            basemaps = [np.asarray(b).reshape(-1) for b in basemaps]
+            if len(basemaps) != len(signals):
+                raise ValueError("%d signals but %d base maps" % (len(signals), len(basemaps)))
+            for i, (s, b) in enumerate(zip(signals, basemaps)):
+                if b.dtype != np.uint8 or len(b) != len(s):
+                    raise ValueError("read %d: the base map must be uint8 [%d], got %s [%d]" % (i, len(s), b.dtype, len(b)))
         offsets = np.zeros(len(signals) + 1, dtype=np.int64)
         np.cumsum(np.array([len(s) for s in signals], dtype=np.int64), out=offsets[1:])
         signal = np.zeros(int(offsets[-1]), dtype=np.float32)
@@ -454,7 +548,9 @@ class DeviceValidationSet(object):
         for o, s, l in zip(offsets[:-1].tolist(), signals, labels):
             signal[o:o + len(s)] = s
             lab[o:o + len(l)] = l
-        return cls(signal, lab, offsets, device)
+        if basemaps is None:
+            return cls(signal, lab, offsets, device)
+        return cls(signal, lab, offsets, device, np.concatenate(basemaps) if basemaps else np.zeros(0, np.uint8))
 
     @classmethod
     def from_npz(cls, paths, loader=None, device=None):
@@ -473,9 +569,9 @@ class DeviceValidationSet(object):
         """Reads that come with their event tables instead of labels: ``signals[r]`` is read r's raw signal (its first
         ``final_signal`` samples are kept, as the reference's collect_examples.py saves them) and ``batch`` a
         ``labelling.EventBatch`` over the same reads.  On a GPU (``device`` a CUDA device, or None where one is there and the
-        native library is built) ``cf_label_events`` makes the labels: signal and labels are the set's device arrays from then on
-        (one upload) and the labels are copied back once for ``self.labels``.  Otherwise (``device="cpu"``, or no GPU)
-        ``batch.label_host`` makes them -- the same bytes."""
+        native library is built) ``cf_label_events`` makes the labels and the base map: signal, labels and base map are the set's
+        device arrays from then on (one upload) and labels and base map are copied back once for ``self.labels`` /
+        ``self.basemap``.  Otherwise (``device="cpu"``, or no GPU) ``batch.label_host`` makes them -- the same bytes."""
         from . import labelling
         kmer = labelling.check_kmer(kmer)
         signals = [np.asarray(s).reshape(-1) for s in signals]
@@ -490,12 +586,15 @@ class DeviceValidationSet(object):
             signal[o:o + n] = s[:n]
         on_card = _label_device(device)
         if on_card is None:
-            return cls(signal, batch.label_host(kmer), offsets, device)
+            labels, basemap = batch.label_host(kmer, base_map=True)
+            return cls(signal, labels, offsets, device, basemap)
         import torch
-        labels_dev = labelling.label_reads(batch, kmer, on_card)
-        vset = cls(signal, labels_dev.cpu().numpy() if labels_dev.numel() else np.zeros(0, np.uint8), offsets, device)
+        labels_dev, basemap_dev = labelling.label_reads(batch, kmer, on_card, base_map=True)
+        back = lambda t: t.cpu().numpy() if t.numel() else np.zeros(0, np.uint8)     # noqa: E731
+        vset = cls(signal, back(labels_dev), offsets, device, back(basemap_dev))
         if signal.size:
-            vset._dev = {"device": labels_dev.device, "signal": torch.from_numpy(signal).to(labels_dev.device), "labels": labels_dev}
+            vset._dev = {"device": labels_dev.device, "signal": torch.from_numpy(signal).to(labels_dev.device), "labels": labels_dev,
+                         "basemap": basemap_dev}
             vset.uploads = 1
         return vset
 
@@ -556,6 +655,20 @@ class DeviceValidationSet(object):
             y[b:b + n] = self.labels[s:s + n]
         return x.reshape(-1, window, 1), y, bounds, tails
 
+    def pack_basemap(self, selection, window):
+        """The base map of the selected stretches, packed like ``pack``'s ``y`` (uint8 [sum N_i * window], zero tails): what
+        ``run_bases_host`` takes.  The card never makes this copy -- the kernel reads the set's base map in place.  ValueError for a
+        set without one."""
+        if self.basemap is None:
+            raise ValueError("this set has no base map (only reads that come with event tables have one: from_events)")
+        read_index, first, length = selection
+        bounds, _tails = layout(length, window)
+        out = np.zeros(int(bounds[-1]), dtype=np.uint8)
+        src = self.offsets[read_index] + first
+        for b, s, n in zip(bounds[:-1].tolist(), src.tolist(), np.asarray(length).tolist()):
+            out[b:b + n] = self.basemap[s:s + n]
+        return out
+
     def check_selection(self, selection):
         """Raise ValueError unless every stretch lies inside its read (the kernels index with these numbers)."""
         read_index, first, length = (np.asarray(a, dtype=np.int64) for a in selection)
@@ -570,13 +683,15 @@ class DeviceValidationSet(object):
     score_host = staticmethod(score_host)
     run_states_host = staticmethod(run_states_host)
     run_borders_host = staticmethod(run_borders_host)
+    run_bases_host = staticmethod(run_bases_host)
     curve_host = staticmethod(curve_host)
     finish = staticmethod(finish)
     layout = staticmethod(layout)
 
     # ------------------------------------------------------------------ the card's side
     def device_arrays(self, device=None):
-        """(signal float32 [max(total, 1)], labels uint8 [max(total, 1)]) on ``device``; uploaded on the first call."""
+        """(signal float32 [max(total, 1)], labels uint8 [max(total, 1)]) on ``device``; uploaded on the first call -- with the base
+        map, when the set has one (``device_basemap``)."""
         import torch
         device = torch.device((self.device or "cuda") if device is None else device)
         if device.type != "cuda":
@@ -586,5 +701,15 @@ class DeviceValidationSet(object):
         if self._dev is None or self._dev["device"] != device:
             up = lambda a, dt: torch.from_numpy(a if a.size else np.zeros(1, dt)).to(device)     # noqa: E731
             self._dev = {"device": device, "signal": up(self.signal, np.float32), "labels": up(self.labels, np.uint8)}
+            if self.basemap is not None:
+                self._dev["basemap"] = up(self.basemap, np.uint8)
             self.uploads += 1
         return self._dev["signal"], self._dev["labels"]
+
+    def device_basemap(self, device=None):
+        """The base map uint8 [max(total, 1)] on ``device`` (it goes up with ``device_arrays``' one upload); ValueError for a set
+        without one."""
+        if self.basemap is None:
+            raise ValueError("this set has no base map (only reads that come with event tables have one: from_events)")
+        self.device_arrays(device)
+        return self._dev["basemap"]

@@ -568,6 +568,39 @@ class HipEngine(object):
             int(min_run), C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()),
             C.c_void_p(stream.cuda_stream)))
 
+    def run_bases_validation(self, probs, y, basemap, src_first, bounds, length, total, longest, thresholds, max_bases, counts_out, work,
+                             min_run=15, max_gap=0, stream=None):
+        """``cf_validation_run_bases``: per threshold (``thresholds``: 1..16 host floats), kind, state, base class (A / C / G / T /
+        other) and length in bases (``min(nb, max_bases)``, ``max_bases`` an int in 1 .. 32) how many runs --
+        ``device_validation.run_bases_host`` -- into ``counts_out`` (int64 CUDA, ``K * 2 * 3 * 5 * (max_bases + 1)`` elements).
+        ``basemap`` is the SET's base map (uint8 CUDA, read in place: packed sample ``bounds[r] + i`` is ``basemap[src_first[r] + i]``;
+        an index outside it counts as no base); ``src_first`` [n], ``length`` [n] and ``bounds`` [n + 1] are int64 CUDA tensors;
+        ``work`` is a uint8 CUDA tensor of at least ``run_states_work_bytes(total, K)`` bytes.  Asynchronous on the stream; equal
+        inputs give equal bits."""
+        import torch
+        from .device_validation import BASE_CLASSES, check_max_bases
+        self._check_validation_tensors("run_bases_validation", [
+            ("probs", probs, torch.float32), ("y", y, torch.uint8), ("basemap", basemap, torch.uint8), ("src_first", src_first, torch.int64),
+            ("bounds", bounds, torch.int64), ("length", length, torch.int64), ("counts_out", counts_out, torch.int64),
+            ("work", work, torch.uint8)])
+        thresholds = [float(t) for t in thresholds]
+        max_bases = check_max_bases(max_bases)
+        k = len(thresholds)
+        n, total, longest = self._check_validation_sizes("run_bases_validation", probs, y, bounds, length, total, longest)
+        if int(src_first.numel()) != n:
+            raise ValueError("run_bases_validation: src_first needs n entries")
+        if int(counts_out.numel()) < k * 2 * 3 * len(BASE_CLASSES) * (max_bases + 1):
+            raise ValueError("run_bases_validation: counts_out needs 2 * 3 * 5 * (max_bases + 1) entries per threshold")
+        if stream is None:
+            stream = torch.cuda.current_stream(probs.device)
+        # n, K, min_run, the (min_run, max_gap) pair, the work space and an empty base map are refused by the library
+        # (CF_ERR_INVALID -> ValueError)
+        N.check(self._lib.cf_validation_run_bases(
+            self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(basemap.data_ptr()), int(basemap.numel()),
+            C.c_void_p(src_first.data_ptr()), C.c_void_p(bounds.data_ptr()), C.c_void_p(length.data_ptr()), n, total, longest,
+            (C.c_double * max(k, 1))(*thresholds), k, max_bases, int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()),
+            C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
+
     def curve_validation(self, probs, y, bounds, length, total, longest, shift, hist_out, stream=None):
         """``cf_validation_curve``: how many samples of label 1 / label 0 / any other label fall into every bin of
         ``device_validation.curve_bin`` at ``shift`` (10 .. 22) -- ``device_validation.curve_host`` -- into ``hist_out`` (int64 CUDA,

@@ -210,7 +210,7 @@ class RNN(object):
         return self.engine.infer_host(np.asarray(windows), return_logits=True)
 
     def score_validation_device(self, vset, selection, thresholds=(0.5,), run_edges=None, curve_shift=None, border_reach=None,
-                                bridge_gap=0, phases=(0,), vote_weight="mean"):
+                                bridge_gap=0, phases=(0,), vote_weight="mean", max_bases=None):
         """One validation round on the card: the stretches ``selection`` (``vset.select``) of a
         ``device_validation.DeviceValidationSet`` -> what ``device_validation.score_host`` returns for them, (right int64 [n],
         ce_sum float64 [n], counts int64 [K, 4]).  With ``run_edges`` (a tuple of up to 7 ascending run lengths, possibly empty)
@@ -218,7 +218,7 @@ class RNN(object):
         [K, 2, len(run_edges) + 1, 3] -- how many true homopolymers were found completely, partly or not at all and how many
         called stretches hold one, per length bin (``cf_validation_run_states`` after the same gather and forward pass, in the
         same copy back; its label work space and the larger result buffer follow the grow-only rule below).  With ``curve_shift``
-        (an int in 10 .. 22) the LAST result -- after the run states when both are asked for -- is what
+        (an int in 10 .. 22) the last of these six results -- after the run states when both are asked for -- is what
         ``device_validation.curve_host`` returns for the round's probabilities, int64 [3, curve_bins(curve_shift)]: the histogram
         ``device_validation.curves_from_histogram`` turns into the whole ROC and precision-recall curves (``cf_validation_curve``,
         same forward pass, same copy back; its room in the result buffer is ``validation_buffers["capacity"]["curve_cells"]``).
@@ -233,10 +233,15 @@ class RNN(object):
         the forward pass writes probabilities and logits for all of them (``validation_buffers["tensors"]["tilings_probs"]`` /
         ``["tilings_logits"]``, room ``capacity["tiling_samples"]``, the same grow-only rule), and ``cf_vote_tilings`` writes the voted
         probabilities and logits (the weighted mean of the logits, not the logit of the voted probability) that everything after it
-        consumes; ``(0,)`` launches and allocates nothing that was not before.
+        consumes; ``(0,)`` launches and allocates nothing that was not before.  With ``max_bases`` (an int in 1 .. 32) ``run_bases``
+        follows the curve histogram as the last result: what ``device_validation.run_bases_host`` returns for the round's
+        probabilities and the set's base map, int64 [K, 2, 3, 5, max_bases + 1] -- the same runs per kind, state, base class (A / C / G /
+        T / other) and length in bases (``cf_validation_run_bases``, same forward pass, same copy back; it reads the set's base map
+        in place, room ``capacity["base_cells"]``, label work space shared with the run states; ``bridge_gap`` applies).  The set must
+        have a base map (``DeviceValidationSet.from_events``; ValueError otherwise).
 
         The tuple is a ``validation_round.RoundResult``: every result is also an attribute -- ``right``, ``ce_sum``, ``counts``,
-        ``run_states``, ``run_borders``, ``curve`` -- that is None when it was not asked for.  ``validation_round.RoundSpec`` checks the
+        ``run_states``, ``run_borders``, ``curve``, ``run_bases`` -- that is None when it was not asked for.  ``validation_round.RoundSpec`` checks the
         options, ``RoundPlan`` holds the sizes and the layout of the result buffer (host-only, both).
 
         The selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes
@@ -247,7 +252,9 @@ class RNN(object):
         import torch
         from .validation_round import RoundPlan, RoundSpec, grow, walk
         self._require_engine()
-        spec = RoundSpec.of(thresholds, run_edges, border_reach, curve_shift, bridge_gap, phases, vote_weight)
+        spec = RoundSpec.of(thresholds, run_edges, border_reach, curve_shift, bridge_gap, phases, vote_weight, max_bases)
+        if spec.max_bases is not None and vset.basemap is None:
+            raise ValueError("score_validation_device: max_bases needs a set with a base map (DeviceValidationSet.from_events)")
         if spec.border_reach is not None and not vset.labels_binary:
             raise ValueError("score_validation_device: border_reach needs a set whose labels are all 0 or 1")
         read_index, first, length = vset.check_selection(selection)
@@ -263,7 +270,8 @@ class RNN(object):
             book["threshold_uploads"] += 1
         t["table"][:3 * (plan.n + 1)].copy_(torch.from_numpy(plan.table(vset.offsets, read_index, first).reshape(-1)))
         book["selection_uploads"] += 1
-        out = walk(self.engine, plan, t, book["thresholds"][1], signal, labels, self.window)
+        out = walk(self.engine, plan, t, book["thresholds"][1], signal, labels, self.window,
+                   None if spec.max_bases is None else vset.device_basemap(device))
         back = out.cpu().numpy()                                                     # synchronises the stream
         self.engine.check_error()
         return plan.results(back)

@@ -22,8 +22,8 @@ import random
 import numpy as np
 
 from . import metrics
-from .device_validation import (BORDER_REACH, RUN_STATES, check_border_reach, curve_thresholds, curves_from_histogram,
-                                run_border_summary, run_state_rates, split_run_borders)
+from .device_validation import (BASE_CLASSES, BORDER_REACH, MAX_BASES, RUN_STATES, check_border_reach, check_max_bases, curve_thresholds,
+                                curves_from_histogram, run_base_rates, run_border_summary, run_state_rates, split_run_borders)
 from .neural_network import build_model as _build_model
 
 
@@ -247,6 +247,9 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     extra = {} if curve_shift is None else {"curve_shift": curve_shift}
     if border_reach is not None:
         extra["border_reach"] = border_reach
+    max_bases = getattr(network, "validation_max_bases", None)
+    if max_bases is not None:
+        extra["max_bases"] = max_bases
     bridge_gap = int(getattr(network, "validation_bridge_gap", 0) or 0)
     if bridge_gap:
         extra["bridge_gap"] = bridge_gap
@@ -269,6 +272,13 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
         _append(report[:-len(".txt")] + "_hp_borders.jsonl", json.dumps({
             "step": int(step), "threshold": 0.5, "reach": int(border_reach), "hp_borders": hp_borders,
             "called_borders": called_borders, **({"bridge_gap": bridge_gap} if bridge_gap else {})}) + "\n")
+    if max_bases is not None:
+        # which homopolymers the round found, by base and by length in bases: one JSON line per round
+        table = np.asarray(network.validation_run_bases)
+        _append(report[:-len(".txt")] + "_hp_bases.jsonl", json.dumps({
+            "step": int(step), "threshold": 0.5, "max_bases": int(max_bases), "classes": list(BASE_CLASSES), "states": list(RUN_STATES),
+            "hp_bases": table[0].tolist(), "called_bases": table[1].tolist(), **run_base_rates(table),
+            **({"bridge_gap": bridge_gap} if bridge_gap else {})}) + "\n")
     if curve_shift is not None:
         # the round's whole ROC and precision-recall curves, reduced to their areas and the best F1: one JSON line per round
         curves = curves_from_histogram(network.validation_curve, curve_shift)
@@ -415,7 +425,7 @@ def score_validation_batch(probs32, logits32, y, bounds, tails, threshold=0.5):
 
 
 def validate(network, squiggles, max_seq_length, file_path, validation_start="random", max_number=856, run_edges=None, curve_shift=None,
-             border_reach=None, bridge_gap=0, loader=None):
+             border_reach=None, bridge_gap=0, loader=None, max_bases=None):
     """networks/train_validate.py:188-295 as one packed launch.
 
     The reference pushes every read through ``test_network`` (one ``sess.run`` each, up to 856 per round); windows are
@@ -436,13 +446,16 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     ``border_reach`` (a ``DeviceValidationSet`` only; an int in 1 .. 128): the round also counts how far the called borders miss
     the true ones and the interruptions at threshold 0.5 (``device_validation.run_borders_host``, on the card); the
     [2, 5 * border_reach + 3] table is left in ``network.validation_run_borders``.
-    ``bridge_gap`` (with ``run_edges`` or ``border_reach``; 0 .. 49): those two tables are counted on the prediction with its gaps of
-    at most that many samples bridged (``infer.bridge_gaps``).
+    ``max_bases`` (a ``DeviceValidationSet`` with a base map only; an int in 1 .. 32): the round also counts its runs at threshold
+    0.5 by base and by length in bases (``device_validation.run_bases_host``, on the card); the [2, 3, 5, max_bases + 1] table is
+    left in ``network.validation_run_bases``.
+    ``bridge_gap`` (with ``run_edges``, ``border_reach`` or ``max_bases``; 0 .. 49): those tables are counted on the prediction with
+    its gaps of at most that many samples bridged (``infer.bridge_gaps``).
     ``loader`` (a list of paths only): what reads a path into ``(raw, labels)`` instead of ``load_npz``.
     Report, prints and return value stay as they are."""
     from .calling import CallRule
     bridge_gap = CallRule.of(max_gap=bridge_gap).max_gap
-    if bridge_gap and run_edges is None and border_reach is None:
+    if bridge_gap and run_edges is None and border_reach is None and max_bases is None:
         raise ValueError("validate: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
     print("Max length is {}".format(max_seq_length))
     print("Validation start is {}".format(validation_start))
@@ -454,10 +467,12 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
         n_samples = int(selection[2].sum())
         if n_reads == 0:
             raise ZeroDivisionError("validation selected no read")
-        if run_edges is None and curve_shift is None and border_reach is None:
+        if run_edges is None and curve_shift is None and border_reach is None and max_bases is None:
             right, ce_sum, counts_k = network.score_validation_device(squiggles, selection)
         else:
             extra = {} if border_reach is None else {"border_reach": border_reach}
+            if max_bases is not None:
+                extra["max_bases"] = max_bases
             if bridge_gap:
                 extra["bridge_gap"] = bridge_gap
             got = network.score_validation_device(squiggles, selection, (0.5,), run_edges=run_edges, curve_shift=curve_shift, **extra)
@@ -468,6 +483,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
                 network.validation_run_borders = got.run_borders[0]
             if curve_shift is not None:
                 network.validation_curve = got.curve
+            if max_bases is not None:
+                network.validation_run_bases = got.run_bases[0]
         acc, loss, counts = squiggles.finish(right, ce_sum, counts_k[0], *squiggles.layout(selection[2], network.window))
     else:
         if run_edges is not None:
@@ -476,6 +493,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
             raise ValueError("validate: curve_shift needs a DeviceValidationSet (the probabilities are binned on the card)")
         if border_reach is not None:
             raise ValueError("validate: border_reach needs a DeviceValidationSet (the borders are compared on the card)")
+        if max_bases is not None:
+            raise ValueError("validate: max_bases needs a DeviceValidationSet with a base map (the bases are counted on the card)")
         signals, labels = select_validation_stretches(squiggles, network.window, max_seq_length, validation_start,
                                                       max_number, **({} if loader is None else {"loader": loader}))
         n_reads = len(signals)
@@ -508,7 +527,7 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
 
 
 def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start="complete", max_number=856, run_edges=None,
-                    border_reach=None, bridge_gap=0, phases=(0,), vote_weight="mean"):
+                    border_reach=None, bridge_gap=0, phases=(0,), vote_weight="mean", max_bases=None):
     """The reference's precision / recall sweep (networks/precision_recall_ROC.py:85-100: ``class_from_threshold`` --
     ``p >= t`` -- then ``compute_f1`` per threshold) over a ``DeviceValidationSet``: ONE forward pass, every threshold counted
     from its probabilities on the card.  The stretches are ``validate``'s (same selection, same tail rule for the true
@@ -524,7 +543,12 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     (``device_validation.run_borders_host``; the rest of the reference's ``check_hp``): ``hp_borders`` -- the true runs against
     the corrected prediction -- and ``called_borders`` -- the called runs against the truth --, each ``border_report``'s dict.
 
-    ``bridge_gap`` (with ``run_edges`` or ``border_reach``; 0 .. 49): the run states and the borders are those of the prediction
+    With ``max_bases`` (an int in 1 .. 32; a set with a base map) every row also says which homopolymers that threshold finds
+    (``device_validation.run_bases_host``; the reference's offline ``prediction_information``): ``hp_bases`` and ``called_bases``
+    -- per state, base class (A / C / G / T / other) and length in bases how many true and called runs, ``[3][5][max_bases + 1]``
+    lists -- and the fields of ``device_validation.run_base_rates``.
+
+    ``bridge_gap`` (with ``run_edges``, ``border_reach`` or ``max_bases``; 0 .. 49): those tables are those of the prediction
     with its gaps of at most that many samples bridged (``infer.bridge_gaps``); tp / fp / tn / fn stay per-sample counts.
 
     ``phases`` / ``vote_weight`` (``infer.check_phases``): shifted-window voting -- every count is taken from the probabilities voted
@@ -533,9 +557,9 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     rule = CallRule.of(max_gap=bridge_gap, phases=phases, vote_weight=vote_weight)
     bridge_gap = rule.max_gap
     voted = {"phases": rule.phases, "vote_weight": rule.vote_weight} if rule.voted else {}      # (0,): the call of before
-    if bridge_gap and run_edges is None and border_reach is None:
+    if bridge_gap and run_edges is None and border_reach is None and max_bases is None:
         raise ValueError("threshold_sweep: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
-    given = {"run_edges": run_edges, "border_reach": border_reach, "bridge_gap": bridge_gap or None}
+    given = {"run_edges": run_edges, "border_reach": border_reach, "bridge_gap": bridge_gap or None, "max_bases": max_bases}
     given = {key: value for key, value in given.items() if value is not None}                  # nothing given: the call of before
     thresholds = [float(t) for t in thresholds]
     selection = vset.select(network.window, max_seq_length, validation_start, max_number)
@@ -557,6 +581,9 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
                              "hp_complete": complete, "hp_found": found, "called_absent": called_absent})
         if borders is not None:
             rows[-1]["hp_borders"], rows[-1]["called_borders"] = border_report(borders[k], border_reach)
+        if max_bases is not None:
+            rows[-1].update({"hp_bases": got.run_bases[k][0].tolist(), "called_bases": got.run_bases[k][1].tolist(),
+                             **run_base_rates(got.run_bases[k])})
     return rows
 
 
@@ -689,6 +716,12 @@ def main(argv):
     CATFISH_VALIDATION_BRIDGE=<int> (1 .. 49; with CATFISH_VALIDATION_RUNS or CATFISH_VALIDATION_BORDERS) counts those two on the
     prediction with its gaps of at most that many samples bridged (``infer.bridge_gaps``); their JSON lines then carry
     ``bridge_gap``.
+    CATFISH_VALIDATION_BASES=1 (16 length bins) or =<int> (1 .. 32; needs CATFISH_DEVICE_VALIDATION=1 and CATFISH_LABEL_KMER: only
+    reads that come with their event tables have a base map) also counts, per round, the true and the called runs at threshold 0.5
+    by state, base (A / C / G / T / other) and length in bases and appends step, threshold, max_bases, classes, states,
+    ``hp_bases``, ``called_bases`` and the rates of ``device_validation.run_base_rates`` as one JSON line to
+    ``<model path>_hp_bases.jsonl``; CATFISH_VALIDATION_BRIDGE applies to it too.  The ``.txt`` reports and the other ``.jsonl``
+    files are unchanged.
     CATFISH_LABEL_KMER=<odd k in 1 .. 15>: both directories hold event files (``raw`` + ``event_base`` / ``event_length``,
     ``labelling.load_event_npz``; ``python -m catfish_amd.convert --events`` writes them) and every read is labelled with that k-mer
     size on the way in (``npz_loader_from_env``; with CATFISH_DEVICE_VALIDATION=1 or CATFISH_DEVICE_DB=reads on the card,
@@ -710,6 +743,11 @@ def main(argv):
         hparams["training_precision"] = os.environ["CATFISH_TRAINING_PRECISION"]
     network = build_model(kind, save=True, **hparams)
     network.initialize_network()
+    bases = os.environ.get("CATFISH_VALIDATION_BASES") or "0"
+    if bases != "0":                                             # ... which homopolymers by base and length in bases, one JSON line per round
+        if os.environ.get("CATFISH_DEVICE_VALIDATION") != "1" or not (os.environ.get("CATFISH_LABEL_KMER") or "").strip():
+            raise ValueError("CATFISH_VALIDATION_BASES needs CATFISH_DEVICE_VALIDATION=1 and CATFISH_LABEL_KMER (reads with event tables)")
+        network.validation_max_bases = MAX_BASES if bases == "1" else check_max_bases(int(bases))
     loader = npz_loader_from_env()                               # load_npz, or event files labelled on the way in (CATFISH_LABEL_KMER)
     from_events = loader is not load_npz
     with_loader = {"loader": loader} if from_events else {}
@@ -743,7 +781,8 @@ def main(argv):
         if bridge:                                               # ... both counted on the bridged prediction
             from .infer import check_bridge
             network.validation_bridge_gap = check_bridge(bridge, 15)
-            if getattr(network, "validation_run_edges", None) is None and getattr(network, "validation_border_reach", None) is None:
+            if getattr(network, "validation_run_edges", None) is None and getattr(network, "validation_border_reach", None) is None \
+                    and getattr(network, "validation_max_bases", None) is None:
                 raise ValueError("CATFISH_VALIDATION_BRIDGE needs CATFISH_VALIDATION_RUNS=1 or CATFISH_VALIDATION_BORDERS")
     began = datetime.datetime.now()
     train_and_validate(network, db_train, n_train, squiggles, stretch, network.model_path, start, most)

@@ -645,6 +645,24 @@ int cf_validation_run_borders_bridged(cf_model* m, const float* probs, const uin
                                       int32_t reach, int32_t max_gap, int32_t min_run, int64_t* counts_out, void* work,
                                       int64_t work_bytes, void* stream);
 
+/* Validation by base (csrc/validation_bases.hpp, csrc/validation_bases_word.hpp; device_validation.run_bases_host is its definition):
+ * the runs of cf_validation_run_states -- same stretches, prediction, runs, kinds and states -- counted by the bases they hold instead of
+ * by their length in samples (the reference's prediction_information / get_bases, networks/process_output.py).  basemap is the set's
+ * base map as cf_label_events writes it (the event's base byte, bit 7 on the event's centre sample), read in place: the base map of
+ * packed sample bounds[r] + i is basemap[src_first[r] + i] (an index outside [0, basemap_total) counts as no base).  The bases of a run are
+ * the marked samples inside it (the sample the last-sample rule adds included); nb = how many.  Class 0..3 = A / C / G / T: nb >= 1 and every
+ * one of them is that upper-case byte; class 4 = anything else, nb == 0 included.  Bin = min(nb, max_bases).
+ *   counts_out   device int64 [n_thresholds][2][3][5][max_bases + 1] (kind, state, class, bin), zeroed and written by the call
+ *   thresholds   HOST double [n_thresholds], 1..16 of them;  max_bases  1 .. 32;  src_first  device int64 [n]
+ *   work         device bytes, >= cf_validation_run_work_bytes(total, n_thresholds); max_gap as for cf_validation_run_states_bridged
+ * Integer arithmetic only, so equal inputs give equal results whatever `longest` (a hint) or the grid.  Asynchronous on `stream`; m may
+ * be NULL.  CF_ERR_INVALID before any launch for what cf_validation_run_states_bridged refuses, a null base map or src_first,
+ * basemap_total outside [1, 2^31) or max_bases outside 1..32. */
+int cf_validation_run_bases(cf_model* m, const float* probs, const uint8_t* y, const uint8_t* basemap, int64_t basemap_total,
+                            const int64_t* src_first, const int64_t* bounds, const int64_t* length, int64_t n, int64_t total,
+                            int64_t longest, const double* thresholds, int32_t n_thresholds, int32_t max_bases, int32_t max_gap,
+                            int32_t min_run, int64_t* counts_out, void* work, int64_t work_bytes, void* stream);
+
 /* Validation curves (csrc/validation_curve.hpp; device_validation.curve_host is its definition): the histogram of a round's
  * probabilities from which the host draws the whole ROC and precision-recall curves (device_validation.curves_from_histogram).
  * With NB = (0x3F800000 >> shift) + 1 bins, a probability with float32 bits u falls into bin min(max((int32_t)u, 0) >> shift, NB - 1)

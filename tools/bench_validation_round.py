@@ -20,6 +20,8 @@ and range of seconds per round, and whether (c)'s range lies below (a)'s and bel
     python tools/bench_validation_round.py --trace-curve 3       # rounds with the curve at shift 14 and shift 10, for rocprofv3
     python tools/bench_validation_round.py --borders --rounds 7  # the border leg, see below
     python tools/bench_validation_round.py --trace-borders 3     # rounds with border_reach=64, for rocprofv3 --kernel-trace --stats
+    python tools/bench_validation_round.py --bases --rounds 7    # the base leg, see below
+    python tools/bench_validation_round.py --trace-bases 3       # rounds with max_bases=16, for rocprofv3 --kernel-trace --stats
 
 The run-state leg (``--run-states``) times the device-resident round itself (``RNN.score_validation_device`` on a seeded selection,
 ending in its copy back), alternating per round: without run states, with ``run_edges=(35, 70, 140)``, and the forward pass of
@@ -35,6 +37,14 @@ The border leg (``--borders``) times the same round, alternating per round: with
 yardstick, in the same process), with ``border_reach=64`` -- at 1 and at 16 thresholds -- and ``HipEngine.run_borders_validation``
 and ``run_states_validation`` alone (launch to synchronise, no copy back) on the round's own probabilities.  Its summary line gives
 the medians, what either step adds to the round and the microseconds per threshold of either call alone.
+
+The base leg (``--bases``) needs reads with event tables, so it makes its own set of the same shape: ``--reads`` reads of
+``--read-len`` samples dealt from 64 distinct ``labelling.synthetic_event_read`` reads, labelled on the card
+(``DeviceValidationSet.from_events``, k = 5).  It times the same round, alternating per round: without run tables, with
+``run_edges=()`` (the yardstick, in the same process), with ``max_bases=16`` -- at 1 and at 16 thresholds -- and
+``HipEngine.run_bases_validation`` and ``run_states_validation`` alone (launch to synchronise, no copy back; both include their
+label passes) on the round's own probabilities.  Its summary line gives the medians, what either step adds to the round, the
+microseconds per threshold of either call alone and their ratio.
 """
 import argparse
 import contextlib
@@ -153,6 +163,51 @@ def borders_leg(net, resident, rounds, emit, reach=64, edges=(35, 70, 140)):
                   borders_over_states_call=stats["borders_call"]["median_s"] / stats["states_call"]["median_s"]))
 
 
+def event_set(reads, read_len, distinct=64):
+    """A resident set of ``reads`` event reads (dealt from ``distinct`` synthetic ones), labelled on the card, with its base map."""
+    from catfish_amd import labelling
+    made = [labelling.synthetic_event_read(read_len, seed=7000 + i) for i in range(min(reads, distinct))]
+    dealt = [made[i % len(made)] for i in range(reads)]
+    batch = labelling.EventBatch.from_reads([(bases, lengths) for _raw, bases, lengths in dealt])
+    return DeviceValidationSet.from_events([raw for raw, _b, _l in dealt], batch, 5)
+
+
+def bases_leg(net, resident, rounds, emit, max_bases=16, edges=()):
+    from catfish_amd import device_validation as dv
+    device = "cuda:%d" % net.device
+    for thresholds in ((0.5,), tuple(float(t) for t in np.linspace(0.2, 0.95, 16))):
+        k = len(thresholds)
+        names = ("plain", "run_states", "bases", "states_call", "bases_call")
+        seconds = {name: [] for name in names}
+        counts = torch.empty(k * 2 * 3 * len(dv.BASE_CLASSES) * (max_bases + 1), dtype=torch.int64, device=device)
+        for rnd in range(-1, rounds):                      # round -1 warms up (buffers grow once)
+            random.seed(rnd)
+            selection = resident.select(net.window, STRETCH, START, MOST)
+            took = {"plain": timed(lambda: net.score_validation_device(resident, selection, thresholds)),
+                    "run_states": timed(lambda: net.score_validation_device(resident, selection, thresholds, run_edges=edges)),
+                    "bases": timed(lambda: net.score_validation_device(resident, selection, thresholds, max_bases=max_bases))}
+            t = net.validation_buffers["tensors"]
+            bounds, _tails = dv.layout(selection[2], net.window)
+            n, total, longest = len(selection[2]), int(bounds[-1]), int(np.diff(bounds).max())
+            src_d, len_d, bounds_d = t["table"][:n], t["table"][n + 1:2 * n + 1], t["table"][2 * (n + 1):3 * (n + 1)]
+            basemap = resident.device_basemap(device)
+            took["states_call"] = timed(lambda: net.engine.run_states_validation(t["probs"][:total], t["y"][:total], bounds_d, len_d, total,
+                                                                                 longest, thresholds, edges, counts, t["run_work"]))
+            took["bases_call"] = timed(lambda: net.engine.run_bases_validation(t["probs"][:total], t["y"][:total], basemap, src_d, bounds_d,
+                                                                               len_d, total, longest, thresholds, max_bases, counts,
+                                                                               t["run_work"]))
+            if rnd >= 0:
+                for name in names:
+                    seconds[name].append(took[name])
+                emit(dict(leg="bases", thresholds=k, round=rnd, **{name + "_s": took[name] for name in names}))
+        stats = {name: spread(v) for name, v in seconds.items()}
+        emit(dict(summary=True, leg="bases", thresholds=k, max_bases=max_bases, edges=list(edges), reads=resident.n_reads, stretch=STRETCH,
+                  rounds=rounds, samples_per_round=resident.n_reads * (STRETCH // 35 * 35), legs=stats,
+                  added_ms={name: 1e3 * (stats[name]["median_s"] - stats["plain"]["median_s"]) for name in ("run_states", "bases")},
+                  call_us_per_threshold={name: 1e6 * stats[name]["median_s"] / k for name in ("states_call", "bases_call")},
+                  bases_over_states_call=stats["bases_call"]["median_s"] / stats["states_call"]["median_s"]))
+
+
 def curve_leg(net, resident, rounds, emit, shifts=(14, 10)):
     from catfish_amd import device_validation as dv
     thresholds = (0.5,)
@@ -205,6 +260,8 @@ def main():
     ap.add_argument("--trace-curve", type=int, default=0, help="this many rounds with the curve at shift 14 and at shift 10, then exit")
     ap.add_argument("--borders", action="store_true", help="the border leg alone, then exit")
     ap.add_argument("--trace-borders", type=int, default=0, help="this many rounds with border_reach=64 at 16 thresholds, then exit")
+    ap.add_argument("--bases", action="store_true", help="the base leg alone (on a set of event reads of its own), then exit")
+    ap.add_argument("--trace-bases", type=int, default=0, help="this many rounds with max_bases=16 at 16 thresholds, then exit")
     args = ap.parse_args()
     rounds = max(5, args.rounds)
     commit = args.commit or commit_id()
@@ -214,6 +271,26 @@ def main():
     with contextlib.redirect_stdout(io.StringIO()):
         net.set_weights(weights)
     out_path = os.path.abspath(args.out)
+    if args.bases or args.trace_bases:
+        resident = event_set(args.reads, args.read_len)
+        if args.trace_bases:
+            for rnd in range(args.trace_bases):
+                random.seed(rnd)
+                selection = resident.select(net.window, STRETCH, START, MOST)
+                net.score_validation_device(resident, selection, tuple(float(t) for t in np.linspace(0.2, 0.95, 16)), run_edges=(), max_bases=16)
+            print(json.dumps(dict(traced="bases", rounds=args.trace_bases, max_bases=16, thresholds=16)))
+        else:
+            os.makedirs(os.path.dirname(out_path), exist_ok=True)
+            with open(out_path, "a") as out:
+                def emit_line(rec):
+                    line = json.dumps(dict(rec, commit=commit))
+                    print(line, flush=True)
+                    out.write(line + "\n")
+                    out.flush()
+
+                bases_leg(net, resident, rounds, emit_line)
+        net.engine.close()
+        return
     with tempfile.TemporaryDirectory() as tmp:
         os.chdir(tmp)
         paths, memory = [], {}
