@@ -2718,10 +2718,19 @@ extern "C" const char* cf_profile_slot_name(int slot) {
 }
 
 // ---- debug hook --------------------------------------------------------------------------
+#include "bf16_stage.hpp"   // the bf16 / bf16x3 activation layout, decoded on the host
+constexpr bool cf_bf16_stage_layout_agrees() {
+    for (int kb = 0; kb < 8; ++kb)
+        for (int hh = 0; hh < 2; ++hh)
+            for (int j = 0; j < 8; ++j)
+                if (cf_bf16_frag_feature(kb, hh, j) != frag_feature32(kb, hh, j)) return false;
+    return true;
+}
+static_assert(cf_bf16_stage_layout_agrees(), "bf16_stage.hpp decodes the layout the bf16 kernels write");
+
 extern "C" int cf_debug_stage(cf_model* m, int stage, int64_t n_windows, float* out_host) {
     if (!m || !out_host) return fail(CF_ERR_INVALID, "cf_debug_stage: null argument");
     if (m->gen) return fail(CF_ERR_INVALID, "cf_debug_stage: not available on the any-size path");
-    if (m->np > 0 && stage != 100) return fail(CF_ERR_INVALID, "cf_debug_stage: only available with CF_PREC_FP32");
     const cf_model::Slot& sl = m->slots[0];
     if (n_windows <= 0 || (stage != 100 && n_windows > sl.last_windows)) return fail(CF_ERR_INVALID, "cf_debug_stage: n_windows exceeds slot 0's last pass");
     HIP_TRY(hipSetDevice(m->device));
@@ -2744,6 +2753,13 @@ extern "C" int cf_debug_stage(cf_model* m, int stage, int64_t n_windows, float* 
         feats = 2 * CF_H; mt = 8; src = sl.d_y[l & 1];
     } else {
         return fail(CF_ERR_INVALID, "cf_debug_stage: no such stage");
+    }
+    if (m->np > 0) {         // bf16 / bf16x3: the same buffers in the layout of bf16_stage.hpp (np = 2: hi + lo)
+        std::vector<uint16_t> frag16((size_t)cf_bf16_stage_elems(n_windows, CF_T, feats, m->np));
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(frag16.data(), src, frag16.size() * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        cf_bf16_stage_decode(frag16.data(), n_windows, CF_T, feats, m->np, out_host);
+        return CF_OK;
     }
     const int64_t n_tiles = (n_windows + CF_TILE - 1) / CF_TILE;
     std::vector<float> frag((size_t)n_tiles * CF_T * mt * 256);

@@ -637,6 +637,11 @@ class HipEngine(object):
                 for i in range(N.CF_PROF_SLOTS) if cnt[i]}
 
     def debug_stage(self, stage, n_windows):
+        """An intermediate activation of slot 0's last pass -> float32 [n_windows, 35, features] (tuned 64 / 32 path only).
+        ``stage``: 0 .. n_layers_res - 1 the residual blocks' outputs, n_layers_res + l the output of biGRU layer l.  Only what
+        survives a pass can be read: the last two blocks (block 0 not when blocks 0 and 1 ran as one fused launch), the two
+        layers before the last one; the last layer's output exists as logits only.  In every precision: with ``precision="bf16"``
+        the values are what the kernels stored, rounded to bf16; with ``"bf16x3"`` hi + lo of the stored split."""
         feats = self.layer_size_res if stage < self.n_layers_res else 2 * self.layer_size
         out = np.empty((n_windows, WINDOW, feats), dtype=np.float32)
         N.check(self._lib.cf_debug_stage(self._handle, int(stage), int(n_windows), out.ctypes.data_as(C.c_void_p)))

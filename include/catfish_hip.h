@@ -745,7 +745,9 @@ const char* cf_profile_slot_name(int slot);
 /* Debug/test hook: copy an intermediate activation of the LAST pass to the
  * host in natural [n_windows, 35, features] order.  stage: 0..n_layers_res-1
  * = residual block outputs, n_layers_res + l = GRU layer l output (not
- * available for the last layer, whose output only exists as logits). */
+ * available for the last layer, whose output only exists as logits).  In the
+ * bf16 precisions the stage is what the kernels stored: the value rounded to
+ * bf16 (CF_PREC_BF16) or hi + lo of its split (CF_PREC_BF16X3). */
 int cf_debug_stage(cf_model* m, int stage, int64_t n_windows, float* out_host);
 
 /* Which card HIP device `device` of this process is -- the reference's per-file loop (catfish/catfish:50-82) shards over one

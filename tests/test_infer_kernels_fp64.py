@@ -55,6 +55,9 @@ Compared with float64 here and nowhere before: every any-size launch of more tha
 160, 176 and 256 units at 2, 3, 4 and 8 waves, the 160-unit launch at exactly 163 840 B among them), the two-tile kernel itself (so
 far only held to the one-tile kernel plus 83 sampled windows), the fused launch and the cooperative / throughput switches on logits,
 stages and per window, the unpipelined bf16x3 kernel, and bf16x3 at 16, 48, 112 and 176 units.
+
+``model_forward(..., bf16=True)`` and its float32 implementation (``arith="float32"``) are the rounding scheme of plain bf16; the
+module that holds those kernels to it is tests/test_infer_bf16_parity.py.
 """
 import json
 import os
@@ -154,19 +157,31 @@ def split(v, keep_lo=True):
 
 class _Product(object):
     """``a @ w`` exactly, or as the bf16x3 kernels evaluate it: w scaled in double, rounded to float, split; a split from its
-    float32 value; a_hi w_hi + a_lo w_hi + a_hi w_lo, un-scaled again (the kernels feed the scaled sum to exp2)."""
+    float32 value; a_hi w_hi + a_lo w_hi + a_hi w_lo, un-scaled again (the kernels feed the scaled sum to exp2).
+    With ``bf16`` as the plain bf16 kernels evaluate it: ``a_hi @ w_hi`` with w_hi = bf16(float(scale w)) and a_hi = bf16(float(a)),
+    accumulated in float64.  Departures from that scheme, for tests/test_infer_bf16_parity_host.py: ``late_scale`` (the weights are
+    rounded before they are scaled), ``keep`` (an index of the weights left in float), ``rounded=False`` (a enters as it is)."""
 
-    def __init__(self, x3):
-        self.x3 = x3
+    def __init__(self, x3, bf16=False):
+        assert not (x3 and bf16)
+        self.x3, self.bf16 = x3, bf16
 
-    def weights(self, w, scale=1.0):
+    def weights(self, w, scale=1.0, late_scale=False, keep=None):
         w = np.asarray(w, dtype=np.float64)
+        if self.bf16:
+            f = (w if late_scale else w * scale).astype(np.float32)
+            hi = bf16_round(f).astype(np.float64)
+            if keep is not None:
+                hi[keep] = f[keep]
+            return (hi * scale if late_scale else hi, None, scale)
         if not self.x3:
             return (w,)
         hi, lo = split((w * scale).astype(np.float32))
         return (hi + lo, hi, scale)
 
-    def __call__(self, a, wp, keep_lo=True):
+    def __call__(self, a, wp, keep_lo=True, rounded=True):
+        if self.bf16:
+            return ((split(a, False)[0] if rounded else np.asarray(a, dtype=np.float64)) @ wp[0]) / wp[2]
         if not self.x3:
             return a @ wp[0]
         ah, al = split(a, keep_lo)
@@ -193,8 +208,10 @@ def _gru_direction(x, wg, bg, wc, bc, reverse, mm, act, defect):
     """oracle.gru_direction in float64 with the products through ``mm``; ``defect``: set of names planted in this direction."""
     n, t, cin = x.shape
     hsz = wc.shape[1]
-    wgx, wgh, wcx, wch = (mm.weights(wg[:cin], GATE_SCALE), mm.weights(wg[cin:], GATE_SCALE), mm.weights(wc[:cin], CAND_SCALE),
-                          mm.weights(wc[cin:], CAND_SCALE))
+    late = "scale_after_rounding" in defect
+    block = (slice(16, 32), slice(0, 16)) if "block_unrounded" in defect else None
+    wgx, wgh, wcx, wch = (mm.weights(wg[:cin], GATE_SCALE, late), mm.weights(wg[cin:], GATE_SCALE, late),
+                          mm.weights(wc[:cin], CAND_SCALE, late), mm.weights(wc[cin:], CAND_SCALE, late, keep=block))
     x2 = x.reshape(n * t, cin)
     xg = (mm(x2, wgx) + bg).reshape(n, t, 2 * hsz)             # the input's share of both pre-activations, all steps at once
     xc = (mm(x2, wcx) + bc).reshape(n, t, hsz)
@@ -207,7 +224,7 @@ def _gru_direction(x, wg, bg, wc, bc, reverse, mm, act, defect):
         if "sigmoid_off" in defect:
             gates = gates + 1e-5 * np.sin(1e3 * pre)
         r, u = gates[:, :hsz], gates[:, hsz:]
-        c = tanh(xc[:, s] + mm(r * h, wch, keep_lo="rh_hi_only" not in defect))
+        c = tanh(xc[:, s] + mm(r * h, wch, keep_lo="rh_hi_only" not in defect, rounded="rh_unrounded" not in defect))
         if "tanh_off" in defect:
             c = c + 1e-5 * np.sin(1e3 * c)
         h = u * h + (1 - u) * c
@@ -215,13 +232,19 @@ def _gru_direction(x, wg, bg, wc, bc, reverse, mm, act, defect):
     return out
 
 
-def _conv_bn(x, w, j, mm):
-    """conv1d SAME + inference batch norm, folded as the packers fold it: W' = W gamma / sqrt(var + eps), b' = (b - mean) gamma /
-    sqrt(var + eps) + beta.  One input channel: plain fp32 arithmetic in every kernel, exact here."""
+def _folded(w, j):
+    """Conv unit j with its batch norm folded in, in double -> (kernel [taps, cin, cout], the 1 / sqrt scale [cout], bias [cout])."""
     k = np.asarray(w[oracle.conv_names(j) + "/kernel"], dtype=np.float64)
     g = lambda name: np.asarray(w[oracle.bn_names(j) + "/" + name], dtype=np.float64)      # noqa: E731
     inv = g("gamma") / np.sqrt(g("moving_variance") + oracle.BN_EPS)
     bias = (np.asarray(w[oracle.conv_names(j) + "/bias"], dtype=np.float64) - g("moving_mean")) * inv + g("beta")
+    return k, inv, bias
+
+
+def _conv_bn(x, w, j, mm, rounded=True):
+    """conv1d SAME + inference batch norm, folded as the packers fold it: W' = W gamma / sqrt(var + eps), b' = (b - mean) gamma /
+    sqrt(var + eps) + beta.  One input channel: plain fp32 arithmetic in every kernel, exact here."""
+    k, inv, bias = _folded(w, j)
     n, t, cin = x.shape
     taps, left = k.shape[0], (k.shape[0] - 1) // 2
     xp = np.zeros((n, t + taps - 1, cin))
@@ -229,24 +252,121 @@ def _conv_bn(x, w, j, mm):
     mm = mm if cin > 1 else _Product(False)
     out = bias
     for i in range(taps):
-        out = out + mm(np.ascontiguousarray(xp[:, i:i + t]).reshape(n * t, cin), mm.weights(k[i] * inv)).reshape(n, t, -1)
+        out = out + mm(np.ascontiguousarray(xp[:, i:i + t]).reshape(n * t, cin), mm.weights(k[i] * inv), rounded=rounded).reshape(n, t, -1)
     return out
 
 
-def model_forward(x, w, n_layers=3, n_layers_res=2, x3=False, act="exact", defects=()):
+def _fma32(a, b, c):
+    """a b + c on float32 arrays with the product exact (in double): rounded to double, then to float.  A true fma rounds once;
+    the two agree except where the double lands on a tie of the float grid."""
+    return (np.asarray(a, dtype=np.float64) * np.asarray(b, dtype=np.float64) + np.asarray(c, dtype=np.float64)).astype(np.float32)
+
+
+def _conv_bn_f32(x, w, j):
+    """``_conv_bn`` as the plain bf16 kernels compute it, float32 throughout: folded weights and bias rounded to float; one input
+    channel as one fma; otherwise bias + sum over taps of bf16(x) @ bf16(W'), products and sums in float32."""
+    k, inv, bias = _folded(w, j)
+    n, t, cin = x.shape
+    taps, left = k.shape[0], (k.shape[0] - 1) // 2
+    b32 = bias.astype(np.float32)
+    if cin == 1:
+        assert taps == 1
+        return _fma32((k[0, 0] * inv).astype(np.float32), x, b32)
+    xp = np.zeros((n, t + taps - 1, cin), dtype=np.float32)
+    xp[:, left:left + t] = bf16_round(x)
+    out = np.broadcast_to(b32, (n * t, b32.shape[0]))
+    for i in range(taps):
+        out = out + np.ascontiguousarray(xp[:, i:i + t]).reshape(n * t, cin) @ bf16_round((k[i] * inv).astype(np.float32))
+    return out.reshape(n, t, -1)
+
+
+def _gru_direction_f32(x, wg, bg, wc, bc, reverse):
+    """One direction as gru_bf16_pipe_kernel / gru_layer_bf16_kernel<., ., 1> compute it, float32 throughout and in the pre-scaled
+    domain: weights bf16(float(scale W)), biases float(scale b), bf16(x), bf16(h) and bf16(r h) into the products, sigmoid =
+    rcp(1 + exp2(.)), tanh = fma(-2, rcp(1 + exp2(.)), 1), h = fma(u, h - c, c); h itself stays float32."""
+    f32 = np.float32
+    n, t, cin = x.shape
+    hsz = wc.shape[1]
+    wgs, wcs = bf16_round((wg * GATE_SCALE).astype(f32)), bf16_round((wc * CAND_SCALE).astype(f32))
+    x2 = bf16_round(x).reshape(n * t, cin)
+    xg = ((bg * GATE_SCALE).astype(f32) + x2 @ wgs[:cin]).reshape(n, t, 2 * hsz)
+    xc = ((bc * CAND_SCALE).astype(f32) + x2 @ wcs[:cin]).reshape(n, t, hsz)
+    one = f32(1.0)
+    h = np.zeros((n, hsz), dtype=f32)
+    out = np.empty((n, t, hsz), dtype=f32)
+    with np.errstate(over="ignore"):
+        for s in (range(t - 1, -1, -1) if reverse else range(t)):
+            gates = one / (one + np.exp2(xg[:, s] + bf16_round(h) @ wgs[cin:]))
+            r, u = gates[:, :hsz], gates[:, hsz:]
+            c = _fma32(f32(-2.0), one / (one + np.exp2(xc[:, s] + bf16_round(r * h) @ wcs[cin:])), one)
+            h = _fma32(u, h - c, c)
+            out[:, s] = h
+    return out
+
+
+def _model_forward_bf16_f32(x, w, n_layers, n_layers_res):
+    """The second implementation of the plain bf16 scheme (``model_forward(..., bf16=True, arith="float32")``): what the kernels do
+    in fp32 is done in float32 here, with numpy's summation order and correctly rounded exp2 and reciprocal."""
+    f32 = np.float32
+    a = np.asarray(x, dtype=f32)
+    a = a[:, :, None] if a.ndim == 2 else a
+    stages = {}
+    zero = f32(0.0)
+    for d in range(n_layers_res):
+        sc = _conv_bn_f32(a, w, 4 * d)
+        o = np.maximum(_conv_bn_f32(a, w, 4 * d + 1), zero)
+        o = np.maximum(_conv_bn_f32(o, w, 4 * d + 2), zero)
+        o = np.maximum(_conv_bn_f32(o, w, 4 * d + 3), zero)
+        a = np.maximum(o + sc, zero)
+        stages["res%d" % d] = a
+    for layer in range(n_layers):
+        outs = []
+        for dname, rev in (("fw", False), ("bw", True)):
+            p = oracle.gru_prefix(layer, dname)
+            outs.append(_gru_direction_f32(a, *(np.asarray(w[p + k], dtype=np.float64) for k in
+                                                ("/gates/kernel", "/gates/bias", "/candidate/kernel", "/candidate/bias")), reverse=rev))
+        a = np.concatenate(outs, axis=2)
+        stages["gru%d" % layer] = a
+    dw = np.asarray(w["final_fully_connected/kernel"], dtype=f32)
+    hsz = a.shape[2] // 2
+    a2 = a.reshape(-1, a.shape[2])
+    logits = a2[:, :hsz] @ dw[:hsz] + a2[:, hsz:] @ dw[hsz:] + np.asarray(w["final_fully_connected/bias"], dtype=f32)
+    stages["logits"] = logits.reshape(-1)
+    return (f32(1.0) / (f32(1.0) + np.exp(-logits))).reshape(-1), stages
+
+
+BF16_DEFECTS = {"rh_unrounded", "block_unrounded", "scale_after_rounding", "conv_in_unrounded", "dense_on_bf16_h"}
+
+
+def model_forward(x, w, n_layers=3, n_layers_res=2, x3=False, act="exact", defects=(), bf16=False, arith="float64"):
     """The network of ``oracle.forward`` in float64 -> (probs [N * 35], stages), with options: ``x3`` the split products of the
     bf16x3 kernels, ``act="kernel"`` the kernels' sigmoid / tanh, ``defects`` (name, layer or None for all, direction or None)
     triples planted in the recurrences: "state_hi_only" (the state enters the gates' product without its lo part), "rh_hi_only"
-    (r.h enters the candidate's product without its lo part), "sigmoid_off" / "tanh_off" (1e-5 sin(1e3 .) added)."""
-    mm = _Product(x3)
+    (r.h enters the candidate's product without its lo part), "sigmoid_off" / "tanh_off" (1e-5 sin(1e3 .) added).
+
+    ``bf16``: the rounding scheme of the plain bf16 kernels (``_Product``): a_hi @ w_hi, accumulated in float64, for every product
+    x3 splits; the layer input, h, r.h and the conv intermediates are rounded where they enter a product and nowhere else (block
+    0's one-channel convolutions, the shortcut sum, biases, the state between steps and the dense head, which runs on the fp32 h,
+    stay exact).  With ``arith="float32"`` the same scheme in the kernels' own arithmetic (``_model_forward_bf16_f32``).  Defects
+    of the bf16 scheme: "rh_unrounded" (r.h enters the candidate's product as it is), "block_unrounded" (rows 16 .. 31, columns
+    0 .. 15 of the candidate's recurrent kernel stay in float), "scale_after_rounding" (weights rounded, then scaled),
+    "conv_in_unrounded" (the 32-channel convolutions take their inputs as they are), "dense_on_bf16_h" (the head reads bf16(h))."""
+    if arith == "float32":
+        assert bf16 and not x3 and act == "exact" and not defects, "the float32 implementation is that of the plain bf16 scheme"
+        return _model_forward_bf16_f32(x, w, n_layers, n_layers_res)
+    assert arith == "float64", arith
+    mm = _Product(x3, bf16)
+    everywhere = {name for name, l, d in defects if l is None and d is None}
+    assert bf16 or not {name for name, _, _ in defects} & BF16_DEFECTS, "these defects are departures from the bf16 scheme"
+    rounded = "conv_in_unrounded" not in everywhere
     a = np.asarray(x, dtype=np.float64)
     a = a[:, :, None] if a.ndim == 2 else a
     stages = {}
     for d in range(n_layers_res):
-        sc = _conv_bn(a, w, 4 * d, mm)
-        o = np.maximum(_conv_bn(a, w, 4 * d + 1, mm), 0)
-        o = np.maximum(_conv_bn(o, w, 4 * d + 2, mm), 0)
-        o = np.maximum(_conv_bn(o, w, 4 * d + 3, mm), 0)
+        sc = _conv_bn(a, w, 4 * d, mm, rounded)
+        o = np.maximum(_conv_bn(a, w, 4 * d + 1, mm, rounded), 0)
+        o = np.maximum(_conv_bn(o, w, 4 * d + 2, mm, rounded), 0)
+        o = np.maximum(_conv_bn(o, w, 4 * d + 3, mm, rounded), 0)
         a = np.maximum(o + sc, 0)
         stages["res%d" % d] = a
     for layer in range(n_layers):
@@ -259,6 +379,8 @@ def model_forward(x, w, n_layers=3, n_layers_res=2, x3=False, act="exact", defec
                                        reverse=rev, mm=mm, act=act, defect=planted))
         a = np.concatenate(outs, axis=2)
         stages["gru%d" % layer] = a
+    if "dense_on_bf16_h" in everywhere:
+        a = split(a, False)[0]
     logits = (a.reshape(-1, a.shape[2]) @ np.asarray(w["final_fully_connected/kernel"], dtype=np.float64)
               + np.asarray(w["final_fully_connected/bias"], dtype=np.float64))
     stages["logits"] = logits.reshape(-1)
