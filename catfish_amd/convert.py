@@ -14,7 +14,8 @@ With h5py installed the CLI also takes FAST5 directly (``infer.load_dac``, one f
 
 ``--events`` converts Tombo-resquiggled reads for TRAINING instead: ``read_x.fast5`` becomes ``read_x.npz`` with the normalised
 signal and the corrected event table (``convert_events``), from which ``catfish_amd.labelling`` makes the per-sample labels for any
-k-mer size.
+k-mer size.  ``--moves`` converts base-called reads that were NOT resquiggled: ``read_x.npz`` holds the normalised signal and the
+basecaller's own Events table (``convert_moves``; ``CATFISH_LABEL_MOVES=1`` labels and trains from a directory of them).
 """
 from __future__ import annotations
 
@@ -87,9 +88,51 @@ def convert_events(src, dst_npz, clipped_bases=None):
     return final
 
 
-def convert_directory(input_dir, output_dir, keep_going=False, events=False):
+BASECALL_PATH = "Analyses/Basecall_1D_000"     # the reference's --hdf-path for reads that were not resquiggled
+
+
+def convert_moves(src, dst_npz, clipped_bases=None, hdf_path=BASECALL_PATH):
+    """One base-called read -> a move ``.npz`` (``labelling.load_move_npz`` reads it; ``CATFISH_LABEL_MOVES=1`` trains from a
+    directory of them); -> the number of labels it yields.  ``raw`` is the signal as ``TrainingRead.raw`` holds it with
+    ``use_tombo=False`` -- ``Signal[first_sample_template:]`` of ``Analyses/Segmentation_000``, median / MAD normalised, whole: its
+    length is where the labels are cut; ``event_state`` (``S<k>``), ``event_move`` and ``event_length`` (seconds, the table's own
+    dtype) are the columns ``model_state``, ``move`` and ``length`` of ``<hdf_path>/BaseCalled_template/Events``;
+    ``clipped_start`` / ``clipped_end`` as in ``convert_events``.  ValueError for a wrong path (the reference's words for a wrong
+    ``hdf_path``) or a table ``labelling.check_move_read`` refuses, ImportError without h5py."""
+    from . import labelling
+    if not os.path.exists(src):
+        raise ValueError("path to FAST5 is not correct: %s" % src)
+    try:
+        import h5py
+    except ImportError:
+        raise ImportError("reading %s needs h5py, which is not installed" % src)
+    default = labelling.DEFAULT_CLIPPED if clipped_bases is None else clipped_bases
+    hdf_path = hdf_path if hdf_path.endswith("/") else hdf_path + "/"
+    with h5py.File(src, "r") as fast5:
+        if hdf_path not in fast5:
+            raise ValueError("hdf path not in hdf file!")
+        if hdf_path + "BaseCalled_template" not in fast5:
+            raise ValueError("hdf path in hdf file, but does not contain BaseCalled_template results!")
+        events = fast5[hdf_path + "BaseCalled_template/Events"]
+        lengths, states, moves = np.asarray(events["length"]), np.asarray(events["model_state"]), np.asarray(events["move"])
+        first_sample = int(fast5["Analyses/Segmentation_000/Summary/segmentation"].attrs["first_sample_template"])
+        clipped = (_clipped_bases(fast5, "start", default), _clipped_bases(fast5, "end", default))
+        read_name = fast5["Raw/Reads/"].visit(str)
+        signal = np.asarray(fast5["Raw/Reads/" + read_name + "/Signal"][()]).reshape(-1)
+    raw = infer.normalize_raw_signal(signal[first_sample:], "median")
+    checked = labelling.check_move_read(states, lengths, moves, clipped, n_raw=len(raw))
+    states, lengths, moves, clipped, final = checked[0], checked[1], checked[2], checked[3], checked[7]
+    tmp = dst_npz + ".part"
+    with open(tmp, "wb") as fh:
+        np.savez(fh, raw=raw, event_state=states.view("S%d" % states.shape[1]).reshape(-1), event_move=moves, event_length=lengths,
+                 clipped_start=np.int64(clipped[0]), clipped_end=np.int64(clipped[1]))
+    os.replace(tmp, dst_npz)
+    return final
+
+
+def convert_directory(input_dir, output_dir, keep_going=False, events=False, moves=False):
     """Every entry of ``input_dir`` (sorted) -> ``output_dir/<name without its last extension>.npy`` (``events``: ``.npz``, through
-    ``convert_events``).
+    ``convert_events``; ``moves``: ``.npz``, through ``convert_moves``).
     -> dict(converted, samples, failed = [(name, error text)]); the first failure raises unless ``keep_going``."""
     os.makedirs(output_dir, exist_ok=True)
     done = {"converted": 0, "samples": 0, "failed": []}
@@ -98,8 +141,8 @@ def convert_directory(input_dir, output_dir, keep_going=False, events=False):
         if os.path.isdir(src):
             continue
         try:
-            if events:
-                done["samples"] += convert_events(src, os.path.join(output_dir, os.path.splitext(name)[0] + ".npz"))
+            if events or moves:
+                done["samples"] += (convert_events if events else convert_moves)(src, os.path.join(output_dir, os.path.splitext(name)[0] + ".npz"))
                 done["converted"] += 1
                 continue
             done["samples"] += convert_read(src, os.path.join(output_dir, os.path.splitext(name)[0] + ".npy"))
@@ -119,8 +162,13 @@ def main(argv=None):
     ap.add_argument("--keep-going", action="store_true", help="report unreadable files at the end instead of stopping at the first")
     ap.add_argument("--events", action="store_true",
                     help="Tombo-resquiggled reads -> event .npz files (normalised signal + the corrected event table) to label and train from")
+    ap.add_argument("--moves", action="store_true",
+                    help="base-called reads that were not resquiggled -> move .npz files (normalised signal + the basecaller's Events table)")
     args = ap.parse_args(argv)
-    done = convert_directory(args.input_dir, args.output_dir, keep_going=args.keep_going, **({"events": True} if args.events else {}))
+    if args.events and args.moves:
+        ap.error("--events and --moves exclude each other")
+    done = convert_directory(args.input_dir, args.output_dir, keep_going=args.keep_going,
+                             **({"events": True} if args.events else {"moves": True} if args.moves else {}))
     print("converted %d reads (%d samples) into %s" % (done["converted"], done["samples"], args.output_dir))
     for name, err in done["failed"]:
         print("FAILED %s: %s" % (name, err))

@@ -339,6 +339,14 @@ class DeviceReadDb(DeviceFedDb):
         v = DeviceValidationSet.from_event_npz(paths, kmer, device)
         return cls(v.signal, v.labels, v.offsets, seed, lessen, neg_per_read)
 
+    @classmethod
+    def from_move_npz(cls, paths, seed=0, lessen=1, neg_per_read=None, device=None):
+        """The reads of ``paths`` (move ``.npz`` files: ``raw`` + a basecaller's Events table, ``labelling.load_move_npz``), in that
+        order, labelled through ``DeviceValidationSet.from_move_npz`` (on the card where there is one); ``raw[:final]`` is kept."""
+        from .device_validation import DeviceValidationSet
+        v = DeviceValidationSet.from_move_npz(paths, device)
+        return cls(v.signal, v.labels, v.offsets, seed, lessen, neg_per_read)
+
     # ------------------------------------------------------------------ the tables
     def host_tables(self):
         if self._tables is None:

@@ -605,6 +605,44 @@ class DeviceValidationSet(object):
         reads = [labelling.load_event_npz(path) for path in paths]
         return cls.from_events([read["raw"] for read in reads], labelling.EventBatch.from_reads(reads), kmer, device)
 
+    @classmethod
+    def from_moves(cls, signals, batch, device=None):
+        """Base-called reads that were not resquiggled: ``signals[r]`` is read r's raw signal (its first ``final`` samples are kept)
+        and ``batch`` a ``labelling.MoveBatch`` over the same reads, whose ``n_raw`` must not exceed the signals' lengths.  As
+        ``from_events``: on a GPU ``cf_label_moves`` makes the labels and the base map and they stay on the card; otherwise
+        ``batch.label_host`` makes them -- the same bytes."""
+        from . import labelling
+        signals = [np.asarray(s).reshape(-1) for s in signals]
+        if len(signals) != batch.n_reads:
+            raise ValueError("%d signals but %d move tables" % (len(signals), batch.n_reads))
+        offsets = np.asarray(batch.sample_offsets, dtype=np.int64).copy()
+        signal = np.zeros(int(offsets[-1]), dtype=np.float32)
+        for r, s in enumerate(signals):
+            o, n = int(offsets[r]), int(offsets[r + 1] - offsets[r])
+            if len(s) < n:
+                raise ValueError("read %d: the labels cover %d samples, the raw signal has %d" % (r, n, len(s)))
+            signal[o:o + n] = s[:n]
+        on_card = _label_device(device)
+        if on_card is None:
+            labels, basemap = batch.label_host(base_map=True)
+            return cls(signal, labels, offsets, device, basemap)
+        import torch
+        labels_dev, basemap_dev, _offsets = labelling.label_moves(batch, on_card, base_map=True)
+        back = lambda t: t.cpu().numpy() if t.numel() else np.zeros(0, np.uint8)     # noqa: E731
+        vset = cls(signal, back(labels_dev), offsets, device, back(basemap_dev))
+        if signal.size:
+            vset._dev = {"device": labels_dev.device, "signal": torch.from_numpy(signal).to(labels_dev.device), "labels": labels_dev,
+                         "basemap": basemap_dev}
+            vset.uploads = 1
+        return vset
+
+    @classmethod
+    def from_move_npz(cls, paths, device=None):
+        """The reads of ``paths`` (move ``.npz`` files, ``labelling.load_move_npz``), in that order, through ``from_moves``."""
+        from . import labelling
+        reads = [labelling.load_move_npz(path) for path in paths]
+        return cls.from_moves([read["raw"] for read in reads], labelling.MoveBatch.from_reads(reads), device)
+
     @property
     def n_reads(self):
         return len(self.lengths)

@@ -323,3 +323,291 @@ def synthetic_event_read(length, seed, hp_fraction=0.06):
     shift = np.median(sig)
     scale = np.median(np.abs(sig - shift))
     return (sig - shift) / scale, letters[np.array(bases, dtype=np.int64)], np.array(lengths, dtype=np.int32)
+
+
+# ----------------------------------------------------------------------------------------------------- labels from a move table
+# The other half of the reference's ``TrainingRead.events`` setter: ``use_tombo=False``, its default.  The basecaller's Events table
+# holds, per event, ``model_state`` (a k-mer), ``move`` and ``length`` in SECONDS; consecutive events with ``move == 0`` ("stays")
+# belong to the event before them.  One read has ``E >= 1`` events, ``n_raw`` samples of raw signal and clips ``(cs, ce)``:
+#
+#     heads    H = {0} u {n >= 1 : move[n] != 0} (move[0] is ignored), M = |H| merged events; merged event j has head h_j and the
+#              stays behind it, up to h_{j+1} - 1 (E - 1 for the last)
+#     length   L_j = length[h_j] + length[h_j + 1] + ..., summed left to right IN THE TABLE'S DTYPE (float32 or float64); for j = 0
+#              the sum starts (length[0] + length[0]): the reference initialises its running length with length[0] and then adds
+#              length[0] again, because it forces move[0] to 0.  n_j = ceil(L_j * 4000), the product in the same dtype
+#     samples  merged event j owns [S_j, S_j + n_j), S the exclusive sum of n, cut at n_raw: final = min(sum n_j, n_raw) labels
+#     class    core[j] = cs <= j < M - ce, and the k bytes of state[h_j] are one byte that is not 'N';
+#              cls[j] = some core[j'] with |j' - j| <= 2 inside the read -- no sliding window: the k-mer comes with the event
+#     base map state[h_j][k // 2] over the event's samples, bit 7 on the sample S_j + n_j // 2 where that lies below final
+#
+# In this branch the reference leaves ``final_signal`` None, so its ``get_pos`` / ``get_neg`` cannot run: it never trained from
+# these labels.  ``classified`` is computed before that and is what tests/golden/label_moves_golden.npz holds.  ``cf_label_moves``
+# (csrc/label_moves.hpp, rules in csrc/label_moves_rule.hpp) computes the same bytes on the card.
+FREQUENCY = 4000              # samples per second: the reference's constant
+
+
+def as_states(states):
+    """The k-mers as uint8 [E, k]: an array of ``S<k>`` / ``U<k>`` items (what h5py and ``astype(str)`` give), or uint8 [E, k].
+    ValueError for k outside 1 .. 15, a k-mer shorter than k (a NUL byte) and a byte >= 128."""
+    arr = np.asarray(states)
+    if arr.dtype.kind == "U":
+        try:
+            arr = np.char.encode(arr.reshape(-1), "ascii").astype("S%d" % max(arr.dtype.itemsize // 4, 1))
+        except UnicodeEncodeError:
+            raise ValueError("model states must be ASCII (bytes below 128)")
+    if arr.dtype.kind == "S":
+        k = arr.dtype.itemsize
+        out = np.ascontiguousarray(arr.reshape(-1)).view(np.uint8).reshape(-1, k) if k else np.zeros((arr.size, 0), np.uint8)
+    elif arr.dtype == np.uint8 and arr.ndim == 2:
+        out = arr
+    else:
+        raise ValueError("model states must be k-character strings or uint8 [n_events, k], got dtype %s with %d axes" % (arr.dtype, arr.ndim))
+    if out.shape[1] < 1 or out.shape[1] > MAX_KMER:
+        raise ValueError("the k-mers must have 1 .. %d bytes, got %d" % (MAX_KMER, out.shape[1]))
+    if out.size and (out.max() >= 128 or out.min() == 0):
+        raise ValueError("every k-mer must be k bytes in 1 .. 127 (bit 7 is the base map's mark)")
+    return np.ascontiguousarray(out)
+
+
+def merge_moves_host(lengths, moves):
+    """(heads int64 [M], n_signals int64 [M]): where the merged events begin, and ``ceil(L_j * 4000)`` with ``L_j`` summed left to
+    right from the head in the dtype of ``lengths`` (float32 or float64), the first length counted twice.  A count the dtype cannot
+    state as a finite number comes back as 2^63 - 1 (``check_move_read`` refuses it)."""
+    lengths = np.asarray(lengths).reshape(-1)
+    if lengths.dtype not in (np.float32, np.float64):
+        raise ValueError("event lengths must be float32 or float64 (seconds), got dtype %s" % lengths.dtype)
+    moves = np.asarray(moves).reshape(-1)
+    n = int(lengths.size)
+    if n == 0 or moves.size != n:
+        raise ValueError("%d event lengths but %d moves" % (n, moves.size))
+    flag = moves != 0
+    flag[0] = True
+    heads = np.flatnonzero(flag).astype(np.int64)
+    count = np.diff(np.append(heads, n))
+    with np.errstate(over="ignore", invalid="ignore"):
+        total = lengths[heads]                                  # (a copy)
+        total[0] = total[0] + lengths[0]
+        active, d = np.flatnonzero(count > 1), 1
+        while active.size:                                      # one stay further per round: every sum goes left to right
+            total[active] = total[active] + lengths[heads[active] + d]
+            d += 1
+            active = active[count[active] > d]
+        product = np.ceil(total * lengths.dtype.type(FREQUENCY))
+    n_signals = np.full(heads.size, np.iinfo(np.int64).max, dtype=np.int64)
+    fits = np.isfinite(product) & (product < 2.0 ** 62)
+    n_signals[fits] = product[fits].astype(np.int64)
+    return heads, n_signals
+
+
+def check_move_read(states, lengths, moves, clipped=(0, 0), n_raw=None):
+    """One read's move table as (states uint8 [E, k], lengths, moves int32 [E], (cs, ce), n_raw, heads, n_signals, final), or
+    ValueError where the reference raises or misaligns: no events, a length that is not finite or not > 0, a merged event of 2^31
+    or more samples, k outside 1 .. 15, a negative clip or ``cs + ce > M``, ``n_raw < 1``.  ``n_raw`` None: the raw signal is as
+    long as the events."""
+    states = as_states(states)
+    lengths = np.asarray(lengths).reshape(-1)
+    if lengths.dtype not in (np.float32, np.float64):
+        raise ValueError("event lengths must be float32 or float64 (seconds), got dtype %s" % lengths.dtype)
+    n = int(states.shape[0])
+    if n == 0:
+        raise ValueError("a read needs at least one event")
+    moves = _as_ints(moves, "event moves")
+    if lengths.size != n or moves.size != n:
+        raise ValueError("%d model states but %d event lengths and %d moves" % (n, lengths.size, moves.size))
+    if not np.all(np.isfinite(lengths)) or not np.all(lengths > 0):
+        raise ValueError("every event length must be finite and > 0")
+    heads, n_signals = merge_moves_host(lengths, moves)
+    if n_signals.max() >= 2 ** 31:
+        raise ValueError("a merged event of 2^31 or more samples")
+    try:
+        cs, ce = clipped
+    except (TypeError, ValueError):
+        raise ValueError("clipped must be (clipped_start, clipped_end), got %r" % (clipped,))
+    cs, ce = _as_int(cs, "clipped_start"), _as_int(ce, "clipped_end")
+    if cs < 0 or ce < 0 or cs + ce > heads.size:
+        raise ValueError("clipped (%d, %d) must be non-negative and leave %d merged events" % (cs, ce, heads.size))
+    covered = int(n_signals.sum())
+    n_raw = covered if n_raw is None else _as_int(n_raw, "n_raw")
+    if n_raw < 1:
+        raise ValueError("n_raw must be >= 1, got %d" % n_raw)
+    moves = np.clip(moves, -2 ** 31, 2 ** 31 - 1).astype(np.int32)             # only "zero or not" counts
+    return states, np.ascontiguousarray(lengths), moves, (cs, ce), n_raw, heads, n_signals, min(covered, n_raw)
+
+
+def move_classes_host(states, heads, clipped_start, clipped_end):
+    """cls uint8 [M]: the merged event's own k-mer is one byte that is not 'N', outside the clips; widened by two each way."""
+    at = states[heads]
+    m = int(heads.size)
+    core = (at == at[:, :1]).all(axis=1) & (at[:, 0] != ord("N"))
+    j = np.arange(m)
+    core &= (j >= int(clipped_start)) & (j < m - int(clipped_end))
+    cls = core.copy()
+    for d in range(1, WIDEN + 1):
+        cls[d:] |= core[:-d]
+        cls[:-d] |= core[d:]
+    return cls.astype(np.uint8)
+
+
+def _label_merged(states, heads, n_signals, clipped, final):
+    cls = move_classes_host(states, heads, clipped[0], clipped[1])
+    return expand_events_host(cls, n_signals)[:final], base_map_host(states[heads, states.shape[1] // 2], n_signals)[:final]
+
+
+def label_move_read_host(states, lengths, moves, clipped=(0, 0), n_raw=None):
+    """One read -> (labels uint8 [final], basemap uint8 [final]); ``check_move_read``'s refusals."""
+    states, _lengths, _moves, clipped, _n_raw, heads, n_signals, final = check_move_read(states, lengths, moves, clipped, n_raw)
+    return _label_merged(states, heads, n_signals, clipped, final)
+
+
+def _move_fields(read):
+    if isinstance(read, dict):
+        return (read["states"], read["lengths"], read["moves"], read.get("clipped", (0, 0)),
+                read.get("n_raw", len(read["raw"]) if read.get("raw") is not None else None))
+    read = tuple(read)
+    if not 3 <= len(read) <= 5:
+        raise ValueError("a read is (states, lengths, moves[, clipped[, n_raw]]) or a dict with those keys")
+    return read + ((0, 0), None)[len(read) - 3:]
+
+
+class MoveBatch(object):
+    """Many reads' move tables, packed -- what ``cf_label_moves`` takes: ``states`` uint8 [n_events, k], ``lengths`` float32 or
+    float64 [n_events] (seconds, one dtype per batch), ``moves`` int32 [n_events], ``event_offsets`` int64 [n_reads + 1],
+    ``clipped`` int32 [n_reads, 2], ``n_raw`` int64 [n_reads]; and what the host's own merge found: ``final`` int64 [n_reads]
+    (labels per read), ``merged`` int64 [n_reads] (M) and ``sample_offsets`` int64 [n_reads + 1], the exclusive sum of ``final``."""
+
+    def __init__(self, states, lengths, moves, event_offsets, clipped, n_raw, final, merged):
+        self.states, self.lengths, self.moves, self.event_offsets, self.clipped, self.n_raw = states, lengths, moves, event_offsets, clipped, n_raw
+        self.final, self.merged = final, merged
+        self.sample_offsets = np.zeros(len(final) + 1, dtype=np.int64)
+        np.cumsum(final, out=self.sample_offsets[1:])
+
+    n_reads = property(lambda self: len(self.event_offsets) - 1)
+    n_events = property(lambda self: int(self.event_offsets[-1]))
+    total = property(lambda self: int(self.sample_offsets[-1]))
+    kmer = property(lambda self: int(self.states.shape[1]))
+
+    @classmethod
+    def from_reads(cls, reads):
+        """``reads``: one ``(states, lengths, moves[, clipped[, n_raw]])`` tuple, or one dict with those keys (``load_move_npz``
+        gives such dicts; their ``raw`` supplies ``n_raw``), per read.  Every refusal of ``check_move_read`` is made here; reads
+        whose k or whose length dtype differ, and a batch of 2^31 or more events or samples, are refused too."""
+        checked = [check_move_read(*_move_fields(read)) for read in reads]
+        if len({c[0].shape[1] for c in checked}) > 1 or len({c[1].dtype for c in checked}) > 1:
+            raise ValueError("the reads of one batch share one k and one length dtype")
+        n_events = sum(c[0].shape[0] for c in checked)
+        total = sum(c[7] for c in checked)
+        if n_events >= 2 ** 31 or total >= 2 ** 31:
+            raise ValueError("a batch of 2^31 or more events or samples (%d events, %d samples): label it in parts" % (n_events, total))
+        event_offsets = np.zeros(len(checked) + 1, dtype=np.int64)
+        np.cumsum(np.array([c[0].shape[0] for c in checked], dtype=np.int64), out=event_offsets[1:])
+        if not checked:
+            return cls(np.zeros((0, 5), np.uint8), np.zeros(0, np.float32), np.zeros(0, np.int32), event_offsets, np.zeros((0, 2), np.int32),
+                       np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64))
+        return cls(np.concatenate([c[0] for c in checked]), np.concatenate([c[1] for c in checked]), np.concatenate([c[2] for c in checked]),
+                   event_offsets, np.array([c[3] for c in checked], dtype=np.int32).reshape(-1, 2),
+                   np.array([c[4] for c in checked], dtype=np.int64), np.array([c[7] for c in checked], dtype=np.int64),
+                   np.array([c[5].size for c in checked], dtype=np.int64))
+
+    def read(self, r):
+        """Read ``r``'s (states, lengths, moves, (cs, ce), n_raw)."""
+        a, b = int(self.event_offsets[r]), int(self.event_offsets[r + 1])
+        return self.states[a:b], self.lengths[a:b], self.moves[a:b], (int(self.clipped[r, 0]), int(self.clipped[r, 1])), int(self.n_raw[r])
+
+    def label_host(self, base_map=False):
+        """labels uint8 [total] of the whole batch (and the base map with ``base_map=True``): the definition, read by read."""
+        labels = np.zeros(self.total, dtype=np.uint8)
+        bmap = np.zeros(self.total, dtype=np.uint8) if base_map else None
+        for r in range(self.n_reads):
+            states, lengths, moves, clipped, n_raw = self.read(r)
+            heads, n_signals = merge_moves_host(lengths, moves)
+            lab, bm = _label_merged(states, heads, n_signals, clipped, min(int(n_signals.sum()), n_raw))
+            o = int(self.sample_offsets[r])
+            labels[o:o + lab.size] = lab
+            if base_map:
+                bmap[o:o + bm.size] = bm
+        return (labels, bmap) if base_map else labels
+
+
+def label_moves(batch, device=None, base_map=False):
+    """The batch's labels on the card through ``cf_label_moves``: (labels, sample_offsets), or (labels, basemap, sample_offsets) with
+    ``base_map=True`` -- torch tensors on ``device`` (default: the current GPU): uint8 [sum(final)] with ``MoveBatch.label_host``'s
+    bytes, and the int64 [n_reads + 1] offsets of the reads in them.  Asynchronous on torch's current stream.  No GPU or no native
+    library is an error: there is no fall-back here."""
+    import torch
+    from . import _native as N
+    device = torch.device("cuda" if device is None else device)
+    if device.type != "cuda":
+        raise ValueError("label_moves: the labels are made on a GPU (MoveBatch.label_host is the host route)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    lib = N.lib()
+    total, n_events, n_reads = batch.total, batch.n_events, batch.n_reads
+    is_f64 = int(batch.lengths.dtype == np.float64)
+    labels = torch.empty(total, dtype=torch.uint8, device=device)
+    bmap = torch.empty(total, dtype=torch.uint8, device=device) if base_map else None
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)     # noqa: E731
+    offsets = up(batch.sample_offsets)
+    if total == 0:
+        N.check(lib.cf_label_moves(None, None, None, is_f64, None, None, None, None, None, n_reads, n_events, 0, batch.kmer, None, None, None, 0, None))
+        return (labels, bmap, offsets) if base_map else (labels, offsets)
+    tables = [up(batch.states.reshape(-1)), up(batch.lengths), None, up(batch.moves), up(batch.event_offsets), up(batch.clipped.reshape(-1)),
+              up(batch.n_raw), offsets]
+    work_bytes = int(lib.cf_label_moves_work_bytes(n_reads, n_events))
+    work = torch.empty(work_bytes, dtype=torch.uint8, device=device)
+    args = [N._p(t) if t is not None else is_f64 for t in tables]
+    with torch.cuda.device(device):
+        N.check(lib.cf_label_moves(None, *args, n_reads, n_events, total, batch.kmer, N._p(labels), N._p(bmap) if base_map else None,
+                                   N._p(work), work_bytes, N.current_stream_ptr(torch, device)))
+    # (tables and work were allocated on the stream the launches run on, so the allocator hands them out again only behind them)
+    return (labels, bmap, offsets) if base_map else (labels, offsets)
+
+
+def load_move_npz(path):
+    """One read with its basecaller's move table: ``raw``, ``event_state`` (``S<k>``, ``U<k>`` or uint8 [E, k]), ``event_move``,
+    ``event_length`` (float32 or float64 seconds, the dtype kept), and optionally ``clipped_start`` / ``clipped_end`` (absent: 0) ->
+    dict(raw, states, lengths, moves, clipped) as ``MoveBatch.from_reads`` takes it.  ``convert.convert_moves`` writes such files."""
+    with np.load(path, allow_pickle=False) as z:
+        for key in ("raw", "event_state", "event_move", "event_length"):
+            if key not in z.files:
+                raise ValueError("%s: no %r (a move .npz holds raw, event_state, event_move and event_length)" % (path, key))
+        clip = lambda key: _as_int(z[key], key) if key in z.files else 0     # noqa: E731
+        return {"raw": np.asarray(z["raw"]).reshape(-1), "states": as_states(z["event_state"]), "lengths": np.asarray(z["event_length"]).reshape(-1),
+                "moves": _as_ints(z["event_move"], "event_move"), "clipped": (clip("clipped_start"), clip("clipped_end"))}
+
+
+def load_labelled_move_npz(path):
+    """(raw[:final], labels) of one move ``.npz``, labelled on the host: what ``train_validate.load_npz`` returns for the ``raw`` +
+    ``base_labels`` file made from it."""
+    read = load_move_npz(path)
+    labels, _ = label_move_read_host(read["states"], read["lengths"], read["moves"], read["clipped"], len(read["raw"]))
+    return read["raw"][:labels.size], labels
+
+
+def moves_from_env(value):
+    """``CATFISH_LABEL_MOVES``: "1" -- the directories hold move files; unset (None), empty or "0" -- they do not."""
+    if value is None or value.strip() in ("", "0"):
+        return False
+    if value.strip() != "1":
+        raise ValueError("CATFISH_LABEL_MOVES must be 1 (or unset), got %r" % (value,))
+    return True
+
+
+def synthetic_move_read(length, seed, stay=0.5, dtype=np.float32):
+    """``synthetic_event_read`` with its event table as a basecaller would have written it: every event split into a head and, with
+    probability ``stay`` each time, further stays; lengths in seconds as ``dtype``; 5-mers around each base.
+    -> (raw float64 [length], states uint8 [E, 5], lengths dtype [E], moves int32 [E])."""
+    raw, bases, samples = synthetic_event_read(length, seed)
+    rng = np.random.default_rng(seed + 7919)
+    padded = np.concatenate((bases[:1], bases[:1], bases, bases[-1:], bases[-1:]))
+    kmers = np.lib.stride_tricks.sliding_window_view(padded, 5)
+    states, lengths, moves = [], [], []
+    for e in range(bases.size):
+        parts = 1
+        while parts < int(samples[e]) and rng.random() < stay:
+            parts += 1
+        cuts = np.sort(rng.choice(np.arange(1, int(samples[e])), size=parts - 1, replace=False)) if parts > 1 else np.zeros(0, np.int64)
+        for q, n in enumerate(np.diff(np.concatenate(([0], cuts, [int(samples[e])])))):
+            states.append(kmers[e])
+            lengths.append(n / float(FREQUENCY))
+            moves.append(0 if q else 1)
+    return raw, np.array(states, dtype=np.uint8), np.array(lengths, dtype=dtype), np.array(moves, dtype=np.int32)

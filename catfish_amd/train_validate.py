@@ -146,9 +146,14 @@ def load_npz(npz_file):
 def npz_loader_from_env():
     """The loader ``main`` reads its ``.npz`` directories with: ``load_npz``, or with ``CATFISH_LABEL_KMER=<odd k>`` set a loader
     of event files (``raw`` + an event table, ``labelling.load_event_npz``) that labels each read with that k -- the same
-    ``(raw, labels)`` the ``raw`` + ``base_labels`` file made from it would give."""
+    ``(raw, labels)`` the ``raw`` + ``base_labels`` file made from it would give; or with ``CATFISH_LABEL_MOVES=1`` a loader of move
+    files (``raw`` + a basecaller's Events table, ``labelling.load_move_npz``).  Both at once is a ValueError."""
     from . import labelling
     kmer = labelling.kmer_from_env(os.environ.get("CATFISH_LABEL_KMER"))
+    if labelling.moves_from_env(os.environ.get("CATFISH_LABEL_MOVES")):
+        if kmer is not None:
+            raise ValueError("CATFISH_LABEL_MOVES and CATFISH_LABEL_KMER exclude each other: a directory holds move files or event files")
+        return labelling.load_labelled_move_npz
     if kmer is None:
         return load_npz
     return lambda npz_file: labelling.load_labelled_event_npz(npz_file, kmer)
@@ -681,6 +686,8 @@ def device_read_db_from_env(npz_files):
             rule = int(rule)
         except ValueError:
             raise ValueError("CATFISH_DEVICE_NEG must be 'positives', 'all' or an integer, got %r" % rule)
+    if labelling.moves_from_env(os.environ.get("CATFISH_LABEL_MOVES")):     # move files, labelled on the card where there is one
+        return DeviceReadDb.from_move_npz(npz_files, seed=0, neg_per_read=None if rule == "all" else rule)
     if kmer is not None:                                         # event files, labelled with that k (on the card where there is one)
         return DeviceReadDb.from_event_npz(npz_files, kmer, seed=0, neg_per_read=None if rule == "all" else rule)
     return DeviceReadDb.from_npz(npz_files, seed=0, neg_per_read=None if rule == "all" else rule)
@@ -726,7 +733,11 @@ def main(argv):
     ``labelling.load_event_npz``; ``python -m catfish_amd.convert --events`` writes them) and every read is labelled with that k-mer
     size on the way in (``npz_loader_from_env``; with CATFISH_DEVICE_VALIDATION=1 or CATFISH_DEVICE_DB=reads on the card,
     ``cf_label_events``) -- the labels a directory of ``raw`` + ``base_labels`` files made from them would hold.  Unset, nothing
-    changes."""
+    changes.
+    CATFISH_LABEL_MOVES=1: both directories hold move files (``raw`` + ``event_state`` / ``event_move`` / ``event_length``,
+    ``labelling.load_move_npz``; ``python -m catfish_amd.convert --moves`` writes them) -- base-called reads that were not
+    resquiggled -- and every read is labelled from its basecaller's move table on the way in (with CATFISH_DEVICE_VALIDATION=1 or
+    CATFISH_DEVICE_DB=reads on the card, ``cf_label_moves``).  Not together with CATFISH_LABEL_KMER.  Unset, nothing changes."""
     args = list(argv[1:])
     if len(args) < 5:
         raise ValueError(_USAGE)
@@ -745,7 +756,9 @@ def main(argv):
     network.initialize_network()
     bases = os.environ.get("CATFISH_VALIDATION_BASES") or "0"
     if bases != "0":                                             # ... which homopolymers by base and length in bases, one JSON line per round
-        if os.environ.get("CATFISH_DEVICE_VALIDATION") != "1" or not (os.environ.get("CATFISH_LABEL_KMER") or "").strip():
+        from . import labelling
+        tables = (os.environ.get("CATFISH_LABEL_KMER") or "").strip() or labelling.moves_from_env(os.environ.get("CATFISH_LABEL_MOVES"))
+        if os.environ.get("CATFISH_DEVICE_VALIDATION") != "1" or not tables:
             raise ValueError("CATFISH_VALIDATION_BASES needs CATFISH_DEVICE_VALIDATION=1 and CATFISH_LABEL_KMER (reads with event tables)")
         network.validation_max_bases = MAX_BASES if bases == "1" else check_max_bases(int(bases))
     loader = npz_loader_from_env()                               # load_npz, or event files labelled on the way in (CATFISH_LABEL_KMER)
@@ -767,7 +780,10 @@ def main(argv):
         from .device_validation import DeviceValidationSet
         if from_events:
             from . import labelling
-            squiggles = DeviceValidationSet.from_event_npz(squiggles, labelling.kmer_from_env(os.environ.get("CATFISH_LABEL_KMER")))
+            if labelling.moves_from_env(os.environ.get("CATFISH_LABEL_MOVES")):
+                squiggles = DeviceValidationSet.from_move_npz(squiggles)
+            else:
+                squiggles = DeviceValidationSet.from_event_npz(squiggles, labelling.kmer_from_env(os.environ.get("CATFISH_LABEL_KMER")))
         else:
             squiggles = DeviceValidationSet.from_npz(squiggles)
         if os.environ.get("CATFISH_VALIDATION_RUNS") == "1":     # ... and the homopolymers found, one JSON line per round

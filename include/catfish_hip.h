@@ -731,6 +731,38 @@ int cf_label_events(cf_model* m, const uint8_t* bases, const int32_t* lengths, c
                     const int64_t* sample_offsets, int64_t n_reads, int64_t n_events, int64_t total, int32_t kmer, uint8_t* labels_out,
                     uint8_t* basemap_out, void* work, int64_t work_bytes, void* stream);
 
+/* Labels from a basecaller's move table (csrc/label_moves.hpp, index and arithmetic rules in csrc/label_moves_rule.hpp;
+ * catfish_amd/labelling.py states the result in numpy -- merge_moves_host, move_classes_host and MoveBatch.label_host are the
+ * definitions).  The reads have NOT been resquiggled: the table is the basecaller's own.  A batch, packed, all device memory: read r
+ * owns events event_offsets[r] .. event_offsets[r + 1] of states (uint8 [n_events][k], the model_state k-mer, bytes below 128),
+ * lengths (float [n_events], or double with lengths_f64 = 1: SECONDS, finite and > 0) and moves (int32 [n_events]);
+ * clipped[2 r] / clipped[2 r + 1] are its clipped_start / clipped_end counted in merged events, n_raw[r] (int64) the samples of its
+ * raw signal, and it owns samples sample_offsets[r] .. sample_offsets[r + 1] of the outputs (its `final` apart, below); total =
+ * sample_offsets[n_reads].  An event with move != 0 -- and the read's first event whatever its move -- is a head; a head and the
+ * events with move == 0 behind it are one merged event.  With M merged events in the read:
+ *   n[j]     = ceil(L * 4000), L = the lengths of merged event j summed left to right from its head in the table's own type (for
+ *              j = 0 the first length counts twice, as the reference's loop has it), the product in that type too
+ *   final    = min(n[0] + .. + n[M - 1], n_raw): the labels the read yields (the caller sizes sample_offsets from it)
+ *   core[j]  = clipped_start <= j < M - clipped_end and the head's k bytes are one byte that is not 'N'
+ *   cls[j]   = some core within two merged events of j, inside the read
+ *   labels_out[first sample of j .. + n[j]), below final  = cls[j]
+ *   basemap_out (NULL ok) there = the k-mer's byte k / 2, bit 7 set on the one sample first + n[j] / 2
+ * work: device scratch of the work-bytes query below, 4-byte aligned: the merged events compacted per read, then M and final per read
+ * as int32 [n_reads][2] at byte 8 * n_events.  Three launches (merge, classes, and cf_label_events' own expansion), asynchronous on
+ * `stream`, capturable; no atomics, sums in a fixed order, so equal inputs give equal bytes.  m may be NULL (the current device is
+ * used).  The tables are not trusted: a sum whose product with 4000 is not a finite number > 0 contributes no samples, counts and
+ * running sums saturate at 2^31 - 1, a read whose event range leaves [0, n_events] has no events, samples that no merged event covers
+ * get label 0 and base 0, a read whose sample range leaves [0, total] is not written, and whatever the tables hold nothing is read
+ * or written outside the buffers.
+ * CF_ERR_INVALID before any launch for a null pointer, a negative size, 2^31 or more events or samples, k outside 1 .. 15,
+ * lengths_f64 other than 0 or 1, misaligned lengths, more than 2^23 workgroups (n_reads + total / 4096) or a work buffer that is too
+ * small; total == 0 is CF_OK with nothing launched. */
+int64_t cf_label_moves_work_bytes(int64_t n_reads, int64_t n_events);
+int cf_label_moves(cf_model* m, const uint8_t* states, const void* lengths, int32_t lengths_f64, const int32_t* moves,
+                   const int64_t* event_offsets, const int32_t* clipped, const int64_t* n_raw, const int64_t* sample_offsets,
+                   int64_t n_reads, int64_t n_events, int64_t total, int32_t k, uint8_t* labels_out, uint8_t* basemap_out, void* work,
+                   int64_t work_bytes, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream) for bench.py's
  * roofline report.  cf_profile_enable(m, N) makes every N-th cf_infer call
  * (N = 1: every call; 0 = off) record events around each of its kernels; cf_profile_read synchronises and returns, for
