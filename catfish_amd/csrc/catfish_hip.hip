@@ -2676,6 +2676,7 @@ extern "C" int cf_opt_step(cf_model* m, int32_t kind, float* params, const float
 #include "tilings.hpp"          // shifted-window voting: cf_retile_windows lays out K tilings of a batch, cf_vote_tilings merges their results
 #include "label_events.hpp"     // labels from event tables: cf_label_events classifies a batch's events and expands them to per-sample labels
 #include "label_moves.hpp"      // labels from a basecaller's move table: cf_label_moves merges stays into their heads, then classifies and expands
+#include "base_votes.hpp"       // per-base calls: cf_base_votes lets every base's samples vote on it and scores the voted bases by base
 
 // ---- profiling ---------------------------------------------------------------------------
 static int prof_collect(cf_model* m) {

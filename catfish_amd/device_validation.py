@@ -508,9 +508,11 @@ class DeviceValidationSet(object):
     """All validation reads of a run, concatenated: ``signal`` float32 [total] (cast once -- the values
     ``pack_validation_windows`` writes into its float32 batch), ``labels`` uint8 [total], ``offsets`` int64 [n_reads + 1],
     ``lengths`` int64 [n_reads]; ``basemap`` uint8 [total] or None -- the per-sample base map of reads that came with their
-    event tables (``labelling.base_map_host``), what ``run_bases_host`` counts bases on."""
+    event tables (``labelling.base_map_host``), what ``run_bases_host`` counts bases on; ``bases`` a ``base_votes.BaseTable`` over the
+    same reads or None -- which samples belong to which base, what a round with ``vote_bases`` votes on (``from_events`` and
+    ``from_moves`` build it)."""
 
-    def __init__(self, signal, labels, offsets, device=None, basemap=None):
+    def __init__(self, signal, labels, offsets, device=None, basemap=None, bases=None):
         self.signal = signal
         self.labels = labels
         self.offsets = offsets
@@ -521,7 +523,8 @@ class DeviceValidationSet(object):
             if basemap.dtype != np.uint8 or basemap.shape != (int(offsets[-1]),):
                 raise ValueError("basemap must be uint8 [%d], got %s %s" % (int(offsets[-1]), basemap.dtype, basemap.shape))
         self.basemap = basemap
-        self._dev = None                 # {"device", "signal", "labels"[, "basemap"]} on the card, uploaded once
+        self.bases = None if bases is None else bases.check_set(offsets)
+        self._dev = None                 # {"device", "signal", "labels"[, "basemap"][, "edges"]} on the card, uploaded once
         self.uploads = 0                 # how often the reads went to a card
         self._binary = None              # every label is 0 or 1 (looked at once)
 
@@ -584,17 +587,19 @@ class DeviceValidationSet(object):
             if len(s) < n:
                 raise ValueError("read %d: the events cover %d samples, the raw signal has %d" % (r, n, len(s)))
             signal[o:o + n] = s[:n]
+        from .base_votes import BaseTable
+        bases = BaseTable.from_events(batch)
         on_card = _label_device(device)
         if on_card is None:
             labels, basemap = batch.label_host(kmer, base_map=True)
-            return cls(signal, labels, offsets, device, basemap)
+            return cls(signal, labels, offsets, device, basemap, bases)
         import torch
         labels_dev, basemap_dev = labelling.label_reads(batch, kmer, on_card, base_map=True)
         back = lambda t: t.cpu().numpy() if t.numel() else np.zeros(0, np.uint8)     # noqa: E731
-        vset = cls(signal, back(labels_dev), offsets, device, back(basemap_dev))
+        vset = cls(signal, back(labels_dev), offsets, device, back(basemap_dev), bases)
         if signal.size:
             vset._dev = {"device": labels_dev.device, "signal": torch.from_numpy(signal).to(labels_dev.device), "labels": labels_dev,
-                         "basemap": basemap_dev}
+                         "basemap": basemap_dev, "edges": torch.from_numpy(bases.edges).to(labels_dev.device)}
             vset.uploads = 1
         return vset
 
@@ -622,17 +627,19 @@ class DeviceValidationSet(object):
             if len(s) < n:
                 raise ValueError("read %d: the labels cover %d samples, the raw signal has %d" % (r, n, len(s)))
             signal[o:o + n] = s[:n]
+        from .base_votes import BaseTable
+        bases = BaseTable.from_moves(batch)
         on_card = _label_device(device)
         if on_card is None:
             labels, basemap = batch.label_host(base_map=True)
-            return cls(signal, labels, offsets, device, basemap)
+            return cls(signal, labels, offsets, device, basemap, bases)
         import torch
         labels_dev, basemap_dev, _offsets = labelling.label_moves(batch, on_card, base_map=True)
         back = lambda t: t.cpu().numpy() if t.numel() else np.zeros(0, np.uint8)     # noqa: E731
-        vset = cls(signal, back(labels_dev), offsets, device, back(basemap_dev))
+        vset = cls(signal, back(labels_dev), offsets, device, back(basemap_dev), bases)
         if signal.size:
             vset._dev = {"device": labels_dev.device, "signal": torch.from_numpy(signal).to(labels_dev.device), "labels": labels_dev,
-                         "basemap": basemap_dev}
+                         "basemap": basemap_dev, "edges": torch.from_numpy(bases.edges).to(labels_dev.device)}
             vset.uploads = 1
         return vset
 
@@ -741,6 +748,8 @@ class DeviceValidationSet(object):
             self._dev = {"device": device, "signal": up(self.signal, np.float32), "labels": up(self.labels, np.uint8)}
             if self.basemap is not None:
                 self._dev["basemap"] = up(self.basemap, np.uint8)
+            if self.bases is not None:
+                self._dev["edges"] = torch.from_numpy(self.bases.edges).to(device)
             self.uploads += 1
         return self._dev["signal"], self._dev["labels"]
 
@@ -751,3 +760,17 @@ class DeviceValidationSet(object):
             raise ValueError("this set has no base map (only reads that come with event tables have one: from_events)")
         self.device_arrays(device)
         return self._dev["basemap"]
+
+    def base_table(self, who="vote_bases"):
+        """The set's ``base_votes.BaseTable``; ValueError (naming the caller) for a set without one or without a base map."""
+        if self.bases is None or self.basemap is None:
+            raise ValueError("%s needs a set with a base table (only reads that come with their event or move tables have one: "
+                             "DeviceValidationSet.from_events / from_moves)" % who)
+        return self.bases
+
+    def device_edges(self, device=None):
+        """The base table's ``edges`` int64 [n_bases + 1] on ``device`` (they go up with ``device_arrays``' one upload); ValueError
+        for a set without a table."""
+        self.base_table("device_edges")
+        self.device_arrays(device)
+        return self._dev["edges"]

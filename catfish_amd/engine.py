@@ -601,6 +601,44 @@ class HipEngine(object):
             (C.c_double * max(k, 1))(*thresholds), k, max_bases, int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()),
             C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
 
+    def base_votes_work_bytes(self, n_bases, n_thresholds):
+        """Bytes of work space ``base_votes_validation`` needs for a set of ``n_bases`` bases and ``n_thresholds`` thresholds."""
+        return int(self._lib.cf_base_votes_work_bytes(int(n_bases), int(n_thresholds)))
+
+    def base_votes_validation(self, probs, labels, basemap, edges, src_first, bounds, length, ranges, total, longest_range, thresholds,
+                              max_bases, confusion_out, runs_out, work, stream=None):
+        """``cf_base_votes``: the samples of every base that lies wholly inside a stretch vote on it, and the voted bases are scored by
+        base -- ``base_votes.vote_host``.  ``probs`` are the round's packed probabilities; ``labels`` / ``basemap`` (uint8) and
+        ``edges`` (int64 [n_bases + 1]) the SET's arrays, read in place; ``src_first`` [n], ``length`` [n], ``bounds`` [n + 1] and
+        ``ranges`` [2 n] (``base_votes.event_ranges``: every a, then every b) int64 CUDA tensors; ``thresholds`` 1..16 host floats.
+        Into ``confusion_out`` (int64 CUDA, ``K * 5 * 2 * 2`` elements) and ``runs_out`` (``K * 2 * 3 * 5 * (max_bases + 1)``); ``work``
+        (uint8 CUDA, at least ``base_votes_work_bytes(n_bases, K)`` bytes, 8-byte aligned) holds the per-base sums (uint64
+        [n_bases]) and states (uint8 [K, n_bases]) afterwards.  Asynchronous on the stream; equal inputs give equal bits."""
+        import torch
+        from . import base_votes
+        from .device_validation import BASE_CLASSES, check_max_bases
+        self._check_validation_tensors("base_votes_validation", [
+            ("probs", probs, torch.float32), ("labels", labels, torch.uint8), ("basemap", basemap, torch.uint8), ("edges", edges, torch.int64),
+            ("src_first", src_first, torch.int64), ("bounds", bounds, torch.int64), ("length", length, torch.int64),
+            ("ranges", ranges, torch.int64), ("confusion_out", confusion_out, torch.int64), ("runs_out", runs_out, torch.int64),
+            ("work", work, torch.uint8)])
+        thresholds = [float(t) for t in thresholds]
+        max_bases = check_max_bases(max_bases)
+        k, n, total = len(thresholds), int(length.numel()), int(total)
+        if int(bounds.numel()) != n + 1 or int(src_first.numel()) != n or int(ranges.numel()) != 2 * n:
+            raise ValueError("base_votes_validation: src_first and length need n entries, bounds n + 1, ranges 2 n")
+        if total < 0 or int(probs.numel()) < total:
+            raise ValueError("base_votes_validation: probs needs %d elements" % total)
+        if int(edges.numel()) < 1:
+            raise ValueError("base_votes_validation: edges needs n_bases + 1 entries")
+        if int(confusion_out.numel()) < k * base_votes.CONFUSION_CELLS or int(runs_out.numel()) < k * 2 * 3 * len(BASE_CLASSES) * (max_bases + 1):
+            raise ValueError("base_votes_validation: confusion_out needs 20 entries per threshold, runs_out 2 * 3 * 5 * (max_bases + 1)")
+        if stream is None:
+            stream = torch.cuda.current_stream(probs.device)
+        # K, the sizes and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
+        base_votes.launch(self._lib, self._handle, probs, total, labels, basemap, edges, int(edges.numel()) - 1, src_first, length, bounds,
+                          ranges, longest_range, thresholds, max_bases, confusion_out, runs_out, work, stream)
+
     def curve_validation(self, probs, y, bounds, length, total, longest, shift, hist_out, stream=None):
         """``cf_validation_curve``: how many samples of label 1 / label 0 / any other label fall into every bin of
         ``device_validation.curve_bin`` at ``shift`` (10 .. 22) -- ``device_validation.curve_host`` -- into ``hist_out`` (int64 CUDA,

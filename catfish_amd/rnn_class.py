@@ -210,7 +210,7 @@ class RNN(object):
         return self.engine.infer_host(np.asarray(windows), return_logits=True)
 
     def score_validation_device(self, vset, selection, thresholds=(0.5,), run_edges=None, curve_shift=None, border_reach=None,
-                                bridge_gap=0, phases=(0,), vote_weight="mean", max_bases=None):
+                                bridge_gap=0, phases=(0,), vote_weight="mean", max_bases=None, vote_bases=None):
         """One validation round on the card: the stretches ``selection`` (``vset.select``) of a
         ``device_validation.DeviceValidationSet`` -> what ``device_validation.score_host`` returns for them, (right int64 [n],
         ce_sum float64 [n], counts int64 [K, 4]).  With ``run_edges`` (a tuple of up to 7 ascending run lengths, possibly empty)
@@ -238,10 +238,16 @@ class RNN(object):
         probabilities and the set's base map, int64 [K, 2, 3, 5, max_bases + 1] -- the same runs per kind, state, base class (A / C / G /
         T / other) and length in bases (``cf_validation_run_bases``, same forward pass, same copy back; it reads the set's base map
         in place, room ``capacity["base_cells"]``, label work space shared with the run states; ``bridge_gap`` applies).  The set must
-        have a base map (``DeviceValidationSet.from_events``; ValueError otherwise).
+        have a base map (``DeviceValidationSet.from_events``; ValueError otherwise).  With ``vote_bases`` (an int in 1 .. 32) two more
+        results come last, ``base_confusion`` int64 [K, 5, 2, 2] and ``base_vote_runs`` int64 [K, 2, 3, 5, vote_bases + 1]: what
+        ``base_votes.vote_host`` returns for the round's probabilities -- the samples of every base that lies wholly inside a stretch
+        vote on it, and the voted bases are counted per class, truth and call, and as runs on the base axis (``cf_base_votes``, same
+        forward pass, same copy back; room ``capacity["vote_cells"]``, per-base work space ``capacity["vote_work"]``; the stretches'
+        base ranges are host work and go up with the selection).  The set must have a base table
+        (``DeviceValidationSet.from_events`` / ``from_moves``; ValueError otherwise).
 
         The tuple is a ``validation_round.RoundResult``: every result is also an attribute -- ``right``, ``ce_sum``, ``counts``,
-        ``run_states``, ``run_borders``, ``curve``, ``run_bases`` -- that is None when it was not asked for.  ``validation_round.RoundSpec`` checks the
+        ``run_states``, ``run_borders``, ``curve``, ``run_bases``, ``base_confusion``, ``base_vote_runs`` -- that is None when it was not asked for.  ``validation_round.RoundSpec`` checks the
         options, ``RoundPlan`` holds the sizes and the layout of the result buffer (host-only, both).
 
         The selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes
@@ -252,7 +258,8 @@ class RNN(object):
         import torch
         from .validation_round import RoundPlan, RoundSpec, grow, walk
         self._require_engine()
-        spec = RoundSpec.of(thresholds, run_edges, border_reach, curve_shift, bridge_gap, phases, vote_weight, max_bases)
+        spec = RoundSpec.of(thresholds, run_edges, border_reach, curve_shift, bridge_gap, phases, vote_weight, max_bases, vote_bases)
+        table = None if spec.vote_bases is None else vset.base_table("score_validation_device: vote_bases")
         if spec.max_bases is not None and vset.basemap is None:
             raise ValueError("score_validation_device: max_bases needs a set with a base map (DeviceValidationSet.from_events)")
         if spec.border_reach is not None and not vset.labels_binary:
@@ -260,7 +267,7 @@ class RNN(object):
         read_index, first, length = vset.check_selection(selection)
         if read_index.size == 0:
             raise ValueError("score_validation_device: no read selected")
-        plan = RoundPlan(spec, length, self.window)
+        plan = RoundPlan(spec, length, self.window, None if table is None else table.n_bases)
         device = torch.device("cuda", self.device)
         signal, labels = vset.device_arrays(device)
         book = self.validation_buffers
@@ -270,8 +277,14 @@ class RNN(object):
             book["threshold_uploads"] += 1
         t["table"][:3 * (plan.n + 1)].copy_(torch.from_numpy(plan.table(vset.offsets, read_index, first).reshape(-1)))
         book["selection_uploads"] += 1
+        edges_d, longest_range = None, 0
+        if table is not None:                                                        # the stretches' base ranges: host work, one more small table
+            from .base_votes import event_ranges
+            a, b = event_ranges(table.edges, vset.offsets[read_index] + first, length)
+            t["vote_ranges"][:2 * plan.n].copy_(torch.from_numpy(np.concatenate((a, b))))
+            edges_d, longest_range = vset.device_edges(device), int((b - a).max())
         out = walk(self.engine, plan, t, book["thresholds"][1], signal, labels, self.window,
-                   None if spec.max_bases is None else vset.device_basemap(device))
+                   None if spec.max_bases is None and table is None else vset.device_basemap(device), edges_d, longest_range)
         back = out.cpu().numpy()                                                     # synchronises the stream
         self.engine.check_error()
         return plan.results(back)
@@ -283,6 +296,19 @@ class RNN(object):
             self._validation_buffers = {"capacity": {}, "tensors": None, "allocations": 0, "thresholds": None, "threshold_uploads": 0,
                                         "selection_uploads": 0}
         return self._validation_buffers
+
+    def call_bases_device(self, vset, threshold=0.5):
+        """The calls in base coordinates: one round over the whole reads of ``vset`` (a ``DeviceValidationSet`` with a base table;
+        ``validation_start="complete"``), ``base_votes.vote_device`` on its probabilities where they lie on the card, then
+        ``base_votes.calls_of`` -> per read a list of ``(first_base_in_read, n_bases, letter or "N", mean probability)``."""
+        from . import base_votes
+        table = vset.base_table("call_bases_device")
+        selection = vset.select(self.window, 0, "complete", max(vset.n_reads, 1))
+        self.score_validation_device(vset, selection, (threshold,))
+        total = int(np.asarray(vset.layout(selection[2], self.window)[0])[-1])
+        sums, state, _confusion, _runs = base_votes.vote_device(self.validation_buffers["tensors"]["probs"][:total], vset, selection,
+                                                               (threshold,), 1, self.window)
+        return base_votes.calls_of(sums.cpu().numpy().view(np.uint64), state[0].cpu().numpy(), table)
 
     def test_network(self, test_x, test_y, read_name, file_path, padding_size, threshold=0.5):
         """rnn_class.py:222-261: accuracy and loss of one padded read + running confusion counters (the per-read

@@ -255,6 +255,9 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     max_bases = getattr(network, "validation_max_bases", None)
     if max_bases is not None:
         extra["max_bases"] = max_bases
+    vote_bases = getattr(network, "validation_vote_bases", None)
+    if vote_bases is not None:
+        extra["vote_bases"] = vote_bases
     bridge_gap = int(getattr(network, "validation_bridge_gap", 0) or 0)
     if bridge_gap:
         extra["bridge_gap"] = bridge_gap
@@ -284,6 +287,14 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
             "step": int(step), "threshold": 0.5, "max_bases": int(max_bases), "classes": list(BASE_CLASSES), "states": list(RUN_STATES),
             "hp_bases": table[0].tolist(), "called_bases": table[1].tolist(), **run_base_rates(table),
             **({"bridge_gap": bridge_gap} if bridge_gap else {})}) + "\n")
+    if vote_bases is not None:
+        # the round's per-base calls: every base voted by its samples, scored by base: one JSON line per round
+        from .base_votes import base_vote_rates
+        confusion, vote_runs = np.asarray(network.validation_base_confusion), np.asarray(network.validation_base_vote_runs)
+        _append(report[:-len(".txt")] + "_base_votes.jsonl", json.dumps({
+            "step": int(step), "threshold": 0.5, "max_bases": int(vote_bases), "classes": list(BASE_CLASSES), "states": list(RUN_STATES),
+            "base_confusion": confusion.tolist(), **base_vote_rates(confusion), "hp_vote_runs": vote_runs[0].tolist(),
+            "called_vote_runs": vote_runs[1].tolist(), **run_base_rates(vote_runs)}) + "\n")
     if curve_shift is not None:
         # the round's whole ROC and precision-recall curves, reduced to their areas and the best F1: one JSON line per round
         curves = curves_from_histogram(network.validation_curve, curve_shift)
@@ -430,7 +441,7 @@ def score_validation_batch(probs32, logits32, y, bounds, tails, threshold=0.5):
 
 
 def validate(network, squiggles, max_seq_length, file_path, validation_start="random", max_number=856, run_edges=None, curve_shift=None,
-             border_reach=None, bridge_gap=0, loader=None, max_bases=None):
+             border_reach=None, bridge_gap=0, loader=None, max_bases=None, vote_bases=None):
     """networks/train_validate.py:188-295 as one packed launch.
 
     The reference pushes every read through ``test_network`` (one ``sess.run`` each, up to 856 per round); windows are
@@ -454,6 +465,10 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     ``max_bases`` (a ``DeviceValidationSet`` with a base map only; an int in 1 .. 32): the round also counts its runs at threshold
     0.5 by base and by length in bases (``device_validation.run_bases_host``, on the card); the [2, 3, 5, max_bases + 1] table is
     left in ``network.validation_run_bases``.
+    ``vote_bases`` (a ``DeviceValidationSet`` with a base table only; an int in 1 .. 32): the round also lets the samples of every
+    base vote on it at threshold 0.5 and scores the voted bases by base (``base_votes.vote_host``, on the card); the [5, 2, 2]
+    confusion table is left in ``network.validation_base_confusion`` and the [2, 3, 5, vote_bases + 1] run table in
+    ``network.validation_base_vote_runs``.
     ``bridge_gap`` (with ``run_edges``, ``border_reach`` or ``max_bases``; 0 .. 49): those tables are counted on the prediction with
     its gaps of at most that many samples bridged (``infer.bridge_gaps``).
     ``loader`` (a list of paths only): what reads a path into ``(raw, labels)`` instead of ``load_npz``.
@@ -472,12 +487,14 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
         n_samples = int(selection[2].sum())
         if n_reads == 0:
             raise ZeroDivisionError("validation selected no read")
-        if run_edges is None and curve_shift is None and border_reach is None and max_bases is None:
+        if run_edges is None and curve_shift is None and border_reach is None and max_bases is None and vote_bases is None:
             right, ce_sum, counts_k = network.score_validation_device(squiggles, selection)
         else:
             extra = {} if border_reach is None else {"border_reach": border_reach}
             if max_bases is not None:
                 extra["max_bases"] = max_bases
+            if vote_bases is not None:
+                extra["vote_bases"] = vote_bases
             if bridge_gap:
                 extra["bridge_gap"] = bridge_gap
             got = network.score_validation_device(squiggles, selection, (0.5,), run_edges=run_edges, curve_shift=curve_shift, **extra)
@@ -490,6 +507,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
                 network.validation_curve = got.curve
             if max_bases is not None:
                 network.validation_run_bases = got.run_bases[0]
+            if vote_bases is not None:
+                network.validation_base_confusion, network.validation_base_vote_runs = got.base_confusion[0], got.base_vote_runs[0]
         acc, loss, counts = squiggles.finish(right, ce_sum, counts_k[0], *squiggles.layout(selection[2], network.window))
     else:
         if run_edges is not None:
@@ -500,6 +519,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
             raise ValueError("validate: border_reach needs a DeviceValidationSet (the borders are compared on the card)")
         if max_bases is not None:
             raise ValueError("validate: max_bases needs a DeviceValidationSet with a base map (the bases are counted on the card)")
+        if vote_bases is not None:
+            raise ValueError("validate: vote_bases needs a DeviceValidationSet with a base table (the bases are voted on the card)")
         signals, labels = select_validation_stretches(squiggles, network.window, max_seq_length, validation_start,
                                                       max_number, **({} if loader is None else {"loader": loader}))
         n_reads = len(signals)
@@ -532,7 +553,7 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
 
 
 def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start="complete", max_number=856, run_edges=None,
-                    border_reach=None, bridge_gap=0, phases=(0,), vote_weight="mean", max_bases=None):
+                    border_reach=None, bridge_gap=0, phases=(0,), vote_weight="mean", max_bases=None, vote_bases=None):
     """The reference's precision / recall sweep (networks/precision_recall_ROC.py:85-100: ``class_from_threshold`` --
     ``p >= t`` -- then ``compute_f1`` per threshold) over a ``DeviceValidationSet``: ONE forward pass, every threshold counted
     from its probabilities on the card.  The stretches are ``validate``'s (same selection, same tail rule for the true
@@ -553,6 +574,11 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     -- per state, base class (A / C / G / T / other) and length in bases how many true and called runs, ``[3][5][max_bases + 1]``
     lists -- and the fields of ``device_validation.run_base_rates``.
 
+    With ``vote_bases`` (an int in 1 .. 32; a set with a base table) every row also carries that threshold's per-base calls
+    (``base_votes.vote_host``: the samples of every base vote on it): ``base_confusion`` -- per base class [truth][called] how many
+    voted bases, a ``[5][2][2]`` list --, the fields of ``base_votes.base_vote_rates`` (per-base precision / recall / F1, overall and
+    per letter) and ``vote_runs``, the fields of ``device_validation.run_base_rates`` over the runs on the base axis.
+
     ``bridge_gap`` (with ``run_edges``, ``border_reach`` or ``max_bases``; 0 .. 49): those tables are those of the prediction
     with its gaps of at most that many samples bridged (``infer.bridge_gaps``); tp / fp / tn / fn stay per-sample counts.
 
@@ -564,7 +590,8 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     voted = {"phases": rule.phases, "vote_weight": rule.vote_weight} if rule.voted else {}      # (0,): the call of before
     if bridge_gap and run_edges is None and border_reach is None and max_bases is None:
         raise ValueError("threshold_sweep: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
-    given = {"run_edges": run_edges, "border_reach": border_reach, "bridge_gap": bridge_gap or None, "max_bases": max_bases}
+    given = {"run_edges": run_edges, "border_reach": border_reach, "bridge_gap": bridge_gap or None, "max_bases": max_bases,
+             "vote_bases": vote_bases}
     given = {key: value for key, value in given.items() if value is not None}                  # nothing given: the call of before
     thresholds = [float(t) for t in thresholds]
     selection = vset.select(network.window, max_seq_length, validation_start, max_number)
@@ -589,6 +616,10 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
         if max_bases is not None:
             rows[-1].update({"hp_bases": got.run_bases[k][0].tolist(), "called_bases": got.run_bases[k][1].tolist(),
                              **run_base_rates(got.run_bases[k])})
+        if vote_bases is not None:
+            from .base_votes import base_vote_rates
+            rows[-1].update({"base_confusion": got.base_confusion[k].tolist(), **base_vote_rates(got.base_confusion[k]),
+                             "vote_runs": run_base_rates(got.base_vote_runs[k])})
     return rows
 
 
@@ -729,6 +760,12 @@ def main(argv):
     ``hp_bases``, ``called_bases`` and the rates of ``device_validation.run_base_rates`` as one JSON line to
     ``<model path>_hp_bases.jsonl``; CATFISH_VALIDATION_BRIDGE applies to it too.  The ``.txt`` reports and the other ``.jsonl``
     files are unchanged.
+    CATFISH_VALIDATION_VOTES=1 (16 length bins) or =<int> (1 .. 32; needs what CATFISH_VALIDATION_BASES needs: only reads that come
+    with their event or move tables have a base table) also lets, per round, the samples of every base vote on it at threshold 0.5
+    (``base_votes.vote_host``, on the card) and appends step, threshold, max_bases, classes, states, ``base_confusion``, the rates of
+    ``base_votes.base_vote_rates`` (per-base precision / recall / F1), ``hp_vote_runs``, ``called_vote_runs`` and the rates of
+    ``device_validation.run_base_rates`` over them as one JSON line to ``<model path>_base_votes.jsonl``.  The ``.txt`` reports and
+    the other ``.jsonl`` files are unchanged.
     CATFISH_LABEL_KMER=<odd k in 1 .. 15>: both directories hold event files (``raw`` + ``event_base`` / ``event_length``,
     ``labelling.load_event_npz``; ``python -m catfish_amd.convert --events`` writes them) and every read is labelled with that k-mer
     size on the way in (``npz_loader_from_env``; with CATFISH_DEVICE_VALIDATION=1 or CATFISH_DEVICE_DB=reads on the card,
@@ -761,6 +798,14 @@ def main(argv):
         if os.environ.get("CATFISH_DEVICE_VALIDATION") != "1" or not tables:
             raise ValueError("CATFISH_VALIDATION_BASES needs CATFISH_DEVICE_VALIDATION=1 and CATFISH_LABEL_KMER (reads with event tables)")
         network.validation_max_bases = MAX_BASES if bases == "1" else check_max_bases(int(bases))
+    votes = os.environ.get("CATFISH_VALIDATION_VOTES") or "0"
+    if votes != "0":                                             # ... and the per-base calls, one JSON line per round
+        from . import labelling
+        tables = (os.environ.get("CATFISH_LABEL_KMER") or "").strip() or labelling.moves_from_env(os.environ.get("CATFISH_LABEL_MOVES"))
+        if os.environ.get("CATFISH_DEVICE_VALIDATION") != "1" or not tables:
+            raise ValueError("CATFISH_VALIDATION_VOTES needs CATFISH_DEVICE_VALIDATION=1 and CATFISH_LABEL_KMER or CATFISH_LABEL_MOVES "
+                             "(reads with event or move tables)")
+        network.validation_vote_bases = MAX_BASES if votes == "1" else check_max_bases(int(votes))
     loader = npz_loader_from_env()                               # load_npz, or event files labelled on the way in (CATFISH_LABEL_KMER)
     from_events = loader is not load_npz
     with_loader = {"loader": loader} if from_events else {}

@@ -763,6 +763,34 @@ int cf_label_moves(cf_model* m, const uint8_t* states, const void* lengths, int3
                    int64_t n_reads, int64_t n_events, int64_t total, int32_t k, uint8_t* labels_out, uint8_t* basemap_out, void* work,
                    int64_t work_bytes, void* stream);
 
+/* Per-base calls (csrc/base_votes.hpp, index and arithmetic rules in csrc/base_votes_rule.hpp; catfish_amd/base_votes.py states the
+ * result in numpy -- vote_host is the definition).  The samples of every base of a round's stretches vote on it, and the voted bases
+ * are scored by base.  All device memory: base e of the set owns samples edges[e] .. edges[e + 1] - 1 (int64 [n_bases + 1], strictly
+ * increasing from 0 to set_total) of labels and basemap (uint8 [set_total], as cf_label_events / cf_label_moves write them); stretch r
+ * is length[r] samples from sample src_first[r] of the set, packed at bounds[r] of probs (float [total]); ranges (int64 [2][n]) holds
+ * the first base at or behind the stretch's start and, n entries on, one past the last base that ends inside it.  With
+ * q(p) = floor(double(p) * 2^32) (NaN and p < 0 count as 0, p > 1 as 1), per voted base of n samples:
+ *   S          = the sum of q over its samples (uint64, exact)
+ *   called_k   = S >= q(float(thresholds[k])) * n;   truth = labels[edges[e]] == 1;   class = A C G T / other of basemap[edges[e]] & 0x7f
+ *   work       = sums uint64 [n_bases] | state uint8 [n_thresholds][n_bases] (bit 0 called, bit 1 truth, bits 2..4 class, bit 7 voted);
+ *                zeroed by the call, so a base no stretch votes holds 0.  >= cf_base_votes_work_bytes(n_bases, n_thresholds), 8-byte aligned
+ *   confusion_out  device int64 [n_thresholds][5][2][2] (class, truth, called) over the voted bases, zeroed and written by the call
+ *   runs_out       device int64 [n_thresholds][2][3][5][max_bases + 1] (kind, state, class, bin), as cf_validation_run_bases lays it out: the
+ *                  maximal streaks of voted bases of ONE stretch with truth (kind 0) or called (kind 1) set, judged against the other
+ *                  bit; bin = min(bases, max_bases); zeroed and written by the call
+ *   thresholds     HOST double [n_thresholds], 1..16 of them;  max_bases 1 .. 32;  longest_range a hint (the widest stretch in bases)
+ * Two launches, asynchronous on `stream`, capturable; integer sums and integer atomics only, so equal inputs give equal bits whatever
+ * the grid.  m may be NULL.  The tables are not trusted: ranges are clamped to [0, n_bases], a base whose samples are not
+ * src <= edges[e] < edges[e + 1] <= src + length, inside the set and inside probs is unvoted (it breaks runs and is counted nowhere),
+ * and nothing is read or written outside the buffers.  Stretches must not share a voted base.
+ * CF_ERR_INVALID before any launch for a null pointer, a negative size, 2^31 or more stretches, samples or bases, n_thresholds outside
+ * 1..16, max_bases outside 1..32 or a work buffer that is too small; n, n_bases, total or set_total == 0 is CF_OK with the tables zeroed. */
+int64_t cf_base_votes_work_bytes(int64_t n_bases, int32_t n_thresholds);
+int cf_base_votes(cf_model* m, const float* probs, int64_t total, const uint8_t* labels, const uint8_t* basemap, int64_t set_total,
+                  const int64_t* edges, int64_t n_bases, const int64_t* src_first, const int64_t* length, const int64_t* bounds,
+                  const int64_t* ranges, int64_t n, int64_t longest_range, const double* thresholds, int32_t n_thresholds, int32_t max_bases,
+                  int64_t* confusion_out, int64_t* runs_out, void* work, int64_t work_bytes, void* stream);
+
 /* Per-kernel device timing (HIP events on the launch stream) for bench.py's
  * roofline report.  cf_profile_enable(m, N) makes every N-th cf_infer call
  * (N = 1: every call; 0 = off) record events around each of its kernels; cf_profile_read synchronises and returns, for
