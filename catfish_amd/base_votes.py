@@ -95,26 +95,12 @@ class BaseTable(object):
         return self
 
     @classmethod
-    def from_events(cls, batch):
-        """The table of a ``labelling.EventBatch``: the running sum of its event lengths."""
-        edges = np.zeros(batch.n_events + 1, dtype=np.int64)
-        np.cumsum(np.asarray(batch.lengths, dtype=np.int64), out=edges[1:])
-        return cls(edges, np.asarray(batch.event_offsets, dtype=np.int64)).check_set(batch.sample_offsets)
+    def from_batch(cls, batch):
+        """The table of a ``labelling.EventBatch`` (a base per event) or ``labelling.MoveBatch`` (a base per merged event that kept a
+        sample): the batch's own ``base_edges``."""
+        return cls(*batch.base_edges()).check_set(batch.sample_offsets)
 
-    @classmethod
-    def from_moves(cls, batch):
-        """The table of a ``labelling.MoveBatch``: the merged events of ``merge_moves_host``, cut at the read's ``final``; merged
-        events left with no sample are dropped."""
-        from .labelling import merge_moves_host
-        edges, base_offsets = [np.zeros(1, dtype=np.int64)], np.zeros(batch.n_reads + 1, dtype=np.int64)
-        for r in range(batch.n_reads):
-            _states, lengths, moves, _clipped, _n_raw = batch.read(r)
-            _heads, n_signals = merge_moves_host(lengths, moves)
-            ends = np.minimum(np.cumsum(n_signals), int(batch.final[r]))
-            ends = ends[np.concatenate(([True], ends[1:] > ends[:-1])) & (ends > 0)]
-            edges.append(ends + int(batch.sample_offsets[r]))
-            base_offsets[r + 1] = base_offsets[r] + ends.size
-        return cls(np.concatenate(edges), base_offsets).check_set(batch.sample_offsets)
+    from_events = from_moves = from_batch
 
 
 def event_ranges(edges, src, length):

@@ -6,8 +6,8 @@
 //   classes  workgroups stride over the reads, a read goes through in pieces of LE_PIECE events.  A piece's bases go to LDS with a
 //            halo of LE_HALO events, clipped to the read (never to the packed array: a run must not continue into the neighbour);
 //            core flags for the piece and two events each side follow, then every thread takes four consecutive events: their
-//            class, and their first sample from a block scan of the lengths (Hillis-Steele over the 256 thread sums in LDS, a
-//            carry from piece to piece).  Both go to the work buffer.
+//            class, and their first sample from a block scan of the lengths (le_block_scan over the 256 thread sums, a carry
+//            from piece to piece).  Both go to the work buffer.
 //   expand   one workgroup per (read, tile of LE_TILE samples) -- le_block_read finds the pair from blockIdx alone.  One binary
 //            search in the read's starts finds the tile's first event; the at most LE_TILE_EVENTS events the tile can meet are
 //            staged in LDS (start, class, base: 24.6 KB).  A thread owns LE_RUN = 16 consecutive samples: one search in LDS for the
@@ -18,6 +18,24 @@
 // Integer only, no atomics: equal inputs give equal bytes.  HBM-bound streaming kernels; no scratch.
 #pragma once
 #include "label_events_rule.hpp"
+
+// The inclusive block scan of one value per thread (Hillis-Steele over the LE_THREADS values in LDS, double-buffered): afterwards
+// s_scan[cur][t] holds the sum of the values of threads 0 .. t, for the cur it returns.  Every thread of the block calls it; it
+// ends in a barrier, and the caller places another before the buffers are written again.  The loop must stay rolled: unrolled,
+// label_event_classes_kernel spills an SGPR.
+template <typename T>
+__device__ inline int le_block_scan(T (*s_scan)[LE_THREADS], int tid, T mine) {
+    s_scan[0][tid] = mine;
+    __syncthreads();
+    int cur = 0;
+#pragma unroll 1
+    for (int step = 1; step < LE_THREADS; step <<= 1) {
+        s_scan[cur ^ 1][tid] = s_scan[cur][tid] + (tid >= step ? s_scan[cur][tid - step] : 0);
+        cur ^= 1;
+        __syncthreads();
+    }
+    return cur;
+}
 
 __global__ __launch_bounds__(LE_THREADS) void label_event_classes_kernel(const uint8_t* __restrict__ bases, const int32_t* __restrict__ lengths,
                                                                          const int64_t* __restrict__ event_offsets,
@@ -51,15 +69,7 @@ __global__ __launch_bounds__(LE_THREADS) void label_event_classes_kernel(const u
                 before[q] = sum;
                 sum += e < ev.n ? le_len(lengths[ev.first + e]) : 0;
             }
-            s_scan[0][tid] = sum;
-            __syncthreads();
-            int cur = 0;
-#pragma unroll 1
-            for (int step = 1; step < LE_THREADS; step <<= 1) {             // (unrolled, the kernel spills an SGPR)
-                s_scan[cur ^ 1][tid] = s_scan[cur][tid] + (tid >= step ? s_scan[cur][tid - step] : 0);
-                cur ^= 1;
-                __syncthreads();
-            }
+            const int cur = le_block_scan(s_scan, tid, sum);
             const int64_t mine = carry + s_scan[cur][tid] - sum;                  // 1024 lengths below 2^31 and a carry below 2^31
 #pragma unroll
             for (int q = 0; q < LE_PER_THREAD; ++q) {

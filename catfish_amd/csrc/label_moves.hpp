@@ -6,8 +6,8 @@
 // merged events, repeated per sample and cut at the end of the raw signal.
 //
 //   merge    workgroups stride over the reads, a read goes through in pieces of LM_PIECE events, four consecutive ones per thread.
-//            Head flags go through a block scan (Hillis-Steele over the 256 thread counts in LDS, a carry from piece to piece): that
-//            is the merged index.  The thread that owns a head walks its stays in global memory -- across piece borders, never
+//            Head flags go through a block scan (le_block_scan of csrc/label_events.hpp over the 256 thread counts, a carry from
+//            piece to piece): that is the merged index.  The thread that owns a head walks its stays in global memory -- across piece borders, never
 //            across the read -- summing the lengths in the table's own type, left to right, one rounding per addition.  It writes
 //            the sample count, the uniform-k-mer flag and the k-mer's middle byte to the read's slot of the compacted tables; the
 //            slots behind the M-th are zeroed, and M goes to counts[2 r].
@@ -44,15 +44,7 @@ __global__ __launch_bounds__(LM_THREADS) void label_moves_merge_kernel(const uin
             for (int q = 0; q < LM_PER_THREAD; ++q)
                 heads |= (lm_is_head(moves_r, p0 + LM_PER_THREAD * tid + q, ev.n) ? 1u : 0u) << q;
             const int32_t mine = __popc(heads);
-            s_scan[0][tid] = mine;
-            __syncthreads();
-            int cur = 0;
-#pragma unroll 1
-            for (int step = 1; step < LM_THREADS; step <<= 1) {
-                s_scan[cur ^ 1][tid] = s_scan[cur][tid] + (tid >= step ? s_scan[cur][tid - step] : 0);
-                cur ^= 1;
-                __syncthreads();
-            }
+            const int cur = le_block_scan(s_scan, tid, mine);
             int64_t j = carry + s_scan[cur][tid] - mine;
 #pragma unroll 1
             for (int q = 0; q < LM_PER_THREAD; ++q) {
@@ -107,15 +99,7 @@ __global__ __launch_bounds__(LM_THREADS) void label_moves_classes_kernel(const i
                 before[q] = sum;
                 sum += e < ev.n ? le_len(mlen[ev.first + e]) : 0;
             }
-            s_scan[0][tid] = sum;
-            __syncthreads();
-            int cur = 0;
-#pragma unroll 1
-            for (int step = 1; step < LM_THREADS; step <<= 1) {
-                s_scan[cur ^ 1][tid] = s_scan[cur][tid] + (tid >= step ? s_scan[cur][tid - step] : 0);
-                cur ^= 1;
-                __syncthreads();
-            }
+            const int cur = le_block_scan(s_scan, tid, sum);
             const int64_t mine = carry + s_scan[cur][tid] - sum;                  // 1024 counts below 2^31 and a carry below 2^31
 #pragma unroll
             for (int q = 0; q < LM_PER_THREAD; ++q) {

@@ -332,20 +332,22 @@ class DeviceReadDb(DeviceFedDb):
         return cls(v.signal, v.labels, v.offsets, seed, lessen, neg_per_read)
 
     @classmethod
-    def from_event_npz(cls, paths, kmer=5, seed=0, lessen=1, neg_per_read=None, device=None):
-        """The reads of ``paths`` (event ``.npz`` files: ``raw`` + an event table, ``labelling.load_event_npz``), in that order,
-        labelled with k-mer size ``kmer`` through ``DeviceValidationSet.from_event_npz`` (on the card where there is one)."""
+    def from_source(cls, paths, source, seed=0, lessen=1, neg_per_read=None, device=None):
+        """The reads of ``paths``, in that order, as ``source`` (a ``labelling.LabelSource``) says they are stored, labelled through
+        ``DeviceValidationSet.from_source`` (event and move files on the card where there is one)."""
         from .device_validation import DeviceValidationSet
-        v = DeviceValidationSet.from_event_npz(paths, kmer, device)
+        v = DeviceValidationSet.from_source(paths, source, device)
         return cls(v.signal, v.labels, v.offsets, seed, lessen, neg_per_read)
 
     @classmethod
+    def from_event_npz(cls, paths, kmer=5, seed=0, lessen=1, neg_per_read=None, device=None):
+        from .labelling import LabelSource
+        return cls.from_source(paths, LabelSource("events", kmer), seed, lessen, neg_per_read, device)
+
+    @classmethod
     def from_move_npz(cls, paths, seed=0, lessen=1, neg_per_read=None, device=None):
-        """The reads of ``paths`` (move ``.npz`` files: ``raw`` + a basecaller's Events table, ``labelling.load_move_npz``), in that
-        order, labelled through ``DeviceValidationSet.from_move_npz`` (on the card where there is one); ``raw[:final]`` is kept."""
-        from .device_validation import DeviceValidationSet
-        v = DeviceValidationSet.from_move_npz(paths, device)
-        return cls(v.signal, v.labels, v.offsets, seed, lessen, neg_per_read)
+        from .labelling import LabelSource
+        return cls.from_source(paths, LabelSource("moves"), seed, lessen, neg_per_read, device)
 
     # ------------------------------------------------------------------ the tables
     def host_tables(self):

@@ -490,27 +490,13 @@ def finish(right, ce_sum, counts_k, bounds, tails):
     return acc, loss.astype(np.float32), (tp, fp, tn - int(np.sum(tails)), fn)
 
 
-def _label_device(device):
-    """Where ``from_events`` makes the labels: the CUDA device to use, or None for the host.  An explicit CUDA device is taken at its
-    word (no GPU or no library is then an error of ``labelling.label_reads``); None means the card where there is one to use."""
-    if device is not None and str(device).split(":")[0] != "cuda":
-        return None
-    import torch
-    if device is None:
-        from . import _native
-        import os
-        if not torch.cuda.is_available() or not os.path.exists(_native.DEFAULT_LIB_PATH):
-            return None
-    return torch.device("cuda" if device is None else device)
-
-
 class DeviceValidationSet(object):
     """All validation reads of a run, concatenated: ``signal`` float32 [total] (cast once -- the values
     ``pack_validation_windows`` writes into its float32 batch), ``labels`` uint8 [total], ``offsets`` int64 [n_reads + 1],
     ``lengths`` int64 [n_reads]; ``basemap`` uint8 [total] or None -- the per-sample base map of reads that came with their
     event tables (``labelling.base_map_host``), what ``run_bases_host`` counts bases on; ``bases`` a ``base_votes.BaseTable`` over the
-    same reads or None -- which samples belong to which base, what a round with ``vote_bases`` votes on (``from_events`` and
-    ``from_moves`` build it)."""
+    same reads or None -- which samples belong to which base, what a round with ``vote_bases`` votes on (``from_tables``
+    builds it)."""
 
     def __init__(self, signal, labels, offsets, device=None, basemap=None, bases=None):
         self.signal = signal
@@ -568,58 +554,20 @@ class DeviceValidationSet(object):
         return cls.from_arrays(signals, labels, device)
 
     @classmethod
-    def from_events(cls, signals, batch, kmer=5, device=None):
-        """Reads that come with their event tables instead of labels: ``signals[r]`` is read r's raw signal (its first
-        ``final_signal`` samples are kept, as the reference's collect_examples.py saves them) and ``batch`` a
-        ``labelling.EventBatch`` over the same reads.  On a GPU (``device`` a CUDA device, or None where one is there and the
-        native library is built) ``cf_label_events`` makes the labels and the base map: signal, labels and base map are the set's
-        device arrays from then on (one upload) and labels and base map are copied back once for ``self.labels`` /
-        ``self.basemap``.  Otherwise (``device="cpu"``, or no GPU) ``batch.label_host`` makes them -- the same bytes."""
+    def from_tables(cls, signals, batch, device=None, kmer=5):
+        """Reads that come with their tables instead of labels: ``signals[r]`` is read r's raw signal (its first ``final_signal``
+        samples are kept, as the reference's collect_examples.py saves them) and ``batch`` a ``labelling.EventBatch`` (resquiggled
+        reads, labelled with k-mer size ``kmer``) or ``labelling.MoveBatch`` (base-called reads; ``n_raw`` must not exceed the
+        signals' lengths) over the same reads.  On a GPU (``labelling.label_device``: ``device`` a CUDA device, or None where one is
+        there and the native library is built) the batch's entry point makes the labels and the base map: signal, labels and base
+        map are the set's device arrays from then on (one upload) and labels and base map are copied back once for ``self.labels``
+        / ``self.basemap``.  Otherwise (``device="cpu"``, or no GPU) ``batch.label_host`` makes them -- the same bytes."""
         from . import labelling
-        kmer = labelling.check_kmer(kmer)
-        signals = [np.asarray(s).reshape(-1) for s in signals]
-        if len(signals) != batch.n_reads:
-            raise ValueError("%d signals but %d event tables" % (len(signals), batch.n_reads))
-        offsets = np.asarray(batch.sample_offsets, dtype=np.int64).copy()
-        signal = np.zeros(int(offsets[-1]), dtype=np.float32)
-        for r, s in enumerate(signals):
-            o, n = int(offsets[r]), int(offsets[r + 1] - offsets[r])
-            if len(s) < n:
-                raise ValueError("read %d: the events cover %d samples, the raw signal has %d" % (r, n, len(s)))
-            signal[o:o + n] = s[:n]
         from .base_votes import BaseTable
-        bases = BaseTable.from_events(batch)
-        on_card = _label_device(device)
-        if on_card is None:
-            labels, basemap = batch.label_host(kmer, base_map=True)
-            return cls(signal, labels, offsets, device, basemap, bases)
-        import torch
-        labels_dev, basemap_dev = labelling.label_reads(batch, kmer, on_card, base_map=True)
-        back = lambda t: t.cpu().numpy() if t.numel() else np.zeros(0, np.uint8)     # noqa: E731
-        vset = cls(signal, back(labels_dev), offsets, device, back(basemap_dev), bases)
-        if signal.size:
-            vset._dev = {"device": labels_dev.device, "signal": torch.from_numpy(signal).to(labels_dev.device), "labels": labels_dev,
-                         "basemap": basemap_dev, "edges": torch.from_numpy(bases.edges).to(labels_dev.device)}
-            vset.uploads = 1
-        return vset
-
-    @classmethod
-    def from_event_npz(cls, paths, kmer=5, device=None):
-        """The reads of ``paths`` (event ``.npz`` files, ``labelling.load_event_npz``), in that order, through ``from_events``."""
-        from . import labelling
-        reads = [labelling.load_event_npz(path) for path in paths]
-        return cls.from_events([read["raw"] for read in reads], labelling.EventBatch.from_reads(reads), kmer, device)
-
-    @classmethod
-    def from_moves(cls, signals, batch, device=None):
-        """Base-called reads that were not resquiggled: ``signals[r]`` is read r's raw signal (its first ``final`` samples are kept)
-        and ``batch`` a ``labelling.MoveBatch`` over the same reads, whose ``n_raw`` must not exceed the signals' lengths.  As
-        ``from_events``: on a GPU ``cf_label_moves`` makes the labels and the base map and they stay on the card; otherwise
-        ``batch.label_host`` makes them -- the same bytes."""
-        from . import labelling
+        kmer = batch.k_of(kmer)
         signals = [np.asarray(s).reshape(-1) for s in signals]
         if len(signals) != batch.n_reads:
-            raise ValueError("%d signals but %d move tables" % (len(signals), batch.n_reads))
+            raise ValueError("%d signals but %d reads with tables" % (len(signals), batch.n_reads))
         offsets = np.asarray(batch.sample_offsets, dtype=np.int64).copy()
         signal = np.zeros(int(offsets[-1]), dtype=np.float32)
         for r, s in enumerate(signals):
@@ -627,28 +575,47 @@ class DeviceValidationSet(object):
             if len(s) < n:
                 raise ValueError("read %d: the labels cover %d samples, the raw signal has %d" % (r, n, len(s)))
             signal[o:o + n] = s[:n]
-        from .base_votes import BaseTable
-        bases = BaseTable.from_moves(batch)
-        on_card = _label_device(device)
+        bases = BaseTable.from_batch(batch)
+        on_card = labelling.label_device(device)
         if on_card is None:
-            labels, basemap = batch.label_host(base_map=True)
+            labels, basemap = batch.label_host(kmer, base_map=True)
             return cls(signal, labels, offsets, device, basemap, bases)
         import torch
-        labels_dev, basemap_dev, _offsets = labelling.label_moves(batch, on_card, base_map=True)
+        labels_dev, basemap_dev, _tables = labelling.label_on_card(batch, kmer, on_card, base_map=True)
         back = lambda t: t.cpu().numpy() if t.numel() else np.zeros(0, np.uint8)     # noqa: E731
         vset = cls(signal, back(labels_dev), offsets, device, back(basemap_dev), bases)
         if signal.size:
-            vset._dev = {"device": labels_dev.device, "signal": torch.from_numpy(signal).to(labels_dev.device), "labels": labels_dev,
-                         "basemap": basemap_dev, "edges": torch.from_numpy(bases.edges).to(labels_dev.device)}
+            vset._dev = {"device": on_card, "signal": torch.from_numpy(signal).to(on_card), "labels": labels_dev, "basemap": basemap_dev,
+                         "edges": torch.from_numpy(bases.edges).to(on_card)}
             vset.uploads = 1
         return vset
 
     @classmethod
+    def from_source(cls, paths, source, device=None):
+        """The reads of ``paths``, in that order, as ``source`` (a ``labelling.LabelSource``) says they are stored: labelled reads
+        through ``from_npz``, event and move files (``source.load``) through ``from_tables``."""
+        if not source.has_tables:
+            return cls.from_npz(paths, device=device)
+        reads = [source.load(path) for path in paths]
+        return cls.from_tables([read["raw"] for read in reads], source.batch(reads), device, source.kmer)
+
+    @classmethod
+    def from_events(cls, signals, batch, kmer=5, device=None):
+        return cls.from_tables(signals, batch, device, kmer)
+
+    @classmethod
+    def from_moves(cls, signals, batch, device=None):
+        return cls.from_tables(signals, batch, device)
+
+    @classmethod
+    def from_event_npz(cls, paths, kmer=5, device=None):
+        from .labelling import LabelSource
+        return cls.from_source(paths, LabelSource("events", kmer), device)
+
+    @classmethod
     def from_move_npz(cls, paths, device=None):
-        """The reads of ``paths`` (move ``.npz`` files, ``labelling.load_move_npz``), in that order, through ``from_moves``."""
-        from . import labelling
-        reads = [labelling.load_move_npz(path) for path in paths]
-        return cls.from_moves([read["raw"] for read in reads], labelling.MoveBatch.from_reads(reads), device)
+        from .labelling import LabelSource
+        return cls.from_source(paths, LabelSource("moves"), device)
 
     @property
     def n_reads(self):

@@ -17,6 +17,8 @@ ValueError (``check_read``); tests/golden/label_events_golden.npz holds the refe
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 MAX_KMER = 15
@@ -175,16 +177,54 @@ def _read_fields(read):
     return read + ((0, 0), None, None)[len(read) - 2:]
 
 
-class EventBatch(object):
-    """Many reads' event tables, packed: ``bases`` uint8 [n_events], ``lengths`` int32 [n_events], ``event_offsets`` int64
-    [n_reads + 1], ``clipped`` int32 [n_reads, 2], ``sample_offsets`` int64 [n_reads + 1] -- what ``cf_label_events`` takes."""
-
-    def __init__(self, bases, lengths, event_offsets, clipped, sample_offsets):
-        self.bases, self.lengths, self.event_offsets, self.clipped, self.sample_offsets = bases, lengths, event_offsets, clipped, sample_offsets
+class TableBatch(object):
+    """What ``EventBatch`` and ``MoveBatch`` share, and what the code that labels either asks of them: ``ENTRY`` and ``WORK_BYTES``, the
+    names of its entry point in the library and of that entry point's work-buffer query; ``device_tables(up)``, the entry point's table
+    arguments in its order (``up`` puts an array on the card; an int stays an int); ``work_args()``, the query's arguments;
+    ``k_of(kmer)``, the k the labels are made with; ``read_labels_host(r, kmer, base_map)``, the definition for one read; and
+    ``base_edges()``, where the bases begin -- ``(edges int64 [n_bases + 1], base_offsets int64 [n_reads + 1])`` as
+    ``base_votes.BaseTable`` takes them."""
 
     n_reads = property(lambda self: len(self.event_offsets) - 1)
     n_events = property(lambda self: int(self.event_offsets[-1]))
     total = property(lambda self: int(self.sample_offsets[-1]))
+
+    def label_host(self, kmer=5, base_map=False):
+        """labels uint8 [total] of the whole batch (and the base map with ``base_map=True``): the definition, read by read.  A
+        ``MoveBatch`` brings its k-mers with it and does not look at ``kmer`` (``k_of``)."""
+        kmer = self.k_of(kmer)
+        labels = np.zeros(self.total, dtype=np.uint8)
+        bmap = np.zeros(self.total, dtype=np.uint8) if base_map else None
+        for r in range(self.n_reads):
+            lab, bm = self.read_labels_host(r, kmer, base_map)
+            o = int(self.sample_offsets[r])
+            labels[o:o + lab.size] = lab
+            if base_map:
+                bmap[o:o + bm.size] = bm
+        return (labels, bmap) if base_map else labels
+
+
+class EventBatch(TableBatch):
+    """Many reads' event tables, packed: ``bases`` uint8 [n_events], ``lengths`` int32 [n_events], ``event_offsets`` int64
+    [n_reads + 1], ``clipped`` int32 [n_reads, 2], ``sample_offsets`` int64 [n_reads + 1] -- what ``cf_label_events`` takes."""
+    ENTRY, WORK_BYTES = "cf_label_events", "cf_label_events_work_bytes"
+
+    def __init__(self, bases, lengths, event_offsets, clipped, sample_offsets):
+        self.bases, self.lengths, self.event_offsets, self.clipped, self.sample_offsets = bases, lengths, event_offsets, clipped, sample_offsets
+
+    k_of = staticmethod(check_kmer)
+
+    def device_tables(self, up):
+        return [up(self.bases), up(self.lengths), up(self.event_offsets), up(self.clipped.reshape(-1)), up(self.sample_offsets)]
+
+    def work_args(self):
+        return (self.n_events,)
+
+    def base_edges(self):
+        """A base per event: the running sum of the event lengths."""
+        edges = np.zeros(self.n_events + 1, dtype=np.int64)
+        np.cumsum(np.asarray(self.lengths, dtype=np.int64), out=edges[1:])
+        return edges, np.asarray(self.event_offsets, dtype=np.int64)
 
     @classmethod
     def from_reads(cls, reads):
@@ -210,48 +250,56 @@ class EventBatch(object):
         a, b = int(self.event_offsets[r]), int(self.event_offsets[r + 1])
         return self.bases[a:b], self.lengths[a:b], (int(self.clipped[r, 0]), int(self.clipped[r, 1]))
 
-    def label_host(self, kmer=5, base_map=False):
-        """labels uint8 [total] of the whole batch (and the base map with ``base_map=True``): ``label_read_host`` read by read."""
-        kmer = check_kmer(kmer)
-        labels = np.zeros(self.total, dtype=np.uint8)
-        bmap = np.zeros(self.total, dtype=np.uint8) if base_map else None
-        for r in range(self.n_reads):
-            bases, lengths, (cs, ce) = self.read(r)
-            o = int(self.sample_offsets[r])
-            lab = expand_events_host(event_classes_host(bases, cs, ce, kmer), lengths)
-            labels[o:o + lab.size] = lab
-            if base_map:
-                bmap[o:o + lab.size] = base_map_host(bases, lengths)
-        return (labels, bmap) if base_map else labels
+    def read_labels_host(self, r, kmer, base_map):
+        bases, lengths, (cs, ce) = self.read(r)
+        return expand_events_host(event_classes_host(bases, cs, ce, kmer), lengths), base_map_host(bases, lengths) if base_map else None
+
+
+def label_device(device, who=None):
+    """The one decision "card or host": the CUDA device (with its index) the labels are made on, or None for the host route.
+    ``who`` names a caller that has no host route (``label_reads``, ``label_moves``): ``device`` None is then the current GPU and
+    anything but a CUDA device a ValueError.  Without ``who`` (``DeviceValidationSet.from_tables``) ``device`` None means the card
+    where there is one to use -- a GPU and the built library -- and a device that is not CUDA means the host.  An explicit CUDA device
+    is taken at its word: no GPU or no library is then an error of the launch, never a fall-back."""
+    if device is not None and str(device).split(":")[0] != "cuda":
+        if who is None:
+            return None
+        raise ValueError("%s: the labels are made on a GPU (%s.label_host is the host route)" % who)
+    import torch
+    if device is None and who is None:
+        from . import _native
+        if not torch.cuda.is_available() or not os.path.exists(_native.DEFAULT_LIB_PATH):
+            return None
+    device = torch.device("cuda" if device is None else device)
+    return torch.device("cuda", torch.cuda.current_device()) if device.index is None else device
+
+
+def label_on_card(batch, kmer, device, base_map):
+    """Either kind of batch through its entry point, on ``device`` (a ``label_device``): (labels, basemap or None, the tables on the
+    card) -- uint8 tensors [total] with ``batch.label_host``'s bytes.  Asynchronous on torch's current stream."""
+    import torch
+    from . import _native as N
+    lib = N.lib()
+    k, total = batch.k_of(kmer), batch.total
+    labels = torch.empty(total, dtype=torch.uint8, device=device)
+    bmap = torch.empty(total, dtype=torch.uint8, device=device) if base_map else None
+    tables = batch.device_tables(lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device))
+    work_bytes = int(getattr(lib, batch.WORK_BYTES)(*batch.work_args())) if total else 0
+    work = torch.empty(work_bytes, dtype=torch.uint8, device=device)
+    p = lambda t: N._p(t) if total and t is not None else None     # noqa: E731   (an empty batch is a call without pointers)
+    with torch.cuda.device(device):
+        N.check(getattr(lib, batch.ENTRY)(None, *[t if isinstance(t, int) else p(t) for t in tables], batch.n_reads, batch.n_events, total, k,
+                                          p(labels), p(bmap), p(work), work_bytes, N.current_stream_ptr(torch, device) if total else None))
+    # (tables and work were allocated on the stream the launches run on, so the allocator hands them out again only behind them)
+    return labels, bmap, tables
 
 
 def label_reads(batch, kmer=5, device=None, base_map=False):
     """The batch's labels on the card through ``cf_label_events``: a torch uint8 tensor [total] on ``device`` (default: the current
     GPU), or (labels, basemap) with ``base_map=True`` -- ``EventBatch.label_host``'s bytes.  Asynchronous on torch's current stream.
     No GPU or no native library is an error: there is no fall-back here."""
-    import torch
-    from . import _native as N
     kmer = check_kmer(kmer)
-    device = torch.device("cuda" if device is None else device)
-    if device.type != "cuda":
-        raise ValueError("label_reads: the labels are made on a GPU (EventBatch.label_host is the host route)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    lib = N.lib()
-    total, n_events = batch.total, batch.n_events
-    labels = torch.empty(total, dtype=torch.uint8, device=device)
-    bmap = torch.empty(total, dtype=torch.uint8, device=device) if base_map else None
-    if total == 0:
-        N.check(lib.cf_label_events(None, None, None, None, None, None, batch.n_reads, n_events, 0, kmer, None, None, None, 0, None))
-        return (labels, bmap) if base_map else labels
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)     # noqa: E731
-    tables = [up(batch.bases), up(batch.lengths), up(batch.event_offsets), up(batch.clipped.reshape(-1)), up(batch.sample_offsets)]
-    work_bytes = int(lib.cf_label_events_work_bytes(n_events))
-    work = torch.empty(work_bytes, dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        N.check(lib.cf_label_events(None, *[N._p(t) for t in tables], batch.n_reads, n_events, total, kmer, N._p(labels),
-                                    N._p(bmap) if base_map else None, N._p(work), work_bytes, N.current_stream_ptr(torch, device)))
-    # (tables and work were allocated on the stream the launches run on, so the allocator hands them out again only behind them)
+    labels, bmap, _tables = label_on_card(batch, kmer, label_device(device, ("label_reads", "EventBatch")), base_map)
     return (labels, bmap) if base_map else labels
 
 
@@ -469,11 +517,12 @@ def _move_fields(read):
     return read + ((0, 0), None)[len(read) - 3:]
 
 
-class MoveBatch(object):
+class MoveBatch(TableBatch):
     """Many reads' move tables, packed -- what ``cf_label_moves`` takes: ``states`` uint8 [n_events, k], ``lengths`` float32 or
     float64 [n_events] (seconds, one dtype per batch), ``moves`` int32 [n_events], ``event_offsets`` int64 [n_reads + 1],
     ``clipped`` int32 [n_reads, 2], ``n_raw`` int64 [n_reads]; and what the host's own merge found: ``final`` int64 [n_reads]
     (labels per read), ``merged`` int64 [n_reads] (M) and ``sample_offsets`` int64 [n_reads + 1], the exclusive sum of ``final``."""
+    ENTRY, WORK_BYTES = "cf_label_moves", "cf_label_moves_work_bytes"
 
     def __init__(self, states, lengths, moves, event_offsets, clipped, n_raw, final, merged):
         self.states, self.lengths, self.moves, self.event_offsets, self.clipped, self.n_raw = states, lengths, moves, event_offsets, clipped, n_raw
@@ -481,10 +530,30 @@ class MoveBatch(object):
         self.sample_offsets = np.zeros(len(final) + 1, dtype=np.int64)
         np.cumsum(final, out=self.sample_offsets[1:])
 
-    n_reads = property(lambda self: len(self.event_offsets) - 1)
-    n_events = property(lambda self: int(self.event_offsets[-1]))
-    total = property(lambda self: int(self.sample_offsets[-1]))
     kmer = property(lambda self: int(self.states.shape[1]))
+
+    def k_of(self, kmer=None):
+        """The k-mers come with the events: whatever k the caller has in mind, the labels are made with the tables' own."""
+        return self.kmer
+
+    def device_tables(self, up):
+        return [up(self.states.reshape(-1)), up(self.lengths), int(self.lengths.dtype == np.float64), up(self.moves), up(self.event_offsets),
+                up(self.clipped.reshape(-1)), up(self.n_raw), up(self.sample_offsets)]
+
+    def work_args(self):
+        return (self.n_reads, self.n_events)
+
+    def base_edges(self):
+        """A base per merged event of ``merge_moves_host``, cut at the read's ``final``; merged events left with no sample are dropped."""
+        edges, base_offsets = [np.zeros(1, dtype=np.int64)], np.zeros(self.n_reads + 1, dtype=np.int64)
+        for r in range(self.n_reads):
+            _states, lengths, moves, _clipped, _n_raw = self.read(r)
+            _heads, n_signals = merge_moves_host(lengths, moves)
+            ends = np.minimum(np.cumsum(n_signals), int(self.final[r]))
+            ends = ends[np.concatenate(([True], ends[1:] > ends[:-1])) & (ends > 0)]
+            edges.append(ends + int(self.sample_offsets[r]))
+            base_offsets[r + 1] = base_offsets[r] + ends.size
+        return np.concatenate(edges), base_offsets
 
     @classmethod
     def from_reads(cls, reads):
@@ -513,19 +582,10 @@ class MoveBatch(object):
         a, b = int(self.event_offsets[r]), int(self.event_offsets[r + 1])
         return self.states[a:b], self.lengths[a:b], self.moves[a:b], (int(self.clipped[r, 0]), int(self.clipped[r, 1])), int(self.n_raw[r])
 
-    def label_host(self, base_map=False):
-        """labels uint8 [total] of the whole batch (and the base map with ``base_map=True``): the definition, read by read."""
-        labels = np.zeros(self.total, dtype=np.uint8)
-        bmap = np.zeros(self.total, dtype=np.uint8) if base_map else None
-        for r in range(self.n_reads):
-            states, lengths, moves, clipped, n_raw = self.read(r)
-            heads, n_signals = merge_moves_host(lengths, moves)
-            lab, bm = _label_merged(states, heads, n_signals, clipped, min(int(n_signals.sum()), n_raw))
-            o = int(self.sample_offsets[r])
-            labels[o:o + lab.size] = lab
-            if base_map:
-                bmap[o:o + bm.size] = bm
-        return (labels, bmap) if base_map else labels
+    def read_labels_host(self, r, kmer, base_map):
+        states, lengths, moves, clipped, n_raw = self.read(r)
+        heads, n_signals = merge_moves_host(lengths, moves)
+        return _label_merged(states, heads, n_signals, clipped, min(int(n_signals.sum()), n_raw))
 
 
 def label_moves(batch, device=None, base_map=False):
@@ -533,33 +593,8 @@ def label_moves(batch, device=None, base_map=False):
     ``base_map=True`` -- torch tensors on ``device`` (default: the current GPU): uint8 [sum(final)] with ``MoveBatch.label_host``'s
     bytes, and the int64 [n_reads + 1] offsets of the reads in them.  Asynchronous on torch's current stream.  No GPU or no native
     library is an error: there is no fall-back here."""
-    import torch
-    from . import _native as N
-    device = torch.device("cuda" if device is None else device)
-    if device.type != "cuda":
-        raise ValueError("label_moves: the labels are made on a GPU (MoveBatch.label_host is the host route)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    lib = N.lib()
-    total, n_events, n_reads = batch.total, batch.n_events, batch.n_reads
-    is_f64 = int(batch.lengths.dtype == np.float64)
-    labels = torch.empty(total, dtype=torch.uint8, device=device)
-    bmap = torch.empty(total, dtype=torch.uint8, device=device) if base_map else None
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)     # noqa: E731
-    offsets = up(batch.sample_offsets)
-    if total == 0:
-        N.check(lib.cf_label_moves(None, None, None, is_f64, None, None, None, None, None, n_reads, n_events, 0, batch.kmer, None, None, None, 0, None))
-        return (labels, bmap, offsets) if base_map else (labels, offsets)
-    tables = [up(batch.states.reshape(-1)), up(batch.lengths), None, up(batch.moves), up(batch.event_offsets), up(batch.clipped.reshape(-1)),
-              up(batch.n_raw), offsets]
-    work_bytes = int(lib.cf_label_moves_work_bytes(n_reads, n_events))
-    work = torch.empty(work_bytes, dtype=torch.uint8, device=device)
-    args = [N._p(t) if t is not None else is_f64 for t in tables]
-    with torch.cuda.device(device):
-        N.check(lib.cf_label_moves(None, *args, n_reads, n_events, total, batch.kmer, N._p(labels), N._p(bmap) if base_map else None,
-                                   N._p(work), work_bytes, N.current_stream_ptr(torch, device)))
-    # (tables and work were allocated on the stream the launches run on, so the allocator hands them out again only behind them)
-    return (labels, bmap, offsets) if base_map else (labels, offsets)
+    labels, bmap, tables = label_on_card(batch, None, label_device(device, ("label_moves", "MoveBatch")), base_map)
+    return (labels, bmap, tables[-1]) if base_map else (labels, tables[-1])
 
 
 def load_move_npz(path):
@@ -590,6 +625,53 @@ def moves_from_env(value):
     if value.strip() != "1":
         raise ValueError("CATFISH_LABEL_MOVES must be 1 (or unset), got %r" % (value,))
     return True
+
+
+class LabelSource(object):
+    """What a run's ``.npz`` directories hold, decided once: ``kind`` "labels" (``raw`` + ``base_labels``), "events" (event files,
+    labelled with the odd k-mer size ``kmer``) or "moves" (move files; ``kmer`` is None: the k-mers come with the events)."""
+    KINDS = ("labels", "events", "moves")
+
+    def __init__(self, kind="labels", kmer=None):
+        if kind not in self.KINDS:
+            raise ValueError("a label source is one of %s, got %r" % (", ".join(self.KINDS), kind))
+        self.kind, self.kmer = kind, check_kmer(kmer) if kind == "events" else None
+
+    @classmethod
+    def from_env(cls, environ=os.environ):
+        """The source ``CATFISH_LABEL_KMER`` / ``CATFISH_LABEL_MOVES`` name (``kmer_from_env``, ``moves_from_env``; neither set:
+        "labels").  The package reads the two variables here and nowhere else; both at once is a ValueError."""
+        kmer = kmer_from_env(environ.get("CATFISH_LABEL_KMER"))
+        if not moves_from_env(environ.get("CATFISH_LABEL_MOVES")):
+            return cls("labels") if kmer is None else cls("events", kmer)
+        if kmer is not None:
+            raise ValueError("CATFISH_LABEL_MOVES and CATFISH_LABEL_KMER exclude each other: a directory holds move files or event files")
+        return cls("moves")
+
+    has_tables = property(lambda self: self.kind != "labels")
+
+    def _per_kind(self, events, moves):
+        if not self.has_tables:
+            raise ValueError("labelled reads come without tables (train_validate.load_npz reads them)")
+        return events if self.kind == "events" else moves
+
+    def load(self, path):
+        """One file's read as ``batch`` takes it: the dict of ``load_event_npz`` / ``load_move_npz``."""
+        return self._per_kind(load_event_npz, load_move_npz)(path)
+
+    def batch(self, reads):
+        """``EventBatch.from_reads`` / ``MoveBatch.from_reads``."""
+        return self._per_kind(EventBatch, MoveBatch).from_reads(reads)
+
+    def loader(self):
+        """The ``path -> (raw, labels)`` loader of this kind of file: ``train_validate.load_npz`` itself, or one that labels each
+        read on the host on the way in -- the ``(raw, labels)`` the ``raw`` + ``base_labels`` file made from it would give."""
+        if self.kind == "moves":
+            return load_labelled_move_npz
+        if self.kind == "events":
+            return lambda path: load_labelled_event_npz(path, self.kmer)
+        from .train_validate import load_npz
+        return load_npz
 
 
 def synthetic_move_read(length, seed, stay=0.5, dtype=np.float32):

@@ -144,19 +144,10 @@ def load_npz(npz_file):
 
 
 def npz_loader_from_env():
-    """The loader ``main`` reads its ``.npz`` directories with: ``load_npz``, or with ``CATFISH_LABEL_KMER=<odd k>`` set a loader
-    of event files (``raw`` + an event table, ``labelling.load_event_npz``) that labels each read with that k -- the same
-    ``(raw, labels)`` the ``raw`` + ``base_labels`` file made from it would give; or with ``CATFISH_LABEL_MOVES=1`` a loader of move
-    files (``raw`` + a basecaller's Events table, ``labelling.load_move_npz``).  Both at once is a ValueError."""
+    """The ``path -> (raw, labels)`` loader of the files ``CATFISH_LABEL_KMER`` / ``CATFISH_LABEL_MOVES`` name
+    (``labelling.LabelSource``): ``load_npz`` itself when neither is set."""
     from . import labelling
-    kmer = labelling.kmer_from_env(os.environ.get("CATFISH_LABEL_KMER"))
-    if labelling.moves_from_env(os.environ.get("CATFISH_LABEL_MOVES")):
-        if kmer is not None:
-            raise ValueError("CATFISH_LABEL_MOVES and CATFISH_LABEL_KMER exclude each other: a directory holds move files or event files")
-        return labelling.load_labelled_move_npz
-    if kmer is None:
-        return load_npz
-    return lambda npz_file: labelling.load_labelled_event_npz(npz_file, kmer)
+    return labelling.LabelSource.from_env().loader()
 
 
 def example_db_from_npz(npz_files, width=34, lessen=1, max_neg_per_read=2000, seed=0, loader=None):
@@ -710,18 +701,14 @@ def device_read_db_from_env(npz_files):
     A host database: it feeds the per-step loop (``get_training_set``)."""
     from .device_db import DeviceReadDb
     from . import labelling
-    kmer = labelling.kmer_from_env(os.environ.get("CATFISH_LABEL_KMER"))
     rule = os.environ.get("CATFISH_DEVICE_NEG", "positives")
     if rule not in ("positives", "all"):
         try:
             rule = int(rule)
         except ValueError:
             raise ValueError("CATFISH_DEVICE_NEG must be 'positives', 'all' or an integer, got %r" % rule)
-    if labelling.moves_from_env(os.environ.get("CATFISH_LABEL_MOVES")):     # move files, labelled on the card where there is one
-        return DeviceReadDb.from_move_npz(npz_files, seed=0, neg_per_read=None if rule == "all" else rule)
-    if kmer is not None:                                         # event files, labelled with that k (on the card where there is one)
-        return DeviceReadDb.from_event_npz(npz_files, kmer, seed=0, neg_per_read=None if rule == "all" else rule)
-    return DeviceReadDb.from_npz(npz_files, seed=0, neg_per_read=None if rule == "all" else rule)
+    # (event and move files are labelled on the card where there is one)
+    return DeviceReadDb.from_source(npz_files, labelling.LabelSource.from_env(), seed=0, neg_per_read=None if rule == "all" else rule)
 
 
 def main(argv):
@@ -766,15 +753,13 @@ def main(argv):
     ``base_votes.base_vote_rates`` (per-base precision / recall / F1), ``hp_vote_runs``, ``called_vote_runs`` and the rates of
     ``device_validation.run_base_rates`` over them as one JSON line to ``<model path>_base_votes.jsonl``.  The ``.txt`` reports and
     the other ``.jsonl`` files are unchanged.
-    CATFISH_LABEL_KMER=<odd k in 1 .. 15>: both directories hold event files (``raw`` + ``event_base`` / ``event_length``,
-    ``labelling.load_event_npz``; ``python -m catfish_amd.convert --events`` writes them) and every read is labelled with that k-mer
-    size on the way in (``npz_loader_from_env``; with CATFISH_DEVICE_VALIDATION=1 or CATFISH_DEVICE_DB=reads on the card,
-    ``cf_label_events``) -- the labels a directory of ``raw`` + ``base_labels`` files made from them would hold.  Unset, nothing
-    changes.
-    CATFISH_LABEL_MOVES=1: both directories hold move files (``raw`` + ``event_state`` / ``event_move`` / ``event_length``,
-    ``labelling.load_move_npz``; ``python -m catfish_amd.convert --moves`` writes them) -- base-called reads that were not
-    resquiggled -- and every read is labelled from its basecaller's move table on the way in (with CATFISH_DEVICE_VALIDATION=1 or
-    CATFISH_DEVICE_DB=reads on the card, ``cf_label_moves``).  Not together with CATFISH_LABEL_KMER.  Unset, nothing changes."""
+    CATFISH_LABEL_KMER=<odd k in 1 .. 15> or CATFISH_LABEL_MOVES=1 (never both): the two directories hold reads with their tables
+    instead of labels -- event files (``raw`` + ``event_base`` / ``event_length``; ``python -m catfish_amd.convert --events`` writes
+    them) or move files (``raw`` + ``event_state`` / ``event_move`` / ``event_length`` of reads that were base-called and not
+    resquiggled; ``convert --moves``).  ``labelling.LabelSource.from_env`` reads the two variables, once, and everything below takes
+    the source from it: every read is labelled on the way in (``source.loader()``; with CATFISH_DEVICE_VALIDATION=1 or
+    CATFISH_DEVICE_DB=reads on the card, ``DeviceValidationSet.from_source`` -> ``cf_label_events`` / ``cf_label_moves``) -- the labels
+    a directory of ``raw`` + ``base_labels`` files made from them would hold.  Unset, nothing changes."""
     args = list(argv[1:])
     if len(args) < 5:
         raise ValueError(_USAGE)
@@ -791,24 +776,21 @@ def main(argv):
         hparams["training_precision"] = os.environ["CATFISH_TRAINING_PRECISION"]
     network = build_model(kind, save=True, **hparams)
     network.initialize_network()
+    from . import labelling
+    source = labelling.LabelSource.from_env()                    # what both directories hold: labelled reads, event files or move files
     bases = os.environ.get("CATFISH_VALIDATION_BASES") or "0"
     if bases != "0":                                             # ... which homopolymers by base and length in bases, one JSON line per round
-        from . import labelling
-        tables = (os.environ.get("CATFISH_LABEL_KMER") or "").strip() or labelling.moves_from_env(os.environ.get("CATFISH_LABEL_MOVES"))
-        if os.environ.get("CATFISH_DEVICE_VALIDATION") != "1" or not tables:
+        if os.environ.get("CATFISH_DEVICE_VALIDATION") != "1" or not source.has_tables:
             raise ValueError("CATFISH_VALIDATION_BASES needs CATFISH_DEVICE_VALIDATION=1 and CATFISH_LABEL_KMER (reads with event tables)")
         network.validation_max_bases = MAX_BASES if bases == "1" else check_max_bases(int(bases))
     votes = os.environ.get("CATFISH_VALIDATION_VOTES") or "0"
     if votes != "0":                                             # ... and the per-base calls, one JSON line per round
-        from . import labelling
-        tables = (os.environ.get("CATFISH_LABEL_KMER") or "").strip() or labelling.moves_from_env(os.environ.get("CATFISH_LABEL_MOVES"))
-        if os.environ.get("CATFISH_DEVICE_VALIDATION") != "1" or not tables:
+        if os.environ.get("CATFISH_DEVICE_VALIDATION") != "1" or not source.has_tables:
             raise ValueError("CATFISH_VALIDATION_VOTES needs CATFISH_DEVICE_VALIDATION=1 and CATFISH_LABEL_KMER or CATFISH_LABEL_MOVES "
                              "(reads with event or move tables)")
         network.validation_vote_bases = MAX_BASES if votes == "1" else check_max_bases(int(votes))
-    loader = npz_loader_from_env()                               # load_npz, or event files labelled on the way in (CATFISH_LABEL_KMER)
-    from_events = loader is not load_npz
-    with_loader = {"loader": loader} if from_events else {}
+    loader = source.loader()                                     # load_npz, or event / move files labelled on the way in
+    with_loader = {"loader": loader} if source.has_tables else {}
     print("Loading training database..")
     if os.environ.get("CATFISH_DEVICE_DB") == "1":               # the training set on the card, batches drawn by a HIP kernel
         from .device_db import device_db_from_npz
@@ -817,20 +799,13 @@ def main(argv):
         db_train = device_read_db_from_env(_npz_files(train_dir))
     else:
         db_train = example_db_from_npz(_npz_files(train_dir), **with_loader)
-    if from_events:
+    if source.has_tables:
         network.validation_loader = loader
     print("Loading validation database..")
     squiggles = _npz_files(val_dir)
     if os.environ.get("CATFISH_DEVICE_VALIDATION") == "1":       # the validation reads on the card, rounds scored by HIP kernels
         from .device_validation import DeviceValidationSet
-        if from_events:
-            from . import labelling
-            if labelling.moves_from_env(os.environ.get("CATFISH_LABEL_MOVES")):
-                squiggles = DeviceValidationSet.from_move_npz(squiggles)
-            else:
-                squiggles = DeviceValidationSet.from_event_npz(squiggles, labelling.kmer_from_env(os.environ.get("CATFISH_LABEL_KMER")))
-        else:
-            squiggles = DeviceValidationSet.from_npz(squiggles)
+        squiggles = DeviceValidationSet.from_source(squiggles, source)
         if os.environ.get("CATFISH_VALIDATION_RUNS") == "1":     # ... and the homopolymers found, one JSON line per round
             network.validation_run_edges = VALIDATION_RUN_EDGES
         if os.environ.get("CATFISH_VALIDATION_CURVE") == "1":    # ... and the round's ROC / PR areas and best F1, one JSON line per round
