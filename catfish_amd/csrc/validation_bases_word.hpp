@@ -6,7 +6,7 @@
 // `is1` / `is0` (the other array is 1 / is 0), `mark` (bit 7 of the base map: the centre sample of an event, one per base) and
 // is[c] = "mark, and the base byte is 'A' / 'C' / 'G' / 'T'".  Bit i is sample 64 * word + i; bits past the stretch are 0 in all.
 //
-// What a run needs from BEFORE the word arrives as a vbs_seg, cf_run_seg (csrc/validation_runs.hpp) without the length and widened
+// What a run needs from BEFORE the word arrives as a vbs_seg, vr_seg (validation_runs_word.hpp) without the length and widened
 // by the marks and the base of the open run, in one 32-bit word:
 //   bit 0     VBS_CUT   the words of the seg are not all run (what came before cannot reach their end)
 //   bit 1, 2  VBS_ALL1 / VBS_ALL0   the other array is 1 / is 0 over the whole open run
@@ -30,6 +30,14 @@
 typedef uint32_t vbs_seg;
 
 struct vbs_masks { uint64_t run, is1, is0, mark, is[4]; };
+
+struct vbs_base_marks {                                    // the masks of the base-map byte as a walk loads them (vb_no_marks'
+    enum { N = 5 };                                        // interface): m[0] = mark, m[1 + c] = is[c]
+    uint64_t m[N];
+    VB_FN static bool is(int c, unsigned b) { return c == 0 ? (b & 0x80u) != 0u : b == (0x80u | (unsigned)"ACGT"[c - 1]); }
+    VB_FN void set(int c, uint64_t v) { m[c] = v; }
+    VB_FN vbs_masks word(uint64_t run, uint64_t is1, uint64_t is0) const { return {run, is1, is0, m[0], {m[1], m[2], m[3], m[4]}}; }
+};
 
 VB_FN vbs_seg vbs_none() { return VBS_CUT | VBS_ALL1 | VBS_ALL0; }               // nothing open: what a stretch starts with
 VB_FN uint32_t vbs_base(vbs_seg v) { return (v >> 4) & 7u; }
@@ -98,3 +106,16 @@ VB_FN void vbs_count(const vbs_masks& w, const vbs_seg in, int max_bases, Add&& 
         add(vbs_cell(all1 ? 0 : all0 ? 2 : 1, base, marks, max_bases));         // complete / absent / incomplete (check_hp)
     }
 }
+
+struct vbs_rule {                                          // (what a walk asks of a step: vb_rule, validation_borders_word.hpp)
+    typedef vbs_seg seg;
+    typedef vbs_base_marks marks;
+    int max_bases;
+    VB_FN static seg none() { return vbs_none(); }
+    VB_FN static seg join(const seg a, const seg b) { return vbs_join(a, b); }
+    VB_FN static seg word(uint64_t run, uint64_t is1, uint64_t is0, const marks& mk) { return vbs_word(mk.word(run, is1, is0)); }
+    template <class Add>
+    VB_FN void events(uint64_t run, uint64_t is1, uint64_t is0, const marks& mk, const seg in, int64_t, bool, Add&& add) const {
+        vbs_count(mk.word(run, is1, is0), in, max_bases, add);
+    }
+};

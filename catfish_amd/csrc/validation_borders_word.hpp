@@ -163,3 +163,27 @@ VB_FN void vb_events(uint64_t run, uint64_t o, const vb_seg in, int64_t first, b
         if (cut) add(vb_cell_interrupted(reach));
     }
 }
+
+// What a walk (csrc/validation_walk.hpp on the card, tests/native/validation_replay_common.hpp serially) asks of a step: its seg
+// with none / word / join, the masks it takes from a third byte per sample (`marks`: N masks, mask c holds the samples whose byte
+// `is(c, byte)`; here none), and the events of one word of one kind -- run / is1 / is0 as above, `first` = the stretch's position of
+// bit 0 in walking order.  validation_runs_word.hpp and validation_bases_word.hpp state theirs the same way.
+struct vb_no_marks {
+    enum { N = 0 };
+    VB_FN static bool is(int, unsigned) { return false; }
+    VB_FN void set(int, uint64_t) {}
+    VB_FN vb_no_marks mirrored() const { return {}; }
+};
+
+struct vb_rule {
+    typedef vb_seg seg;
+    typedef vb_no_marks marks;
+    int reach;
+    VB_FN static seg none() { return vb_none(); }
+    VB_FN static seg join(const seg a, const seg b) { return vb_join(a, b); }
+    VB_FN static seg word(uint64_t run, uint64_t is1, uint64_t, const marks&) { return vb_word(run, is1); }
+    template <class Add>
+    VB_FN void events(uint64_t run, uint64_t is1, uint64_t, const marks&, const seg in, int64_t first, bool mirror, Add&& add) const {
+        vb_events(run, is1, in, first, mirror, reach, add);
+    }
+};

@@ -85,7 +85,7 @@ def score_host(probs, logits, y, bounds, thresholds):
     return right, ce_sum, counts
 
 
-MAX_RUN_EDGES = 7           # length-bin edges per run-state call (CF_RUN_MAX_EDGES, csrc/validation_runs.hpp)
+MAX_RUN_EDGES = 7           # length-bin edges per run-state call (CF_RUN_MAX_EDGES, csrc/validation_runs_word.hpp)
 RUN_STATES = ("complete", "incomplete", "absent")          # check_hp's states, in the order of the table's last axis
 
 
@@ -121,6 +121,34 @@ def _states_of(starts, ends, other):
     return np.where(ones[ends + 1] - ones[starts] == size, 0, np.where(zeros[ends + 1] - zeros[starts] == size, 2, 1))
 
 
+def _stretch_predictions(probs, y, bounds, lengths, thresholds, min_run, max_gap):
+    """What ``run_states_host``, ``run_bases_host`` and ``run_borders_host`` share.  At the call: the checks of ``min_run`` /
+    ``max_gap`` and the arrays as they are read.  Returned: an iterator over the non-empty stretches, ``(b0, n, truth, preds)`` --
+    ``truth`` = ``y`` over the stretch alone and ``preds`` the list of ``(k, pred)`` of every threshold, ``pred`` = the corrected
+    prediction over the stretch alone, int64 0 / 1."""
+    from .infer import bridge_gaps, check_bridge, correct_short
+    if int(min_run) < 1:
+        raise ValueError("min_run must be >= 1")
+    max_gap = check_bridge(max_gap, min_run)
+    p = np.asarray(probs, dtype=np.float64).reshape(-1)
+    y = np.asarray(y).reshape(-1)
+    bounds = np.asarray(bounds, dtype=np.int64)
+    lengths = np.asarray(lengths, dtype=np.int64)
+
+    def stretches():
+        for b0, n in zip(bounds[:len(lengths)].tolist(), lengths.tolist()):
+            if n > 0:
+                called = [(p[b0:b0 + n] >= float(t)).astype(np.int64) for t in thresholds]
+                yield b0, n, y[b0:b0 + n], [(k, np.asarray(correct_short(bridge_gaps(c, max_gap), int(min_run)))) for k, c in enumerate(called)]
+
+    return stretches()
+
+
+def _kinds(truth, pred):
+    """``(kind, mask, other)``: kind 0, the runs of ``truth == 1`` judged against ``pred``; kind 1, those of ``pred == 1`` against ``truth``."""
+    return ((0, truth == 1, pred), (1, pred == 1, truth))
+
+
 def run_states_host(probs, y, bounds, lengths, thresholds, edges=(), min_run=15, max_gap=0):
     """What ``cf_validation_run_states`` returns, in numpy: int64 [K, 2, B, 3] -- per threshold, kind, length bin and state how
     many runs (the reference's offline networks/process_output.py:235-273).
@@ -135,23 +163,12 @@ def run_states_host(probs, y, bounds, lengths, thresholds, edges=(), min_run=15,
 
     ``max_gap > 0`` (``cf_validation_run_states_bridged``): the prediction is ``correct_short(infer.bridge_gaps((double)p >= t,
     max_gap), min_run)`` over the stretch alone; ValueError for ``min_run + max_gap > 64``."""
-    from .infer import bridge_gaps, check_bridge, correct_short
     edges = np.asarray(check_run_edges(edges), dtype=np.int64)
-    if int(min_run) < 1:
-        raise ValueError("min_run must be >= 1")
-    max_gap = check_bridge(max_gap, min_run)
-    p = np.asarray(probs, dtype=np.float64).reshape(-1)
-    y = np.asarray(y).reshape(-1)
-    bounds = np.asarray(bounds, dtype=np.int64)
-    lengths = np.asarray(lengths, dtype=np.int64)
+    stretches = _stretch_predictions(probs, y, bounds, lengths, thresholds, min_run, max_gap)
     out = np.zeros((len(thresholds), 2, len(edges) + 1, 3), dtype=np.int64)
-    for b0, n in zip(bounds[:len(lengths)].tolist(), lengths.tolist()):
-        if n <= 0:
-            continue
-        truth = y[b0:b0 + n]
-        for k, t in enumerate(thresholds):
-            pred = np.asarray(correct_short(bridge_gaps((p[b0:b0 + n] >= float(t)).astype(np.int64), max_gap), int(min_run)))
-            for kind, (mask, other) in enumerate(((truth == 1, pred), (pred == 1, truth))):
+    for _b0, _n, truth, preds in stretches:
+        for k, pred in preds:
+            for kind, mask, other in _kinds(truth, pred):
                 starts, ends = _runs_of(mask)
                 bins = np.searchsorted(edges, ends - starts + 1, side="right")
                 np.add.at(out[k, kind], (bins, _states_of(starts, ends, other)), 1)
@@ -205,26 +222,15 @@ def run_bases_host(probs, y, basemap, bounds, lengths, thresholds, max_bases=MAX
     last-sample rule adds counts.  Class 0..3 (``BASE_CLASSES``): ``nb >= 1`` and every one of them is that upper-case letter (a byte
     comparison); class 4, "other": anything else -- mixed, ``N``, lower case, or no base at all.  Bin = ``min(nb, max_bases)``.
     Summed over class and bin the table is ``run_states_host(..., edges=())`` with its axes as [K, 2, 3]."""
-    from .infer import bridge_gaps, check_bridge, correct_short
     max_bases = check_max_bases(max_bases)
-    if int(min_run) < 1:
-        raise ValueError("min_run must be >= 1")
-    max_gap = check_bridge(max_gap, min_run)
-    p = np.asarray(probs, dtype=np.float64).reshape(-1)
-    y = np.asarray(y).reshape(-1)
+    stretches = _stretch_predictions(probs, y, bounds, lengths, thresholds, min_run, max_gap)
     basemap = np.asarray(basemap, dtype=np.uint8).reshape(-1)
-    bounds = np.asarray(bounds, dtype=np.int64)
-    lengths = np.asarray(lengths, dtype=np.int64)
     out = np.zeros((len(thresholds), 2, 3, len(BASE_CLASSES), max_bases + 1), dtype=np.int64)
-    for b0, n in zip(bounds[:len(lengths)].tolist(), lengths.tolist()):
-        if n <= 0:
-            continue
-        truth, bmap = y[b0:b0 + n], basemap[b0:b0 + n]
-        for k, t in enumerate(thresholds):
-            pred = np.asarray(correct_short(bridge_gaps((p[b0:b0 + n] >= float(t)).astype(np.int64), max_gap), int(min_run)))
-            for kind, (mask, other) in enumerate(((truth == 1, pred), (pred == 1, truth))):
+    for b0, n, truth, preds in stretches:
+        for k, pred in preds:
+            for kind, mask, other in _kinds(truth, pred):
                 starts, ends = _runs_of(mask)
-                cls, bins = _bases_of(starts, ends, bmap, max_bases)
+                cls, bins = _bases_of(starts, ends, basemap[b0:b0 + n], max_bases)
                 np.add.at(out[k, kind], (_states_of(starts, ends, other), cls, bins), 1)
     return out
 
@@ -309,27 +315,15 @@ def run_borders_host(probs, y, bounds, lengths, thresholds, reach=BORDER_REACH, 
     of ``clip(r, -R, R) + R``; [4R+2, 5R+2) of ``min(g, R) - 1`` over the interruption lengths g; [5R+2] runs with an interruption.
 
     ``max_gap > 0`` (``cf_validation_run_borders_bridged``): the bridged prediction of ``run_states_host``."""
-    from .infer import bridge_gaps, check_bridge, correct_short
     reach = check_border_reach(reach)
-    if int(min_run) < 1:
-        raise ValueError("min_run must be >= 1")
-    max_gap = check_bridge(max_gap, min_run)
-    p = np.asarray(probs, dtype=np.float64).reshape(-1)
-    y = np.asarray(y).reshape(-1)
-    bounds = np.asarray(bounds, dtype=np.int64)
-    lengths = np.asarray(lengths, dtype=np.int64)
+    stretches = _stretch_predictions(probs, y, bounds, lengths, thresholds, min_run, max_gap)
     out = np.zeros((len(thresholds), 2, 5 * reach + 3), dtype=np.int64)
-    for b0, n in zip(bounds[:len(lengths)].tolist(), lengths.tolist()):
-        if n <= 0:
-            continue
-        truth = y[b0:b0 + n]
+    for _b0, _n, truth, preds in stretches:
         if np.any((truth != 0) & (truth != 1)):
             raise ValueError("run borders need labels of 0 or 1, got %r" % (truth[(truth != 0) & (truth != 1)][0],))
-        truth = truth == 1
-        for k, t in enumerate(thresholds):
-            pred = np.asarray(correct_short(bridge_gaps((p[b0:b0 + n] >= float(t)).astype(np.int64), max_gap), int(min_run))) == 1
-            _borders_of(truth, pred, reach, out[k, 0])
-            _borders_of(pred, truth, reach, out[k, 1])
+        for k, pred in preds:
+            for kind, mask, other in _kinds(truth, pred):
+                _borders_of(mask, other == 1, reach, out[k, kind])
     return out
 
 

@@ -502,6 +502,21 @@ class HipEngine(object):
                                               C.c_void_p(counts_out.data_ptr()), C.c_void_p(partials.data_ptr()), int(partials.numel()),
                                               C.c_void_p(stream.cuda_stream)))
 
+    def _run_step_arguments(self, what, probs, y, bounds, length, total, longest, thresholds, counts_out, work, stream, own=()):
+        """What ``run_states_validation``, ``run_borders_validation`` and ``run_bases_validation`` check and convert alike (``own``:
+        the step's own tensors, checked between ``y`` and ``bounds``) -> (n, total, longest, K, thresholds as a C array, stream).
+        n, K, min_run, the (min_run, max_gap) pair and the work space are refused by the library (CF_ERR_INVALID -> ValueError)."""
+        import torch
+        self._check_validation_tensors(what, [("probs", probs, torch.float32), ("y", y, torch.uint8)] + list(own) + [
+            ("bounds", bounds, torch.int64), ("length", length, torch.int64), ("counts_out", counts_out, torch.int64),
+            ("work", work, torch.uint8)])
+        thresholds = [float(t) for t in thresholds]
+        k = len(thresholds)
+        n, total, longest = self._check_validation_sizes(what, probs, y, bounds, length, total, longest)
+        if stream is None:
+            stream = torch.cuda.current_stream(probs.device)
+        return n, total, longest, k, (C.c_double * max(k, 1))(*thresholds), stream
+
     def run_states_work_bytes(self, total, n_thresholds):
         """Bytes of work space ``run_states_validation`` needs for ``total`` packed samples and ``n_thresholds`` thresholds."""
         return int(self._lib.cf_validation_run_work_bytes(int(total), int(n_thresholds)))
@@ -514,25 +529,18 @@ class HipEngine(object):
         (int64 CUDA, ``K * 2 * (len(edges) + 1) * 3`` elements).  ``bounds`` [n + 1] and ``length`` [n] are int64 CUDA tensors;
         ``work`` is a uint8 CUDA tensor of at least ``run_states_work_bytes(total, K)`` bytes.  Asynchronous on the stream; equal
         inputs give equal bits."""
-        import torch
-        self._check_validation_tensors("run_states_validation", [
-            ("probs", probs, torch.float32), ("y", y, torch.uint8), ("bounds", bounds, torch.int64), ("length", length, torch.int64),
-            ("counts_out", counts_out, torch.int64), ("work", work, torch.uint8)])
-        thresholds = [float(t) for t in thresholds]
+        n, total, longest, k, thresholds, stream = self._run_step_arguments("run_states_validation", probs, y, bounds, length, total, longest,
+                                                                            thresholds, counts_out, work, stream)
         edges = [int(e) for e in edges]
-        k = len(thresholds)
-        n, total, longest = self._check_validation_sizes("run_states_validation", probs, y, bounds, length, total, longest)
         if int(counts_out.numel()) < k * 2 * (len(edges) + 1) * 3:
             raise ValueError("run_states_validation: counts_out needs 2 * (edges + 1) * 3 entries per threshold")
-        if stream is None:
-            stream = torch.cuda.current_stream(probs.device)
-        # n, K, the edges, min_run, the (min_run, max_gap) pair and the work space are refused by the library (CF_ERR_INVALID ->
-        # ValueError); ``max_gap`` 0 is ``cf_validation_run_states``, anything else bridges the prediction first
+        # the edges are refused by the library too; ``max_gap`` 0 is ``cf_validation_run_states``, anything else bridges the
+        # prediction first
         N.check(self._lib.cf_validation_run_states_bridged(
             self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
-            C.c_void_p(length.data_ptr()), n, total, longest, (C.c_double * max(k, 1))(*thresholds), k,
-            (C.c_int64 * max(len(edges), 1))(*edges), len(edges), int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()),
-            C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
+            C.c_void_p(length.data_ptr()), n, total, longest, thresholds, k, (C.c_int64 * max(len(edges), 1))(*edges), len(edges),
+            int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()),
+            C.c_void_p(stream.cuda_stream)))
 
     def run_borders_work_bytes(self, total, n_thresholds):
         """Bytes of work space ``run_borders_validation`` needs (``run_states_work_bytes``' rule: the two can share a buffer)."""
@@ -547,26 +555,17 @@ class HipEngine(object):
         tensors; ``work`` is a uint8 CUDA tensor of at least ``run_borders_work_bytes(total, K)`` bytes.  A label other than 1
         counts as 0 here (``RNN.score_validation_device`` refuses such sets).  Asynchronous on the stream; equal inputs give equal
         bits."""
-        import torch
         from .device_validation import check_border_reach
-        self._check_validation_tensors("run_borders_validation", [
-            ("probs", probs, torch.float32), ("y", y, torch.uint8), ("bounds", bounds, torch.int64), ("length", length, torch.int64),
-            ("counts_out", counts_out, torch.int64), ("work", work, torch.uint8)])
-        thresholds = [float(t) for t in thresholds]
+        n, total, longest, k, thresholds, stream = self._run_step_arguments("run_borders_validation", probs, y, bounds, length, total, longest,
+                                                                            thresholds, counts_out, work, stream)
         reach = check_border_reach(reach)
-        k = len(thresholds)
-        n, total, longest = self._check_validation_sizes("run_borders_validation", probs, y, bounds, length, total, longest)
         if int(counts_out.numel()) < k * 2 * (5 * reach + 3):
             raise ValueError("run_borders_validation: counts_out needs 2 * (5 * reach + 3) entries per threshold")
-        if stream is None:
-            stream = torch.cuda.current_stream(probs.device)
-        # n, K, min_run, the (min_run, max_gap) pair and the work space are refused by the library (CF_ERR_INVALID -> ValueError);
         # ``max_gap`` 0 is ``cf_validation_run_borders``, anything else bridges the prediction first
         N.check(self._lib.cf_validation_run_borders_bridged(
             self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
-            C.c_void_p(length.data_ptr()), n, total, longest, (C.c_double * max(k, 1))(*thresholds), k, reach, int(max_gap),
-            int(min_run), C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()),
-            C.c_void_p(stream.cuda_stream)))
+            C.c_void_p(length.data_ptr()), n, total, longest, thresholds, k, reach, int(max_gap), int(min_run),
+            C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
 
     def run_bases_validation(self, probs, y, basemap, src_first, bounds, length, total, longest, thresholds, max_bases, counts_out, work,
                              min_run=15, max_gap=0, stream=None):
@@ -579,27 +578,20 @@ class HipEngine(object):
         inputs give equal bits."""
         import torch
         from .device_validation import BASE_CLASSES, check_max_bases
-        self._check_validation_tensors("run_bases_validation", [
-            ("probs", probs, torch.float32), ("y", y, torch.uint8), ("basemap", basemap, torch.uint8), ("src_first", src_first, torch.int64),
-            ("bounds", bounds, torch.int64), ("length", length, torch.int64), ("counts_out", counts_out, torch.int64),
-            ("work", work, torch.uint8)])
-        thresholds = [float(t) for t in thresholds]
+        n, total, longest, k, thresholds, stream = self._run_step_arguments(
+            "run_bases_validation", probs, y, bounds, length, total, longest, thresholds, counts_out, work, stream,
+            own=(("basemap", basemap, torch.uint8), ("src_first", src_first, torch.int64)))
         max_bases = check_max_bases(max_bases)
-        k = len(thresholds)
-        n, total, longest = self._check_validation_sizes("run_bases_validation", probs, y, bounds, length, total, longest)
         if int(src_first.numel()) != n:
             raise ValueError("run_bases_validation: src_first needs n entries")
         if int(counts_out.numel()) < k * 2 * 3 * len(BASE_CLASSES) * (max_bases + 1):
             raise ValueError("run_bases_validation: counts_out needs 2 * 3 * 5 * (max_bases + 1) entries per threshold")
-        if stream is None:
-            stream = torch.cuda.current_stream(probs.device)
-        # n, K, min_run, the (min_run, max_gap) pair, the work space and an empty base map are refused by the library
-        # (CF_ERR_INVALID -> ValueError)
+        # an empty base map is refused by the library too
         N.check(self._lib.cf_validation_run_bases(
             self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(basemap.data_ptr()), int(basemap.numel()),
             C.c_void_p(src_first.data_ptr()), C.c_void_p(bounds.data_ptr()), C.c_void_p(length.data_ptr()), n, total, longest,
-            (C.c_double * max(k, 1))(*thresholds), k, max_bases, int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()),
-            C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
+            thresholds, k, max_bases, int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()),
+            int(work.numel()), C.c_void_p(stream.cuda_stream)))
 
     def base_votes_work_bytes(self, n_bases, n_thresholds):
         """Bytes of work space ``base_votes_validation`` needs for a set of ``n_bases`` bases and ``n_thresholds`` thresholds."""

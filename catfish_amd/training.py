@@ -14,8 +14,11 @@ checkpoint), so trained weights go straight back into the HIP engine or a checkp
 """
 from __future__ import annotations
 
+import gc
+
 import numpy as np
 
+from .batching import quiet_gc
 from .train_mode import STEP_KINDS, TrainMode, geometry
 
 
@@ -408,7 +411,12 @@ class Trainer(object):
                 rewind()
         torch.cuda.current_stream(dev).wait_stream(side)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        # No finaliser may run while the stream captures: a dead cycle that still holds an earlier trainer's graph or engine
+        # frees device objects when the cyclic collector reaches it, which a capture in progress does not allow (the process
+        # aborts).  torch.cuda.graph collected on entry once and no longer does (torch.compiler.config.force_cudagraph_gc), so
+        # collect here, before the capture, and keep the collector off until it ends.
+        gc.collect()
+        with quiet_gc(), torch.cuda.graph(g):
             if prologue:
                 prologue(b)
             b["out"] = self.step.run(b)                     # the loss to read after a replay

@@ -10,6 +10,7 @@ import pytest
 from catfish_amd import device_validation as dv
 from catfish_amd import train_validate as tv
 from catfish_amd.device_validation import DeviceValidationSet
+from test_run_states_replay import planted_stretches
 
 pytestmark = pytest.mark.gpu
 
@@ -30,86 +31,6 @@ def engine(ckpt_weights):
 def _dev(array):
     import torch
     return torch.from_numpy(np.ascontiguousarray(array)).to("cuda:0")
-
-
-def planted_stretches(piece):
-    """[(called uint8 with values 0 / 1 / 2 = an index into LEVELS, truth uint8), ...]"""
-    rng = np.random.default_rng(3)
-    out = []
-
-    def blank(n):
-        return np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
-
-    for n in (0, 1, 2, 14, 15, 16, 63, 64, 65, 127, 128, 129, 4095, 4096, 4097, piece - 1, piece, piece + 1, 2 * piece + 1, 3 * piece + 17):
-        if n <= 65:                                        # random runs, every level
-            for _ in range(3):
-                flips = rng.random(n) < 0.15
-                called = (np.cumsum(flips) & 1).astype(np.uint8) * rng.choice(np.uint8([1, 1, 2]), size=n)
-                out.append((called, (np.cumsum(rng.random(n) < 0.2) & 1).astype(np.uint8)))
-            continue
-        # runs of 33 that END (boundary index + phase = 0 mod 4) or START (= 2 mod 4) exactly at, one sample before and one
-        # after a multiple of 64 -- word, wave (4096) and piece boundaries alike; phase and the rotation of the shift go through
-        # every combination over the variants.  The other array holds, run by run, the same run (complete), the run with its
-        # middle sample missing (incomplete), nothing (absent) or the run widened by three samples (complete one way, incomplete
-        # the other); truth and prediction swap roles from variant to variant
-        for variant in range(12 if n < piece - 1 else 6):
-            phase, turn = (variant // 3, variant % 3) if n < piece - 1 else (2 * (variant // 3), variant % 3)
-            runs, other = blank(n)
-            count = 0
-            for j in range(1, n // 64 + 1):
-                kind = (j + phase) % 4
-                d = ((j >> 1) + turn) % 3 - 1
-                first = j * 64 - 33 + d if kind == 0 else j * 64 + d
-                if kind not in (0, 2) or first < 4 or first + 33 + 4 > n:
-                    continue
-                runs[first:first + 33] = 1
-                if count % 4 != 2:
-                    other[first:first + 33] = 1
-                if count % 4 == 1:
-                    other[first + 16] = 0
-                if count % 4 == 3:
-                    other[first - 3:first + 36] = 1
-                count += 1
-            out.append((runs, other) if variant % 2 else (other, runs))
-    p = piece
-    called, truth = blank(3 * p)
-    truth[p:2 * p] = 1                                     # a run of exactly one whole piece, found completely
-    called[p:2 * p] = 1
-    out.append((called.copy(), truth.copy()))
-    called[p + p // 2] = 0                                 # ... and with one sample missing: incomplete, and two called runs
-    out.append((called.copy(), truth.copy()))
-    out.append((truth.copy(), called.copy()))
-    called, truth = blank(3 * p + 2)
-    truth[1:3 * p + 1] = 1                                 # three pieces long, across three piece boundaries; called nowhere: absent
-    out.append((called.copy(), truth.copy()))
-    out.append((truth.copy(), called.copy()))
-    out.append((np.ones(2 * p + 1, np.uint8), np.ones(2 * p + 1, np.uint8)))             # one run of 2 P + 1 ones
-    out.append((np.full(2 * p + 1, 2, np.uint8), np.ones(2 * p + 1, np.uint8)))          # ... called by probabilities of exactly 0.5
-    out.append(blank(2 * p + 1))                                                           # zeros
-    alternating = (np.arange(4097) & 1).astype(np.uint8)                                  # 32 true runs per word
-    out.append((np.ones(4097, np.uint8), alternating))
-    out.append((np.zeros(4097, np.uint8), 1 - alternating))
-    out.append((np.repeat(np.uint8([0, 1, 0, 1, 0]), [100, 1000, 1, 2000, 996]), alternating))
-    called, truth = blank(400)                             # called runs of 14, 15 and 16 over one long true run
-    truth[10:390] = 1
-    called[20:34] = 1
-    called[100:115] = 1
-    called[200:216] = 1
-    out.append((called.copy(), truth.copy()))
-    for n in (129, 130, 193, p + 1, p + 2):                # the last-sample rule at n - 2, for either kind and for both
-        for who in range(3):
-            called, truth = blank(n)
-            if who != 1:
-                truth[n - 40:n - 1] = 1
-            if who != 0:
-                called[n - 30:n - 1] = 1
-            out.append((called, truth))
-    called, truth = blank(300)                             # a label that is neither 0 nor 1 inside a called run
-    called[50:250] = 1
-    truth[60:240] = 1
-    truth[100] = 2
-    out.append((called, truth))
-    return out
 
 
 @pytest.fixture(scope="module")
