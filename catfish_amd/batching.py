@@ -8,6 +8,8 @@ device (cf_postprocess), span extraction (``hp_in_pred``) on the host over the u
 """
 from __future__ import annotations
 
+from collections import deque, namedtuple
+
 import numpy as np
 
 from .infer import WINDOW_SIZE, padding_size_for
@@ -36,6 +38,55 @@ class quiet_gc(object):
             import gc
             gc.enable()
         return False
+
+
+def engine_of(model):
+    """The engine of a network object (or the engine itself); a network without weights has none yet."""
+    engine = model.engine if hasattr(model, "engine") else model
+    if engine is None:
+        raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
+    return engine
+
+
+def windows_of(lengths):
+    """Windows a read of n samples occupies in a packed launch, vectorised.  infer.py:32-36 pads a read to whole windows and gives a
+    multiple of the window a full extra one: n // 35 + 1.  Its padded samples are ``windows_of(n) * WINDOW_SIZE``."""
+    return np.asarray(lengths, dtype=np.int64) // WINDOW_SIZE + 1
+
+
+def _windows_for(lengths, window):
+    """``windows_of`` for any window: another one than the default goes through ``padding_size_for`` like the reference, which pads a
+    multiple of ANY window by a literal 35."""
+    if window == WINDOW_SIZE:
+        return windows_of(lengths)
+    return np.array([(int(n) + padding_size_for(int(n), window)) // window for n in lengths], dtype=np.int64)
+
+
+BatchTables = namedtuple("BatchTables", "dac_off win_off s_off lengths n_windows n_samples")
+
+
+def batch_tables(lengths):
+    """The tables of reads packed back to back: where each read's raw samples start (``dac_off``), its first window (``win_off``) and
+    its first padded sample (``s_off``), each closed by the total; the lengths as int64; the batch's windows and padded samples."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    dac_off = np.zeros(len(lengths) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=dac_off[1:])
+    win_off = np.zeros(len(lengths) + 1, dtype=np.int64)
+    np.cumsum(windows_of(lengths), out=win_off[1:])
+    n_windows = int(win_off[-1])
+    return BatchTables(dac_off, win_off, win_off * WINDOW_SIZE, lengths, n_windows, n_windows * WINDOW_SIZE)
+
+
+def in_flight(items, depth, finish):
+    """Keep up to ``depth`` batches submitted: ``items`` submits one per element, lazily; ``finish(item)`` is yielded for each in
+    submission order, and never more than ``depth`` are held unfinished."""
+    pending = deque()
+    for item in items:
+        pending.append(item)
+        if len(pending) == depth:
+            yield finish(pending.popleft())
+    while pending:
+        yield finish(pending.popleft())
 
 
 class PackedReads(object):
@@ -68,10 +119,8 @@ def pack_reads(signals, window=WINDOW_SIZE):
     """signals: iterable of 1-D normalised arrays -> PackedReads."""
     signals = [np.asarray(s).reshape(-1) for s in signals]
     lengths = np.array([len(s) for s in signals], dtype=np.int64)
-    pads = np.array([padding_size_for(int(n), window) for n in lengths], dtype=np.int64)
-    n_win = (lengths + pads) // window
     win_offsets = np.zeros(len(signals) + 1, dtype=np.int64)
-    np.cumsum(n_win, out=win_offsets[1:])
+    np.cumsum(_windows_for(lengths, window), out=win_offsets[1:])
     x = np.zeros(int(win_offsets[-1]) * window, dtype=np.float32)
     for s, off in zip(signals, win_offsets[:-1] * window):
         x[off:off + len(s)] = s
@@ -84,8 +133,7 @@ def length_buckets(lengths, max_windows, window=WINDOW_SIZE):
     Buckets only bound the launch size: windows are independent, so reads of different lengths
     share a bucket without any extra padding.
     """
-    lengths = np.asarray(lengths, dtype=np.int64)
-    n_win = np.array([(int(n) + padding_size_for(int(n), window)) // window for n in lengths], dtype=np.int64)
+    n_win = _windows_for(np.asarray(lengths, dtype=np.int64), window)
     order = np.argsort(-n_win, kind="stable")
     buckets, cur, cur_w = [], [], 0
     for i in order:
@@ -169,9 +217,7 @@ def infer_reads(model, signals, max_windows=None, threshold=0.5, min_run=15, max
     ``vote_weight`` as in ``infer_packed`` (``max_windows`` bounds the base layout of a launch: K tilings make it about K times as
     large)."""
     from .calling import CallRule
-    engine = model.engine if hasattr(model, "engine") else model
-    if engine is None:
-        raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
+    engine = engine_of(model)
     rule = CallRule.of(threshold, min_run, max_gap, phases, vote_weight)
     signals = [np.asarray(s).reshape(-1) for s in signals]
     if max_windows is None:
@@ -196,9 +242,7 @@ def infer_reads_dac(model, dac_reads, max_windows=None, threshold=0.5, min_run=1
     """
     import torch
     from . import calling
-    engine = model.engine if hasattr(model, "engine") else model
-    if engine is None:
-        raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
+    engine = engine_of(model)
     rule = calling.CallRule.of(threshold, min_run, max_gap, phases, vote_weight)
     dac_reads = [np.ascontiguousarray(np.asarray(r).reshape(-1), dtype=np.int16) for r in dac_reads]
     if max_windows is None:
@@ -207,19 +251,13 @@ def infer_reads_dac(model, dac_reads, max_windows=None, threshold=0.5, min_run=1
     out = [None] * len(dac_reads)
     probs_out = [None] * len(dac_reads)
     for bucket in length_buckets([len(r) for r in dac_reads], max_windows):
-        lengths = np.array([len(dac_reads[i]) for i in bucket], dtype=np.int64)
-        dac_off = np.zeros(len(bucket) + 1, dtype=np.int64)
-        np.cumsum(lengths, out=dac_off[1:])
-        n_win = np.array([(int(n) + padding_size_for(int(n))) // WINDOW_SIZE for n in lengths], dtype=np.int64)
-        win_off = np.zeros(len(bucket) + 1, dtype=np.int64)
-        np.cumsum(n_win, out=win_off[1:])
+        dac_off, win_off, s_off, lengths, n_windows, _padded = batch_tables([len(dac_reads[i]) for i in bucket])
         flat = np.concatenate([dac_reads[i] for i in bucket]) if len(bucket) else np.zeros(0, np.int16)
         d_dac = torch.from_numpy(flat).to(dev)
         d_doff = torch.from_numpy(dac_off).to(dev)
         d_woff = torch.from_numpy(win_off).to(dev)
-        x_all, x = calling.tiling_buffer(rule, int(win_off[-1]), len(bucket), dev)
+        x_all, x = calling.tiling_buffer(rule, n_windows, len(bucket), dev)
         engine.normalize_device(d_dac, d_doff, d_woff, out=x)
-        s_off = win_off * WINDOW_SIZE
         d_soff, d_len = torch.from_numpy(s_off).to(dev), torch.from_numpy(lengths).to(dev)
         result, probs = calling.spans_of_batch(engine, rule, x_all, d_soff, d_len, s_off, lengths)
         p_host = probs.cpu().numpy() if return_probs else None

@@ -17,8 +17,8 @@ import numpy as np
 
 from . import _native as N
 from . import calling
+from .batching import batch_tables, in_flight, quiet_gc
 from .calling import CallRule
-from .infer import WINDOW_SIZE
 
 
 class _Ticket(object):
@@ -59,7 +59,8 @@ class ReadPipeline(object):
         if overlap_kernels is None and "CATFISH_PIPE_OVERLAP" in os.environ:
             overlap_kernels = os.environ["CATFISH_PIPE_OVERLAP"] != "0"
         self.overlap_kernels = True if overlap_kernels is None else bool(overlap_kernels)
-        self.out = [None] * self.depth                           # pinned (starts, ends, counts) per in-flight slot, grown on demand
+        self.out = [None] * self.depth                           # pinned (starts, ends) per in-flight slot, grown on demand
+        self.counts = [torch.empty(2, dtype=torch.int64, pin_memory=True) for _ in range(self.depth)]     # ... and its two run counts
         self.inflight = [None] * self.depth
         self.cap = int(max_samples_per_batch)
         # two pinned staging buffers (double buffering)
@@ -90,6 +91,36 @@ class ReadPipeline(object):
         self.stage_free[slot].synchronize()                     # previous H2D out of this staging buffer is done
         return slot
 
+    def _native_load(self, slot, load, head, n_reads, n_threads):
+        """One call of the library's file loader into staging slot ``slot``: ``load(*head, staging buffer, its capacity, lengths out,
+        total out, threads)`` -> (rc, lengths, total, message).  The library's error text is per THREAD, so it is read here, on the
+        thread that made the call (another one would see a stale or empty text)."""
+        lengths = np.empty(max(0, n_reads), dtype=np.int64)
+        total = C.c_int64(0)
+        # threads: a quarter of the CPUs this rank owns (placement.bind: 32 per rank on an 8-GPU node), 2 .. 8: a 1110-file batch takes
+        # 6.8 / 2.3 / 1.8 / 1.7 ms with 1 / 4 / 8 / 16 threads (tools/exp_loader_threads.py) -- past 8 nothing is gained, and in
+        # bf16 the batch's forward pass takes 2.3 ms, so the loader sets the pace below that
+        rc = load(*head, C.c_void_p(self.stage[slot].data_ptr()), self.cap, lengths.ctypes.data_as(C.c_void_p), C.byref(total),
+                  int(self._file_threads if n_threads is None else n_threads))
+        msg = self.eng._lib.cf_last_error().decode("utf-8", "replace") if rc != N.CF_OK else ""
+        return rc, lengths, int(total.value), msg
+
+    def _launch_loaded(self, slot, loaded):
+        """What the outcome of ``_native_load`` means.  Out of host memory raises: it is not "a file of another kind", and loading the
+        same bytes again through the general loader would only hide it.  Any other failure (a file that is not a one-dimensional
+        int16 ``.npy``, reads that do not fit the staging buffer) or an empty batch -> None: the batch needs the general loader and
+        nothing has been consumed (``last_preload_note`` says why, naming the offending file).  Otherwise the batch is launched."""
+        rc, lengths, total, msg = loaded
+        if rc == N.CF_ERR_NOMEM:
+            raise N.CatfishHipError(rc, msg)
+        self.last_preload_note = msg
+        if rc != N.CF_OK or len(lengths) == 0:
+            return None
+        if slot != self.k % self.depth or self.inflight[slot] is not None:
+            raise RuntimeError("ReadPipeline: a preloaded batch must be launched before anything else is submitted")
+        self.k += 1
+        return self._launch(slot, lengths, total)
+
     def submit_files(self, paths, n_threads=None):
         """Launch one batch straight from files: one-dimensional little-endian int16 ``.npy`` reads (the format
         ``infer.load_dac`` takes when there is no HDF5) are read by the library's host thread pool (``cf_load_npy_int16``)
@@ -99,86 +130,37 @@ class ReadPipeline(object):
         paths = [os.fsencode(p) for p in paths]
         if not paths or not all(p.endswith(b".npy") for p in paths):      # infer.load_dac's own dispatch: only .npy takes this path
             return None
-        if n_threads is None:
-            # a quarter of the CPUs this rank owns (placement.bind: 32 per rank on an 8-GPU node), 2 .. 8: a 1110-file batch takes
-            # 6.8 / 2.3 / 1.8 / 1.7 ms with 1 / 4 / 8 / 16 threads (tools/exp_loader_threads.py) -- past 8 nothing is gained, and in
-            # bf16 the batch's forward pass takes 2.3 ms, so the loader sets the pace below that
-            n_threads = self._file_threads
         slot = self._claim_slot()
         blob = b"\x00".join(paths) + b"\x00"
         bounds = np.zeros(len(paths) + 1, dtype=np.int64)
         np.cumsum([len(p) + 1 for p in paths], out=bounds[1:])
-        lengths = np.empty(len(paths), dtype=np.int64)
-        total = C.c_int64(0)
-        rc = self.eng._lib.cf_load_npy_int16(blob, bounds.ctypes.data_as(C.c_void_p), len(paths),
-                                             C.c_void_p(self.stage[slot].data_ptr()), self.cap,
-                                             lengths.ctypes.data_as(C.c_void_p), C.byref(total), int(n_threads))
-        if rc == N.CF_ERR_NOMEM:
-            N.check(rc)         # out of host memory is not "a file of another kind": loading the same bytes again through the general loader would only hide it
-        if rc != N.CF_OK:
-            return None
-        self.k += 1
-        return self._launch(slot, lengths, int(total.value))
-
-    def submit_listing(self, listing, lo, hi, n_threads=None):
-        """``submit_files`` for entries [lo, hi) of a ``sharding.DirListing``: the library opens them relative to the listing's
-        directory (``cf_listing_load_npy_int16``), so not even a path string per file is built -- 12 500 files cost a rank 14 ms of
-        Python that way, a third of a bf16 shard's time.  None when the batch needs the general loader (an entry that is not a
-        ``.npy`` int16 vector, or reads that do not fit the staging buffer): nothing has been consumed then."""
-        if hi <= lo:
-            return None
-        slot = self._claim_slot()
-        lengths = np.empty(hi - lo, dtype=np.int64)
-        total = C.c_int64(0)
-        rc = self.eng._lib.cf_listing_load_npy_int16(listing._handle, int(lo), int(hi), C.c_void_p(self.stage[slot].data_ptr()), self.cap,
-                                                     lengths.ctypes.data_as(C.c_void_p), C.byref(total),
-                                                     int(self._file_threads if n_threads is None else n_threads))
-        if rc == N.CF_ERR_NOMEM:
-            N.check(rc)
-        if rc != N.CF_OK:
-            return None
-        self.k += 1
-        return self._launch(slot, lengths, int(total.value))
+        head = (blob, bounds.ctypes.data_as(C.c_void_p), len(paths))
+        return self._launch_loaded(slot, self._native_load(slot, self.eng._lib.cf_load_npy_int16, head, len(paths), n_threads))
 
     # ---- the same with the file reads one batch AHEAD, in a helper thread (the native call releases the GIL): while the main thread
     # waits for the GPU and assembles the results of the batch before, the next batch's files are read into the other staging slot.
     # In bf16 a 1110-read batch takes the GPU 2.3 ms and its files 2.1 ms to read: back to back on one thread the host set the pace.
     def preload_listing(self, listing, lo, hi, n_threads=None):
-        """Start reading entries [lo, hi) of ``listing`` into the staging slot the NEXT launch will use; -> a handle for
-        ``launch_preloaded``.  At most one preload may be pending, and nothing else may be submitted until it has been launched or
-        dropped (``drop_preloaded``): the caller is ``EngineBatchRunner.run_listing``."""
+        """Start reading entries [lo, hi) of ``listing`` (a ``sharding.DirListing``) into the staging slot the NEXT launch will use;
+        -> a handle for ``launch_preloaded``.  The library opens the entries relative to the listing's directory
+        (``cf_listing_load_npy_int16``), so not even a path string per file is built -- 12 500 files cost a rank 14 ms of Python that
+        way, a third of a bf16 shard's time.  At most one preload may be pending, and nothing else may be submitted until it has
+        been launched or dropped (``drop_preloaded``): the caller is ``EngineBatchRunner.run_listing``."""
         import concurrent.futures
         if getattr(self, "_loader", None) is None:
             self._loader = concurrent.futures.ThreadPoolExecutor(max_workers=1, thread_name_prefix="catfish-files")
         slot = self.k % self.depth
-        stage, cap = self.stage[slot], self.cap
-        threads = int(self._file_threads if n_threads is None else n_threads)
-        lib, handle, free = self.eng._lib, listing._handle, self.stage_free[slot]
+        load, head, free = self.eng._lib.cf_listing_load_npy_int16, (listing._handle, int(lo), int(hi)), self.stage_free[slot]
 
         def work():
             free.synchronize()                                   # the H2D copy that last read from this staging buffer is done
-            lengths = np.empty(max(0, hi - lo), dtype=np.int64)
-            total = C.c_int64(0)
-            rc = lib.cf_listing_load_npy_int16(handle, int(lo), int(hi), C.c_void_p(stage.data_ptr()), cap,
-                                               lengths.ctypes.data_as(C.c_void_p), C.byref(total), threads)
-            # the library's error text is per THREAD: read it here, where the call ran (the main thread would see a stale or empty one)
-            msg = lib.cf_last_error().decode("utf-8", "replace") if rc != N.CF_OK else ""
-            return rc, lengths, int(total.value), msg
+            return self._native_load(slot, load, head, hi - lo, n_threads)
         return (slot, self._loader.submit(work))
 
     def launch_preloaded(self, pre):
         """Launch the batch ``preload_listing`` read.  None when it needs the general loader (nothing has been consumed)."""
         slot, fut = pre
-        rc, lengths, total, msg = fut.result()
-        if rc == N.CF_ERR_NOMEM:
-            raise N.CatfishHipError(rc, msg)
-        self.last_preload_note = msg if rc != N.CF_OK else ""    # why the batch goes to the general loader (names the offending file)
-        if rc != N.CF_OK or len(lengths) == 0:
-            return None
-        if slot != self.k % self.depth or self.inflight[slot] is not None:
-            raise RuntimeError("ReadPipeline: a preloaded batch must be launched before anything else is submitted")
-        self.k += 1
-        return self._launch(slot, lengths, total)
+        return self._launch_loaded(slot, fut.result())
 
     @staticmethod
     def drop_preloaded(pre):
@@ -208,33 +190,39 @@ class ReadPipeline(object):
             np.concatenate(dac_reads, out=host[:total], casting="unsafe")     # one C call instead of a Python loop over the reads
         return self._launch(slot, lengths, total)
 
+    def _pinned(self, store, slot, rows, *kinds):
+        """``store[slot]``: this slot's pinned buffers, one per (dtype, trailing shape) of ``kinds`` with ``rows`` rows each --
+        allocated at first use and again, larger, when a batch needs more rows than they have."""
+        if store[slot] is None or store[slot][0].shape[0] < rows:
+            store[slot] = tuple(self.torch.empty((rows,) + tail, dtype=dtype, pin_memory=True) for dtype, tail in kinds)
+        return store[slot]
+
+    def _stage_tables(self, slot, tables):
+        """The four small tables of a batch (``batching.batch_tables``) end to end in this slot's pinned block.  They go up from
+        PINNED memory too, as one copy: a pageable source makes the runtime pin user pages for the transfer, and host allocator
+        activity (munmap) near such mappings stalls the GPU queues."""
+        n_r = len(tables.lengths)
+        n_tab = 4 * (n_r + 1)
+        block, = self._pinned(self.tab, slot, max(n_tab, 1024), (self.torch.int64, ()))
+        tab = block.numpy()
+        tab[0:n_r + 1] = tables.dac_off
+        tab[n_r + 1:2 * n_r + 2] = tables.win_off
+        tab[2 * n_r + 2:3 * n_r + 3] = tables.s_off
+        tab[3 * n_r + 3:4 * n_r + 3] = tables.lengths
+        return block[:n_tab]
+
     def _launch(self, slot, lengths, total):
         """Everything after staging: tables up, H2D, normalise, forward, post-process, run lists down."""
         torch, rule = self.torch, self.rule
-        n_reads = len(lengths)
-        dac_off = np.zeros(n_reads + 1, dtype=np.int64)
-        np.cumsum(lengths, out=dac_off[1:])
-        n_win = lengths // WINDOW_SIZE + 1                      # infer.py:32-36: a multiple of 35 gets a full extra window
-        win_off = np.zeros(n_reads + 1, dtype=np.int64)
-        np.cumsum(n_win, out=win_off[1:])
-        # the four small tables go up from PINNED memory too, as one copy: a pageable source makes the runtime pin user
-        # pages for the transfer, and host allocator activity (munmap) near such mappings stalls the GPU queues
-        n_r = n_reads
-        n_tab = 4 * (n_r + 1)
-        if self.tab[slot] is None or self.tab[slot].numel() < n_tab:
-            self.tab[slot] = torch.empty(max(n_tab, 1024), dtype=torch.int64, pin_memory=True)
-        tab = self.tab[slot].numpy()
-        tab[0:n_r + 1] = dac_off
-        tab[n_r + 1:2 * n_r + 2] = win_off
-        tab[2 * n_r + 2:3 * n_r + 3] = win_off * WINDOW_SIZE
-        tab[3 * n_r + 3:4 * n_r + 3] = lengths
+        n_r = len(lengths)
+        tables = batch_tables(lengths)
+        tab = self._stage_tables(slot, tables)
         with torch.cuda.stream(self.copy):
             d_dac = self.stage[slot][:total].to(self.dev, non_blocking=True)
-            d_tab = self.tab[slot][:n_tab].to(self.dev, non_blocking=True)
+            d_tab = tab.to(self.dev, non_blocking=True)
             d_doff, d_woff = d_tab[0:n_r + 1], d_tab[n_r + 1:2 * n_r + 2]
             d_soff, d_len = d_tab[2 * n_r + 2:3 * n_r + 3], d_tab[3 * n_r + 3:4 * n_r + 3]
             self.stage_free[slot].record(self.copy)
-            n_windows = int(win_off[-1])
             h2d_done = torch.cuda.Event()
             h2d_done.record(self.copy)
         k_norm = self.copy if self.overlap_kernels else self.compute
@@ -243,9 +231,9 @@ class ReadPipeline(object):
             # overlap mode: normalisation rides on the copy stream and overlaps the previous batch's biGRU kernels (which leave
             # wave slots and 15 KiB of LDS free on every CU) instead of delaying this batch's
             k_norm.wait_event(h2d_done)
-            x_all, x = calling.tiling_buffer(rule, n_windows, n_reads, self.dev)
+            x_all, x = calling.tiling_buffer(rule, tables.n_windows, n_r, self.dev)
             self.eng.normalize_device(d_dac, d_doff, d_woff, out=x, stream=k_norm)
-            total = n_windows * WINDOW_SIZE
+            total = tables.n_samples
             calling.retile_tilings(self.eng, rule, x_all, d_soff, d_len, total, stream=k_norm)
             copied = torch.cuda.Event()
             copied.record(k_norm)
@@ -267,18 +255,10 @@ class ReadPipeline(object):
                 max_runs=max_runs)
             spans_done = torch.cuda.Event()
             spans_done.record(k_post)
-        if self.out[slot] is None or self.out[slot][0].numel() < max_runs:
-            self.out[slot] = (torch.empty(max_runs, dtype=torch.int64, pin_memory=True),
-                              torch.empty(max_runs, dtype=torch.int64, pin_memory=True),
-                              torch.empty(2, dtype=torch.int64, pin_memory=True))
-        t.starts_h, t.ends_h, t.counts_h = self.out[slot]
-        t.rows_h = None
-        if self.scores:
-            if self.out_scores[slot] is None or self.out_scores[slot][0].numel() < max_runs:
-                self.out_scores[slot] = (torch.empty(max_runs, dtype=torch.int64, pin_memory=True),
-                                         torch.empty(max_runs, 3, dtype=torch.float64, pin_memory=True),
-                                         torch.empty(max_runs, 2, dtype=torch.float32, pin_memory=True))
-            t.rows_h = self.out_scores[slot]
+        t.starts_h, t.ends_h = self._pinned(self.out, slot, max_runs, (torch.int64, ()), (torch.int64, ()))
+        t.counts_h = self.counts[slot]
+        t.rows_h = self._pinned(self.out_scores, slot, max_runs, (torch.int64, ()), (torch.float64, (3,)),
+                                (torch.float32, (2,))) if self.scores else None
         with torch.cuda.stream(self.down):                       # D2H of the (unsorted) run lists, whole capacity: ~1 MB
             self.down.wait_event(spans_done)
             t.starts_h[:max_runs].copy_(t.starts, non_blocking=True)
@@ -289,7 +269,7 @@ class ReadPipeline(object):
                     h[:max_runs].copy_(d, non_blocking=True)
             t.done = torch.cuda.Event()
             t.done.record(self.down)
-        t.lengths, t.s_off, t.max_runs, t.labels = lengths, win_off * WINDOW_SIZE, max_runs, labels
+        t.lengths, t.s_off, t.max_runs, t.labels = lengths, tables.s_off, max_runs, labels
         t.keep = (d_dac, d_tab, x, probs, slot)                  # keep device buffers alive until collected
         t.tilings = (x_all, probs_all) if rule.voted else None   # every tiling's input and probabilities, alive until collected
         self.inflight[slot] = t
@@ -337,18 +317,8 @@ class ReadPipeline(object):
 
     def run(self, batches, as_lists=True):
         """Iterate over batches (lists of int16 reads) with up to ``depth - 1`` batches in flight ahead; yields results in order."""
-        from collections import deque
-        from .batching import quiet_gc
-        pending = deque()
         with quiet_gc():                      # list building must not trigger collections that walk the whole process
-            for b in batches:
-                if len(pending) == self.depth:
-                    yield self.collect(pending.popleft(), as_lists)
-                pending.append(self.submit(b))
-                if len(pending) == self.depth:
-                    yield self.collect(pending.popleft(), as_lists)
-            while pending:
-                yield self.collect(pending.popleft(), as_lists)
+            yield from in_flight((self.submit(b) for b in batches), self.depth, lambda t: self.collect(t, as_lists))
 
 
 StreamingPipeline = ReadPipeline      # the name the documents use for it

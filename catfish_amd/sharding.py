@@ -24,11 +24,14 @@ import os
 
 import numpy as np
 
-from .infer import WINDOW_SIZE, padding_size_for
+from . import batching
+from .batching import engine_of, in_flight, quiet_gc
+from .infer import WINDOW_SIZE
 
 
 def windows_of(length, window=WINDOW_SIZE):
-    return (int(length) + padding_size_for(int(length), window)) // window
+    """Windows of ONE read, as an int (the rule is ``batching.windows_of``'s)."""
+    return int(batching._windows_for([int(length)], window)[0])
 
 
 def shard_costs(costs, world_size):
@@ -70,9 +73,12 @@ def shard_contiguous(costs, world_size):
 
 def shard_reads(lengths, world_size):
     """LPT partition of reads by window count (the unit of device work)."""
-    return shard_costs([windows_of(n) for n in lengths], world_size)
+    return shard_costs(batching.windows_of(lengths), world_size)
 
 
+# Rank and world size are resolved in two ways, on purpose: ``run_sharded_indexed`` asks the process group (rank 0 of 1 without
+# one); ``chunk_files_local`` and the empty case of ``infer_reads_sharded`` ask the launcher's environment (``dist_env``).  The two
+# differ when only one of them is set, so neither stands in for the other.
 def dist_env():
     """(rank, world_size, local_rank) from the launcher's environment (torch.distributed.run); 0, 1, 0 without one."""
     return (int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1")),
@@ -488,9 +494,7 @@ class EngineBatchRunner(object):
 
     def __init__(self, model, max_samples_per_batch, threshold=0.5, min_run=15, max_gap=0, phases=(0,), vote_weight="mean"):
         from .pipeline import ReadPipeline
-        self.engine = model.engine if hasattr(model, "engine") else model
-        if self.engine is None:
-            raise RuntimeError("network has no weights: call restore_network() or initialize_network() first")
+        self.engine = engine_of(model)
         self.max_samples = int(max_samples_per_batch)
         # one rule (calling.CallRule) for both routes: the pipeline checks it
         self.pipe = ReadPipeline(self.engine, self.max_samples, threshold=threshold, min_run=min_run, max_gap=max_gap, phases=phases,
@@ -500,68 +504,56 @@ class EngineBatchRunner(object):
     def run(self, batches, compact=False):
         """``batches``: iterable of lists of raw reads -> yields per batch, in order, ``[(spans, length)]`` or (``compact``)
         a ``SpanTable`` of the batch."""
-        self.compact = bool(compact)
-        return self._drive(self._submit_reads(reads) for reads in batches)
+        return self._drive((self._submit_reads(reads) for reads in batches), compact)
 
     def run_files(self, path_batches, compact=False):
         """The same from batches of FILE NAMES: int16 ``.npy`` reads go from disk into the pipeline's pinned staging buffer
         through the library's host thread pool (``ReadPipeline.submit_files``); a batch that needs the general loader (other
         formats, or more samples than the size on disk suggested) is loaded with ``infer.load_dac`` and re-cut by its true
         lengths.  Results come out in the order of the names, one item per submitted batch."""
-        self.compact = bool(compact)
-        from .infer import load_dac
-
-        def items():
-            for paths in path_batches:
-                ticket = self.pipe.submit_files(paths)
-                if ticket is not None:
-                    yield (ticket, None)
-                    continue
-                reads = [load_dac(p) for p in paths]
-                for idx in _batches_by_samples(list(range(len(reads))), [_padded(len(r)) for r in reads], self.max_samples):
-                    yield self._submit_reads([reads[i] for i in idx])
-        return self._drive(items())
+        return self._drive(self._file_batches(path_batches, lambda paths: paths, lambda paths, _pre: self.pipe.submit_files(paths)),
+                           compact)
 
     def run_listing(self, paths, ranges, compact=False):
         """``run_files`` for index ranges of a ``ListingPaths``: batch [lo, hi) goes from the listing's directory into the pinned
-        staging buffer without a path string per file (``ReadPipeline.submit_listing``); a batch that needs the general loader is
-        handled like in ``run_files``, from the paths of just that batch."""
-        if getattr(self, "pipe", None) is None or type(self).run_files is not EngineBatchRunner.run_files:
-            # a runner that brings its own file handling (tests stand the oracle in for the engine): hand it the paths
-            return self.run_files(([paths[i] for i in range(lo, hi)] for lo, hi in ranges), compact)
-        self.compact = bool(compact)
-        from .infer import load_dac
+        staging buffer without a path string per file, and its files are read one batch AHEAD (``ReadPipeline.preload_listing``, a
+        helper thread) while the main thread waits for the GPU and assembles batch k - 1; a batch that needs the general loader
+        is handled like in ``run_files``, from the paths of just that batch."""
+        return self._drive(self._file_batches(ranges, lambda r: [paths[i] for i in range(*r)],
+                                              lambda _r, pre: self.pipe.launch_preloaded(pre),
+                                              ahead=lambda r: self.pipe.preload_listing(paths.listing, *r)), compact)
 
-        def items():
-            # the files of batch k + 1 are read (helper thread, ``preload_listing``) while the main thread waits for the GPU and
-            # assembles batch k - 1: a preload starts right after the launch before it and is launched first thing afterwards
-            pre = None
-            try:
-                todo = iter(ranges)
+    def _file_batches(self, batches, names_of, stage, ahead=None):
+        """The one walk over batches of files -> what ``_drive`` takes.  ``stage(batch, its preload)`` hands a batch to the pipeline
+        (a ticket) or refuses it (None: nothing consumed); a refused batch goes through the general loader -- ``infer.load_dac``
+        over ``names_of(batch)``, re-cut by the true padded lengths -- with nothing preloading meanwhile.  ``ahead(batch)``, when
+        given, starts the NEXT batch's preload right after each launch (after a refused batch: after its re-cut); at most one is
+        pending, and one that will not be launched is dropped however the walk ends."""
+        from .infer import load_dac
+        def start(batch):
+            return None if ahead is None or batch is None else ahead(batch)
+        pre = None
+        try:
+            todo = iter(batches)
+            nxt = next(todo, None)
+            pre = start(nxt)
+            while nxt is not None:
+                cur, mine, pre = nxt, pre, None
+                ticket = stage(cur, mine)
                 nxt = next(todo, None)
-                if nxt is not None:
-                    pre = self.pipe.preload_listing(paths.listing, *nxt)
-                while nxt is not None:
-                    lo, hi = nxt
-                    mine, pre = pre, None
-                    ticket = self.pipe.launch_preloaded(mine)
-                    nxt = next(todo, None)
-                    if ticket is not None:
-                        if nxt is not None:
-                            pre = self.pipe.preload_listing(paths.listing, *nxt)
-                        yield (ticket, None)
-                        continue
-                    reads = [load_dac(paths[i]) for i in range(lo, hi)]          # general loader, nothing preloading meanwhile
-                    for idx in _batches_by_samples(list(range(len(reads))), [_padded(len(r)) for r in reads], self.max_samples):
-                        yield self._submit_reads([reads[i] for i in idx])
-                    if nxt is not None:
-                        pre = self.pipe.preload_listing(paths.listing, *nxt)
-            finally:
+                if ticket is not None:
+                    pre = start(nxt)
+                    yield (ticket, None)
+                    continue
+                reads = [load_dac(p) for p in names_of(cur)]
+                for idx in _batches_by_samples(list(range(len(reads))), [_padded(len(r)) for r in reads], self.max_samples):
+                    yield self._submit_reads([reads[i] for i in idx])
+                pre = start(nxt)
+        finally:
+            if pre is not None:
                 self.pipe.drop_preloaded(pre)
-        return self._drive(items())
 
     def _submit_reads(self, reads):
-        from . import batching
         from .infer import is_dac, normalize_raw_signal
         if all(is_dac(r) for r in reads):
             return (self.pipe.submit([np.ascontiguousarray(r, dtype=np.int16) for r in reads]), None)
@@ -571,17 +563,11 @@ class EngineBatchRunner(object):
                                            threshold=self.threshold, min_run=self.min_run, max_gap=self.max_gap,
                                            phases=self.phases, vote_weight=self.vote_weight))
 
-    def _drive(self, items):
+    def _drive(self, items, compact):
         """Up to the pipeline's depth of batches in flight: ``items`` submits lazily (each element is (ticket, host-path results
         or None)), results are finished in order."""
-        from collections import deque
-        pending = deque()
-        for item in items:
-            pending.append(item)
-            if len(pending) == self.pipe.depth:
-                yield self._finish(pending.popleft())
-        while pending:
-            yield self._finish(pending.popleft())
+        self.compact = bool(compact)
+        return in_flight(items, self.pipe.depth, self._finish)
 
     def _finish(self, item):
         ticket, host_res = item
@@ -621,30 +607,21 @@ def _prefetched(gen, depth=3):
         yield item
 
 
+def _own_file_handling(runner):
+    """The one place that says whether a runner reads files ITS way rather than through ``EngineBatchRunner``'s pipeline: it has no
+    ``pipe``, or its class overrides ``run_files`` (tests stand the oracle in for the engine like that, or rebind the class).  Such
+    a runner is handed path names, never ranges of a native listing."""
+    return getattr(runner, "pipe", None) is None or getattr(type(runner), "run_files", None) is not EngineBatchRunner.run_files
+
+
 def _spans_of_shard(model, reads, mine, lengths, load_fn, max_samples_per_batch, batch_runner, compact, size_hints=None):
     """This rank's device work: the reads ``mine`` (indices into ``reads``) through the batch runner, batches cut at
     ``max_samples_per_batch`` samples, files loaded a bounded number of batches ahead.  ``compact``: a ``SpanTable`` (arrays
     end to end) instead of ``[(spans, length)]`` lists.  ``size_hints`` (estimated samples per item, e.g. from the size on
     disk): ``reads`` are file names for ``infer.load_dac`` and the runner may read them itself (``run_files``: the library's
     native loader straight into pinned memory instead of one Python call per file)."""
+    from functools import partial
     runner = batch_runner if batch_runner is not None else EngineBatchRunner(model, max_samples_per_batch)
-    if size_hints is not None and isinstance(reads, ListingPaths) and hasattr(runner, "run_listing"):
-        # contiguous indices of a native listing: the batches travel as (lo, hi), the names stay in the library
-        ranges = ((idx[0], idx[-1] + 1) for idx in _batches_by_samples(mine, size_hints, max_samples_per_batch, ramp=RAMP))
-        if compact:
-            return SpanTable.concat(list(runner.run_listing(reads, ranges, compact=True)))
-        out = []
-        for res in runner.run_listing(reads, ranges):
-            out.extend(res)
-        return out
-    if size_hints is not None and hasattr(runner, "run_files"):
-        path_batches = ([reads[i] for i in idx] for idx in _batches_by_samples(mine, size_hints, max_samples_per_batch, ramp=RAMP))
-        if compact:
-            return SpanTable.concat(list(runner.run_files(path_batches, compact=True)))
-        out = []
-        for res in runner.run_files(path_batches):
-            out.extend(res)
-        return out
 
     def batches():
         if lengths is not None:
@@ -661,15 +638,27 @@ def _spans_of_shard(model, reads, mine, lengths, load_fn, max_samples_per_batch,
                 tot += len(r)
             if cur:
                 yield cur
-    source = _prefetched(batches(), depth=3) if load_fn is not None else batches()
+
+    # the route, chosen once; only a runner that is handed loaded reads may be one that knows no ``compact=``
+    takes_compact = True
+    if size_hints is not None and hasattr(runner, "run_files"):
+        cuts = _batches_by_samples(mine, size_hints, max_samples_per_batch, ramp=RAMP)
+        if isinstance(reads, ListingPaths) and not _own_file_handling(runner):
+            # contiguous indices of a native listing: the batches travel as (lo, hi), the names stay in the library
+            results = partial(runner.run_listing, reads, ((idx[0], idx[-1] + 1) for idx in cuts))
+        else:
+            results = partial(runner.run_files, ([reads[i] for i in idx] for idx in cuts))
+    else:
+        results = partial(runner.run, _prefetched(batches(), depth=3) if load_fn is not None else batches())
+        takes_compact = isinstance(runner, EngineBatchRunner)
     if compact:
-        if isinstance(runner, EngineBatchRunner):
-            return SpanTable.concat(list(runner.run(source, compact=True)))
-        return SpanTable.concat([SpanTable.from_lists(res) for res in runner.run(source)])
+        if takes_compact:
+            return SpanTable.concat(list(results(compact=True)))
+        return SpanTable.concat([SpanTable.from_lists(res) for res in results()])
     # the per-read lists of batch k are built while the GPU runs batch k + 1 (0.3 ms per batch with the cyclic collector
     # off, see batching.quiet_gc)
     out = []
-    for res in runner.run(source):
+    for res in results():
         out.extend(res)
     return out
 
@@ -699,7 +688,7 @@ def infer_reads_sharded(model, reads, lengths=None, load_fn=None, max_samples_pe
     if costs is None:
         if lengths is None:
             raise ValueError("infer_reads_sharded: pass lengths or costs together with load_fn")
-        costs = [windows_of(x) for x in lengths]
+        costs = batching.windows_of(lengths).tolist()
     if max_samples_per_batch is None:
         max_samples_per_batch = 32768 * WINDOW_SIZE
     if n == 0:
@@ -715,7 +704,6 @@ def infer_reads_sharded(model, reads, lengths=None, load_fn=None, max_samples_pe
         return _spans_of_shard(model, reads, mine, lengths, load_fn, max_samples_per_batch, batch_runner, compact,
                                size_hints=size_hints)
 
-    from .batching import quiet_gc
     with quiet_gc():
         if as_table:
             return run_sharded_indexed(costs, work, rank=rank, world_size=world_size, gather_group=gather_group,
@@ -734,20 +722,20 @@ def _file_costs(paths):
     return out
 
 
-def _padded(n, window=WINDOW_SIZE):
-    """Samples a read of ``n`` samples occupies in a packed launch (infer.py:32-36: whole windows, a multiple gets an extra one)."""
-    return (int(n) // window + 1) * window
+def _padded(n):
+    """Samples a read of ``n`` samples occupies in a packed launch: whole windows (``batching.windows_of``)."""
+    return windows_of(n) * WINDOW_SIZE
 
 
 def _sample_hints(file_sizes):
     """What a file will occupy in a packed launch, estimated from its size on disk: its samples (int16 behind numpy's usual 128-byte
-    header) rounded up to whole windows the way ``infer.py:32-36`` pads them (a multiple of 35 gets a full extra window).  Only used
+    header) rounded up to whole windows (``batching.windows_of``).  Only used
     to cut batches before anything is read -- a batch that turns out too big is re-cut by its true lengths.  Counting PADDED samples
     matters: a batch is capped at the engine's windows per pass, and 1120 reads of 4096 samples are 132 160 windows, not 131 072 --
     every full batch used to spill 1088 windows into a second, nearly empty forward pass (0.42 of 2.9 ms per batch in bf16; kernel trace
     of round 5)."""
     n = np.maximum(1, (np.asarray(file_sizes, dtype=np.int64) - 128) // 2)
-    return (n // WINDOW_SIZE + 1) * WINDOW_SIZE
+    return batching.windows_of(n) * WINDOW_SIZE
 
 
 def infer_files_sharded(model, paths, max_samples_per_batch=None, batch_runner=None, rank=None, world_size=None,
@@ -785,7 +773,6 @@ def chunk_files_local(model, paths, chunk_size=1000, max_samples_per_batch=None,
     if len(costs) != len(paths):
         raise ValueError("file_sizes must hold one size per path")
     mine = shard_contiguous(costs, world_size)[rank]
-    from .batching import quiet_gc
     with quiet_gc():
         t0 = time.perf_counter()
         table = _spans_of_shard(model, paths, mine, None, load_dac, max_samples_per_batch, batch_runner, True,
