@@ -2673,6 +2673,7 @@ extern "C" int cf_opt_step(cf_model* m, int32_t kind, float* params, const float
 #include "validation_borders.hpp" // ... cf_validation_run_borders the rest of check_hp: how far called borders miss, and the interruptions
 #include "validation_bases.hpp" // ... cf_validation_run_bases the same runs by base and by length in bases, read from the set's base map
 #include "validation_curve.hpp" // ... and cf_validation_curve bins the probabilities at every threshold step: whole ROC / PR curves and AUC
+#include "validation_scores.hpp" // ... and cf_validation_run_scores the probabilities under the runs of every state: what the misses scored
 #include "tilings.hpp"          // shifted-window voting: cf_retile_windows lays out K tilings of a batch, cf_vote_tilings merges their results
 #include "label_events.hpp"     // labels from event tables: cf_label_events classifies a batch's events and expands them to per-sample labels
 #include "label_moves.hpp"      // labels from a basecaller's move table: cf_label_moves merges stays into their heads, then classifies and expands

@@ -26,6 +26,35 @@
 
 #define CF_CURVE_THREADS 256
 
+// Steps 2 and 3 over the `span` keys in s_key (a power of two in [2, 2 * CF_SCORE_CHUNK]; the caller's barrier is behind their
+// writes): the bitonic sort, then one atomic per run of equal keys below `cells`.  validation_scores.hpp combines its keys the same way.
+__device__ __forceinline__ void vc_sort_count(uint32_t* s_key, unsigned span, unsigned cells, unsigned long long* __restrict__ hist) {
+    for (unsigned k = 2; k <= span; k <<= 1) {
+        for (unsigned j = k >> 1; j >= 1; j >>= 1) {
+            for (unsigned t = threadIdx.x; t < (span >> 1); t += CF_CURVE_THREADS) {
+                const unsigned i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i | j;              // i < l < span
+                const uint32_t a = s_key[i], b = s_key[l];
+                if ((a > b) == ((i & k) == 0u)) {                                  // ascending where bit k of i is clear
+                    s_key[i] = b;
+                    s_key[l] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (unsigned i = threadIdx.x; i < span; i += CF_CURVE_THREADS) {
+        const uint32_t key = s_key[i];
+        if (key >= cells || (i > 0u && s_key[i - 1u] == key)) continue;            // no sample here, or not the first of its run
+        unsigned lo = i + 1u, hi = span;                                           // the run ends before the first other key in (i, span]
+        while (lo < hi) {
+            const unsigned mid = (lo + hi) >> 1;
+            if (s_key[mid] == key) lo = mid + 1u;
+            else hi = mid;
+        }
+        atomicAdd(&hist[key], (unsigned long long)(lo - i));
+    }
+}
+
 __global__ __launch_bounds__(CF_CURVE_THREADS) void validation_curve_kernel(const float* __restrict__ probs, const uint8_t* __restrict__ y,
                                                                             const int64_t* __restrict__ bounds,
                                                                             const int64_t* __restrict__ length, int64_t total, int shift,
@@ -48,30 +77,7 @@ __global__ __launch_bounds__(CF_CURVE_THREADS) void validation_curve_kernel(cons
             s_key[i] = key;
         }
         __syncthreads();
-        for (unsigned k = 2; k <= span; k <<= 1) {
-            for (unsigned j = k >> 1; j >= 1; j >>= 1) {
-                for (unsigned t = threadIdx.x; t < (span >> 1); t += CF_CURVE_THREADS) {
-                    const unsigned i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i | j;          // i < l < span
-                    const uint32_t a = s_key[i], b = s_key[l];
-                    if ((a > b) == ((i & k) == 0u)) {                              // ascending where bit k of i is clear
-                        s_key[i] = b;
-                        s_key[l] = a;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        for (unsigned i = threadIdx.x; i < span; i += CF_CURVE_THREADS) {
-            const uint32_t key = s_key[i];
-            if (key >= cells || (i > 0u && s_key[i - 1u] == key)) continue;        // no sample here, or not the first of its run
-            unsigned lo = i + 1u, hi = span;                                       // the run ends before the first other key in (i, span]
-            while (lo < hi) {
-                const unsigned mid = (lo + hi) >> 1;
-                if (s_key[mid] == key) lo = mid + 1u;
-                else hi = mid;
-            }
-            atomicAdd(&hist[key], (unsigned long long)(lo - i));
-        }
+        vc_sort_count(s_key, span, cells, hist);
         __syncthreads();                                                           // s_key is written again by this workgroup's next chunk
     }
 }

@@ -18,7 +18,9 @@ how many homopolymers a round found, bit for bit), ``run_borders_host`` what the
 ``run_bases_host`` what the base step returns (``cf_validation_run_bases``, csrc/validation_bases.hpp: the same runs by base and by
 length in bases, from the set's base map, bit for bit), ``curve_host`` what the curve step returns (``cf_validation_curve``,
 csrc/validation_curve.hpp: the round's probabilities binned at every threshold step, bit for bit; ``curves_from_histogram`` turns
-that table into the whole ROC and precision-recall curves, their areas and the best F1).  The object is host-only until ``device_arrays`` is called and usable without a GPU.
+that table into the whole ROC and precision-recall curves, their areas and the best F1), ``run_scores_host`` what the score step
+returns (``cf_validation_run_scores``, csrc/validation_scores.hpp: the probabilities under the runs of every state, bit for bit;
+``run_score_summary`` gives their count, mean and quartiles).  The object is host-only until ``device_arrays`` is called and usable without a GPU.
 What a round on the card decides before its first launch -- the checked options, the buffer sizes, the layout of the result buffer and
 the named results -- is ``validation_round`` (host-only too).
 """
@@ -472,6 +474,82 @@ def curves_from_histogram(hist, shift=CURVE_SHIFT):
                         "recall": float(recall[best])}}
 
 
+SCORE_SHIFT_MIN, SCORE_SHIFT_MAX, RUN_SCORE_SHIFT = 14, 22, 16     # VS_SHIFT_MIN / VS_SHIFT_MAX, csrc/validation_scores_word.hpp
+
+
+def check_score_shift(shift):
+    """``shift`` as an int in 14 .. 22 (ValueError otherwise; no bool, no fraction).  At 14 and sixteen thresholds a score table is
+    6.2 M cells already; below it would be gigabytes."""
+    if isinstance(shift, (bool, np.bool_)) or not isinstance(shift, (int, np.integer)) or not SCORE_SHIFT_MIN <= shift <= SCORE_SHIFT_MAX:
+        raise ValueError("score shift must be an int in %d .. %d, got %r" % (SCORE_SHIFT_MIN, SCORE_SHIFT_MAX, shift))
+    return int(shift)
+
+
+def score_cells(shift=RUN_SCORE_SHIFT):
+    """Cells of one threshold's score table: ``2 * 3 * (curve_bins(shift) + 1)`` -- 97 548 at shift 16."""
+    return 2 * len(RUN_STATES) * (curve_bins(check_score_shift(shift)) + 1)
+
+
+def run_scores_host(probs, y, bounds, lengths, thresholds, shift=RUN_SCORE_SHIFT, min_run=15, max_gap=0):
+    """What ``cf_validation_run_scores`` returns, in numpy: int64 [K, 2, 3, NB + 1], NB = ``curve_bins(shift)`` -- per threshold,
+    kind and state of a run the histogram of the probabilities of the samples under those runs, and in the last cell their
+    fixed-point sum (the reference's offline networks/process_output.py:15-137 ``check_for_false_neg`` collects
+    ``predicted_scores[a:b + 1]`` of every missed homopolymer, and ``main`` :276-357 those of the "tp" and "fp" runs).
+
+    Stretches, thresholds, the corrected prediction (``max_gap`` included), runs (``_runs_of``, the last-sample rule included),
+    kinds and states are ``run_states_host``'s.  Every sample ``start .. end`` of a run of kind q and state s at threshold k adds one
+    to ``out[k, q, s, curve_bin(bits of float32 p, shift)]`` and ``base_votes.q_of(p)`` -- ``floor(double(p) * 2^32)``, NaN and
+    ``p < 0`` as 0, ``p > 1`` as 2^32 -- to ``out[k, q, s, NB]``.  The sample the last-sample rule adds to a run counts with its own
+    probability (the reference's slice counts it too), and a sample that lies in a true run and in a called run counts once under
+    each kind.  ``shift`` is an int in 14 .. 22 (``check_score_shift``)."""
+    from .base_votes import q_of
+    nb = curve_bins(check_score_shift(shift))
+    stretches = _stretch_predictions(probs, y, bounds, lengths, thresholds, min_run, max_gap)
+    p32 = np.ascontiguousarray(np.asarray(probs, dtype=np.float32).reshape(-1))
+    out = np.zeros((len(thresholds), 2, 3, nb + 1), dtype=np.int64)
+    for b0, n, truth, preds in stretches:
+        bins = curve_bin(p32[b0:b0 + n].view(np.uint32), shift)
+        q_to = np.concatenate(([0], np.cumsum(q_of(p32[b0:b0 + n]).astype(np.int64))))
+        for k, pred in preds:
+            for kind, mask, other in _kinds(truth, pred):
+                starts, ends = _runs_of(mask)
+                if not starts.size:
+                    continue
+                states = _states_of(starts, ends, other)
+                edge = np.zeros(n + 1, dtype=np.int64)                     # the state of every sample's run, + 1; 0 outside the runs
+                np.add.at(edge, starts, states + 1)
+                np.add.at(edge, ends + 1, -(states + 1))
+                painted = np.cumsum(edge[:n])
+                inside = painted > 0
+                out[k, kind, :, :nb] += np.bincount((painted[inside] - 1) * nb + bins[inside], minlength=3 * nb).reshape(3, nb)
+                np.add.at(out[k, kind, :, nb], states, q_to[ends + 1] - q_to[starts])
+    return out
+
+
+def run_score_summary(table_k, shift=RUN_SCORE_SHIFT):
+    """One threshold's ``[2, 3, NB + 1]`` score table -> ``[kind][state]`` dicts: ``n`` (samples), ``mean`` = sum / (n * 2^32), and
+    ``q1`` / ``median`` / ``q3`` as ``(low, high)``: ``low`` is the lower edge of the bin that holds the lower-quantile sample (sample
+    ``ceil(n * f)`` of the sorted ones, as ``_lower_median`` picks the middle one), ``high`` the lower edge of the next bin, 1.0 for
+    the top bin -- the sample's probability lies in ``[low, high)``, or is clamped into the top bin.  An empty row gives None for
+    all of them but ``n``."""
+    nb = curve_bins(check_score_shift(shift))
+    table = np.asarray(table_k)
+    if table.shape != (2, 3, nb + 1):
+        raise ValueError("one threshold's score table at shift %d is [2, 3, %d], got %s" % (shift, nb + 1, table.shape))
+    edges = np.concatenate((curve_thresholds(shift).astype(np.float64), [1.0]))
+
+    def summary(row):
+        n = int(row[:nb].sum())
+        if not n:
+            return {"n": 0, "mean": None, "q1": None, "median": None, "q3": None}
+        upto = np.cumsum(row[:nb])
+        span = lambda rank: (lambda at: (float(edges[at]), float(edges[at + 1])))(int(np.searchsorted(upto, rank)))     # noqa: E731
+        return {"n": n, "mean": int(row[nb]) / (n << 32),"q1": span((n + 3) // 4), "median": span((n + 1) // 2),
+                "q3": span((3 * n + 3) // 4)}
+
+    return [[summary(table[kind, state]) for state in range(3)] for kind in range(2)]
+
+
 def finish(right, ce_sum, counts_k, bounds, tails):
     """The divisions of ``train_validate.score_validation_batch`` on the raw results: (acc float32 [n], loss float32 [n],
     (tp, fp, tn, fn)).  ``acc`` = count as float32 / size as float32; ``loss`` = ``ce_sum / size`` in double, then float32;
@@ -691,6 +769,7 @@ class DeviceValidationSet(object):
     run_borders_host = staticmethod(run_borders_host)
     run_bases_host = staticmethod(run_bases_host)
     curve_host = staticmethod(curve_host)
+    run_scores_host = staticmethod(run_scores_host)
     finish = staticmethod(finish)
     layout = staticmethod(layout)
 

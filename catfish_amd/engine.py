@@ -542,6 +542,29 @@ class HipEngine(object):
             int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()),
             C.c_void_p(stream.cuda_stream)))
 
+    def run_scores_work_bytes(self, total, n_thresholds):
+        """Bytes of work space ``run_scores_validation`` needs: the labels of ``run_states_work_bytes`` and a byte of paint per sample
+        and threshold behind them."""
+        return int(self._lib.cf_validation_run_scores_work_bytes(int(total), int(n_thresholds)))
+
+    def run_scores_validation(self, probs, y, bounds, length, total, longest, thresholds, shift, table_out, work, min_run=15, stream=None,
+                              max_gap=0):
+        """``cf_validation_run_scores``: per threshold (``thresholds``: 1..16 host floats), kind and state of a run the histogram of the
+        probabilities of the samples under those runs at ``shift`` (14 .. 22) and, in each row's last cell, their fixed-point sum --
+        ``device_validation.run_scores_host`` -- into ``table_out`` (int64 CUDA, ``K * score_cells(shift)`` elements, zeroed and
+        written by the call).  ``bounds`` [n + 1] and ``length`` [n] are int64 CUDA tensors; ``work`` is a uint8 CUDA tensor of at
+        least ``run_scores_work_bytes(total, K)`` bytes.  Asynchronous on the stream; equal inputs give equal bits."""
+        n, total, longest, k, thresholds, stream = self._run_step_arguments("run_scores_validation", probs, y, bounds, length, total, longest,
+                                                                            thresholds, table_out, work, stream)
+        if isinstance(shift, bool) or int(shift) != shift:
+            raise ValueError("run_scores_validation: shift must be an int, got %r" % (shift,))
+        # the shift, the room in table_out and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
+        N.check(self._lib.cf_validation_run_scores(
+            self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
+            C.c_void_p(length.data_ptr()), n, total, longest, thresholds, k, int(shift), int(max_gap), int(min_run),
+            C.c_void_p(table_out.data_ptr()), int(table_out.numel()), C.c_void_p(work.data_ptr()), int(work.numel()),
+            C.c_void_p(stream.cuda_stream)))
+
     def run_borders_work_bytes(self, total, n_thresholds):
         """Bytes of work space ``run_borders_validation`` needs (``run_states_work_bytes``' rule: the two can share a buffer)."""
         return int(self._lib.cf_validation_run_borders_work_bytes(int(total), int(n_thresholds)))

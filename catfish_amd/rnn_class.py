@@ -210,7 +210,7 @@ class RNN(object):
         return self.engine.infer_host(np.asarray(windows), return_logits=True)
 
     def score_validation_device(self, vset, selection, thresholds=(0.5,), run_edges=None, curve_shift=None, border_reach=None,
-                                bridge_gap=0, phases=(0,), vote_weight="mean", max_bases=None, vote_bases=None):
+                                bridge_gap=0, phases=(0,), vote_weight="mean", max_bases=None, vote_bases=None, score_shift=None):
         """One validation round on the card: the stretches ``selection`` (``vset.select``) of a
         ``device_validation.DeviceValidationSet`` -> what ``device_validation.score_host`` returns for them, (right int64 [n],
         ce_sum float64 [n], counts int64 [K, 4]).  With ``run_edges`` (a tuple of up to 7 ascending run lengths, possibly empty)
@@ -244,10 +244,15 @@ class RNN(object):
         vote on it, and the voted bases are counted per class, truth and call, and as runs on the base axis (``cf_base_votes``, same
         forward pass, same copy back; room ``capacity["vote_cells"]``, per-base work space ``capacity["vote_work"]``; the stretches'
         base ranges are host work and go up with the selection).  The set must have a base table
-        (``DeviceValidationSet.from_events`` / ``from_moves``; ValueError otherwise).
+        (``DeviceValidationSet.from_events`` / ``from_moves``; ValueError otherwise).  With ``score_shift`` (an int in 14 .. 22)
+        ``run_scores`` is the last result of all: what ``device_validation.run_scores_host`` returns for the probabilities the round
+        thresholds (the voted ones with ``phases``), int64 [K, 2, 3, curve_bins(score_shift) + 1] -- per kind and state of a run the
+        histogram of the probabilities under those runs and their fixed-point sum (``cf_validation_run_scores``, same forward pass,
+        same copy back; room ``capacity["score_cells"]``, a byte of paint per sample behind the labels in the label work space;
+        ``bridge_gap`` applies).
 
         The tuple is a ``validation_round.RoundResult``: every result is also an attribute -- ``right``, ``ce_sum``, ``counts``,
-        ``run_states``, ``run_borders``, ``curve``, ``run_bases``, ``base_confusion``, ``base_vote_runs`` -- that is None when it was not asked for.  ``validation_round.RoundSpec`` checks the
+        ``run_states``, ``run_borders``, ``curve``, ``run_bases``, ``base_confusion``, ``base_vote_runs``, ``run_scores`` -- that is None when it was not asked for.  ``validation_round.RoundSpec`` checks the
         options, ``RoundPlan`` holds the sizes and the layout of the result buffer (host-only, both).
 
         The selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes
@@ -258,7 +263,7 @@ class RNN(object):
         import torch
         from .validation_round import RoundPlan, RoundSpec, grow, walk
         self._require_engine()
-        spec = RoundSpec.of(thresholds, run_edges, border_reach, curve_shift, bridge_gap, phases, vote_weight, max_bases, vote_bases)
+        spec = RoundSpec.of(thresholds, run_edges, border_reach, curve_shift, bridge_gap, phases, vote_weight, max_bases, vote_bases, score_shift)
         table = None if spec.vote_bases is None else vset.base_table("score_validation_device: vote_bases")
         if spec.max_bases is not None and vset.basemap is None:
             raise ValueError("score_validation_device: max_bases needs a set with a base map (DeviceValidationSet.from_events)")

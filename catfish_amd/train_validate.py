@@ -22,8 +22,9 @@ import random
 import numpy as np
 
 from . import metrics
-from .device_validation import (BASE_CLASSES, BORDER_REACH, MAX_BASES, RUN_STATES, check_border_reach, check_max_bases, curve_thresholds,
-                                curves_from_histogram, run_base_rates, run_border_summary, run_state_rates, split_run_borders)
+from .device_validation import (BASE_CLASSES, BORDER_REACH, MAX_BASES, RUN_SCORE_SHIFT, RUN_STATES, check_border_reach, check_max_bases,
+                                curve_thresholds, curves_from_histogram, run_base_rates, run_border_summary, run_score_summary,
+                                run_state_rates, split_run_borders)
 from .neural_network import build_model as _build_model
 
 
@@ -249,6 +250,9 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     vote_bases = getattr(network, "validation_vote_bases", None)
     if vote_bases is not None:
         extra["vote_bases"] = vote_bases
+    score_shift = getattr(network, "validation_score_shift", None)
+    if score_shift is not None:
+        extra["score_shift"] = score_shift
     bridge_gap = int(getattr(network, "validation_bridge_gap", 0) or 0)
     if bridge_gap:
         extra["bridge_gap"] = bridge_gap
@@ -286,6 +290,12 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
             "step": int(step), "threshold": 0.5, "max_bases": int(vote_bases), "classes": list(BASE_CLASSES), "states": list(RUN_STATES),
             "base_confusion": confusion.tolist(), **base_vote_rates(confusion), "hp_vote_runs": vote_runs[0].tolist(),
             "called_vote_runs": vote_runs[1].tolist(), **run_base_rates(vote_runs)}) + "\n")
+    if score_shift is not None:
+        # what the samples under the round's runs scored, by state of the run: one JSON line per round
+        hp_scores, called_scores = run_score_summary(network.validation_run_scores, score_shift)
+        _append(report[:-len(".txt")] + "_hp_scores.jsonl", _json_line({
+            "step": int(step), "threshold": 0.5, "shift": int(score_shift), "states": list(RUN_STATES), "hp_scores": hp_scores,
+            "called_scores": called_scores, **({"bridge_gap": bridge_gap} if bridge_gap else {})}))
     if curve_shift is not None:
         # the round's whole ROC and precision-recall curves, reduced to their areas and the best F1: one JSON line per round
         curves = curves_from_histogram(network.validation_curve, curve_shift)
@@ -432,7 +442,7 @@ def score_validation_batch(probs32, logits32, y, bounds, tails, threshold=0.5):
 
 
 def validate(network, squiggles, max_seq_length, file_path, validation_start="random", max_number=856, run_edges=None, curve_shift=None,
-             border_reach=None, bridge_gap=0, loader=None, max_bases=None, vote_bases=None):
+             border_reach=None, bridge_gap=0, loader=None, max_bases=None, vote_bases=None, score_shift=None):
     """networks/train_validate.py:188-295 as one packed launch.
 
     The reference pushes every read through ``test_network`` (one ``sess.run`` each, up to 856 per round); windows are
@@ -460,13 +470,16 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     base vote on it at threshold 0.5 and scores the voted bases by base (``base_votes.vote_host``, on the card); the [5, 2, 2]
     confusion table is left in ``network.validation_base_confusion`` and the [2, 3, 5, vote_bases + 1] run table in
     ``network.validation_base_vote_runs``.
-    ``bridge_gap`` (with ``run_edges``, ``border_reach`` or ``max_bases``; 0 .. 49): those tables are counted on the prediction with
-    its gaps of at most that many samples bridged (``infer.bridge_gaps``).
+    ``score_shift`` (a ``DeviceValidationSet`` only; an int in 14 .. 22): the round also bins the probabilities under its runs at
+    threshold 0.5 by kind and state of the run (``device_validation.run_scores_host``, on the card); the [2, 3, NB + 1] table is left
+    in ``network.validation_run_scores``.
+    ``bridge_gap`` (with ``run_edges``, ``border_reach``, ``max_bases`` or ``score_shift``; 0 .. 49): those tables are counted on the
+    prediction with its gaps of at most that many samples bridged (``infer.bridge_gaps``).
     ``loader`` (a list of paths only): what reads a path into ``(raw, labels)`` instead of ``load_npz``.
     Report, prints and return value stay as they are."""
     from .calling import CallRule
     bridge_gap = CallRule.of(max_gap=bridge_gap).max_gap
-    if bridge_gap and run_edges is None and border_reach is None and max_bases is None:
+    if bridge_gap and run_edges is None and border_reach is None and max_bases is None and score_shift is None:
         raise ValueError("validate: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
     print("Max length is {}".format(max_seq_length))
     print("Validation start is {}".format(validation_start))
@@ -478,7 +491,7 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
         n_samples = int(selection[2].sum())
         if n_reads == 0:
             raise ZeroDivisionError("validation selected no read")
-        if run_edges is None and curve_shift is None and border_reach is None and max_bases is None and vote_bases is None:
+        if run_edges is None and curve_shift is None and border_reach is None and max_bases is None and vote_bases is None and score_shift is None:
             right, ce_sum, counts_k = network.score_validation_device(squiggles, selection)
         else:
             extra = {} if border_reach is None else {"border_reach": border_reach}
@@ -486,6 +499,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
                 extra["max_bases"] = max_bases
             if vote_bases is not None:
                 extra["vote_bases"] = vote_bases
+            if score_shift is not None:
+                extra["score_shift"] = score_shift
             if bridge_gap:
                 extra["bridge_gap"] = bridge_gap
             got = network.score_validation_device(squiggles, selection, (0.5,), run_edges=run_edges, curve_shift=curve_shift, **extra)
@@ -500,6 +515,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
                 network.validation_run_bases = got.run_bases[0]
             if vote_bases is not None:
                 network.validation_base_confusion, network.validation_base_vote_runs = got.base_confusion[0], got.base_vote_runs[0]
+            if score_shift is not None:
+                network.validation_run_scores = got.run_scores[0]
         acc, loss, counts = squiggles.finish(right, ce_sum, counts_k[0], *squiggles.layout(selection[2], network.window))
     else:
         if run_edges is not None:
@@ -512,6 +529,8 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
             raise ValueError("validate: max_bases needs a DeviceValidationSet with a base map (the bases are counted on the card)")
         if vote_bases is not None:
             raise ValueError("validate: vote_bases needs a DeviceValidationSet with a base table (the bases are voted on the card)")
+        if score_shift is not None:
+            raise ValueError("validate: score_shift needs a DeviceValidationSet (the scores under runs are binned on the card)")
         signals, labels = select_validation_stretches(squiggles, network.window, max_seq_length, validation_start,
                                                       max_number, **({} if loader is None else {"loader": loader}))
         n_reads = len(signals)
@@ -544,7 +563,7 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
 
 
 def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start="complete", max_number=856, run_edges=None,
-                    border_reach=None, bridge_gap=0, phases=(0,), vote_weight="mean", max_bases=None, vote_bases=None):
+                    border_reach=None, bridge_gap=0, phases=(0,), vote_weight="mean", max_bases=None, vote_bases=None, score_shift=None):
     """The reference's precision / recall sweep (networks/precision_recall_ROC.py:85-100: ``class_from_threshold`` --
     ``p >= t`` -- then ``compute_f1`` per threshold) over a ``DeviceValidationSet``: ONE forward pass, every threshold counted
     from its probabilities on the card.  The stretches are ``validate``'s (same selection, same tail rule for the true
@@ -570,7 +589,13 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     voted bases, a ``[5][2][2]`` list --, the fields of ``base_votes.base_vote_rates`` (per-base precision / recall / F1, overall and
     per letter) and ``vote_runs``, the fields of ``device_validation.run_base_rates`` over the runs on the base axis.
 
-    ``bridge_gap`` (with ``run_edges``, ``border_reach`` or ``max_bases``; 0 .. 49): those tables are those of the prediction
+    With ``score_shift`` (an int in 14 .. 22) every row also says what the samples under that threshold's runs scored
+    (``device_validation.run_scores_host``; the reference's offline ``check_for_false_neg``): ``hp_scores`` and ``called_scores`` --
+    per state [complete, incomplete, absent] of the true and of the called runs ``device_validation.run_score_summary``'s dict (n,
+    mean, q1 / median / q3 as the edges of their bin), so ``hp_scores[2]`` tells how close the missed homopolymers were to the
+    threshold and ``called_scores[2]`` how confident the calls that hold none.
+
+    ``bridge_gap`` (with ``run_edges``, ``border_reach``, ``max_bases`` or ``score_shift``; 0 .. 49): those tables are those of the prediction
     with its gaps of at most that many samples bridged (``infer.bridge_gaps``); tp / fp / tn / fn stay per-sample counts.
 
     ``phases`` / ``vote_weight`` (``infer.check_phases``): shifted-window voting -- every count is taken from the probabilities voted
@@ -579,10 +604,10 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     rule = CallRule.of(max_gap=bridge_gap, phases=phases, vote_weight=vote_weight)
     bridge_gap = rule.max_gap
     voted = {"phases": rule.phases, "vote_weight": rule.vote_weight} if rule.voted else {}      # (0,): the call of before
-    if bridge_gap and run_edges is None and border_reach is None and max_bases is None:
+    if bridge_gap and run_edges is None and border_reach is None and max_bases is None and score_shift is None:
         raise ValueError("threshold_sweep: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
     given = {"run_edges": run_edges, "border_reach": border_reach, "bridge_gap": bridge_gap or None, "max_bases": max_bases,
-             "vote_bases": vote_bases}
+             "vote_bases": vote_bases, "score_shift": score_shift}
     given = {key: value for key, value in given.items() if value is not None}                  # nothing given: the call of before
     thresholds = [float(t) for t in thresholds]
     selection = vset.select(network.window, max_seq_length, validation_start, max_number)
@@ -611,6 +636,8 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
             from .base_votes import base_vote_rates
             rows[-1].update({"base_confusion": got.base_confusion[k].tolist(), **base_vote_rates(got.base_confusion[k]),
                              "vote_runs": run_base_rates(got.base_vote_runs[k])})
+        if score_shift is not None:
+            rows[-1]["hp_scores"], rows[-1]["called_scores"] = run_score_summary(got.run_scores[k], score_shift)
     return rows
 
 
@@ -738,6 +765,12 @@ def main(argv):
     round, how far the called borders miss the true ones and the interruptions at threshold 0.5 and appends step, threshold,
     reach, ``hp_borders`` and ``called_borders`` (``border_report``; None as null) as one JSON line to
     ``<model path>_hp_borders.jsonl``; the ``.txt`` reports and the other ``.jsonl`` files are unchanged.
+    CATFISH_VALIDATION_SCORES=1 (with CATFISH_DEVICE_VALIDATION=1) also bins, per round, the probabilities under the true and the
+    called runs at threshold 0.5 by state of the run (``device_validation.run_scores_host`` at shift ``RUN_SCORE_SHIFT``, on the card)
+    and appends step, threshold, shift, states, ``hp_scores`` and ``called_scores`` (``device_validation.run_score_summary``: n, mean
+    and quartile bins per state; None as null) as one JSON line to ``<model path>_hp_scores.jsonl``: how close the missed
+    homopolymers were to the threshold.  CATFISH_VALIDATION_BRIDGE applies to it too.  The ``.txt`` reports and the other ``.jsonl``
+    files are unchanged.
     CATFISH_VALIDATION_BRIDGE=<int> (1 .. 49; with CATFISH_VALIDATION_RUNS or CATFISH_VALIDATION_BORDERS) counts those two on the
     prediction with its gaps of at most that many samples bridged (``infer.bridge_gaps``); their JSON lines then carry
     ``bridge_gap``.
@@ -813,12 +846,14 @@ def main(argv):
         borders = os.environ.get("CATFISH_VALIDATION_BORDERS") or "0"
         if borders != "0":                                       # ... and how far the called borders miss, one JSON line per round
             network.validation_border_reach = BORDER_REACH if borders == "1" else check_border_reach(int(borders))
+        if os.environ.get("CATFISH_VALIDATION_SCORES") == "1":   # ... and what the samples under the runs scored, one JSON line per round
+            network.validation_score_shift = RUN_SCORE_SHIFT
         bridge = int(os.environ.get("CATFISH_VALIDATION_BRIDGE") or "0")
         if bridge:                                               # ... both counted on the bridged prediction
             from .infer import check_bridge
             network.validation_bridge_gap = check_bridge(bridge, 15)
             if getattr(network, "validation_run_edges", None) is None and getattr(network, "validation_border_reach", None) is None \
-                    and getattr(network, "validation_max_bases", None) is None:
+                    and getattr(network, "validation_max_bases", None) is None and getattr(network, "validation_score_shift", None) is None:
                 raise ValueError("CATFISH_VALIDATION_BRIDGE needs CATFISH_VALIDATION_RUNS=1 or CATFISH_VALIDATION_BORDERS")
     began = datetime.datetime.now()
     train_and_validate(network, db_train, n_train, squiggles, stretch, network.model_path, start, most)

@@ -17,21 +17,23 @@ from .tilings import tiling_size
 
 RESULTS = ("right", "ce_sum", "counts", "run_states", "run_borders", "curve")     # the order in the result buffer and in the tuple
 EXTRA_RESULTS = ("run_bases",)          # ... and after them, with keys in ``offset`` / ``cells`` / ``need`` only when asked for
-VOTE_RESULTS = base_votes.VOTE_RESULTS  # ... and last the two per-base tables of ``vote_bases``, under the same rule
+VOTE_RESULTS = base_votes.VOTE_RESULTS  # ... then the two per-base tables of ``vote_bases``, under the same rule
+SCORE_RESULTS = ("run_scores",)         # ... and last the scores under runs of ``score_shift``, under the same rule
 
 
-class RoundSpec(namedtuple("RoundSpec", "thresholds run_edges border_reach curve_shift rule max_bases vote_bases", defaults=(None, None))):
+class RoundSpec(namedtuple("RoundSpec", "thresholds run_edges border_reach curve_shift rule max_bases vote_bases score_shift",
+                           defaults=(None, None, None))):
     """The options of a round, checked: ``thresholds`` (a tuple of floats, at least one), ``run_edges`` / ``border_reach`` /
-    ``curve_shift`` / ``max_bases`` / ``vote_bases`` (None: that result is not asked for; ``vote_bases`` is the ``max_bases`` of the
-    per-base vote-run table) and the ``calling.CallRule`` that carries ``bridge_gap`` (``max_gap``), ``phases`` and ``vote_weight``.
+    ``curve_shift`` / ``max_bases`` / ``vote_bases`` / ``score_shift`` (None: that result is not asked for; ``vote_bases`` is the
+    ``max_bases`` of the per-base vote-run table, ``score_shift`` the bin shift of the scores under runs) and the ``calling.CallRule`` that carries ``bridge_gap`` (``max_gap``), ``phases`` and ``vote_weight``.
     Build one with ``RoundSpec.of``."""
     __slots__ = ()
 
     @classmethod
     def of(cls, thresholds=(0.5,), run_edges=None, border_reach=None, curve_shift=None, bridge_gap=0, phases=(0,), vote_weight="mean",
-           max_bases=None, vote_bases=None):
+           max_bases=None, vote_bases=None, score_shift=None):
         """The checked spec, or the ValueError of the first of ``CallRule.of``, the thresholds, ``check_run_edges``, ``curve_bins``,
-        ``check_border_reach``, ``check_max_bases``, ``base_votes.check_vote_bases`` that refuses."""
+        ``check_border_reach``, ``check_max_bases``, ``base_votes.check_vote_bases``, ``check_score_shift`` that refuses."""
         rule = CallRule.of(max_gap=bridge_gap, phases=phases, vote_weight=vote_weight)
         thresholds = tuple(float(t) for t in thresholds)
         if not thresholds:
@@ -47,7 +49,9 @@ class RoundSpec(namedtuple("RoundSpec", "thresholds run_edges border_reach curve
             max_bases = dv.check_max_bases(max_bases)
         if vote_bases is not None:
             vote_bases = base_votes.check_vote_bases(vote_bases)
-        return cls(thresholds, run_edges, border_reach, curve_shift, rule, max_bases, vote_bases)
+        if score_shift is not None:
+            score_shift = dv.check_score_shift(score_shift)
+        return cls(thresholds, run_edges, border_reach, curve_shift, rule, max_bases, vote_bases, score_shift)
 
     @property
     def k_all(self):
@@ -61,14 +65,14 @@ class RoundSpec(namedtuple("RoundSpec", "thresholds run_edges border_reach curve
 
 class RoundResult(tuple):
     """What ``RNN.score_validation_device`` returns: the tuple ``(right, ce_sum, counts[, run_states][, run_borders][, curve]
-    [, run_bases][, base_confusion, base_vote_runs])`` -- only the results asked for, in that order -- with every result as an
+    [, run_bases][, base_confusion, base_vote_runs][, run_scores])`` -- only the results asked for, in that order -- with every result as an
     attribute of that name too (None when not asked for)."""
 
     def __new__(cls, right, ce_sum, counts, run_states=None, run_borders=None, curve=None, run_bases=None, base_confusion=None,
-                base_vote_runs=None):
-        fields = (right, ce_sum, counts, run_states, run_borders, curve, run_bases, base_confusion, base_vote_runs)
+                base_vote_runs=None, run_scores=None):
+        fields = (right, ce_sum, counts, run_states, run_borders, curve, run_bases, base_confusion, base_vote_runs, run_scores)
         self = super().__new__(cls, (item for item in fields if item is not None))
-        for name, item in zip(RESULTS + EXTRA_RESULTS + VOTE_RESULTS, fields):
+        for name, item in zip(RESULTS + EXTRA_RESULTS + VOTE_RESULTS + SCORE_RESULTS, fields):
             setattr(self, name, item)
         return self
 
@@ -83,7 +87,9 @@ class RoundPlan(object):
     ``need["base_cells"]``; a round that does not ask has no such key anywhere), then those of ``VOTE_RESULTS`` under the same rule
     (``base_confusion``: ``k_all * 20`` cells, ``base_vote_runs``: ``k_all * 2 * 3 * 5 * (vote_bases + 1)``; ``need["vote_cells"]`` is
     their sum and ``need["vote_work"]`` the bytes of per-base sums and states one threshold group writes, for the set's ``n_bases``),
-    ``out_cells`` in all."""
+    then those of ``SCORE_RESULTS`` (``run_scores``: ``k_all * score_cells(score_shift)`` cells, ``need["score_cells"]``; such a round
+    paints behind its labels, so its ``run_work`` and ``need["run_work"]`` are ``cf_validation_run_scores_work_bytes``, twice the
+    labels), ``out_cells`` in all."""
 
     def __init__(self, spec, length, window, n_bases=None):
         self.spec = spec
@@ -113,6 +119,11 @@ class RoundPlan(object):
                 self.cells[name] = k_all * per_k
                 self.offset[name] = self.out_cells
                 self.out_cells += self.cells[name]
+        if spec.score_shift is not None:
+            self.run_work = 2 * self.run_work
+            self.cells["run_scores"] = k_all * dv.score_cells(spec.score_shift)
+            self.offset["run_scores"] = self.out_cells
+            self.out_cells += self.cells["run_scores"]
         self.need = {"samples": max(total, 1), "reads": n, "slots": total // dv.SCORE_CHUNK + n, "thresholds": k_all}
         if spec.run_edges is not None:
             self.need.update({"run_cells": self.cells["run_states"], "run_work": self.run_work})
@@ -125,6 +136,8 @@ class RoundPlan(object):
         if spec.vote_bases is not None:
             self.need.update({"vote_cells": sum(self.cells[name] for name in VOTE_RESULTS),
                               "vote_work": base_votes.work_bytes(n_bases, min(k_all, dv.MAX_THRESHOLDS))})
+        if spec.score_shift is not None:
+            self.need.update({"score_cells": self.cells["run_scores"], "run_work": self.run_work})
         if spec.rule.voted:
             self.need["tiling_samples"] = tiling_size(total, n, spec.rule.n_tilings)
 
@@ -145,8 +158,8 @@ class RoundPlan(object):
         """The copied-back result buffer (host int64, ``out_cells`` elements) -> ``RoundResult``: right int64 [n], ce_sum float64 [n]
         (the cells hold the doubles' bits), counts int64 [K, 4], run states int64 [K, 2, len(run_edges) + 1, 3], borders int64
         [K, 2, 5 * border_reach + 3], curve histogram int64 [3, curve_bins(curve_shift)], run bases int64
-        [K, 2, 3, 5, max_bases + 1], base confusion int64 [K, 5, 2, 2], base vote runs int64 [K, 2, 3, 5, vote_bases + 1]; every item
-        its own copy."""
+        [K, 2, 3, 5, max_bases + 1], base confusion int64 [K, 5, 2, 2], base vote runs int64 [K, 2, 3, 5, vote_bases + 1], run scores
+        int64 [K, 2, 3, curve_bins(score_shift) + 1]; every item its own copy."""
         spec, k_all = self.spec, self.spec.k_all
         return RoundResult(
             self.cut(back, "right").copy(), self.cut(back, "ce_sum").view(np.float64).copy(),
@@ -158,7 +171,8 @@ class RoundPlan(object):
             self.cut(back, "run_bases").reshape(k_all, 2, 3, len(dv.BASE_CLASSES), spec.max_bases + 1).copy(),
             None if spec.vote_bases is None else self.cut(back, "base_confusion").reshape(k_all, len(dv.BASE_CLASSES), 2, 2).copy(),
             None if spec.vote_bases is None else
-            self.cut(back, "base_vote_runs").reshape(k_all, 2, 3, len(dv.BASE_CLASSES), spec.vote_bases + 1).copy())
+            self.cut(back, "base_vote_runs").reshape(k_all, 2, 3, len(dv.BASE_CLASSES), spec.vote_bases + 1).copy(),
+            None if spec.score_shift is None else self.cut(back, "run_scores").reshape(k_all, 2, 3, -1).copy())
 
 
 def grow(book, need, device):
@@ -174,11 +188,11 @@ def grow(book, need, device):
                            "table": torch.empty(3 * (cap["reads"] + 1), dtype=torch.int64, device=device),
                            "partials": torch.empty(cap["slots"], dtype=torch.float64, device=device),
                            # right [reads] | ce_sum [reads], double bits | counts [4 per threshold] | run states | borders |
-                           # curve histogram | run bases | base confusion | base vote runs: one copy back
+                           # curve histogram | run bases | base confusion | base vote runs | run scores: one copy back
                            "out": torch.empty(2 * cap["reads"] + 4 * cap["thresholds"] + cap.get("run_cells", 0)
                                               + cap.get("border_cells", 0) + cap.get("curve_cells", 0) + cap.get("base_cells", 0)
-                                              + cap.get("vote_cells", 0), dtype=torch.int64, device=device)}
-        if "run_work" in cap:                                                    # corrected labels, one array per threshold of a group
+                                              + cap.get("vote_cells", 0) + cap.get("score_cells", 0), dtype=torch.int64, device=device)}
+        if "run_work" in cap:                                     # corrected labels (and paint), one array per threshold of a group
             book["tensors"]["run_work"] = torch.empty(cap["run_work"], dtype=torch.uint8, device=device)
         if "vote_work" in cap:                                                   # per-base sums and states (8-byte aligned), and every
             book["tensors"]["vote_work"] = torch.empty(cap["vote_work"] // 8, dtype=torch.int64, device=device).view(torch.uint8)
@@ -192,8 +206,8 @@ def grow(book, need, device):
 
 def walk(engine, plan, t, thresholds_d, signal, labels, window, basemap=None, edges=None, longest_range=0):
     """Every launch of a round, on the current stream, over the buffers ``t`` (``grow``) with the selection table uploaded: gather,
-    (retile,) forward pass, (vote,) then per threshold group score, run states, borders, run bases, base votes, and the curve
-    histogram last.  ``thresholds_d``: the thresholds as a float64 CUDA tensor; ``basemap``: the set's base map on the card, which a
+    (retile,) forward pass, (vote,) then per threshold group score, run states, borders, run bases, base votes, run scores, and the
+    curve histogram last.  ``thresholds_d``: the thresholds as a float64 CUDA tensor; ``basemap``: the set's base map on the card, which a
     round with ``max_bases`` or ``vote_bases`` reads in place; ``edges``: the set's base table on the card and ``longest_range`` the
     widest stretch in bases, for a round with ``vote_bases`` (its ranges are in ``t["vote_ranges"]`` already).  -> the result
     buffer's ``plan.out_cells`` cells, still on the card."""
@@ -220,6 +234,8 @@ def walk(engine, plan, t, thresholds_d, signal, labels, window, basemap=None, ed
     if spec.vote_bases is not None:
         confusion_d, vote_runs_d = plan.cut(out, "base_confusion"), plan.cut(out, "base_vote_runs")
         confusion_per_k, vote_per_k = plan.cells["base_confusion"] // spec.k_all, plan.cells["base_vote_runs"] // spec.k_all
+    if spec.score_shift is not None:
+        scores_d, score_per_k = plan.cut(out, "run_scores"), plan.cells["run_scores"] // spec.k_all
     for k0, k1 in spec.groups:
         engine.score_validation(probs, logits, y, bounds_d, total, longest, thresholds_d[k0:k1], right_d, ce_d, counts_d[4 * k0:4 * k1],
                                 t["partials"])
@@ -236,6 +252,9 @@ def walk(engine, plan, t, thresholds_d, signal, labels, window, basemap=None, ed
             engine.base_votes_validation(probs, labels, basemap, edges, src_d, bounds_d, len_d, t["vote_ranges"][:2 * n], total, longest_range,
                                          spec.thresholds[k0:k1], spec.vote_bases, confusion_d[confusion_per_k * k0:confusion_per_k * k1],
                                          vote_runs_d[vote_per_k * k0:vote_per_k * k1], t["vote_work"])
+        if spec.score_shift is not None:
+            engine.run_scores_validation(probs, y, bounds_d, len_d, total, longest, spec.thresholds[k0:k1], spec.score_shift,
+                                         scores_d[score_per_k * k0:score_per_k * k1], t["run_work"], min_run=rule.min_run, max_gap=rule.max_gap)
     if spec.curve_shift is not None:
         engine.curve_validation(probs, y, bounds_d, len_d, total, longest, spec.curve_shift, curve_d)
     return out

@@ -677,6 +677,27 @@ int cf_validation_run_bases(cf_model* m, const float* probs, const uint8_t* y, c
 int cf_validation_curve(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length, int64_t n,
                         int64_t total, int64_t longest, int32_t shift, int64_t* hist_out, int64_t hist_capacity, void* stream);
 
+/* Scores under runs (csrc/validation_scores.hpp, csrc/validation_scores_word.hpp; device_validation.run_scores_host is its
+ * definition): the probabilities of the samples under the runs of every state -- what the reference's offline check_for_false_neg
+ * (networks/process_output.py:15-137) collects for the missed homopolymers.  Stretches, prediction (bridged when max_gap > 0, under
+ * cf_validation_run_states_bridged's domain rule), runs, kinds and states as for cf_validation_run_states.  With NB the bins of
+ * cf_validation_curve at `shift`, every sample of a run of kind q and state s at threshold k adds one to cell bin(p) of row
+ * [k][q][s] and floor(p * 2^32) (NaN and p < 0 as 0, p > 1 as 2^32) to the row's last cell.
+ *   table_out    device int64 [n_thresholds][2][3][NB + 1], zeroed and written by the call;  table_capacity  its entries
+ *   thresholds   HOST double [n_thresholds], 1..16 of them;  shift  14 .. 22 (16: NB = 16 257)
+ *   work         device bytes, >= cf_validation_run_scores_work_bytes(total, n_thresholds) (twice cf_validation_run_work_bytes: the
+ *                labels and, behind them, one byte of paint per sample); 16-byte aligned for the bit-mask post-processing kernel
+ * Two launches behind the label passes: a workgroup walks a stretch mirrored and forward and paints every sample with the state of
+ * its run, then one workgroup per cf_validation_score_chunk() samples sorts its cells in LDS and issues one 64-bit integer atomic per
+ * DISTINCT cell and one per non-zero sum.  Integers only, so equal inputs give equal results whatever `longest` (a hint) or the grid.
+ * Asynchronous on `stream`; m may be NULL.  CF_ERR_INVALID before any launch for a null pointer, n outside [1, 2^31), total >= 2^31,
+ * n_thresholds outside 1..16, a shift outside 14 .. 22, min_run < 1, a (min_run, max_gap) pair outside the bridging domain,
+ * table_capacity or work_bytes too small (the message names the size needed). */
+int64_t cf_validation_run_scores_work_bytes(int64_t total, int32_t n_thresholds);
+int cf_validation_run_scores(cf_model* m, const float* probs, const uint8_t* y, const int64_t* bounds, const int64_t* length, int64_t n,
+                             int64_t total, int64_t longest, const double* thresholds, int32_t n_thresholds, int32_t shift, int32_t max_gap,
+                             int32_t min_run, int64_t* table_out, int64_t table_capacity, void* work, int64_t work_bytes, void* stream);
+
 /* Shifted-window voting (csrc/tilings.hpp, index rules in csrc/tilings_rule.hpp; catfish_amd/tilings.py states both steps in numpy --
  * retile_host and vote_host are their definitions).  A read is cut into 35-sample windows at one fixed phase; these two calls let the
  * same reads go through the forward pass in K tilings whose window borders fall phi_j samples apart, and merge the per-sample

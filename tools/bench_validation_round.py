@@ -22,6 +22,7 @@ and range of seconds per round, and whether (c)'s range lies below (a)'s and bel
     python tools/bench_validation_round.py --trace-borders 3     # rounds with border_reach=64, for rocprofv3 --kernel-trace --stats
     python tools/bench_validation_round.py --bases --rounds 7    # the base leg, see below
     python tools/bench_validation_round.py --trace-bases 3       # rounds with max_bases=16, for rocprofv3 --kernel-trace --stats
+    python tools/bench_validation_round.py --scores --rounds 7   # the score leg, see below
 
 The run-state leg (``--run-states``) times the device-resident round itself (``RNN.score_validation_device`` on a seeded selection,
 ending in its copy back), alternating per round: without run states, with ``run_edges=(35, 70, 140)``, and the forward pass of
@@ -45,6 +46,13 @@ The base leg (``--bases``) needs reads with event tables, so it makes its own se
 ``HipEngine.run_bases_validation`` and ``run_states_validation`` alone (launch to synchronise, no copy back; both include their
 label passes) on the round's own probabilities.  Its summary line gives the medians, what either step adds to the round, the
 microseconds per threshold of either call alone and their ratio.
+
+The score leg (``--scores``) times the same round, alternating per round: with ``run_edges=(35, 70, 140)`` alone (the base line), the
+same with ``score_shift=16`` and with ``score_shift=14``, and with ``curve_shift=14`` instead (the curve step, in the same process)
+-- at 1 and at 16 thresholds -- and ``HipEngine.run_scores_validation`` at both shifts, ``run_states_validation`` and
+``curve_validation`` alone (launch to synchronise, no copy back; the run steps include their label passes) on the round's own
+probabilities.  Its summary line gives the medians, the milliseconds either shift and the curve add to the round with run states,
+and the milliseconds of every call alone.
 """
 import argparse
 import contextlib
@@ -208,6 +216,46 @@ def bases_leg(net, resident, rounds, emit, max_bases=16, edges=()):
                   bases_over_states_call=stats["bases_call"]["median_s"] / stats["states_call"]["median_s"]))
 
 
+def scores_leg(net, resident, rounds, emit, shifts=(16, 14), edges=(35, 70, 140)):
+    from catfish_amd import device_validation as dv
+    device = "cuda:%d" % net.device
+    for thresholds in ((0.5,), tuple(float(t) for t in np.linspace(0.2, 0.95, 16))):
+        k = len(thresholds)
+        rounds_of = ["run_states"] + ["scores_%d" % s for s in shifts] + ["curve_14"]
+        calls = ["scores_call_%d" % s for s in shifts] + ["states_call", "curve_call"]
+        seconds = {name: [] for name in rounds_of + calls}
+        table = torch.empty(k * max(dv.score_cells(s) for s in shifts), dtype=torch.int64, device=device)
+        hist = torch.empty(3 * dv.curve_bins(14), dtype=torch.int64, device=device)
+        for rnd in range(-1, rounds):                      # round -1 warms up (buffers grow once)
+            random.seed(rnd)
+            selection = resident.select(net.window, STRETCH, START, MOST)
+            took = {"run_states": timed(lambda: net.score_validation_device(resident, selection, thresholds, run_edges=edges))}
+            for s in shifts:
+                took["scores_%d" % s] = timed(lambda: net.score_validation_device(resident, selection, thresholds, run_edges=edges, score_shift=s))
+            took["curve_14"] = timed(lambda: net.score_validation_device(resident, selection, thresholds, run_edges=edges, curve_shift=14))
+            t = net.validation_buffers["tensors"]
+            bounds, _tails = dv.layout(selection[2], net.window)
+            n, total, longest = len(selection[2]), int(bounds[-1]), int(np.diff(bounds).max())
+            len_d, bounds_d = t["table"][n + 1:2 * n + 1], t["table"][2 * (n + 1):3 * (n + 1)]
+            probs, y = t["probs"][:total], t["y"][:total]
+            for s in shifts:
+                took["scores_call_%d" % s] = timed(lambda: net.engine.run_scores_validation(probs, y, bounds_d, len_d, total, longest, thresholds,
+                                                                                            s, table, t["run_work"]))
+            took["states_call"] = timed(lambda: net.engine.run_states_validation(probs, y, bounds_d, len_d, total, longest, thresholds, edges,
+                                                                                 table, t["run_work"]))
+            took["curve_call"] = timed(lambda: net.engine.curve_validation(probs, y, bounds_d, len_d, total, longest, 14, hist))
+            if rnd >= 0:
+                for name in seconds:
+                    seconds[name].append(took[name])
+                emit(dict(leg="scores", thresholds=k, round=rnd, **{name + "_s": took[name] for name in seconds}))
+        stats = {name: spread(v) for name, v in seconds.items()}
+        emit(dict(summary=True, leg="scores", thresholds=k, shifts=list(shifts), edges=list(edges), reads=resident.n_reads, stretch=STRETCH,
+                  rounds=rounds, samples_per_round=resident.n_reads * (STRETCH // 35 * 35), legs=stats,
+                  added_ms={name: 1e3 * (stats[name]["median_s"] - stats["run_states"]["median_s"]) for name in rounds_of[1:]},
+                  call_ms={name: 1e3 * stats[name]["median_s"] for name in calls},
+                  table_bytes={str(s): 8 * k * dv.score_cells(s) for s in shifts}))
+
+
 def curve_leg(net, resident, rounds, emit, shifts=(14, 10)):
     from catfish_amd import device_validation as dv
     thresholds = (0.5,)
@@ -261,6 +309,7 @@ def main():
     ap.add_argument("--borders", action="store_true", help="the border leg alone, then exit")
     ap.add_argument("--trace-borders", type=int, default=0, help="this many rounds with border_reach=64 at 16 thresholds, then exit")
     ap.add_argument("--bases", action="store_true", help="the base leg alone (on a set of event reads of its own), then exit")
+    ap.add_argument("--scores", action="store_true", help="the score leg alone, then exit")
     ap.add_argument("--trace-bases", type=int, default=0, help="this many rounds with max_bases=16 at 16 thresholds, then exit")
     args = ap.parse_args()
     rounds = max(5, args.rounds)
@@ -347,7 +396,7 @@ def main():
                 out.write(line + "\n")
                 out.flush()
 
-            if args.resident_rounds or args.run_states or args.curve or args.borders:
+            if args.resident_rounds or args.run_states or args.curve or args.borders or args.scores:
                 if args.resident_rounds:
                     routes[2][1](-1)
                     took = [routes[2][1](rnd)[0] for rnd in range(args.resident_rounds)]
@@ -359,6 +408,8 @@ def main():
                     curve_leg(net, resident, rounds, emit)
                 if args.borders:
                     borders_leg(net, resident, rounds, emit)
+                if args.scores:
+                    scores_leg(net, resident, rounds, emit)
                 os.chdir(ROOT)
                 net.engine.close()
                 return
