@@ -232,6 +232,17 @@ def test_bounds_of_the_any_size_conv_float64_parity_module_follow_from_its_profi
         assert 0.99 * want[k] <= b <= want[k], (k, b, want[k])
 
 
+def test_bounds_of_the_tuned_float64_parity_module_follow_from_its_profile():
+    """The same for tests/test_tuned_train_fp64.py and profiles/tuned_train_fp64_parity.jsonl: each bound is at most 4 x the
+    largest yardstick the profile records for the quantity (float32 torch, plus the summation-order term where the module names
+    the quantity), at most the older tests' bound, and not so far below that it is a different number."""
+    import test_tuned_train_fp64 as m
+    want = m.bounds_from_profile()
+    assert sorted(want) == sorted(m.BOUNDS) == sorted(m.OLDER_BOUNDS)
+    for k, b in m.BOUNDS.items():
+        assert 0.99 * want[k] <= b <= want[k], (k, b, want[k])
+
+
 @pytest.mark.parametrize("kind,steps_before", [(0, 0), (1, 0), (1, 999), (1, 50000)])
 def test_opt_step_bounds_admit_a_plain_float32_evaluation(kind, steps_before):
     """The derived bounds tests/test_train_kernels_fp64.py holds cf_opt_step to, applied to the update written out in numpy
