@@ -1,5 +1,6 @@
-"""The whole training step of ANY geometry on the HIP kernels, without autograd (``Trainer(..., native=True)`` at every
-geometry other than the shipped 64 / 32 one, RNN or ResNetRNN type).
+"""The whole training step of ANY geometry on the HIP kernels, without autograd (``Trainer(..., native=True)`` for every
+model the tuned kernels do not take, RNN or ResNetRNN type: every size other than 64 / 32, 64 units without a conv stack, and 64 / 32
+with more than ``train_mode.TUNED_MAX_BLOCKS`` blocks).
 
     conv stack forward            cf_gen_conv_forward (BN as an epilogue affine of the step's gamma / beta, z stashed)
     biGRU layers forward          cf_gru_anysize_train_forward + cf_gen_dropout (the tuned kernels' in-kernel mask hash)

@@ -21,7 +21,8 @@ I/O (``numpy_weights``, ``state_tf``) and the torch-autograd reference path keep
 
 ``FlatTrainStep`` is what does not depend on the kernels: the constructor, re-homing the variables into the flat buffers, batch
 loading, gradient views and the optimizer launch.  ``NativeTrainStep`` is the step of the shipped geometry (64 GRU units, 32 conv
-channels) on the kernels tuned for it; ``anysize_step.AnySizeTrainStep`` is the step of every other geometry.
+channels, a conv stack of 1 .. ``TUNED_MAX_BLOCKS`` blocks) on the kernels tuned for it; ``anysize_step.AnySizeTrainStep`` is the
+step of every other model.
 """
 from __future__ import annotations
 
@@ -33,6 +34,7 @@ from . import _native as N
 from ._native import _p
 from .anysize_walk import flat_layout
 from .native_train import T, _stack_maps, dropout_scale_frag, frag_to_nat, nat_to_frag
+from .train_mode import TUNED_MAX_BLOCKS
 
 
 class FlatTrainStep(object):
@@ -53,14 +55,14 @@ class FlatTrainStep(object):
         self._rehome()
 
     def _set_layout(self, layout):
-        """Adopt a ``flat_layout``, checked against the model's variables and, at 32 conv channels, against the size of the tuned
-        conv-stack kernels' parameter buffer, which is this layout's head."""
+        """Adopt a ``flat_layout``, checked against the model's variables and, at 32 conv channels and a depth the tuned conv-stack
+        kernels have, against the size of their parameter buffer, which is this layout's head."""
         self.entries, self.units, self.layers, self.head_off, self.zero_off = layout
         for name, _, shape in self.entries:
             if tuple(self.net.params[name].shape) != tuple(shape):
                 raise ValueError("%s: shape %s, the geometry needs %s" % (name, tuple(self.net.params[name].shape), shape))
-        tuned = int(self.lib.cf_res_train_param_floats(self.n_blocks)) if self.units and self.units[0][3] == 32 else 0
-        assert tuned in (0, self.layers[0][0])                                  # 0: the tuned kernels have no stack of this depth
+        if self.units and self.units[0][3] == 32 and self.n_blocks <= TUNED_MAX_BLOCKS:
+            assert int(self.lib.cf_res_train_param_floats(self.n_blocks)) == self.layers[0][0]
         self.n_total = self.zero_off + 1
 
     def _rehome(self):
@@ -126,6 +128,9 @@ class NativeTrainStep(FlatTrainStep):
     def __init__(self, net, opt, engine, keep_prob, seed=None):
         if net.n_layers_res < 1:
             raise ValueError("the native training step needs the ResNetRNN type (n_layers_res >= 1)")
+        if net.n_layers_res > TUNED_MAX_BLOCKS:
+            raise ValueError("the tuned training kernels take a conv stack of 1..%d blocks, not %d: anysize_step.AnySizeTrainStep "
+                             "trains a deeper one" % (TUNED_MAX_BLOCKS, net.n_layers_res))
         super().__init__(net, opt, engine, keep_prob, seed=seed)
         # weight gradients of layer L on a second stream, next to the backward recurrence of layer L - 1 (which needs only dX of layer
         # L): at the reference's batch of 256 windows the step is a chain of launches of 16 tiles on 256 CUs, and the twelve-wave wgrad

@@ -338,9 +338,10 @@ class RNN(object):
     def train_network(self, train_x, train_y, step):
         """rnn_class.py:201-210: one optimizer step on a batch (TF-1 update rules, dropout on the biGRU outputs).
 
-        ``training.Trainer`` takes the step; which path it trains through (the HIP kernels of the whole step at the shipped
-        64 / 32 geometry or, with ``native_training=True``, at any other; autograd around the any-size recurrences; the torch
-        restatement, which is the CPU mode and the test reference) is one row of the table in ``train_mode.py``.  The inference engine picks
+        ``training.Trainer`` takes the step; which path it trains through (the tuned HIP kernels of the whole step at 64 / 32
+        with a conv stack of 1 .. 4 blocks; with ``native_training=True`` the any-size ones for every other model, a 64-unit RNN and
+        a 64 / 32 stack of five blocks included; autograd around the any-size recurrences; the torch restatement, which is the CPU
+        mode, the test reference and where a 64-unit RNN trains by default) is one row of the table in ``train_mode.py``.  The inference engine picks
         the updated weights up lazily, at the next ``infer``.  TensorBoard summaries (the reference's second forward,
         :206-208) are not written.
         """

@@ -67,9 +67,11 @@ def generate_random_hyperparameters(network_type, learning_rate_min=-4, learning
     size, keep probability, and for ResNetRNN a residual depth that is drawn and then DROPPED -- the reference stores
     ``n_layers`` under ``n_layers_res`` (:109) -- and the residual width.
 
-    Every draw builds: the shipped geometry (``layer_size`` 64 / ``layer_size_res`` 32, any depth) runs on the tuned HIP
-    kernels and trains natively; other sizes infer on the any-size HIP kernels (csrc/generic.hpp) and train through torch
-    autograd with the recurrence on the same kernel family (anysize_train.py).
+    Every draw builds and takes a step (tests/test_train_draws_host.py enumerates the grid): ``layer_size`` 64 / ``layer_size_res``
+    32 at depths 1 .. 4 trains natively on the tuned HIP kernels; every other ResNetRNN draw -- other sizes, and 64 / 32 at depth 5,
+    which the tuned conv-stack kernels do not have -- infers on the any-size HIP kernels (csrc/generic.hpp) and trains through torch
+    autograd with the recurrence on the same kernel family (anysize_train.py), or natively on it with ``native_training=True``.
+    The RNN type does the same, except that at 64 units it trains on plain torch unless ``native_training=True`` is given.
     """
     rs = np.random
     plan = [("learning_rate", lambda: float(10 ** rs.randint(learning_rate_min, learning_rate_max))),
@@ -743,8 +745,11 @@ def main(argv):
     max_validation_length [validation_start [max_number]]``.  The training "database" argument is a directory of NPZ
     reads (the reference takes a ZODB file); hyper-parameters are a random draw as in the reference (:328) unless
     CATFISH_SHIPPED_HPARAMS=1 asks for the shipped network's (the reference's commented block :329-332).
-    CATFISH_NATIVE_TRAINING=1 trains with ``native_training=True`` (the whole step on the HIP kernels at any geometry).
-    CATFISH_TRAINING_PRECISION=bf16x3 trains with ``training_precision="bf16x3"`` (any geometry but the shipped one).
+    CATFISH_NATIVE_TRAINING=1 trains with ``native_training=True``: the whole step on the HIP kernels, the tuned ones at 64 / 32
+    with a conv stack of 1 .. 4 blocks, the any-size ones for every other draw (64 units without a conv stack and 64 / 32 at depth 5
+    among them).
+    CATFISH_TRAINING_PRECISION=bf16x3 trains with ``training_precision="bf16x3"`` (every draw that trains on the any-size kernels;
+    refused where the tuned ones or plain torch train).
     CATFISH_DEVICE_DB=1 keeps the training windows on the card (``device_db.DeviceExampleDb``): the steps between two
     checkpoint rounds run back to back, each drawing its own batch.
     CATFISH_DEVICE_DB=reads trains from the labelled reads as they are (``device_db.DeviceReadDb``).  Despite the variable's name

@@ -19,7 +19,7 @@ import gc
 import numpy as np
 
 from .batching import quiet_gc
-from .train_mode import STEP_KINDS, TrainMode, geometry
+from .train_mode import STEP_KINDS, TrainMode, geometry, tuned_geometry
 
 
 def _names(n_layers, n_layers_res):
@@ -74,8 +74,8 @@ class TorchResNetRNN(object):
         if x.dim() == 3:
             x = x[:, :, 0]
         a = x[:, None, :]                                # [N, C, T]
-        if engine is not None and not geometry(p, self.n_layers_res)[2]:     # recurrence on the any-size HIP kernels
-            return self._logits_anysize(a, keep_prob, generator, engine, masks)
+        if engine is not None and not tuned_geometry(*geometry(p, self.n_layers_res)[:2], self.n_layers_res):
+            return self._logits_anysize(a, keep_prob, generator, engine, masks)      # recurrence on the any-size HIP kernels
         native_res = engine is not None and self.n_layers_res > 0 and self.dtype == torch.float32
         if native_res:                                   # residual conv stack on the HIP training kernels
             from .native_train import native_res_stack, res_unit_names
@@ -126,8 +126,8 @@ class TorchResNetRNN(object):
                 p["final_fully_connected/bias"]).reshape(n, t_len)
 
     def _logits_anysize(self, a, keep_prob, generator, engine, masks):
-        """Any geometry other than 64 / 32: conv stack, dropout and head in torch, every biGRU layer one forward and one
-        backward launch of the any-size HIP kernels (catfish_amd/anysize_train.py)."""
+        """Every model the tuned training kernels do not take (``train_mode.tuned_geometry``): conv stack, dropout and head in torch,
+        every biGRU layer one forward and one backward launch of the any-size HIP kernels (catfish_amd/anysize_train.py)."""
         torch = self.torch
         p = self.params
         from .anysize_train import anysize_bigru
@@ -328,18 +328,22 @@ class AutogradStep(object):
 class Trainer(object):
     """One training step = forward + backward + optimizer update.
 
-    On a GPU with the ResNetRNN type the step runs entirely on the HIP training kernels through the C ABI
+    On a GPU at 64 units, 32 channels and a conv stack of 1 .. ``train_mode.TUNED_MAX_BLOCKS`` blocks the step runs entirely on the
+    tuned HIP training kernels through the C ABI
     (``catfish_amd/native_step.py``: conv stack, biGRU layers, dense head + loss, optimizer; no autograd), captured ONCE
     into a HIP graph (``torch.cuda.CUDAGraph``) and replayed per batch; batches are copied into static input buffers.
     Dropout masks inside the graph come from torch's default (graph-safe) CUDA generator.  ``native=False`` (and the CPU)
-    run the torch-autograd restatement of the same graph -- the reference the native step is tested against.  Which of the five
+    run the torch-autograd restatement of the same graph -- the reference the native step is tested against.  Every other model
+    on a GPU in float32 -- other sizes, 64 / 32 with a deeper stack and, with ``native=True``, 64 units without a conv stack -- trains
+    on the any-size kernels: the whole step with ``native=True``, autograd around the recurrences with ``native=None`` (where the
+    64-unit RNN type stays on torch).  Which of the four
     paths a trainer takes is one row of the table in ``catfish_amd/train_mode.py`` (``self.mode``); every path is one object
     with ``alloc`` / ``load_batch`` / ``run`` / ``grads`` (``self.step``), run eagerly, captured (``_capture_step``) or captured
     behind the on-card sampler (``_capture_fed``).  ``step_impl`` is that object where the whole step is native, else None.
 
     ``precision="bf16x3"`` (opt-in; the default "fp32" changes nothing) evaluates the matrix products on the serial chain of the
     any-size biGRU recurrences, forward and backward, as split bf16 products; everything else stays fp32.  It exists where those
-    kernels train: on a GPU, in float32, at a geometry other than the shipped 64 / 32, with ``native`` None or True.
+    kernels train: on a GPU, in float32, in the two ``anysize_*`` rows of that table.
     """
 
     def __init__(self, weights, n_layers, n_layers_res, optimizer_choice, learning_rate, keep_prob, device=None,

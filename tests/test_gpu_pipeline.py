@@ -420,15 +420,23 @@ def test_other_hyperparameter_draws_train_save_load_infer(network_type, hpm, tmp
 
 
 @pytest.mark.timeout(900)
-@pytest.mark.parametrize("network_type,seed", [("ResNetRNN", 0), ("ResNetRNN", 3), ("RNN", 1), ("ResNetRNN", 11)])
-def test_train_validate_script_with_the_reference_default_random_draw(network_type, seed, tmp_path, monkeypatch):
+@pytest.mark.parametrize("network_type,seed,native_training", [("ResNetRNN", 0, None), ("ResNetRNN", 3, None), ("RNN", 1, None),
+                                                               ("ResNetRNN", 11, None), ("ResNetRNN", 25, None), ("RNN", 13, "1")],
+                         ids=["ResNetRNN-0", "ResNetRNN-3", "RNN-1", "ResNetRNN-11", "ResNetRNN-25", "RNN-13-native"])
+def test_train_validate_script_with_the_reference_default_random_draw(network_type, seed, native_training, tmp_path, monkeypatch):
     """`python -m catfish_amd.train_validate <type> <train dir> <n> <val dir> <len> <start>` as the reference runs it
     (networks/train_validate.py:299-347): hyper-parameters drawn at random (:328) -- whatever geometry comes up builds,
-    trains two batches, checkpoints, validates and writes both reports; the model directory loads back."""
+    trains two batches, checkpoints, validates and writes both reports; the model directory loads back.  ``native_training`` is the
+    value of CATFISH_NATIVE_TRAINING (None: unset).  Seed 25 draws 64 / 32 with five blocks, one more than the tuned training
+    kernels have; seed 13 with the variable set a 64-unit RNN on the native step (tests/test_train_draws_host.py holds both draws)."""
     pytest.importorskip("torch")
     from catfish_amd import neural_network, train_validate as tv
     monkeypatch.chdir(tmp_path)
     monkeypatch.delenv("CATFISH_SHIPPED_HPARAMS", raising=False)
+    if native_training is None:
+        monkeypatch.delenv("CATFISH_NATIVE_TRAINING", raising=False)
+    else:
+        monkeypatch.setenv("CATFISH_NATIVE_TRAINING", native_training)
     (tmp_path / "train").mkdir()
     (tmp_path / "val").mkdir()
     for i in range(2):

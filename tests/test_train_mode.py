@@ -6,7 +6,7 @@ import itertools
 import numpy as np
 import pytest
 
-from catfish_amd.train_mode import KINDS, STEP_KINDS, TrainMode, geometry
+from catfish_amd.train_mode import KINDS, STEP_KINDS, TUNED_MAX_BLOCKS, TrainMode, geometry, tuned_geometry
 from oracle import catfish_oracle as oracle
 
 X3 = "precision='bf16x3' is a mode of the any-size training recurrences; "
@@ -18,11 +18,14 @@ NATIVE_NEEDS = "native=True runs the fp32 HIP training kernels: it needs device=
 PER_LAYER = {"fuse_layers": False}
 WIDE = {"layer_size": 128, "layer_size_res": 64}
 WIDE_RNN = {"layer_size": 128, "layer_size_res": 32}           # no conv stack: c counts as 32
+SHIPPED_SIZES = {"layer_size": 64, "layer_size_res": 32}       # 64 / 32 where the any-size kernels train it
 
 # (shipped, device type, float32, native, conv stack, precision) -> (kind, engine keywords, Trainer.native, Trainer.anysize) or the
 # ValueError's text.  Produced by evaluating the mode expressions of Trainer.__init__ at commit e39d6a2 (training.py:317-348 there),
 # transcribed into a script, over the grid -- not by the function under test.  Shipped rows are 64 / 32, the others 128 / 64.
-GRID = {
+# That constructor knew a conv stack only as present or absent, and its two ``tuned_autograd`` rows could not take a step
+# (tests/test_train_draws_fp64.py); ``GRID`` below adds the depth class and says where they went.
+RECORDED = {
     (True, 'cpu', True, None, True, 'fp32'): ('torch', None, False, False),
     (True, 'cpu', True, None, True, 'bf16x3'): X3_SHIPPED,
     (True, 'cpu', True, None, False, 'fp32'): ('torch', None, False, False),
@@ -122,45 +125,102 @@ GRID = {
 }
 
 
+DEPTHS = {0: (0,), 1: (1, TUNED_MAX_BLOCKS), 5: (TUNED_MAX_BLOCKS + 1, 12)}      # depth class -> the depths a row is evaluated at
+
+# The three recorded decisions that changed, by their row with the depth class.  The 64-unit RNN with native=True and 64 / 32 in
+# float64 were ``tuned_autograd``; the first is now the any-size step (and takes bf16x3, as every row of that kind), the second
+# trains on torch as every other float64 model on the card.
+MOVED = {
+    (True, "cuda", True, True, 0, "fp32"): ("anysize_step", SHIPPED_SIZES, True, False),
+    (True, "cuda", True, True, 0, "bf16x3"): ("anysize_step", SHIPPED_SIZES, True, False),
+    (True, "cuda", False, None, 1, "fp32"): ("torch", None, False, False),
+}
+
+
+def _with_depth_class():
+    """(shipped, device type, float32, native, depth class 0 | 1 | 5, precision) -> decision.  Class 0 (no conv stack) and class 1
+    (1 .. 4 blocks) are the recorded rows without and with a conv stack.  Class 5 (deeper than the tuned kernels go) is at every
+    size what the recorded constructor decided for a conv stack at 128 / 64, with the row's own sizes as engine keywords."""
+    grid = {}
+    for (shipped, dev, f32, native, conv, precision), want in RECORDED.items():
+        grid[(shipped, dev, f32, native, 1 if conv else 0, precision)] = want
+        if conv and not shipped:
+            grid[(False, dev, f32, native, 5, precision)] = want
+            deep = want if isinstance(want, str) or want[1] is None else (want[0], SHIPPED_SIZES) + want[2:]
+            grid[(True, dev, f32, native, 5, precision)] = deep
+    assert set(MOVED) <= set(grid) and all("tuned_autograd" in grid[row] or grid[row] == X3_SHIPPED for row in MOVED)
+    grid.update(MOVED)
+    return grid
+
+
+GRID = _with_depth_class()
+
+
+def _modes(row):
+    """The row's decision at every depth of its class (one TrainMode, or one ValueError's text, per depth)."""
+    shipped, dev, f32, native, depth_class, precision = row
+    h, c = (64, 32) if shipped else (128, 64 if depth_class else 32)
+    out = []
+    for depth in DEPTHS[depth_class]:
+        try:
+            out.append(TrainMode.of(h, c, depth, dev, f32, native, precision, dtype_name="torch.float32" if f32 else "torch.float64"))
+        except ValueError as e:
+            out.append(str(e))
+    return out
+
+
 def _mode(row):
-    shipped, dev, f32, native, conv, precision = row
-    h, c = (64, 32) if shipped else (128, 64 if conv else 32)
-    return TrainMode.of(h, c, 1 if conv else 0, dev, f32, native, precision, dtype_name="torch.float32" if f32 else "torch.float64")
+    """The one decision of the row's depth class, or None if its depths disagree."""
+    modes = _modes(row)
+    return modes[0] if all(m == modes[0] for m in modes) else None
 
 
 def test_the_whole_grid_is_what_the_constructor_decided():
-    grid = list(itertools.product((True, False), ("cpu", "cuda"), (True, False), (None, True, False), (True, False), ("fp32", "bf16x3")))
-    assert len(grid) == 96 and sorted(map(repr, grid)) == sorted(map(repr, GRID))
+    grid = list(itertools.product((True, False), ("cpu", "cuda"), (True, False), (None, True, False), (0, 1, 5), ("fp32", "bf16x3")))
+    assert len(grid) == 144 and sorted(map(repr, grid)) == sorted(map(repr, GRID))
+    assert len(RECORDED) == 96 and sum("tuned_autograd" in v for v in RECORDED.values()) == 2
     for row in grid:
         want = GRID[row]
-        if isinstance(want, str):
-            with pytest.raises(ValueError) as e:
-                _mode(row)
-            assert str(e.value) == want, row
-        else:
-            m = _mode(row)
-            assert tuple(m) == want and (m.kind, m.engine_kwargs, m.native, m.anysize) == want, row
-            assert type(m.native) is bool and type(m.anysize) is bool
-            with pytest.raises(AttributeError):
-                m.kind = "torch"
+        for m in _modes(row):                                  # both ends of the depth class decide alike
+            if isinstance(want, str):
+                assert m == want, row
+            else:
+                assert not isinstance(m, str), (row, m)
+                assert tuple(m) == want and (m.kind, m.engine_kwargs, m.native, m.anysize) == want, row
+                assert type(m.native) is bool and type(m.anysize) is bool
+                with pytest.raises(AttributeError):
+                    m.kind = "torch"
+    # every recorded decision stands, apart from the three that moved
+    for (shipped, dev, f32, native, conv, precision), want in RECORDED.items():
+        row = (shipped, dev, f32, native, 1 if conv else 0, precision)
+        assert GRID[row] == want or row in MOVED, row
 
 
-def test_the_five_kinds_partition_the_rows_that_do_not_raise():
+def test_the_four_kinds_partition_the_rows_that_do_not_raise():
     rows = {row: _mode(row) for row, want in GRID.items() if not isinstance(want, str)}
-    assert len(rows) == 40
+    assert len(rows) == 63 and None not in rows.values()          # 40 recorded, 11 more in each deep class, one refusal lifted
     by_kind = {k: [r for r, m in rows.items() if m.kind == k] for k in KINDS}
     assert sum(len(v) for v in by_kind.values()) == len(rows) and all(by_kind[k] for k in KINDS)
-    assert STEP_KINDS == ("tuned_step", "anysize_step")
+    assert KINDS == ("tuned_step", "anysize_step", "anysize_autograd", "torch") and STEP_KINDS == ("tuned_step", "anysize_step")
     for row, m in rows.items():
         assert (m.engine_kwargs is None) == (m.kind == "torch")
         assert m.anysize == (m.kind == "anysize_autograd")
+        assert m.native == (m.kind in STEP_KINDS)
         if m.kind != "torch":
-            assert m.engine_kwargs == (PER_LAYER if m.kind.startswith("tuned") else WIDE if row[4] else WIDE_RNN)
-    # the two combinations no test trains through land where they always did: an engine with per-layer launches and no step
-    odd = [(True, "cuda", True, True, False, "fp32"), (True, "cuda", False, None, True, "fp32")]
-    assert sorted(by_kind["tuned_autograd"]) == sorted(odd)
-    for row in odd:
-        assert tuple(rows[row]) == ("tuned_autograd", PER_LAYER, True, False)
+            assert m.engine_kwargs == (PER_LAYER if m.kind == "tuned_step" else SHIPPED_SIZES if row[0] else WIDE if row[4] else WIDE_RNN)
+    # the tuned step is 64 / 32 on the card in float32 with 1 .. 4 blocks and nothing else; no input reaches ``tuned_autograd``
+    assert set(by_kind["tuned_step"]) == {(True, "cuda", True, None, 1, "fp32"), (True, "cuda", True, True, 1, "fp32")}
+    assert not any("tuned_autograd" in repr(v) for v in GRID.values())
+    # 64 / 32 where the tuned kernels do not go: five blocks as any other size, the RNN type only when native=True asks
+    assert rows[(True, "cuda", True, None, 5, "fp32")].kind == "anysize_autograd" and rows[(True, "cuda", True, True, 5, "fp32")].kind == "anysize_step"
+    assert rows[(True, "cuda", True, None, 0, "fp32")].kind == "torch" and rows[(True, "cuda", True, True, 0, "fp32")].kind == "anysize_step"
+    assert GRID[(True, "cuda", True, None, 1, "bf16x3")] == GRID[(True, "cuda", True, True, 1, "bf16x3")] == X3_SHIPPED
+
+
+def test_tuned_geometry_is_64_32_with_one_to_four_blocks():
+    assert TUNED_MAX_BLOCKS == 4
+    assert [d for d in range(0, 14) if tuned_geometry(64, 32, d)] == [1, 2, 3, 4]
+    assert not any(tuned_geometry(h, c, d) for h, c in ((64, 16), (32, 32), (128, 32), (64, 64)) for d in range(0, 6))
 
 
 def test_geometry_with_and_without_a_conv_stack():

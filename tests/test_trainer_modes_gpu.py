@@ -163,21 +163,23 @@ def test_explicit_masks_go_through_the_autograd_step(golden, ckpt_weights):
 
 
 # ---------------------------------------------------------------------------------------------------- attributes per kind
-# kind -> (geometry, native, the CPU table's row (tests/test_train_mode.py::GRID), step class or None, does the test step it)
-KINDS = {"tuned_step": ("shipped", None, (True, "cuda", True, None, True, "fp32"), "NativeTrainStep", True),
-         "anysize_step": ((32, 32, 2, 0), True, (False, "cuda", True, True, False, "fp32"), "AnySizeTrainStep", True),
-         "anysize_autograd": ((32, 32, 2, 0), None, (False, "cuda", True, None, False, "fp32"), None, True),
-         # admitted by the constructor, trained through by no test: constructed here, and no step is asked of it (its recurrences
-         # would be the tuned biGRU kernels on a one-channel input, which nothing has ever launched)
-         "tuned_autograd": ((64, 32, 2, 0), True, (True, "cuda", True, True, False, "fp32"), None, False),
-         "torch": ((32, 32, 2, 0), False, (False, "cuda", True, False, False, "fp32"), None, True)}
+# name -> (kind, geometry, native, the CPU table's row (tests/test_train_mode.py::GRID), step class or None); every one is stepped
+KINDS = {"tuned_step": ("tuned_step", "shipped", None, (True, "cuda", True, None, 1, "fp32"), "NativeTrainStep"),
+         "anysize_step": ("anysize_step", (32, 32, 2, 0), True, (False, "cuda", True, True, 0, "fp32"), "AnySizeTrainStep"),
+         "anysize_autograd": ("anysize_autograd", (32, 32, 2, 0), None, (False, "cuda", True, None, 0, "fp32"), None),
+         # 64 units where the tuned kernels do not go: without a conv stack (a one-feature input) when native=True asks, and with
+         # five blocks, one more than the tuned conv-stack kernels have
+         "anysize_step-rnn64": ("anysize_step", (64, 32, 2, 0), True, (True, "cuda", True, True, 0, "fp32"), "AnySizeTrainStep"),
+         "anysize_autograd-64-32-x5": ("anysize_autograd", (64, 32, 2, 5), None, (True, "cuda", True, None, 5, "fp32"), None),
+         "anysize_step-64-32-x5": ("anysize_step", (64, 32, 2, 5), True, (True, "cuda", True, True, 5, "fp32"), "AnySizeTrainStep"),
+         "torch": ("torch", (32, 32, 2, 0), False, (False, "cuda", True, False, 0, "fp32"), None)}
 
 
-@pytest.mark.parametrize("kind", sorted(KINDS))
-def test_attributes_follow_the_table(kind, ckpt_weights):
+@pytest.mark.parametrize("name", sorted(KINDS))
+def test_attributes_follow_the_table(name, ckpt_weights):
     from test_train_mode import GRID
     from catfish_amd.training import AutogradStep
-    geo, native, row, step_class, stepped = KINDS[kind]
+    kind, geo, native, row, step_class = KINDS[name]
     want_kind, engine_kwargs, want_native, want_anysize = GRID[row]
     assert want_kind == kind
     tr = _trainer(geo, ckpt_weights, native, 1.0)
@@ -189,15 +191,14 @@ def test_attributes_follow_the_table(kind, ckpt_weights):
         else:
             assert type(tr.step_impl).__name__ == step_class and tr.step is tr.step_impl
         assert tr.use_graph and tr._graph is None and tr._fed is None and tr.last_loss is None
-        if stepped:
-            twin = _db()
-            x, y, _ = twin.get_training_set(64)
-            loss = tr.train_step(x, y)
-            assert tr._graph is not None and tr._fed is None and tr.last_loss == loss
-            db = _db()
-            losses = tr.train_steps(db, 2, 64)
-            assert tr._graph is not None and tr._fed is not None and tr._fed["key"] == (64, 2) and tr.last_loss == float(losses[-1])
-            assert float(tr.opt.t) == 3.0
+        twin = _db()
+        x, y, _ = twin.get_training_set(64)
+        loss = tr.train_step(x, y)
+        assert tr._graph is not None and tr._fed is None and tr.last_loss == loss
+        db = _db()
+        losses = tr.train_steps(db, 2, 64)
+        assert tr._graph is not None and tr._fed is not None and tr._fed["key"] == (64, 2) and tr.last_loss == float(losses[-1])
+        assert float(tr.opt.t) == 3.0 and np.isfinite(losses).all() and np.isfinite(loss)
     finally:
         if tr.engine is not None:
             tr.engine.close()
