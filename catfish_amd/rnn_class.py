@@ -213,66 +213,49 @@ class RNN(object):
                                 bridge_gap=0, phases=(0,), vote_weight="mean", max_bases=None, vote_bases=None, score_shift=None):
         """One validation round on the card: the stretches ``selection`` (``vset.select``) of a
         ``device_validation.DeviceValidationSet`` -> what ``device_validation.score_host`` returns for them, (right int64 [n],
-        ce_sum float64 [n], counts int64 [K, 4]).  With ``run_edges`` (a tuple of up to 7 ascending run lengths, possibly empty)
-        a fourth result follows: what ``device_validation.run_states_host`` returns for the round's probabilities, int64
-        [K, 2, len(run_edges) + 1, 3] -- how many true homopolymers were found completely, partly or not at all and how many
-        called stretches hold one, per length bin (``cf_validation_run_states`` after the same gather and forward pass, in the
-        same copy back; its label work space and the larger result buffer follow the grow-only rule below).  With ``curve_shift``
-        (an int in 10 .. 22) the last of these six results -- after the run states when both are asked for -- is what
-        ``device_validation.curve_host`` returns for the round's probabilities, int64 [3, curve_bins(curve_shift)]: the histogram
-        ``device_validation.curves_from_histogram`` turns into the whole ROC and precision-recall curves (``cf_validation_curve``,
-        same forward pass, same copy back; its room in the result buffer is ``validation_buffers["capacity"]["curve_cells"]``).
-        With ``border_reach`` (an int in 1 .. 128) one more result sits after the run states and before the curve histogram: what
-        ``device_validation.run_borders_host`` returns for the round's probabilities, int64 [K, 2, 5 * border_reach + 3] -- how far
-        the called borders miss the true ones and how often a homopolymer is called in pieces (``cf_validation_run_borders``, same
-        forward pass, same copy back; room ``capacity["border_cells"]``, label work space shared with the run states).  The set's
-        labels must all be 0 or 1 then (ValueError).  ``bridge_gap`` (0 .. 49): the prediction the run states and the borders are
-        counted on has its gaps of at most that many samples bridged first (``infer.bridge_gaps``; ``cf_validation_run_states_bridged``
-        and ``cf_validation_run_borders_bridged``); the per-sample counts are not touched.  ``phases`` / ``vote_weight``
-        (``infer.check_phases``; shifted-window voting, ``tilings.py``): after the gather ``cf_retile_windows`` lays out the K tilings,
-        the forward pass writes probabilities and logits for all of them (``validation_buffers["tensors"]["tilings_probs"]`` /
-        ``["tilings_logits"]``, room ``capacity["tiling_samples"]``, the same grow-only rule), and ``cf_vote_tilings`` writes the voted
-        probabilities and logits (the weighted mean of the logits, not the logit of the voted probability) that everything after it
-        consumes; ``(0,)`` launches and allocates nothing that was not before.  With ``max_bases`` (an int in 1 .. 32) ``run_bases``
-        follows the curve histogram as the last result: what ``device_validation.run_bases_host`` returns for the round's
-        probabilities and the set's base map, int64 [K, 2, 3, 5, max_bases + 1] -- the same runs per kind, state, base class (A / C / G /
-        T / other) and length in bases (``cf_validation_run_bases``, same forward pass, same copy back; it reads the set's base map
-        in place, room ``capacity["base_cells"]``, label work space shared with the run states; ``bridge_gap`` applies).  The set must
-        have a base map (``DeviceValidationSet.from_events``; ValueError otherwise).  With ``vote_bases`` (an int in 1 .. 32) two more
-        results come last, ``base_confusion`` int64 [K, 5, 2, 2] and ``base_vote_runs`` int64 [K, 2, 3, 5, vote_bases + 1]: what
-        ``base_votes.vote_host`` returns for the round's probabilities -- the samples of every base that lies wholly inside a stretch
-        vote on it, and the voted bases are counted per class, truth and call, and as runs on the base axis (``cf_base_votes``, same
-        forward pass, same copy back; room ``capacity["vote_cells"]``, per-base work space ``capacity["vote_work"]``; the stretches'
-        base ranges are host work and go up with the selection).  The set must have a base table
-        (``DeviceValidationSet.from_events`` / ``from_moves``; ValueError otherwise).  With ``score_shift`` (an int in 14 .. 22)
-        ``run_scores`` is the last result of all: what ``device_validation.run_scores_host`` returns for the probabilities the round
-        thresholds (the voted ones with ``phases``), int64 [K, 2, 3, curve_bins(score_shift) + 1] -- per kind and state of a run the
-        histogram of the probabilities under those runs and their fixed-point sum (``cf_validation_run_scores``, same forward pass,
-        same copy back; room ``capacity["score_cells"]``, a byte of paint per sample behind the labels in the label work space;
-        ``bridge_gap`` applies).
+        ce_sum float64 [n], counts int64 [K, 4]), followed by every optional result asked for, in the order of this table (one row of
+        ``validation_round.OPTIONS`` each; K thresholds, NB(s) = ``curve_bins(s)``; all int64, all from the same forward pass, in the
+        same copy back):
 
-        The tuple is a ``validation_round.RoundResult``: every result is also an attribute -- ``right``, ``ce_sum``, ``counts``,
-        ``run_states``, ``run_borders``, ``curve``, ``run_bases``, ``base_confusion``, ``base_vote_runs``, ``run_scores`` -- that is None when it was not asked for.  ``validation_round.RoundSpec`` checks the
-        options, ``RoundPlan`` holds the sizes and the layout of the result buffer (host-only, both).
+        option (range)                                 result, shape                                    definition               entry point
+        ``run_edges`` (<= 7 ascending lengths, or ())  ``run_states`` [K, 2, len(run_edges) + 1, 3]     ``dv.run_states_host``   ``cf_validation_run_states_bridged``
+        ``border_reach`` (1 .. 128)                    ``run_borders`` [K, 2, 5 * border_reach + 3]     ``dv.run_borders_host``  ``cf_validation_run_borders_bridged``
+        ``curve_shift`` (10 .. 22)                     ``curve`` [3, NB(curve_shift)]                   ``dv.curve_host``        ``cf_validation_curve``
+        ``max_bases`` (1 .. 32)                        ``run_bases`` [K, 2, 3, 5, max_bases + 1]        ``dv.run_bases_host``    ``cf_validation_run_bases``
+        ``vote_bases`` (1 .. 32)                       ``base_confusion`` [K, 5, 2, 2],                 ``base_votes.vote_host`` ``cf_base_votes``
+                                                       ``base_vote_runs`` [K, 2, 3, 5, vote_bases + 1]
+        ``score_shift`` (14 .. 22)                     ``run_scores`` [K, 2, 3, NB(score_shift) + 1]    ``dv.run_scores_host``   ``cf_validation_run_scores``
 
-        The selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes
-        probabilities and logits (the weights just trained, as ``score_windows`` uses them), ``cf_validation_score`` reduces them
-        -- more than 16 thresholds in groups of 16 over the same forward pass -- and ONE copy brings the results back; all on
-        the current stream.  The work buffers stay on the object and grow only when a round is larger than every one before
-        (``validation_buffers``: capacities and how often each was allocated or uploaded)."""
+        (``dv``: ``device_validation``, whose definitions say what is counted.)  What a result needs from the set is refused as a
+        ValueError before any launch: ``border_reach`` labels that are all 0 or 1, ``max_bases`` a base map
+        (``DeviceValidationSet.from_events``), ``vote_bases`` a base table (``from_events`` / ``from_moves``); the last two read the set's
+        arrays in place, and the votes' base ranges are host work that goes up with the selection.  ``bridge_gap`` (0 .. 49): the
+        prediction that ``run_states``, ``run_borders``, ``run_bases`` and ``run_scores`` are counted on has its gaps of at most that many
+        samples bridged first (``infer.bridge_gaps``); the per-sample counts, the curve and the votes are not touched.  ``phases`` /
+        ``vote_weight`` (``infer.check_phases``; shifted-window voting, ``tilings.py``): after the gather ``cf_retile_windows`` lays out the
+        tilings, the forward pass scores all of them, and ``cf_vote_tilings`` writes the voted probabilities and logits (the weighted
+        mean of the logits, not the logit of the voted probability) that every result, fixed or optional, is taken from; ``(0,)``
+        launches and allocates nothing that was not before.
+
+        The tuple is a ``validation_round.RoundResult``: every result is also an attribute of its name, None when not asked for.
+        ``RoundSpec`` checks the options, ``RoundPlan`` holds the sizes and the layout of the result buffer (host-only, both).  The
+        selection goes up as ONE small int64 array; ``cf_validation_gather`` packs the batch, the forward pass writes probabilities and
+        logits (the weights just trained, as ``score_windows`` uses them), ``cf_validation_score`` reduces them -- more than 16
+        thresholds in groups of 16 over the same forward pass -- and ONE copy brings the results back; all on the current stream.  The
+        work buffers stay on the object and grow only when a round is larger than every one before (``validation_buffers``: its
+        ``capacity`` has the keys of ``RoundPlan.need``, its counters say how often each was allocated or uploaded)."""
         import torch
         from .validation_round import RoundPlan, RoundSpec, grow, walk
         self._require_engine()
         spec = RoundSpec.of(thresholds, run_edges, border_reach, curve_shift, bridge_gap, phases, vote_weight, max_bases, vote_bases, score_shift)
-        table = None if spec.vote_bases is None else vset.base_table("score_validation_device: vote_bases")
-        if spec.max_bases is not None and vset.basemap is None:
-            raise ValueError("score_validation_device: max_bases needs a set with a base map (DeviceValidationSet.from_events)")
-        if spec.border_reach is not None and not vset.labels_binary:
-            raise ValueError("score_validation_device: border_reach needs a set whose labels are all 0 or 1")
+        asked = [row for row, _value in spec.asked]
+        for row in reversed(asked):                                                  # (last row first: the first refusal is the one it was)
+            if row.needs is not None:
+                row.needs(vset)
         read_index, first, length = vset.check_selection(selection)
         if read_index.size == 0:
             raise ValueError("score_validation_device: no read selected")
-        plan = RoundPlan(spec, length, self.window, None if table is None else table.n_bases)
+        plan = RoundPlan(spec, length, self.window, None if vset.bases is None else vset.bases.n_bases)
         device = torch.device("cuda", self.device)
         signal, labels = vset.device_arrays(device)
         book = self.validation_buffers
@@ -283,13 +266,13 @@ class RNN(object):
         t["table"][:3 * (plan.n + 1)].copy_(torch.from_numpy(plan.table(vset.offsets, read_index, first).reshape(-1)))
         book["selection_uploads"] += 1
         edges_d, longest_range = None, 0
-        if table is not None:                                                        # the stretches' base ranges: host work, one more small table
+        if "vote_work" in plan.need:                                                 # the stretches' base ranges: host work, one more small table
             from .base_votes import event_ranges
-            a, b = event_ranges(table.edges, vset.offsets[read_index] + first, length)
+            a, b = event_ranges(vset.bases.edges, vset.offsets[read_index] + first, length)
             t["vote_ranges"][:2 * plan.n].copy_(torch.from_numpy(np.concatenate((a, b))))
             edges_d, longest_range = vset.device_edges(device), int((b - a).max())
         out = walk(self.engine, plan, t, book["thresholds"][1], signal, labels, self.window,
-                   None if spec.max_bases is None and table is None else vset.device_basemap(device), edges_d, longest_range)
+                   vset.device_basemap(device) if any(row.basemap for row in asked) else None, edges_d, longest_range)
         back = out.cpu().numpy()                                                     # synchronises the stream
         self.engine.check_error()
         return plan.results(back)

@@ -18,6 +18,7 @@ import datetime
 import json
 import os
 import random
+from collections import namedtuple
 
 import numpy as np
 
@@ -26,6 +27,7 @@ from .device_validation import (BASE_CLASSES, BORDER_REACH, MAX_BASES, RUN_SCORE
                                 curve_thresholds, curves_from_histogram, run_base_rates, run_border_summary, run_score_summary,
                                 run_state_rates, split_run_borders)
 from .neural_network import build_model as _build_model
+from .validation_round import CHECK_ORDER, OPTIONS
 
 
 def reshape_input(data, window, n_inputs):
@@ -226,9 +228,85 @@ def border_report(row, reach):
     return tuple(out)
 
 
+def _state_fields(run_edges, table):
+    complete, found, called_absent = run_state_rates(table)
+    return {"hp_states": table[0].tolist(), "called_states": table[1].tolist(), "hp_complete": complete, "hp_found": found,
+            "called_absent": called_absent}
+
+
+def _base_fields(max_bases, table):
+    return {"hp_bases": table[0].tolist(), "called_bases": table[1].tolist(), **run_base_rates(table)}
+
+
+def _vote_fields(vote_bases, confusion, vote_runs):
+    from .base_votes import base_vote_rates
+    return {"base_confusion": confusion.tolist(), **base_vote_rates(confusion), "vote_runs": run_base_rates(vote_runs)}
+
+
+def _vote_line(vote_bases, confusion, vote_runs):
+    from .base_votes import base_vote_rates
+    return {"threshold": 0.5, "max_bases": int(vote_bases), "classes": list(BASE_CLASSES), "states": list(RUN_STATES),
+            "base_confusion": confusion.tolist(), **base_vote_rates(confusion), "hp_vote_runs": vote_runs[0].tolist(),
+            "called_vote_runs": vote_runs[1].tolist(), **run_base_rates(vote_runs)}
+
+
+def _curve_line(shift, histogram):
+    curves = curves_from_histogram(histogram, shift)
+    return {"shift": int(shift), **{key: curves[key] for key in ("roc_auc", "roc_auc_slack", "pr_auc", "best_f1", "n_pos", "n_neg", "n_other")}}
+
+
+# How each optional result of a round (``validation_round.OPTIONS``, same keys in the same order) is reported.  The network carries the
+# option as ``validation_<option>`` and ``validate`` leaves every result in ``validation_<result>`` ([0] of a per-threshold one).
+#   refusal      why ``validate`` cannot count it over a list of paths
+#   sweep        (value, one threshold's table or tables) -> what it adds to a ``threshold_sweep`` row; None: nothing
+#   line         (value, the round's table or tables) -> its JSON line per checkpoint round, after ``step`` and before ``bridge_gap``
+#   suffix       ... appended to ``<model path><suffix>.jsonl``
+#   nan_as_null  ... through ``_json_line``; otherwise ``json.dumps``
+Report = namedtuple("Report", "refusal sweep line suffix nan_as_null")
+REPORTS = {
+    "run_edges": Report(
+        "validate: run_edges needs a DeviceValidationSet (the run states are counted on the card)", _state_fields,
+        lambda edges, table: {"threshold": 0.5, "edges": list(edges), "states": list(RUN_STATES), **_state_fields(edges, table)},
+        "_hp_states", False),
+    "border_reach": Report(
+        "validate: border_reach needs a DeviceValidationSet (the borders are compared on the card)",
+        lambda reach, table: dict(zip(("hp_borders", "called_borders"), border_report(table, reach))),
+        lambda reach, table: {"threshold": 0.5, "reach": int(reach), **dict(zip(("hp_borders", "called_borders"), border_report(table, reach)))},
+        "_hp_borders", False),
+    "curve_shift": Report(
+        "validate: curve_shift needs a DeviceValidationSet (the probabilities are binned on the card)", None, _curve_line, "_curves", True),
+    "max_bases": Report(
+        "validate: max_bases needs a DeviceValidationSet with a base map (the bases are counted on the card)", _base_fields,
+        lambda most, table: {"threshold": 0.5, "max_bases": int(most), "classes": list(BASE_CLASSES), "states": list(RUN_STATES),
+                             **_base_fields(most, table)},
+        "_hp_bases", False),
+    "vote_bases": Report(
+        "validate: vote_bases needs a DeviceValidationSet with a base table (the bases are voted on the card)", _vote_fields, _vote_line,
+        "_base_votes", False),
+    "score_shift": Report(
+        "validate: score_shift needs a DeviceValidationSet (the scores under runs are binned on the card)",
+        lambda shift, table: dict(zip(("hp_scores", "called_scores"), run_score_summary(table, shift))),
+        lambda shift, table: {"threshold": 0.5, "shift": int(shift), "states": list(RUN_STATES),
+                              **dict(zip(("hp_scores", "called_scores"), run_score_summary(table, shift)))},
+        "_hp_scores", True)}
+_REPORT_ORDER = tuple(sorted(OPTIONS, key=lambda row: not row.per_threshold))       # the files in the order the round launches: the curve last
+
+
+def _given(**options):
+    """The options that were given (not None), in the order of the tables: what a round is asked for, and nothing else."""
+    return {option: options[option] for option in REPORTS if options.get(option) is not None}
+
+
+def _bridged(given):
+    """Whether ``bridge_gap`` changes any of the results asked for."""
+    return any(row.bridged for row in OPTIONS if row.option in given)
+
+
 def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     """What the reference does at a checkpoint step (networks/train_validate.py:154-175): save, score the batch just
-    trained on, run one round of validation; the report lines go to ``report`` in that order."""
+    trained on, run one round of validation; the report lines go to ``report`` in that order.  Every optional result the network asks
+    for (``network.validation_<option>``, a row of ``REPORTS``) is appended as one JSON line to its own file next to the report, which
+    stays the reference's."""
     network.save_network_to_model_path(step)
     saved = "Saved checkpoint at step {}\n".format(step)
     print(saved)
@@ -240,70 +318,21 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     print("Validated in {}".format(datetime.datetime.now() - clock))
     _append(report, "\nTraining accuracy: {}\nTraining loss: {}\n".format(batch_acc, batch_loss))
     clock = datetime.datetime.now()
-    run_edges = getattr(network, "validation_run_edges", None)
-    curve_shift = getattr(network, "validation_curve_shift", None)
-    border_reach = getattr(network, "validation_border_reach", None)
-    extra = {} if curve_shift is None else {"curve_shift": curve_shift}
-    if border_reach is not None:
-        extra["border_reach"] = border_reach
-    max_bases = getattr(network, "validation_max_bases", None)
-    if max_bases is not None:
-        extra["max_bases"] = max_bases
-    vote_bases = getattr(network, "validation_vote_bases", None)
-    if vote_bases is not None:
-        extra["vote_bases"] = vote_bases
-    score_shift = getattr(network, "validation_score_shift", None)
-    if score_shift is not None:
-        extra["score_shift"] = score_shift
+    given = _given(**{option: getattr(network, "validation_" + option, None) for option in REPORTS})
+    extra = dict(given)
     bridge_gap = int(getattr(network, "validation_bridge_gap", 0) or 0)
     if bridge_gap:
         extra["bridge_gap"] = bridge_gap
     if getattr(network, "validation_loader", None) is not None:
         extra["loader"] = network.validation_loader
-    if run_edges is None:
-        _acc, precision, recall = validate(network, *validation, **extra)
-    else:
-        # the homopolymers the round found, next to the report (which stays the reference's): one JSON line per round
-        _acc, precision, recall = validate(network, *validation, run_edges=run_edges, **extra)
-        table = np.asarray(network.validation_run_states)
-        complete, found, called_absent = run_state_rates(table)
-        _append(report[:-len(".txt")] + "_hp_states.jsonl", json.dumps({
-            "step": int(step), "threshold": 0.5, "edges": list(run_edges), "states": list(RUN_STATES),
-            "hp_states": table[0].tolist(), "called_states": table[1].tolist(), "hp_complete": complete, "hp_found": found,
-            "called_absent": called_absent, **({"bridge_gap": bridge_gap} if bridge_gap else {})}) + "\n")
-    if border_reach is not None:
-        # how far the round's called borders miss the true ones, and how often a homopolymer comes in pieces: one JSON line per round
-        hp_borders, called_borders = border_report(network.validation_run_borders, border_reach)
-        _append(report[:-len(".txt")] + "_hp_borders.jsonl", json.dumps({
-            "step": int(step), "threshold": 0.5, "reach": int(border_reach), "hp_borders": hp_borders,
-            "called_borders": called_borders, **({"bridge_gap": bridge_gap} if bridge_gap else {})}) + "\n")
-    if max_bases is not None:
-        # which homopolymers the round found, by base and by length in bases: one JSON line per round
-        table = np.asarray(network.validation_run_bases)
-        _append(report[:-len(".txt")] + "_hp_bases.jsonl", json.dumps({
-            "step": int(step), "threshold": 0.5, "max_bases": int(max_bases), "classes": list(BASE_CLASSES), "states": list(RUN_STATES),
-            "hp_bases": table[0].tolist(), "called_bases": table[1].tolist(), **run_base_rates(table),
-            **({"bridge_gap": bridge_gap} if bridge_gap else {})}) + "\n")
-    if vote_bases is not None:
-        # the round's per-base calls: every base voted by its samples, scored by base: one JSON line per round
-        from .base_votes import base_vote_rates
-        confusion, vote_runs = np.asarray(network.validation_base_confusion), np.asarray(network.validation_base_vote_runs)
-        _append(report[:-len(".txt")] + "_base_votes.jsonl", json.dumps({
-            "step": int(step), "threshold": 0.5, "max_bases": int(vote_bases), "classes": list(BASE_CLASSES), "states": list(RUN_STATES),
-            "base_confusion": confusion.tolist(), **base_vote_rates(confusion), "hp_vote_runs": vote_runs[0].tolist(),
-            "called_vote_runs": vote_runs[1].tolist(), **run_base_rates(vote_runs)}) + "\n")
-    if score_shift is not None:
-        # what the samples under the round's runs scored, by state of the run: one JSON line per round
-        hp_scores, called_scores = run_score_summary(network.validation_run_scores, score_shift)
-        _append(report[:-len(".txt")] + "_hp_scores.jsonl", _json_line({
-            "step": int(step), "threshold": 0.5, "shift": int(score_shift), "states": list(RUN_STATES), "hp_scores": hp_scores,
-            "called_scores": called_scores, **({"bridge_gap": bridge_gap} if bridge_gap else {})}))
-    if curve_shift is not None:
-        # the round's whole ROC and precision-recall curves, reduced to their areas and the best F1: one JSON line per round
-        curves = curves_from_histogram(network.validation_curve, curve_shift)
-        line = {"step": int(step), "shift": int(curve_shift)}
-        line.update({key: curves[key] for key in ("roc_auc", "roc_auc_slack", "pr_auc", "best_f1", "n_pos", "n_neg", "n_other")})
-        _append(report[:-len(".txt")] + "_curves.jsonl", _json_line(line))
+    _acc, precision, recall = validate(network, *validation, **extra)
+    for row in _REPORT_ORDER:
+        if row.option in given:
+            how = REPORTS[row.option]
+            record = {"step": int(step), **how.line(given[row.option], *(np.asarray(getattr(network, "validation_" + name)) for name in row.names))}
+            if bridge_gap and row.bridged:
+                record["bridge_gap"] = bridge_gap
+            _append(report[:-len(".txt")] + how.suffix + ".jsonl", _json_line(record) if how.nan_as_null else json.dumps(record) + "\n")
     print("Validated in {}".format(datetime.datetime.now() - clock))
     _append(report, "Validation precision: {}\nValidation recall: {}\n".format(precision, recall))
     return batch_acc
@@ -458,30 +487,29 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
     accuracy / loss are left out of the averages, which still divide by the number of reads (:248-256); no read
     selected -> ZeroDivisionError.
 
-    ``run_edges`` (a ``DeviceValidationSet`` only): the round also counts the homopolymers found at threshold 0.5
-    (``device_validation.run_states_host``, on the card); the [2, B, 3] table is left in ``network.validation_run_states``.
-    ``curve_shift`` (a ``DeviceValidationSet`` only; an int in 10 .. 22): the round also bins its probabilities
-    (``device_validation.curve_host``, on the card); the [3, NB] histogram is left in ``network.validation_curve``.
-    ``border_reach`` (a ``DeviceValidationSet`` only; an int in 1 .. 128): the round also counts how far the called borders miss
-    the true ones and the interruptions at threshold 0.5 (``device_validation.run_borders_host``, on the card); the
-    [2, 5 * border_reach + 3] table is left in ``network.validation_run_borders``.
-    ``max_bases`` (a ``DeviceValidationSet`` with a base map only; an int in 1 .. 32): the round also counts its runs at threshold
-    0.5 by base and by length in bases (``device_validation.run_bases_host``, on the card); the [2, 3, 5, max_bases + 1] table is
-    left in ``network.validation_run_bases``.
-    ``vote_bases`` (a ``DeviceValidationSet`` with a base table only; an int in 1 .. 32): the round also lets the samples of every
-    base vote on it at threshold 0.5 and scores the voted bases by base (``base_votes.vote_host``, on the card); the [5, 2, 2]
-    confusion table is left in ``network.validation_base_confusion`` and the [2, 3, 5, vote_bases + 1] run table in
-    ``network.validation_base_vote_runs``.
-    ``score_shift`` (a ``DeviceValidationSet`` only; an int in 14 .. 22): the round also bins the probabilities under its runs at
-    threshold 0.5 by kind and state of the run (``device_validation.run_scores_host``, on the card); the [2, 3, NB + 1] table is left
-    in ``network.validation_run_scores``.
+    The optional results of a round on the card (a ``DeviceValidationSet`` only; a list of paths is refused with the row's text in
+    ``REPORTS``), each counted at threshold 0.5 and left on the network -- ``RNN.score_validation_device`` has the ranges of the options
+    and the definitions:
+
+        ``run_edges``     the homopolymers found, per length bin           ``network.validation_run_states`` [2, B, 3]
+        ``border_reach``  how far the called borders miss, interruptions   ``network.validation_run_borders`` [2, 5 * border_reach + 3]
+        ``curve_shift``   the probabilities binned (no threshold)          ``network.validation_curve`` [3, NB]
+        ``max_bases``     the runs by base and length in bases; needs a    ``network.validation_run_bases`` [2, 3, 5, max_bases + 1]
+                          set with a base map
+        ``vote_bases``    every base voted by its samples, scored by       ``network.validation_base_confusion`` [5, 2, 2] and
+                          base; needs a set with a base table              ``network.validation_base_vote_runs`` [2, 3, 5, vote_bases + 1]
+        ``score_shift``   the probabilities under the runs, by kind and    ``network.validation_run_scores`` [2, 3, NB + 1]
+                          state of the run
+
     ``bridge_gap`` (with ``run_edges``, ``border_reach``, ``max_bases`` or ``score_shift``; 0 .. 49): those tables are counted on the
     prediction with its gaps of at most that many samples bridged (``infer.bridge_gaps``).
     ``loader`` (a list of paths only): what reads a path into ``(raw, labels)`` instead of ``load_npz``.
     Report, prints and return value stay as they are."""
     from .calling import CallRule
     bridge_gap = CallRule.of(max_gap=bridge_gap).max_gap
-    if bridge_gap and run_edges is None and border_reach is None and max_bases is None and score_shift is None:
+    given = _given(run_edges=run_edges, border_reach=border_reach, curve_shift=curve_shift, max_bases=max_bases, vote_bases=vote_bases,
+                   score_shift=score_shift)
+    if bridge_gap and not _bridged(given):
         raise ValueError("validate: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
     print("Max length is {}".format(max_seq_length))
     print("Validation start is {}".format(validation_start))
@@ -493,46 +521,19 @@ def validate(network, squiggles, max_seq_length, file_path, validation_start="ra
         n_samples = int(selection[2].sum())
         if n_reads == 0:
             raise ZeroDivisionError("validation selected no read")
-        if run_edges is None and curve_shift is None and border_reach is None and max_bases is None and vote_bases is None and score_shift is None:
+        if not given:
             right, ce_sum, counts_k = network.score_validation_device(squiggles, selection)
         else:
-            extra = {} if border_reach is None else {"border_reach": border_reach}
-            if max_bases is not None:
-                extra["max_bases"] = max_bases
-            if vote_bases is not None:
-                extra["vote_bases"] = vote_bases
-            if score_shift is not None:
-                extra["score_shift"] = score_shift
-            if bridge_gap:
-                extra["bridge_gap"] = bridge_gap
-            got = network.score_validation_device(squiggles, selection, (0.5,), run_edges=run_edges, curve_shift=curve_shift, **extra)
+            got = network.score_validation_device(squiggles, selection, (0.5,), **given, **({"bridge_gap": bridge_gap} if bridge_gap else {}))
             right, ce_sum, counts_k = got[:3]
-            if run_edges is not None:
-                network.validation_run_states = got.run_states[0]
-            if border_reach is not None:
-                network.validation_run_borders = got.run_borders[0]
-            if curve_shift is not None:
-                network.validation_curve = got.curve
-            if max_bases is not None:
-                network.validation_run_bases = got.run_bases[0]
-            if vote_bases is not None:
-                network.validation_base_confusion, network.validation_base_vote_runs = got.base_confusion[0], got.base_vote_runs[0]
-            if score_shift is not None:
-                network.validation_run_scores = got.run_scores[0]
+            for row in OPTIONS:
+                for name in row.names if row.option in given else ():
+                    setattr(network, "validation_" + name, getattr(got, name)[0] if row.per_threshold else getattr(got, name))
         acc, loss, counts = squiggles.finish(right, ce_sum, counts_k[0], *squiggles.layout(selection[2], network.window))
     else:
-        if run_edges is not None:
-            raise ValueError("validate: run_edges needs a DeviceValidationSet (the run states are counted on the card)")
-        if curve_shift is not None:
-            raise ValueError("validate: curve_shift needs a DeviceValidationSet (the probabilities are binned on the card)")
-        if border_reach is not None:
-            raise ValueError("validate: border_reach needs a DeviceValidationSet (the borders are compared on the card)")
-        if max_bases is not None:
-            raise ValueError("validate: max_bases needs a DeviceValidationSet with a base map (the bases are counted on the card)")
-        if vote_bases is not None:
-            raise ValueError("validate: vote_bases needs a DeviceValidationSet with a base table (the bases are voted on the card)")
-        if score_shift is not None:
-            raise ValueError("validate: score_shift needs a DeviceValidationSet (the scores under runs are binned on the card)")
+        for row in CHECK_ORDER:                            # what is counted on the card cannot be asked of paths
+            if row.option in given:
+                raise ValueError(REPORTS[row.option].refusal)
         signals, labels = select_validation_stretches(squiggles, network.window, max_seq_length, validation_start,
                                                       max_number, **({} if loader is None else {"loader": loader}))
         n_reads = len(signals)
@@ -571,31 +572,25 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     from its probabilities on the card.  The stretches are ``validate``'s (same selection, same tail rule for the true
     negatives).  -> a list of dicts {threshold, tp, fp, tn, fn, precision, recall, f1}, one per threshold, in order.
 
-    With ``run_edges`` (up to 7 ascending run lengths, possibly none) every row also says how many homopolymers that threshold
-    finds (``device_validation.run_states_host``; the reference's offline networks/process_output.py:235-273): ``hp_states`` and
-    ``called_states`` -- per length bin [complete, incomplete, absent] of the true runs against the corrected prediction and of
-    the called runs against the truth --, ``hp_complete`` and ``hp_found`` (complete, complete + incomplete over all true runs)
-    and ``called_absent`` (called runs that hold no homopolymer sample over all called runs); 0 for an empty denominator.
+    Every optional result given adds its fields to every row (``REPORTS[option].sweep``; the options' ranges and what is counted:
+    ``RNN.score_validation_device``; the reference does all of this offline, networks/process_output.py):
 
-    With ``border_reach`` (an int in 1 .. 128) every row also says how far that threshold's borders miss
-    (``device_validation.run_borders_host``; the rest of the reference's ``check_hp``): ``hp_borders`` -- the true runs against
-    the corrected prediction -- and ``called_borders`` -- the called runs against the truth --, each ``border_report``'s dict.
-
-    With ``max_bases`` (an int in 1 .. 32; a set with a base map) every row also says which homopolymers that threshold finds
-    (``device_validation.run_bases_host``; the reference's offline ``prediction_information``): ``hp_bases`` and ``called_bases``
-    -- per state, base class (A / C / G / T / other) and length in bases how many true and called runs, ``[3][5][max_bases + 1]``
-    lists -- and the fields of ``device_validation.run_base_rates``.
-
-    With ``vote_bases`` (an int in 1 .. 32; a set with a base table) every row also carries that threshold's per-base calls
-    (``base_votes.vote_host``: the samples of every base vote on it): ``base_confusion`` -- per base class [truth][called] how many
-    voted bases, a ``[5][2][2]`` list --, the fields of ``base_votes.base_vote_rates`` (per-base precision / recall / F1, overall and
-    per letter) and ``vote_runs``, the fields of ``device_validation.run_base_rates`` over the runs on the base axis.
-
-    With ``score_shift`` (an int in 14 .. 22) every row also says what the samples under that threshold's runs scored
-    (``device_validation.run_scores_host``; the reference's offline ``check_for_false_neg``): ``hp_scores`` and ``called_scores`` --
-    per state [complete, incomplete, absent] of the true and of the called runs ``device_validation.run_score_summary``'s dict (n,
-    mean, q1 / median / q3 as the edges of their bin), so ``hp_scores[2]`` tells how close the missed homopolymers were to the
-    threshold and ``called_scores[2]`` how confident the calls that hold none.
+        ``run_edges``     ``hp_states`` and ``called_states`` -- per length bin [complete, incomplete, absent] of the true runs against the
+                          corrected prediction and of the called runs against the truth --, ``hp_complete`` and ``hp_found`` (complete,
+                          complete + incomplete over all true runs) and ``called_absent`` (called runs that hold no homopolymer sample over
+                          all called runs); 0 for an empty denominator (:235-273)
+        ``border_reach``  ``hp_borders`` and ``called_borders``, each ``border_report``'s dict: how far that threshold's borders miss (the
+                          rest of ``check_hp``)
+        ``max_bases``     ``hp_bases`` and ``called_bases`` -- per state, base class (A / C / G / T / other) and length in bases how many true
+                          and called runs, ``[3][5][max_bases + 1]`` lists -- and the fields of ``device_validation.run_base_rates``
+                          (``prediction_information``); a set with a base map
+        ``vote_bases``    ``base_confusion`` -- per base class [truth][called] how many voted bases, a ``[5][2][2]`` list --, the fields of
+                          ``base_votes.base_vote_rates`` (per-base precision / recall / F1, overall and per letter) and ``vote_runs``, the
+                          fields of ``run_base_rates`` over the runs on the base axis; a set with a base table
+        ``score_shift``   ``hp_scores`` and ``called_scores`` -- per state of the true and of the called runs
+                          ``device_validation.run_score_summary``'s dict (n, mean, q1 / median / q3 as the edges of their bin), so
+                          ``hp_scores[2]`` tells how close the missed homopolymers were to the threshold and ``called_scores[2]`` how
+                          confident the calls that hold none (``check_for_false_neg``)
 
     ``bridge_gap`` (with ``run_edges``, ``border_reach``, ``max_bases`` or ``score_shift``; 0 .. 49): those tables are those of the prediction
     with its gaps of at most that many samples bridged (``infer.bridge_gaps``); tp / fp / tn / fn stay per-sample counts.
@@ -606,41 +601,36 @@ def threshold_sweep(network, vset, thresholds, max_seq_length, validation_start=
     rule = CallRule.of(max_gap=bridge_gap, phases=phases, vote_weight=vote_weight)
     bridge_gap = rule.max_gap
     voted = {"phases": rule.phases, "vote_weight": rule.vote_weight} if rule.voted else {}      # (0,): the call of before
-    if bridge_gap and run_edges is None and border_reach is None and max_bases is None and score_shift is None:
+    given = _given(run_edges=run_edges, border_reach=border_reach, max_bases=max_bases, vote_bases=vote_bases, score_shift=score_shift)
+    if bridge_gap and not _bridged(given):
         raise ValueError("threshold_sweep: bridge_gap changes the run states and the borders only: give run_edges or border_reach")
-    given = {"run_edges": run_edges, "border_reach": border_reach, "bridge_gap": bridge_gap or None, "max_bases": max_bases,
-             "vote_bases": vote_bases, "score_shift": score_shift}
-    given = {key: value for key, value in given.items() if value is not None}                  # nothing given: the call of before
+    bridged = {"bridge_gap": bridge_gap} if bridge_gap else {}                                  # nothing given: the call of before
     thresholds = [float(t) for t in thresholds]
     selection = vset.select(network.window, max_seq_length, validation_start, max_number)
     if len(selection[0]) == 0:
         raise ZeroDivisionError("validation selected no read")
-    got = network.score_validation_device(vset, selection, thresholds, **given, **voted)
+    got = network.score_validation_device(vset, selection, thresholds, **given, **bridged, **voted)
     counts = got[2]
-    run_states = None if run_edges is None else got.run_states
-    borders = None if border_reach is None else got.run_borders
     tail = int(vset.layout(selection[2], network.window)[1].sum())
     rows = []
     for k, (t, (tp, fp, tn_raw, fn)) in enumerate(zip(thresholds, np.asarray(counts).tolist())):
         precision, recall = metrics.precision_recall(tp, fp, fn)
         rows.append({"threshold": t, "tp": tp, "fp": fp, "tn": tn_raw - tail, "fn": fn, "precision": precision, "recall": recall,
                      "f1": metrics.f1(precision, recall)})
-        if run_states is not None:
-            complete, found, called_absent = run_state_rates(run_states[k])
-            rows[-1].update({"hp_states": run_states[k][0].tolist(), "called_states": run_states[k][1].tolist(),
-                             "hp_complete": complete, "hp_found": found, "called_absent": called_absent})
-        if borders is not None:
-            rows[-1]["hp_borders"], rows[-1]["called_borders"] = border_report(borders[k], border_reach)
-        if max_bases is not None:
-            rows[-1].update({"hp_bases": got.run_bases[k][0].tolist(), "called_bases": got.run_bases[k][1].tolist(),
-                             **run_base_rates(got.run_bases[k])})
-        if vote_bases is not None:
-            from .base_votes import base_vote_rates
-            rows[-1].update({"base_confusion": got.base_confusion[k].tolist(), **base_vote_rates(got.base_confusion[k]),
-                             "vote_runs": run_base_rates(got.base_vote_runs[k])})
-        if score_shift is not None:
-            rows[-1]["hp_scores"], rows[-1]["called_scores"] = run_score_summary(got.run_scores[k], score_shift)
+        for row in OPTIONS:
+            if row.option in given and REPORTS[row.option].sweep is not None:
+                rows[-1].update(REPORTS[row.option].sweep(given[row.option], *(getattr(got, name)[k] for name in row.names)))
     return rows
+
+
+def _interrupted_shares(row):
+    """Of a ``threshold_sweep`` row with borders: the share of the true (called) runs that are not absent and have at least one
+    interruption in the other array."""
+    out = {}
+    for name, part in (("hp_interrupted", row["hp_borders"]), ("called_interrupted", row["called_borders"])):
+        judged = int(np.sum(part["left"]))
+        out[name] = part["interrupted_runs"] / judged if judged else 0
+    return out
 
 
 def bridge_sweep(network, vset, gaps, max_seq_length, threshold=0.5, validation_start="complete", max_number=856, run_edges=(),
@@ -656,9 +646,7 @@ def bridge_sweep(network, vset, gaps, max_seq_length, threshold=0.5, validation_
                               border_reach=border_reach, bridge_gap=gap)[0]
         out = {"bridge_gap": int(gap)}
         out.update({key: row[key] for key in ("hp_complete", "hp_found", "called_absent", "hp_states", "called_states")})
-        for name, part in (("hp_interrupted", row["hp_borders"]), ("called_interrupted", row["called_borders"])):
-            judged = int(np.sum(part["left"]))
-            out[name] = part["interrupted_runs"] / judged if judged else 0
+        out.update(_interrupted_shares(row))
         rows.append(out)
     return rows
 
@@ -681,9 +669,7 @@ def tiling_sweep(network, vset, phase_sets, max_seq_length, weight="mean", thres
         out = {"phases": list(phases), "weight": weight}
         out.update({key: row[key] for key in ("tp", "fp", "tn", "fn", "precision", "recall", "f1", "hp_complete", "hp_found",
                                               "called_absent", "hp_states", "called_states")})
-        for name, part in (("hp_interrupted", row["hp_borders"]), ("called_interrupted", row["called_borders"])):
-            judged = int(np.sum(part["left"]))
-            out[name] = part["interrupted_runs"] / judged if judged else 0
+        out.update(_interrupted_shares(row))
         rows.append(out)
     return rows
 
@@ -857,8 +843,7 @@ def main(argv):
         if bridge:                                               # ... both counted on the bridged prediction
             from .infer import check_bridge
             network.validation_bridge_gap = check_bridge(bridge, 15)
-            if getattr(network, "validation_run_edges", None) is None and getattr(network, "validation_border_reach", None) is None \
-                    and getattr(network, "validation_max_bases", None) is None and getattr(network, "validation_score_shift", None) is None:
+            if not _bridged(_given(**{option: getattr(network, "validation_" + option, None) for option in REPORTS})):
                 raise ValueError("CATFISH_VALIDATION_BRIDGE needs CATFISH_VALIDATION_RUNS=1 or CATFISH_VALIDATION_BORDERS")
     began = datetime.datetime.now()
     train_and_validate(network, db_train, n_train, squiggles, stretch, network.model_path, start, most)

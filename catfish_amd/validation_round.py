@@ -6,7 +6,9 @@ Spec, plan and result are ints and numpy only and usable without a GPU; torch is
 statements of what every launch computes stay in ``device_validation``."""
 from __future__ import annotations
 
+import math
 from collections import namedtuple
+from operator import attrgetter
 
 import numpy as np
 
@@ -15,17 +17,112 @@ from . import device_validation as dv
 from .calling import CallRule
 from .tilings import tiling_size
 
-RESULTS = ("right", "ce_sum", "counts", "run_states", "run_borders", "curve")     # the order in the result buffer and in the tuple
-EXTRA_RESULTS = ("run_bases",)          # ... and after them, with keys in ``offset`` / ``cells`` / ``need`` only when asked for
-VOTE_RESULTS = base_votes.VOTE_RESULTS  # ... then the two per-base tables of ``vote_bases``, under the same rule
-SCORE_RESULTS = ("run_scores",)         # ... and last the scores under runs of ``score_shift``, under the same rule
+
+# ------------------------------------------------------------------ what the rows of ``OPTIONS`` below name: checks and launches
+def _checked_curve_shift(shift):
+    dv.curve_bins(shift)
+    return int(shift)
+
+
+def _needs_binary_labels(vset):
+    if not vset.labels_binary:
+        raise ValueError("score_validation_device: border_reach needs a set whose labels are all 0 or 1")
+
+
+def _needs_base_map(vset):
+    if vset.basemap is None:
+        raise ValueError("score_validation_device: max_bases needs a set with a base map (DeviceValidationSet.from_events)")
+
+
+def _needs_base_table(vset):
+    vset.base_table("score_validation_device: vote_bases")
+
+
+def _run_step(method):
+    """The launch of a step that corrects the thresholded prediction in the label work space and counts its runs."""
+    def launch(engine, plan, on, thresholds, value, outs):
+        rule = plan.spec.rule
+        getattr(engine, method)(on.probs, on.y, on.bounds, on.length, plan.total, plan.longest, thresholds, value, outs[0], on.t["run_work"],
+                                min_run=rule.min_run, max_gap=rule.max_gap)
+    return launch
+
+
+def _run_bases(engine, plan, on, thresholds, value, outs):
+    rule = plan.spec.rule
+    engine.run_bases_validation(on.probs, on.y, on.basemap, on.src, on.bounds, on.length, plan.total, plan.longest, thresholds, value, outs[0],
+                                on.t["run_work"], min_run=rule.min_run, max_gap=rule.max_gap)
+
+
+def _base_votes(engine, plan, on, thresholds, value, outs):
+    engine.base_votes_validation(on.probs, on.labels, on.basemap, on.edges, on.src, on.bounds, on.length, on.t["vote_ranges"][:2 * plan.n],
+                                 plan.total, on.longest_range, thresholds, value, outs[0], outs[1], on.t["vote_work"])
+
+
+def _curve(engine, plan, on, thresholds, value, outs):
+    engine.curve_validation(on.probs, on.y, on.bounds, on.length, plan.total, plan.longest, value, outs[0])
+
+
+class Option(namedtuple("Option", "option check results need_key launch run_work bridged per_threshold listed work needs basemap",
+                        defaults=(True, False, None, None, False))):
+    """One optional result of a round (two for ``vote_bases``), stated once:
+
+    ``option``         the ``RoundSpec`` field and keyword; None there: not asked for
+    ``check``          value -> the checked value, or ValueError
+    ``results``        ``(name, shape)`` per result, ``shape(value)`` being one threshold's (the whole result's when not
+                       ``per_threshold``); its cells in the result buffer are the product of the shape, per threshold
+    ``need_key``       where ``RoundPlan.need`` states the cells of all its results
+    ``launch``         ``(engine, plan, on, thresholds of the group, value, the group's cells of every result)``: its ``HipEngine`` call
+    ``run_work``       label-sized arrays it uses per threshold of a group in the shared work space ``run_work``: 0 none, 1 the corrected
+                       labels, 2 labels and paint behind them; the round's work space is the largest of these
+    ``bridged``        ``bridge_gap`` changes it
+    ``per_threshold``  launched once per threshold group after ``score_validation``, a leading K axis; otherwise once after the groups
+    ``listed``         history, pinned by the host tests: the results that existed when ``RoundPlan`` was written have their ``offset`` and
+                       ``cells`` keys (0 cells) in a round that does not ask for them; the later ones have no key then
+    ``work``           ``(need key, bytes(n_bases, thresholds of a group))`` of a work space of its own that depends on the set's bases
+    ``needs``          vset -> ValueError when the set lacks what the result is counted from
+    ``basemap``        reads the set's base map on the card"""
+    __slots__ = ()
+
+    @property
+    def names(self):
+        return tuple(name for name, _shape in self.results)
+
+    def shapes(self, value, k_all):
+        """``[(name, shape)]`` of its results in a round of ``k_all`` thresholds."""
+        lead = (k_all,) if self.per_threshold else ()
+        return [(name, lead + tuple(shape(value))) for name, shape in self.results]
+
+
+_BASES = len(dv.BASE_CLASSES)
+OPTIONS = (                                                         # in the order of the result buffer
+    Option("run_edges", dv.check_run_edges, (("run_states", lambda edges: (2, len(edges) + 1, 3)),), "run_cells",
+           _run_step("run_states_validation"), run_work=1, bridged=True, listed=True),
+    Option("border_reach", dv.check_border_reach, (("run_borders", lambda reach: (2, dv.border_cells(reach))),), "border_cells",
+           _run_step("run_borders_validation"), run_work=1, bridged=True, listed=True, needs=_needs_binary_labels),
+    Option("curve_shift", _checked_curve_shift, (("curve", lambda shift: (3, dv.curve_bins(shift))),), "curve_cells",
+           _curve, run_work=0, bridged=False, per_threshold=False, listed=True),
+    Option("max_bases", dv.check_max_bases, (("run_bases", lambda most: (2, 3, _BASES, most + 1)),), "base_cells",
+           _run_bases, run_work=1, bridged=True, needs=_needs_base_map, basemap=True),
+    Option("vote_bases", base_votes.check_vote_bases,
+           (("base_confusion", lambda most: (_BASES, 2, 2)), ("base_vote_runs", lambda most: (2, 3, _BASES, most + 1))), "vote_cells",
+           _base_votes, run_work=0, bridged=False, work=("vote_work", base_votes.work_bytes), needs=_needs_base_table, basemap=True),
+    Option("score_shift", dv.check_score_shift, (("run_scores", lambda shift: (2, 3, dv.curve_bins(shift) + 1)),), "score_cells",
+           _run_step("run_scores_validation"), run_work=2, bridged=True))
+# history: the curve was the second option to exist, so its check still refuses before the borders' when both values are wrong
+CHECK_ORDER = tuple(sorted(OPTIONS, key=lambda row: row.option not in ("run_edges", "curve_shift")))
+
+FIXED_RESULTS = ("right", "ce_sum", "counts")
+# the tiers the results were added in; all of them, in the order of the result buffer and of the tuple, are ``ALL_RESULTS``
+RESULTS = FIXED_RESULTS + tuple(name for row in OPTIONS if row.listed for name in row.names)
+EXTRA_RESULTS, VOTE_RESULTS, SCORE_RESULTS = (row.names for row in OPTIONS if not row.listed)
+ALL_RESULTS = FIXED_RESULTS + tuple(name for row in OPTIONS for name in row.names)
+assert VOTE_RESULTS == base_votes.VOTE_RESULTS and base_votes.CONFUSION_CELLS == _BASES * 2 * 2
 
 
 class RoundSpec(namedtuple("RoundSpec", "thresholds run_edges border_reach curve_shift rule max_bases vote_bases score_shift",
                            defaults=(None, None, None))):
-    """The options of a round, checked: ``thresholds`` (a tuple of floats, at least one), ``run_edges`` / ``border_reach`` /
-    ``curve_shift`` / ``max_bases`` / ``vote_bases`` / ``score_shift`` (None: that result is not asked for; ``vote_bases`` is the
-    ``max_bases`` of the per-base vote-run table, ``score_shift`` the bin shift of the scores under runs) and the ``calling.CallRule`` that carries ``bridge_gap`` (``max_gap``), ``phases`` and ``vote_weight``.
+    """The options of a round, checked: ``thresholds`` (a tuple of floats, at least one), one field per row of ``OPTIONS`` (None: that
+    result is not asked for) and the ``calling.CallRule`` that carries ``bridge_gap`` (``max_gap``), ``phases`` and ``vote_weight``.
     Build one with ``RoundSpec.of``."""
     __slots__ = ()
 
@@ -34,24 +131,16 @@ class RoundSpec(namedtuple("RoundSpec", "thresholds run_edges border_reach curve
            max_bases=None, vote_bases=None, score_shift=None):
         """The checked spec, or the ValueError of the first of ``CallRule.of``, the thresholds, ``check_run_edges``, ``curve_bins``,
         ``check_border_reach``, ``check_max_bases``, ``base_votes.check_vote_bases``, ``check_score_shift`` that refuses."""
+        given = dict(run_edges=run_edges, border_reach=border_reach, curve_shift=curve_shift, max_bases=max_bases, vote_bases=vote_bases,
+                     score_shift=score_shift)
         rule = CallRule.of(max_gap=bridge_gap, phases=phases, vote_weight=vote_weight)
         thresholds = tuple(float(t) for t in thresholds)
         if not thresholds:
             raise ValueError("score_validation_device: no threshold given")
-        if run_edges is not None:
-            run_edges = dv.check_run_edges(run_edges)
-        if curve_shift is not None:
-            dv.curve_bins(curve_shift)
-            curve_shift = int(curve_shift)
-        if border_reach is not None:
-            border_reach = dv.check_border_reach(border_reach)
-        if max_bases is not None:
-            max_bases = dv.check_max_bases(max_bases)
-        if vote_bases is not None:
-            vote_bases = base_votes.check_vote_bases(vote_bases)
-        if score_shift is not None:
-            score_shift = dv.check_score_shift(score_shift)
-        return cls(thresholds, run_edges, border_reach, curve_shift, rule, max_bases, vote_bases, score_shift)
+        for row in CHECK_ORDER:
+            if given[row.option] is not None:
+                given[row.option] = row.check(given[row.option])
+        return cls(thresholds=thresholds, rule=rule, **given)
 
     @property
     def k_all(self):
@@ -62,34 +151,49 @@ class RoundSpec(namedtuple("RoundSpec", "thresholds run_edges border_reach curve
         """``(k0, k1)`` of every launch group: at most ``MAX_THRESHOLDS`` thresholds each, over the same forward pass."""
         return [(k0, min(self.k_all, k0 + dv.MAX_THRESHOLDS)) for k0 in range(0, self.k_all, dv.MAX_THRESHOLDS)]
 
+    @property
+    def rows(self):
+        """``(row, value)`` for every row of ``OPTIONS``, the value None where the option is not asked for."""
+        return zip(OPTIONS, _VALUES(self))
+
+    @property
+    def asked(self):
+        """``[(row, value)]`` of the options asked for, in the order of ``OPTIONS``."""
+        return [(row, value) for row, value in zip(OPTIONS, _VALUES(self)) if value is not None]
+
+
+_VALUES = attrgetter(*(row.option for row in OPTIONS))
+
 
 class RoundResult(tuple):
     """What ``RNN.score_validation_device`` returns: the tuple ``(right, ce_sum, counts[, run_states][, run_borders][, curve]
-    [, run_bases][, base_confusion, base_vote_runs][, run_scores])`` -- only the results asked for, in that order -- with every result as an
-    attribute of that name too (None when not asked for)."""
+    [, run_bases][, base_confusion, base_vote_runs][, run_scores])`` -- only the results asked for, in the order of ``ALL_RESULTS`` -- with
+    every result as an attribute of that name too (None when not asked for)."""
 
-    def __new__(cls, right, ce_sum, counts, run_states=None, run_borders=None, curve=None, run_bases=None, base_confusion=None,
-                base_vote_runs=None, run_scores=None):
-        fields = (right, ce_sum, counts, run_states, run_borders, curve, run_bases, base_confusion, base_vote_runs, run_scores)
+    def __new__(cls, right, ce_sum, counts, *optional, **named):
+        named.update(zip(ALL_RESULTS[3:], optional))
+        fields = (right, ce_sum, counts) + tuple(named.pop(name, None) for name in ALL_RESULTS[3:])
+        if named:
+            raise TypeError("RoundResult has no result %s" % ", ".join(sorted(named)))
         self = super().__new__(cls, (item for item in fields if item is not None))
-        for name, item in zip(RESULTS + EXTRA_RESULTS + VOTE_RESULTS + SCORE_RESULTS, fields):
+        for name, item in zip(ALL_RESULTS, fields):
             setattr(self, name, item)
         return self
 
 
 class RoundPlan(object):
     """Sizes and layout of one round of ``spec`` over stretches of ``length`` samples packed at ``window``: ``n``, ``bounds``,
-    ``tails`` (``device_validation.layout``), ``total``, ``longest``; ``need``, the capacity every grow-only buffer must have (a key
-    is there only when its result is asked for); ``run_work``, the bytes of corrected labels one threshold group writes
-    (``cf_validation_run_work_bytes`` = ``cf_validation_run_borders_work_bytes``, never below 1); and the one int64 result buffer:
-    ``cells[name]`` cells from ``offset[name]`` for every name of ``RESULTS`` (0 cells for a result not asked for), then those of
-    ``EXTRA_RESULTS`` that are asked for (``run_bases``: ``k_all * 2 * 3 * 5 * (max_bases + 1)`` cells after the curve,
-    ``need["base_cells"]``; a round that does not ask has no such key anywhere), then those of ``VOTE_RESULTS`` under the same rule
-    (``base_confusion``: ``k_all * 20`` cells, ``base_vote_runs``: ``k_all * 2 * 3 * 5 * (vote_bases + 1)``; ``need["vote_cells"]`` is
-    their sum and ``need["vote_work"]`` the bytes of per-base sums and states one threshold group writes, for the set's ``n_bases``),
-    then those of ``SCORE_RESULTS`` (``run_scores``: ``k_all * score_cells(score_shift)`` cells, ``need["score_cells"]``; such a round
-    paints behind its labels, so its ``run_work`` and ``need["run_work"]`` are ``cf_validation_run_scores_work_bytes``, twice the
-    labels), ``out_cells`` in all."""
+    ``tails`` (``device_validation.layout``), ``total``, ``longest``; ``need``, the capacity every grow-only buffer must have;
+    ``run_work``, the bytes of the label work space one threshold group writes; and the one int64 result buffer of ``out_cells``
+    cells: ``cells[name]`` cells from ``offset[name]``, the three fixed results first and then, row by row of ``OPTIONS``, the results
+    asked for -- ``k_all`` times the product of the row's shape (the curve: once).
+
+    ``need``: ``samples``, ``reads``, ``slots``, ``thresholds`` always; per row asked for its ``need_key`` (the cells of its results),
+    ``run_work`` when it uses the label work space, and its own ``work`` entry (``vote_work``: the per-base sums and states one group
+    writes, for the set's ``n_bases``); ``tiling_samples`` for a voted round.  A key is there only when something asks for it.
+    ``run_work``: ``min(k_all, 16)`` label arrays of ``total`` rounded up to 64 (``cf_validation_run_work_bytes`` =
+    ``cf_validation_run_borders_work_bytes``, never below 1), twice that in a round with the scores, which paint behind their labels
+    (``cf_validation_run_scores_work_bytes``).  A ``listed`` row that is not asked for keeps its keys in ``cells`` (0) and ``offset``."""
 
     def __init__(self, spec, length, window, n_bases=None):
         self.spec = spec
@@ -98,46 +202,27 @@ class RoundPlan(object):
         self.bounds, self.tails = dv.layout(self.length, window)
         self.total = total = int(self.bounds[-1])
         self.longest = int(np.diff(self.bounds).max())
-        k_all = spec.k_all
-        self.run_work = max(min(k_all, dv.MAX_THRESHOLDS) * ((total + 63) // 64 * 64), 1)
-        self.cells = {"right": n, "ce_sum": n, "counts": 4 * k_all,
-                      "run_states": 0 if spec.run_edges is None else k_all * 2 * (len(spec.run_edges) + 1) * 3,
-                      "run_borders": 0 if spec.border_reach is None else k_all * 2 * dv.border_cells(spec.border_reach),
-                      "curve": 0 if spec.curve_shift is None else 3 * dv.curve_bins(spec.curve_shift)}
-        self.offset, self.out_cells = {}, 0
-        for name in RESULTS:
-            self.offset[name] = self.out_cells
-            self.out_cells += self.cells[name]
-        if spec.max_bases is not None:
-            self.cells["run_bases"] = k_all * 2 * 3 * len(dv.BASE_CLASSES) * (spec.max_bases + 1)
-            self.offset["run_bases"] = self.out_cells
-            self.out_cells += self.cells["run_bases"]
-        if spec.vote_bases is not None:
-            if n_bases is None:
-                raise ValueError("RoundPlan: a round with vote_bases needs the set's n_bases")
-            for name, per_k in zip(VOTE_RESULTS, (base_votes.CONFUSION_CELLS, 2 * 3 * len(dv.BASE_CLASSES) * (spec.vote_bases + 1))):
-                self.cells[name] = k_all * per_k
-                self.offset[name] = self.out_cells
-                self.out_cells += self.cells[name]
-        if spec.score_shift is not None:
-            self.run_work = 2 * self.run_work
-            self.cells["run_scores"] = k_all * dv.score_cells(spec.score_shift)
-            self.offset["run_scores"] = self.out_cells
-            self.out_cells += self.cells["run_scores"]
+        k_all, k_group = spec.k_all, min(spec.k_all, dv.MAX_THRESHOLDS)
+        self.run_work = max(k_group * ((total + 63) // 64 * 64), 1) * max([1] + [row.run_work for row, _value in spec.asked])
+        self.cells = {"right": n, "ce_sum": n, "counts": 4 * k_all}
         self.need = {"samples": max(total, 1), "reads": n, "slots": total // dv.SCORE_CHUNK + n, "thresholds": k_all}
-        if spec.run_edges is not None:
-            self.need.update({"run_cells": self.cells["run_states"], "run_work": self.run_work})
-        if spec.border_reach is not None:
-            self.need.update({"border_cells": self.cells["run_borders"], "run_work": self.run_work})
-        if spec.curve_shift is not None:
-            self.need["curve_cells"] = self.cells["curve"]
-        if spec.max_bases is not None:
-            self.need.update({"base_cells": self.cells["run_bases"], "run_work": self.run_work})
-        if spec.vote_bases is not None:
-            self.need.update({"vote_cells": sum(self.cells[name] for name in VOTE_RESULTS),
-                              "vote_work": base_votes.work_bytes(n_bases, min(k_all, dv.MAX_THRESHOLDS))})
-        if spec.score_shift is not None:
-            self.need.update({"score_cells": self.cells["run_scores"], "run_work": self.run_work})
+        for row, value in spec.rows:
+            if value is None:
+                if row.listed:
+                    self.cells.update(dict.fromkeys(row.names, 0))
+                continue
+            self.cells.update((name, math.prod(shape)) for name, shape in row.shapes(value, k_all))
+            self.need[row.need_key] = sum(self.cells[name] for name in row.names)
+            if row.run_work:
+                self.need["run_work"] = self.run_work
+            if row.work:
+                if n_bases is None:
+                    raise ValueError("RoundPlan: a round with %s needs the set's n_bases" % row.option)
+                self.need[row.work[0]] = row.work[1](n_bases, k_group)
+        self.offset, self.out_cells = {}, 0
+        for name, cells in self.cells.items():
+            self.offset[name] = self.out_cells
+            self.out_cells += cells
         if spec.rule.voted:
             self.need["tiling_samples"] = tiling_size(total, n, spec.rule.n_tilings)
 
@@ -156,23 +241,13 @@ class RoundPlan(object):
 
     def results(self, back):
         """The copied-back result buffer (host int64, ``out_cells`` elements) -> ``RoundResult``: right int64 [n], ce_sum float64 [n]
-        (the cells hold the doubles' bits), counts int64 [K, 4], run states int64 [K, 2, len(run_edges) + 1, 3], borders int64
-        [K, 2, 5 * border_reach + 3], curve histogram int64 [3, curve_bins(curve_shift)], run bases int64
-        [K, 2, 3, 5, max_bases + 1], base confusion int64 [K, 5, 2, 2], base vote runs int64 [K, 2, 3, 5, vote_bases + 1], run scores
-        int64 [K, 2, 3, curve_bins(score_shift) + 1]; every item its own copy."""
-        spec, k_all = self.spec, self.spec.k_all
-        return RoundResult(
-            self.cut(back, "right").copy(), self.cut(back, "ce_sum").view(np.float64).copy(),
-            self.cut(back, "counts").reshape(k_all, 4).copy(),
-            None if spec.run_edges is None else self.cut(back, "run_states").reshape(k_all, 2, len(spec.run_edges) + 1, 3).copy(),
-            None if spec.border_reach is None else self.cut(back, "run_borders").reshape(k_all, 2, -1).copy(),
-            None if spec.curve_shift is None else self.cut(back, "curve").reshape(3, -1).copy(),
-            None if spec.max_bases is None else
-            self.cut(back, "run_bases").reshape(k_all, 2, 3, len(dv.BASE_CLASSES), spec.max_bases + 1).copy(),
-            None if spec.vote_bases is None else self.cut(back, "base_confusion").reshape(k_all, len(dv.BASE_CLASSES), 2, 2).copy(),
-            None if spec.vote_bases is None else
-            self.cut(back, "base_vote_runs").reshape(k_all, 2, 3, len(dv.BASE_CLASSES), spec.vote_bases + 1).copy(),
-            None if spec.score_shift is None else self.cut(back, "run_scores").reshape(k_all, 2, 3, -1).copy())
+        (the cells hold the doubles' bits), counts int64 [K, 4], and every result asked for as int64 of its row's ``Option.shapes``;
+        every item its own copy."""
+        k_all = self.spec.k_all
+        return RoundResult(self.cut(back, "right").copy(), self.cut(back, "ce_sum").view(np.float64).copy(),
+                           self.cut(back, "counts").reshape(k_all, 4).copy(),
+                           **{name: self.cut(back, name).reshape(shape).copy()
+                              for row, value in self.spec.asked for name, shape in row.shapes(value, k_all)})
 
 
 def grow(book, need, device):
@@ -187,11 +262,10 @@ def grow(book, need, device):
                            "y": torch.empty(cap["samples"], dtype=torch.uint8, device=device),
                            "table": torch.empty(3 * (cap["reads"] + 1), dtype=torch.int64, device=device),
                            "partials": torch.empty(cap["slots"], dtype=torch.float64, device=device),
-                           # right [reads] | ce_sum [reads], double bits | counts [4 per threshold] | run states | borders |
-                           # curve histogram | run bases | base confusion | base vote runs | run scores: one copy back
-                           "out": torch.empty(2 * cap["reads"] + 4 * cap["thresholds"] + cap.get("run_cells", 0)
-                                              + cap.get("border_cells", 0) + cap.get("curve_cells", 0) + cap.get("base_cells", 0)
-                                              + cap.get("vote_cells", 0) + cap.get("score_cells", 0), dtype=torch.int64, device=device)}
+                           # right [reads] | ce_sum [reads], double bits | counts [4 per threshold] | the cells of every row of
+                           # ``OPTIONS`` that a round has asked for: one copy back
+                           "out": torch.empty(2 * cap["reads"] + 4 * cap["thresholds"] + sum(cap.get(row.need_key, 0) for row in OPTIONS),
+                                              dtype=torch.int64, device=device)}
         if "run_work" in cap:                                     # corrected labels (and paint), one array per threshold of a group
             book["tensors"]["run_work"] = torch.empty(cap["run_work"], dtype=torch.uint8, device=device)
         if "vote_work" in cap:                                                   # per-base sums and states (8-byte aligned), and every
@@ -204,20 +278,22 @@ def grow(book, need, device):
     return book["tensors"]
 
 
+Round = namedtuple("Round", "t probs y labels basemap edges src bounds length longest_range")      # what the rows' launches read
+
+
 def walk(engine, plan, t, thresholds_d, signal, labels, window, basemap=None, edges=None, longest_range=0):
     """Every launch of a round, on the current stream, over the buffers ``t`` (``grow``) with the selection table uploaded: gather,
-    (retile,) forward pass, (vote,) then per threshold group score, run states, borders, run bases, base votes, run scores, and the
-    curve histogram last.  ``thresholds_d``: the thresholds as a float64 CUDA tensor; ``basemap``: the set's base map on the card, which a
-    round with ``max_bases`` or ``vote_bases`` reads in place; ``edges``: the set's base table on the card and ``longest_range`` the
-    widest stretch in bases, for a round with ``vote_bases`` (its ranges are in ``t["vote_ranges"]`` already).  -> the result
-    buffer's ``plan.out_cells`` cells, still on the card."""
+    (retile,) forward pass, (vote,) then per threshold group ``score_validation`` and the ``per_threshold`` rows of ``OPTIONS`` that are
+    asked for, in their order, and after the groups the other rows (the curve histogram).  ``thresholds_d``: the thresholds as a float64
+    CUDA tensor; ``basemap``: the set's base map on the card, which a row with ``basemap`` reads in place; ``edges``: the set's base
+    table on the card and ``longest_range`` the widest stretch in bases, for a round with ``vote_bases`` (its ranges are in
+    ``t["vote_ranges"]`` already).  -> the result buffer's ``plan.out_cells`` cells, still on the card."""
     import torch
     spec, rule, n, total, longest = plan.spec, plan.spec.rule, plan.n, plan.total, plan.longest
     src_d, len_d, bounds_d = (t["table"][i * (n + 1):i * (n + 1) + count] for i, count in ((0, n), (1, n), (2, n + 1)))
     x, y, probs, logits = t["x"][:total], t["y"][:total], t["probs"][:total], t["logits"][:total]
     out = t["out"][:plan.out_cells]
     right_d, ce_d, counts_d = plan.cut(out, "right"), plan.cut(out, "ce_sum").view(torch.float64), plan.cut(out, "counts")
-    runs_d, borders_d, curve_d = plan.cut(out, "run_states"), plan.cut(out, "run_borders"), plan.cut(out, "curve")
     if rule.voted:
         size = plan.need["tiling_samples"]
         x_all, probs_all, logits_all = t["tilings_x"][:size], t["tilings_probs"][:size], t["tilings_logits"][:size]
@@ -228,33 +304,15 @@ def walk(engine, plan, t, thresholds_d, signal, labels, window, basemap=None, ed
     else:
         engine.gather_validation(signal, labels, src_d, len_d, bounds_d, total, longest, x, y)
         engine.infer_device(x.view(-1, window), out=probs, logits=logits)
-    run_per_k, border_per_k = plan.cells["run_states"] // spec.k_all, plan.cells["run_borders"] // spec.k_all
-    if spec.max_bases is not None:
-        bases_d, base_per_k = plan.cut(out, "run_bases"), plan.cells["run_bases"] // spec.k_all
-    if spec.vote_bases is not None:
-        confusion_d, vote_runs_d = plan.cut(out, "base_confusion"), plan.cut(out, "base_vote_runs")
-        confusion_per_k, vote_per_k = plan.cells["base_confusion"] // spec.k_all, plan.cells["base_vote_runs"] // spec.k_all
-    if spec.score_shift is not None:
-        scores_d, score_per_k = plan.cut(out, "run_scores"), plan.cells["run_scores"] // spec.k_all
+    on = Round(t, probs, y, labels, basemap, edges, src_d, bounds_d, len_d, longest_range)
+    steps = [(row, value, [(plan.cut(out, name), plan.cells[name] // spec.k_all) for name in row.names]) for row, value in spec.asked]
     for k0, k1 in spec.groups:
         engine.score_validation(probs, logits, y, bounds_d, total, longest, thresholds_d[k0:k1], right_d, ce_d, counts_d[4 * k0:4 * k1],
                                 t["partials"])
-        if spec.run_edges is not None:
-            engine.run_states_validation(probs, y, bounds_d, len_d, total, longest, spec.thresholds[k0:k1], spec.run_edges,
-                                         runs_d[run_per_k * k0:run_per_k * k1], t["run_work"], min_run=rule.min_run, max_gap=rule.max_gap)
-        if spec.border_reach is not None:
-            engine.run_borders_validation(probs, y, bounds_d, len_d, total, longest, spec.thresholds[k0:k1], spec.border_reach,
-                                          borders_d[border_per_k * k0:border_per_k * k1], t["run_work"], min_run=rule.min_run, max_gap=rule.max_gap)
-        if spec.max_bases is not None:
-            engine.run_bases_validation(probs, y, basemap, src_d, bounds_d, len_d, total, longest, spec.thresholds[k0:k1], spec.max_bases,
-                                        bases_d[base_per_k * k0:base_per_k * k1], t["run_work"], min_run=rule.min_run, max_gap=rule.max_gap)
-        if spec.vote_bases is not None:
-            engine.base_votes_validation(probs, labels, basemap, edges, src_d, bounds_d, len_d, t["vote_ranges"][:2 * n], total, longest_range,
-                                         spec.thresholds[k0:k1], spec.vote_bases, confusion_d[confusion_per_k * k0:confusion_per_k * k1],
-                                         vote_runs_d[vote_per_k * k0:vote_per_k * k1], t["vote_work"])
-        if spec.score_shift is not None:
-            engine.run_scores_validation(probs, y, bounds_d, len_d, total, longest, spec.thresholds[k0:k1], spec.score_shift,
-                                         scores_d[score_per_k * k0:score_per_k * k1], t["run_work"], min_run=rule.min_run, max_gap=rule.max_gap)
-    if spec.curve_shift is not None:
-        engine.curve_validation(probs, y, bounds_d, len_d, total, longest, spec.curve_shift, curve_d)
+        for row, value, outs in steps:
+            if row.per_threshold:
+                row.launch(engine, plan, on, spec.thresholds[k0:k1], value, [cells[per_k * k0:per_k * k1] for cells, per_k in outs])
+    for row, value, outs in steps:
+        if not row.per_threshold:
+            row.launch(engine, plan, on, None, value, [cells for cells, _per_k in outs])
     return out
