@@ -1,5 +1,8 @@
 """ctypes binding of the C ABI declared in include/catfish_hip.h.
 
+The header is the only statement of that ABI: the signature table, the constants and the layout of the four structs are read
+from it once, at import (``parse_header``); nothing here restates a signature.
+
 The product path has NO CPU fallback: if the HIP library has not been built
 (``python -c "import __graft_entry__ as g; g.build()"`` or
 ``python -m catfish_amd.build``) importing a symbol from here raises.
@@ -8,11 +11,13 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB_PATH = os.path.join(_HERE, "csrc", "libcatfish_hip.so")
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "catfish_hip.h")
 
 
 def debug_knobs_on():
@@ -32,20 +37,96 @@ def _lib_path():
 
 
 LIB_PATH = DEFAULT_LIB_PATH
-CF_ABI_VERSION = 9            # include/catfish_hip.h
 
-CF_OK = 0
-CF_ERR_INVALID = -1
-CF_ERR_HIP = -2
-CF_ERR_NOMEM = -3
-CF_ERR_IO = -4
-CF_WINDOW = 35
-CF_PROF_SLOTS = 12
-PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16": 2}
+
+class NativeLibraryMissing(RuntimeError):
+    pass
+
+
+class CatfishHipError(RuntimeError):
+    def __init__(self, code, msg):
+        RuntimeError.__init__(self, "catfish_hip error %d: %s" % (code, msg))
+        self.code = code
+
+
+# ---------------------------------------------------------------------- the header as the table
+_SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "float": C.c_float, "double": C.c_double}
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(-?\d+)[ \t]*$", re.M)
+_STRUCT = re.compile(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*\w+\s*;")
+_OPAQUE = re.compile(r"typedef\s+struct\s+\w+\s+\w+")
+_DECLARATION = re.compile(r"([^()]*?)\b(cf_\w+)\s*\(([^()]*)\)")
+
+
+def _ctype(text, where, is_return=False):
+    """One return type, parameter or struct field of the header -> its ctypes type; ``const`` and the name are dropped.
+    ``char*`` is ``c_char_p``, every other pointer or ``[]`` parameter ``c_void_p``, ``void`` as a return type None."""
+    words = re.sub(r"\bconst\b", " ", text).split("[")[0].replace("*", " * ").split()
+    stars = words.count("*") + ("[" in text)
+    if stars:
+        return C.c_char_p if stars == 1 and words[0] == "char" else C.c_void_p
+    if is_return and words == ["void"]:
+        return None
+    if not words or words[0] not in _SCALARS or len(words) > (1 if is_return else 2):
+        raise ValueError("catfish_hip.h: cannot type `%s` in `%s`" % (" ".join(text.split()), where))
+    return _SCALARS[words[0]]
+
+
+def parse_header(text):
+    """The text of include/catfish_hip.h -> (symbols, constants, structs): ``{name: (restype, [argtypes])}`` of every
+    ``ret cf_name(params);`` declaration, ``{NAME: value}`` of every ``#define NAME <integer>`` and ``{name: [(field, ctype)]}``
+    of every ``typedef struct`` with a body (a pointer field is ``c_void_p``).  Comments and preprocessor lines are stripped
+    first.  Anything else raises ValueError and names the declaration -- an unknown scalar type, a function-pointer parameter,
+    a ``cf_*(`` without its ``);`` -- so that a header edit never drops a symbol silently."""
+    text = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", text, flags=re.S))
+    constants = {m.group(1): int(m.group(2)) for m in _DEFINE.finditer(text)}
+    text = re.sub(r'extern\s+"C"\s*\{', " ", re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M))
+    structs = {}
+    for m in _STRUCT.finditer(text):
+        fields = [f for f in m.group(2).split(";") if f.strip()]
+        structs[m.group(1)] = [(f.split("[")[0].replace("*", " ").split()[-1], _ctype(f, "struct " + m.group(1))) for f in fields]
+    symbols = {}
+    for statement in _STRUCT.sub(" ", text).split(";"):
+        statement = " ".join(statement.split())
+        named = re.search(r"\b(cf_\w+)\s*\(", statement)
+        if named is None:
+            if statement not in ("", "}") and not _OPAQUE.fullmatch(statement):      # "}" closes extern "C"
+                raise ValueError("catfish_hip.h: cannot parse `%s`" % statement[:160])
+            continue
+        m = _DECLARATION.fullmatch(statement)
+        if m is None:
+            raise ValueError("catfish_hip.h: cannot parse the declaration of %s: `%s`" % (named.group(1), statement[:160]))
+        name, params = m.group(2), m.group(3).strip()
+        symbols[name] = (_ctype(m.group(1), name, is_return=True),
+                         [] if params in ("", "void") else [_ctype(p, name) for p in params.split(",")])
+    return symbols, constants, structs
+
+
+def _read_header():
+    try:
+        with open(HEADER) as fh:
+            return fh.read()
+    except OSError as e:
+        raise NativeLibraryMissing("%s cannot be read (%s): the binding takes every signature from it" % (HEADER, e.strerror))
+
+
+# name -> (restype, argtypes) of every symbol the header declares; parsed here, once per process
+SYMBOLS, _CONSTANTS, _STRUCTS = parse_header(_read_header())
+
+CF_ABI_VERSION = _CONSTANTS["CF_ABI_VERSION"]
+CF_OK = _CONSTANTS["CF_OK"]
+CF_ERR_INVALID = _CONSTANTS["CF_ERR_INVALID"]
+CF_ERR_HIP = _CONSTANTS["CF_ERR_HIP"]
+CF_ERR_NOMEM = _CONSTANTS["CF_ERR_NOMEM"]
+CF_ERR_IO = _CONSTANTS["CF_ERR_IO"]
+CF_WINDOW = _CONSTANTS["CF_WINDOW"]
+CF_PROF_SLOTS = _CONSTANTS["CF_PROF_SLOTS"]
+PRECISIONS = {"fp32": _CONSTANTS["CF_PREC_FP32"], "bf16x3": _CONSTANTS["CF_PREC_BF16X3"], "bf16": _CONSTANTS["CF_PREC_BF16"]}
 
 _f32p = C.POINTER(C.c_float)
 
 
+# The four structs stay hand-written (build_weight_structs needs their typed pointers) and are held to the header below.
 class cf_hparams(C.Structure):
     _fields_ = [("layer_size", C.c_int32), ("n_layers", C.c_int32),
                 ("layer_size_res", C.c_int32), ("n_layers_res", C.c_int32),
@@ -70,166 +151,21 @@ class cf_weights(C.Structure):
                 ("dense_kernel", _f32p), ("dense_bias", _f32p)]
 
 
-class NativeLibraryMissing(RuntimeError):
-    pass
+def check_struct(cls, fields):
+    """Raise unless the ctypes Structure ``cls`` has the fields the header gives (``parse_header``'s ``[(name, ctype)]``): the
+    same names in the same order, each the same scalar type or, where the header has a pointer, a pointer."""
+    mine = [(name, C.c_void_p if hasattr(kind, "contents") else kind) for name, kind in cls._fields_]
+    if mine != fields:
+        header, binding = (", ".join("%s %s" % (kind.__name__, name) for name, kind in rows) for rows in (fields, mine))
+        raise ValueError("catfish_hip.h: struct %s is {%s} in the header, {%s} in the binding" % (cls.__name__, header, binding))
 
 
-class CatfishHipError(RuntimeError):
-    def __init__(self, code, msg):
-        RuntimeError.__init__(self, "catfish_hip error %d: %s" % (code, msg))
-        self.code = code
-
+for _cls in (cf_hparams, cf_conv_bn, cf_gru_dir, cf_weights):
+    if _cls.__name__ not in _STRUCTS:
+        raise ValueError("catfish_hip.h: no typedef struct %s" % _cls.__name__)
+    check_struct(_cls, _STRUCTS[_cls.__name__])
 
 _lib = None
-
-# name -> (restype, argtypes); every symbol include/catfish_hip.h declares
-SYMBOLS = {
-    "cf_model_create": (C.c_int, [C.POINTER(cf_weights), C.POINTER(cf_hparams), C.c_int, C.POINTER(C.c_void_p)]),
-    "cf_model_destroy": (None, [C.c_void_p]),
-    "cf_model_param_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
-    "cf_model_load_params": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_infer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "cf_infer_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_infer_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_infer_host_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "cf_check_error": (C.c_int, [C.c_void_p]),
-    "cf_clear_error": (C.c_int, [C.c_void_p]),
-    "cf_launch_regimes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
-    "cf_postprocess": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                                 C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
-    "cf_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_normalize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "cf_chunks_from_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
-    "cf_load_npy_int16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]),
-    "cf_stat_files": (C.c_int, [C.c_char_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32]),
-    "cf_postprocess_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_int32,
-                                       C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_span_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_void_p,
-                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_postprocess_spans_bridged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_float, C.c_int32,
-                                               C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_span_scores_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                                        C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_crc32c": (C.c_uint32, [C.c_void_p, C.c_int64, C.c_uint32]),
-    "cf_listing_open": (C.c_int, [C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
-    "cf_listing_from_names": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
-    "cf_listing_sizes": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32]),
-    "cf_listing_names": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]),
-    "cf_listing_close": (None, [C.c_void_p]),
-    "cf_listing_load_npy_int16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]),
-    "cf_listing_split_npy_int16": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_char_p, C.c_char_p, C.c_int32, C.c_void_p]),
-    "cf_chunks_json": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                   C.c_void_p, C.c_int64]),
-    "cf_gru_pack_map": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
-    "cf_gru_train_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                       C.c_void_p]),
-    "cf_gru_train_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gru_train_forward_dropout": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                               C.c_void_p, C.c_float, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p]),
-    "cf_gru_train_backward_dropout": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_uint32, C.c_int32,
-                                                C.c_void_p, C.c_void_p]),
-    "cf_gru_anysize_train_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gru_anysize_train_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_int64, C.c_void_p]),
-    "cf_gru_anysize_train_shape": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.POINTER(C.c_int64)]),
-    "cf_anysize_infer_shape": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.c_int64]),
-    "cf_gru_anysize_x3_pack_floats": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
-    "cf_gen_repack_x3": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_gru_anysize_train_forward_x3": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gru_anysize_train_backward_x3": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   C.c_int64, C.c_void_p]),
-    "cf_dropout_scale": (C.c_int, [C.c_void_p, C.c_float, C.c_uint32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "cf_gru_wgrad_workspace_floats": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int64]),
-    "cf_gru_train_wgrad": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "cf_res_train_param_floats": (C.c_int64, [C.c_int32]),
-    "cf_res_train_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64]),
-    "cf_res_train_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_res_train_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                        C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_train_head_workspace_floats": (C.c_int64, [C.c_void_p, C.c_int64]),
-    "cf_train_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
-                                C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_opt_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
-                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_train_workspace_floats": (C.c_int64, [C.c_int32, C.c_int32, C.c_int64]),
-    "cf_gen_head_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64]),
-    "cf_gen_conv_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_conv_backward_data": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_bn_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_conv_wgrad": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_gru_dx": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_gru_wgrad": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_dropout": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_head": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_x_frag": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_head_backward_workspace_floats": (C.c_int64, [C.c_int32, C.c_int64]),
-    "cf_gen_head_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_signal_grad": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_bn_backward_data": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_gen_bn_stat_grads": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_sample_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p,
-                                  C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_sample_batch_logged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_uint32, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
-    "cf_validation_score_chunk": (C.c_int, []),
-    "cf_validation_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_validation_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p,
-                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_validation_run_piece": (C.c_int, []),
-    "cf_validation_run_work_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
-    "cf_validation_run_states": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
-                                           C.c_void_p]),
-    "cf_validation_run_states_bridged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                                                   C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                                   C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_validation_run_borders_work_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
-    "cf_validation_run_borders": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                            C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_validation_run_borders_bridged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64,
-                                                    C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                                    C.c_int64, C.c_void_p]),
-    "cf_validation_run_bases": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                          C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                          C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_validation_curve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_int32,
-                                      C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_validation_run_scores_work_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
-    "cf_validation_run_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                           C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p,
-                                           C.c_int64, C.c_void_p]),
-    "cf_retile_windows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
-    "cf_vote_tilings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32,
-                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "cf_label_events_work_bytes": (C.c_int64, [C.c_int64]),
-    "cf_label_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
-                                  C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_label_moves_work_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
-    "cf_label_moves": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                 C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_base_votes_work_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
-    "cf_base_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
-                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
-                                C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
-    "cf_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
-    "cf_profile_reset": (C.c_int, [C.c_void_p]),
-    "cf_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
-    "cf_profile_slot_name": (C.c_char_p, [C.c_int]),
-    "cf_debug_stage": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p]),
-    "cf_device_identity": (C.c_int, [C.c_int, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64]),
-    "cf_workspace_bytes": (C.c_int64, [C.c_void_p]),
-    "cf_last_error": (C.c_char_p, []),
-    "cf_version": (C.c_char_p, []),
-    "cf_abi_version": (C.c_int, []),
-}
 
 
 def _preload_torch_hip_runtime():
@@ -290,14 +226,29 @@ def check(rc):
         raise CatfishHipError(rc, msg)
 
 
+# ---------------------------------------------------------------------- the one way to pass a tensor, a stream or an array
 def _p(t):
-    """A torch tensor's first element as the ``void*`` the C ABI takes."""
-    return C.c_void_p(t.data_ptr())
+    """A torch tensor's first element as the ``void*`` the C ABI takes; None (an optional buffer left out) stays None = NULL."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream_ptr(stream):
+    """A ``torch.cuda.Stream`` as the ``void* stream`` of the launch functions."""
+    return C.c_void_p(stream.cuda_stream)
 
 
 def current_stream_ptr(torch, dev):
     """torch's current stream on ``dev`` as the ``void* stream`` of the launch functions."""
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    return stream_ptr(torch.cuda.current_stream(dev))
+
+
+def np_ptr(a):
+    """A contiguous numpy array's data as ``void*`` (the pointer keeps the array alive); None stays None = NULL."""
+    if a is None:
+        return None
+    if not a.flags.c_contiguous:
+        raise ValueError("np_ptr needs a C-contiguous array")
+    return a.ctypes.data_as(C.c_void_p)
 
 
 def _as_f32(a):

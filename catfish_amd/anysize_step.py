@@ -83,7 +83,7 @@ class AnySizeTrainStep(FlatTrainStep):
             step_ptr = _p(self.opt.t)
 
             def dropout(layer, src, dst):
-                N.check(lib.cf_gen_dropout(hd, h, kp, self.seed, layer, step_ptr, None if scales is None else _p(scales[layer]), _p(src),
+                N.check(lib.cf_gen_dropout(hd, h, kp, self.seed, layer, step_ptr, _p(scales[layer] if scales else None), _p(src),
                                            _p(dst), npad, stream))
                 return dst
 

@@ -128,17 +128,15 @@ def _make_function():
                 tiles = npad // 16
                 y_frag = torch.empty(tiles, T, 2 * h16, 64, 4, dtype=torch.float32, device=x.device)
                 stash = torch.empty(tiles, T, 2, 3, h16, 64, 4, dtype=torch.float32, device=x.device)
-                stream = torch.cuda.current_stream(x.device).cuda_stream
+                stream = N.current_stream_ptr(torch, x.device)
                 x3 = precision == "bf16x3"
                 forward_call = lib.cf_gru_anysize_train_forward
                 if x3:                                          # split both packs on the device; the backward keeps the split wtpack
                     nw, nt = x3_pack_floats(lib, h, kbx)
                     wpack_x3, wtpack_x3 = wpack.new_empty(nw), wpack.new_empty(nt)
-                    repack_x3(lib, handle, h, kbx, wpack, wpack_x3, wtpack, wtpack_x3, C.c_void_p(stream))
+                    repack_x3(lib, handle, h, kbx, wpack, wpack_x3, wtpack, wtpack_x3, stream)
                     wpack, wtpack, forward_call = wpack_x3, wtpack_x3, lib.cf_gru_anysize_train_forward_x3
-                N.check(forward_call(handle, h, kbx, C.c_void_p(wpack.data_ptr()), C.c_void_p(bpack.data_ptr()),
-                                     C.c_void_p(x_frag.data_ptr()), C.c_void_p(y_frag.data_ptr()),
-                                     C.c_void_p(stash.data_ptr()), npad, C.c_void_p(stream)))
+                N.check(forward_call(handle, h, kbx, N._p(wpack), N._p(bpack), N._p(x_frag), N._p(y_frag), N._p(stash), npad, stream))
                 y = frag_to_nat(y_frag)
             ctx.engine, ctx.n, ctx.npad, ctx.h, ctx.cin, ctx.x3 = engine, n, npad, h, cin, x3
             ctx.save_for_backward(xp, y, y_frag, stash, wtpack, wg_f, wc_f, wg_b, wc_b)
@@ -155,11 +153,9 @@ def _make_function():
                 dyp = torch.nn.functional.pad(dyp, (0, 0, 0, 0, 0, npad - n))
             dy_frag = nat_to_frag(dyp.contiguous())
             da = torch.empty_like(stash)
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            stream = N.current_stream_ptr(torch, dev)
             backward_call = lib.cf_gru_anysize_train_backward_x3 if ctx.x3 else lib.cf_gru_anysize_train_backward
-            N.check(backward_call(handle, h, C.c_void_p(wtpack.data_ptr()), C.c_void_p(y_frag.data_ptr()),
-                                  C.c_void_p(stash.data_ptr()), C.c_void_p(dy_frag.data_ptr()),
-                                  C.c_void_p(da.data_ptr()), npad, C.c_void_p(stream)))
+            N.check(backward_call(handle, h, N._p(wtpack), N._p(y_frag), N._p(stash), N._p(dy_frag), N._p(da), npad, stream))
             x2 = xp[:, :, :cin].reshape(npad * T, cin)
             dx = None
             grads = []

@@ -164,7 +164,7 @@ class AnySizeWalk(object):
             for u, src, res, relu, out in ((j, a, None, 0, b["sc"]), (j + 1, a, None, 1, b["o1"][k]), (j + 2, b["o1"][k], None, 1, b["o2"][k]),
                                            (j + 3, b["o2"][k], b["sc"], 1, b["a"][k])):
                 off, kw, cin, cout = self.units[u]
-                N.check(lib.cf_gen_conv_forward(hd, kw, cin, cout, _p(pf[off:]), _p(src), None if res is None else _p(res), relu,
+                N.check(lib.cf_gen_conv_forward(hd, kw, cin, cout, _p(pf[off:]), _p(src), _p(res), relu,
                                                 _p(b["z"][u]), _p(out), npad, stream))
             a = b["a"][k]
         if self.n_blocks == 0:
@@ -235,7 +235,7 @@ class AnySizeWalk(object):
 
             def unit_bwd(u, grad, mask, relu, src):
                 off, kw, cin, cout = units[u]
-                msk = None if mask is None else _p(mask)
+                msk = _p(mask)
                 if need_w:
                     N.check(lib.cf_gen_bn_backward(hd, kw, cin, cout, _p(pf[off:]), _p(grad), msk, relu, _p(b["z"][u]), _p(dz[u - j]),
                                                    _p(bws), bwsn, _p(gf[off:]), npad, stream))
@@ -246,7 +246,7 @@ class AnySizeWalk(object):
 
             def unit_dx(u, out, add=None):
                 off, kw, cin, cout = units[u]
-                N.check(lib.cf_gen_conv_backward_data(hd, kw, cin, cout, _p(pf[off:]), _p(dz[u - j]), None if add is None else _p(add),
+                N.check(lib.cf_gen_conv_backward_data(hd, kw, cin, cout, _p(pf[off:]), _p(dz[u - j]), _p(add),
                                                       _p(out), npad, stream))
 
             unit_bwd(j + 3, dA, b["a"][k], 1, b["o2"][k])

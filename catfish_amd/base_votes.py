@@ -270,13 +270,13 @@ def launch(lib, handle, probs, total, labels, basemap, edges, n_bases, src_first
     """``cf_base_votes`` on CUDA tensors that the caller has checked (``HipEngine.base_votes_validation`` and ``vote_device`` do)."""
     import ctypes as C
     from . import _native as N
+    from ._native import _p as p
     thresholds = [float(t) for t in thresholds]
     k = len(thresholds)
-    p = lambda t: C.c_void_p(t.data_ptr())                 # noqa: E731
     N.check(lib.cf_base_votes(handle, p(probs), int(total), p(labels), p(basemap), int(min(labels.numel(), basemap.numel())), p(edges),
                               int(n_bases), p(src_first), p(length), p(bounds), p(ranges), int(src_first.numel()), int(longest_range),
                               (C.c_double * max(k, 1))(*thresholds), k, int(max_bases), p(confusion_out), p(runs_out), p(work),
-                              int(work.numel()), C.c_void_p(stream.cuda_stream)))
+                              int(work.numel()), N.stream_ptr(stream)))
 
 
 def work_bytes(n_bases, n_thresholds):

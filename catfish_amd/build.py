@@ -12,10 +12,11 @@ import shutil
 import subprocess
 import sys
 
+from ._native import HEADER          # the one path to include/catfish_hip.h
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(_HERE, "csrc", "catfish_hip.hip")
 OUT = os.path.join(_HERE, "csrc", "libcatfish_hip.so")
-HEADER = os.path.join(os.path.dirname(_HERE), "include", "catfish_hip.h")
 
 
 def hipcc_path():

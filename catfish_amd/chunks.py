@@ -21,10 +21,6 @@ from . import _native as N
 _PLAIN_KEYS = re.compile(r'[^\x20-\x7e]|["\\]')
 
 
-def _ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def _i64(a):
     return np.ascontiguousarray(a, dtype=np.int64)
 
@@ -60,9 +56,9 @@ class ChunkTable(object):
         hp_b, non_b = np.zeros(n_reads + 1, np.int64), np.zeros(n_reads + 1, np.int64)
         hp_s, hp_e = np.empty(hp_cap, np.int64), np.empty(hp_cap, np.int64)
         non_s, non_e = np.empty(non_cap, np.int64), np.empty(non_cap, np.int64)
-        N.check(N.lib().cf_chunks_from_spans(_ptr(span_bounds), _ptr(span_start), _ptr(span_end), _ptr(lengths), n_reads,
-                                             int(chunk_size), _ptr(hp_b), _ptr(hp_s), _ptr(hp_e), hp_cap,
-                                             _ptr(non_b), _ptr(non_s), _ptr(non_e), non_cap))
+        N.check(N.lib().cf_chunks_from_spans(N.np_ptr(span_bounds), N.np_ptr(span_start), N.np_ptr(span_end), N.np_ptr(lengths), n_reads,
+                                             int(chunk_size), N.np_ptr(hp_b), N.np_ptr(hp_s), N.np_ptr(hp_e), hp_cap,
+                                             N.np_ptr(non_b), N.np_ptr(non_s), N.np_ptr(non_e), non_cap))
         return cls(lengths, hp_b, hp_s[:hp_b[-1]], hp_e[:hp_b[-1]], non_b, non_s[:non_b[-1]], non_e[:non_b[-1]])
 
     @classmethod
@@ -124,18 +120,17 @@ class ChunkTable(object):
             key_len = np.array([len(e) for e in enc], dtype=np.int64)
         key_bounds = np.zeros(len(names) + 1, np.int64)
         np.cumsum(key_len, out=key_bounds[1:])
-        keys = np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, np.uint8)
         whole = np.ascontiguousarray(~self.has_hp, dtype=np.uint8)
         out = []
         for bounds, start, end, flag in ((self.hp_bounds, self.hp_start, self.hp_end, None),
                                          (self.nonhp_bounds, self.nonhp_start, self.nonhp_end, whole)):
             cap = int(key_bounds[-1]) + 48 * int(bounds[-1]) + 40 * len(names) + 64
-            buf = np.empty(cap, np.uint8)
-            n = N.lib().cf_chunks_json(_ptr(keys), _ptr(key_bounds), len(names), _ptr(bounds), _ptr(start), _ptr(end),
-                                       _ptr(flag) if flag is not None else None, _ptr(buf), cap)
+            buf = C.create_string_buffer(cap)                   # ``const char* keys`` / ``char* out``: bytes and a string buffer
+            n = N.lib().cf_chunks_json(blob, N.np_ptr(key_bounds), len(names), N.np_ptr(bounds), N.np_ptr(start), N.np_ptr(end),
+                                       N.np_ptr(flag), buf, cap)
             if n < 0:
                 N.check(int(n))
-            out.append(buf[:n].tobytes())
+            out.append(C.string_at(buf, n))
         return tuple(out)
 
     def to_dicts(self, names):

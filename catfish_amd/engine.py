@@ -66,6 +66,23 @@ class HipEngine(object):
     def workspace_bytes(self):
         return int(self._lib.cf_workspace_bytes(self._handle))
 
+    def _tensors(self, what, rows):
+        """The one check of tensor arguments; each row is ``(name, tensor, torch dtype[, minimum numel])``.  ValueError for
+        whatever is not a contiguous CUDA tensor of that dtype, lives on another card than the model, or is too short.  It sits on
+        the path of every call (``tools/bench_latency.py``): no torch import, no object made per row."""
+        for row in rows:
+            t, dtype = row[1], row[2]
+            try:                                               # whatever is no torch.Tensor lacks one of these
+                ok = t.dtype == dtype and t.is_cuda and t.is_contiguous()
+            except AttributeError:
+                ok = False
+            if not ok:
+                raise ValueError("%s: %s must be a contiguous %s CUDA tensor" % (what, row[0], str(dtype).replace("torch.", "")))
+            if t.get_device() != self.device:
+                raise ValueError("%s: %s lives on cuda:%d, model on cuda:%d" % (what, row[0], t.get_device(), self.device))
+            if len(row) > 3 and t.numel() < row[3]:
+                raise ValueError("%s: %s needs %d elements, has %d" % (what, row[0], row[3], t.numel()))
+
     # ------------------------------------------------------------------ device weights
     def param_count(self):
         """Values of the flat parameter vector of this engine's geometry (``cf_model_param_floats``): the checkpoint's inference
@@ -82,15 +99,12 @@ class HipEngine(object):
         stream).  Afterwards the engine computes exactly what ``HipEngine`` built from the same values computes.  The first call
         builds the gather map (host work, one upload); later calls only launch.  fp32 engines only: ValueError otherwise."""
         import torch
-        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or not params.is_cuda:
-            raise ValueError("params must be a float32 CUDA tensor")
-        if params.device.index != self.device:
-            raise ValueError("params live on cuda:%s, model on cuda:%d" % (params.device.index, self.device))
-        if not params.is_contiguous() or params.numel() != self.param_count():
-            raise ValueError("params must be a contiguous tensor of %d values, got %d" % (self.param_count(), params.numel()))
+        self._tensors("load_params_device", [("params", params, torch.float32)])
+        if params.numel() != self.param_count():
+            raise ValueError("load_params_device: params must hold %d values, got %d" % (self.param_count(), params.numel()))
         if stream is None:
-            stream = torch.cuda.current_stream(params.device)
-        N.check(self._lib.cf_model_load_params(self._handle, C.c_void_p(params.data_ptr()), C.c_void_p(stream.cuda_stream)))
+            stream = torch.cuda.current_stream(self.device)
+        N.check(self._lib.cf_model_load_params(self._handle, N._p(params), N.stream_ptr(stream)))
 
     # ------------------------------------------------------------------ inference
     @staticmethod
@@ -111,11 +125,9 @@ class HipEngine(object):
         out = np.empty(n * WINDOW, dtype=np.float32)
         if return_logits:
             logits = np.empty(n * WINDOW, dtype=np.float32)
-            N.check(self._lib.cf_infer_host_logits(self._handle, x32.ctypes.data_as(C.c_void_p), n,
-                                                   out.ctypes.data_as(C.c_void_p), logits.ctypes.data_as(C.c_void_p)))
+            N.check(self._lib.cf_infer_host_logits(self._handle, N.np_ptr(x32), n, N.np_ptr(out), N.np_ptr(logits)))
             return out, logits
-        N.check(self._lib.cf_infer_host(self._handle, x32.ctypes.data_as(C.c_void_p), n,
-                                        out.ctypes.data_as(C.c_void_p)))
+        N.check(self._lib.cf_infer_host(self._handle, N.np_ptr(x32), n, N.np_ptr(out)))
         return out
 
     def check_error(self):
@@ -147,42 +159,37 @@ class HipEngine(object):
 
         ``logits``: optional float32 CUDA tensor of N*35 elements that receives the pre-sigmoid values."""
         import torch
-        if not x.is_cuda or x.dtype != torch.float32:
-            raise ValueError("infer_device needs a float32 CUDA tensor")
-        if x.device.index != self.device:
-            raise ValueError("tensor lives on cuda:%s, model on cuda:%d" % (x.device.index, self.device))
-        n = self._check_windows(tuple(x.shape))
-        x = x.contiguous()
+        x = x.contiguous()                                     # any strides are fine for the input: it is copied here
+        rows = [("x", x, torch.float32)]
+        if out is not None:
+            rows.append(("out", out, torch.float32))
+        if logits is not None:
+            rows.append(("logits", logits, torch.float32))
+        self._tensors("infer_device", rows)
+        n = self._check_windows(x.shape)
         if out is None:
             out = torch.empty(n * WINDOW, dtype=torch.float32, device=x.device)
-        elif out.numel() != n * WINDOW or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 tensor of %d elements" % (n * WINDOW))
+        elif out.numel() != n * WINDOW:
+            raise ValueError("infer_device: out must have %d elements, has %d" % (n * WINDOW, out.numel()))
+        if logits is not None and logits.numel() != n * WINDOW:
+            raise ValueError("infer_device: logits must have %d elements, has %d" % (n * WINDOW, logits.numel()))
         if stream is None:
-            stream = torch.cuda.current_stream(x.device)
+            stream = torch.cuda.current_stream(self.device)
         if logits is not None:
-            if logits.numel() != n * WINDOW or logits.dtype != torch.float32 or not logits.is_contiguous() or not logits.is_cuda:
-                raise ValueError("logits must be a contiguous float32 CUDA tensor of %d elements" % (n * WINDOW))
-            N.check(self._lib.cf_infer_logits(self._handle, C.c_void_p(x.data_ptr()), n, C.c_void_p(out.data_ptr()),
-                                              C.c_void_p(logits.data_ptr()), C.c_void_p(stream.cuda_stream)))
+            N.check(self._lib.cf_infer_logits(self._handle, N._p(x), n, N._p(out), N._p(logits), N.stream_ptr(stream)))
             return out
-        N.check(self._lib.cf_infer(self._handle, C.c_void_p(x.data_ptr()), n, C.c_void_p(out.data_ptr()),
-                                   C.c_void_p(stream.cuda_stream)))
+        N.check(self._lib.cf_infer(self._handle, N._p(x), n, N._p(out), N.stream_ptr(stream)))
         return out
 
-    @staticmethod
-    def _check_packed(probs, read_offsets, read_lengths, run_tables=()):
-        """The packed layout every post-processing call takes: contiguous float32 CUDA ``probs``, contiguous int64 CUDA tables,
-        ``n_reads + 1`` offsets -> (n_reads, total)."""
+    def _check_packed(self, what, probs, read_offsets, read_lengths, own=()):
+        """The packed layout every post-processing call takes: float32 ``probs``, int64 tables (and the call's ``own`` rows for
+        ``_tensors``), ``n_reads + 1`` offsets -> (n_reads, total)."""
         import torch
-        if not probs.is_cuda or probs.dtype != torch.float32 or not probs.is_contiguous():
-            raise ValueError("probs must be a contiguous float32 CUDA tensor")
-        for t in (read_offsets, read_lengths) + tuple(run_tables):
-            if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("read_offsets, read_lengths, starts and counts must be contiguous int64 CUDA tensors" if run_tables
-                                 else "read_offsets/read_lengths must be contiguous int64 CUDA tensors")
+        self._tensors(what, [("probs", probs, torch.float32), ("read_offsets", read_offsets, torch.int64),
+                             ("read_lengths", read_lengths, torch.int64)] + list(own))
         n_reads = int(read_lengths.numel())
         if int(read_offsets.numel()) != n_reads + 1:
-            raise ValueError("read_offsets must have n_reads + 1 entries")
+            raise ValueError("%s: read_offsets must have n_reads + 1 entries" % what)
         return n_reads, int(probs.numel())
 
     def postprocess_device(self, probs, read_offsets, read_lengths, threshold=0.5, min_run=15, out=None, stream=None):
@@ -192,15 +199,15 @@ class HipEngine(object):
         read_lengths: int64 CUDA [n_reads] (real lengths) -> uint8 CUDA labels [total] (padding = 0).
         """
         import torch
-        n_reads, total = self._check_packed(probs, read_offsets, read_lengths)
+        n_reads, total = self._check_packed("postprocess_device", probs, read_offsets, read_lengths)
         if out is None:
             out = torch.empty(total, dtype=torch.uint8, device=probs.device)
+        else:
+            self._tensors("postprocess_device", [("out", out, torch.uint8, total)])
         if stream is None:
-            stream = torch.cuda.current_stream(probs.device)
-        N.check(self._lib.cf_postprocess(self._handle, C.c_void_p(probs.data_ptr()),
-                                         C.c_void_p(read_offsets.data_ptr()), C.c_void_p(read_lengths.data_ptr()),
-                                         n_reads, total, float(threshold), int(min_run),
-                                         C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream)))
+            stream = torch.cuda.current_stream(self.device)
+        N.check(self._lib.cf_postprocess(self._handle, N._p(probs), N._p(read_offsets), N._p(read_lengths), n_reads, total,
+                                         float(threshold), int(min_run), N._p(out), N.stream_ptr(stream)))
         return out
 
     def postprocess_spans_launch(self, probs, read_offsets, read_lengths, rule, signal=None, stream=None, want_labels=False, max_runs=None):
@@ -212,7 +219,7 @@ class HipEngine(object):
         [total] -- written only when ``want_labels`` or the scores need them, else None: the library never writes labels -- and the
         three score tensors or None."""
         import torch
-        n_reads, total = self._check_packed(probs, read_offsets, read_lengths)
+        n_reads, total = self._check_packed("postprocess_spans_launch", probs, read_offsets, read_lengths)
         max_runs = rule.max_runs(total) if max_runs is None else int(max_runs)
         dev = probs.device
         labels = torch.empty(total, dtype=torch.uint8, device=dev) if want_labels or rule.scores_by_labels else None
@@ -220,11 +227,9 @@ class HipEngine(object):
         ends = torch.empty(max_runs, dtype=torch.int64, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
         if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        head = (self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(read_offsets.data_ptr()), C.c_void_p(read_lengths.data_ptr()), n_reads,
-                total, rule.threshold)
-        tail = (rule.min_run, C.c_void_p(labels.data_ptr()) if labels is not None else None, max_runs, C.c_void_p(starts.data_ptr()),
-                C.c_void_p(ends.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(stream.cuda_stream))
+            stream = torch.cuda.current_stream(self.device)
+        head = (self._handle, N._p(probs), N._p(read_offsets), N._p(read_lengths), n_reads, total, rule.threshold)
+        tail = (rule.min_run, N._p(labels), max_runs, N._p(starts), N._p(ends), N._p(counts), N.stream_ptr(stream))
         if rule.bridged:
             N.check(self._lib.cf_postprocess_spans_bridged(*head, rule.max_gap, *tail))
         else:
@@ -281,46 +286,38 @@ class HipEngine(object):
         ``labels`` (uint8 CUDA [total], what ``cf_postprocess_spans_bridged`` wrote): a run lasts while its labels are non-zero
         instead of while ``p >= threshold`` (``cf_span_scores_labels``) -- bridged runs hold samples below the threshold."""
         import torch
-        n_reads, total = self._check_packed(probs, read_offsets, read_lengths, (starts, counts))
-        if signal is not None and (not signal.is_cuda or signal.dtype != torch.float32 or not signal.is_contiguous()
-                                   or int(signal.numel()) != total):
-            raise ValueError("signal must be a contiguous float32 CUDA tensor with as many samples as probs")
+        what = "span_scores_device"
+        n_reads, total = self._check_packed(what, probs, read_offsets, read_lengths, [
+            ("starts", starts, torch.int64), ("counts", counts, torch.int64, 1)]
+            + [(name, t, dtype) for name, t, dtype in (("signal", signal, torch.float32), ("labels", labels, torch.uint8)) if t is not None])
+        for name, t in (("signal", signal), ("labels", labels)):
+            if t is not None and int(t.numel()) != total:
+                raise ValueError("%s: %s must have as many samples as probs" % (what, name))
         max_runs = int(starts.numel())
-        if int(counts.numel()) < 1:
-            raise ValueError("counts must hold the number of starts")
         dev = probs.device
         if out is None:
             out = (torch.empty(max_runs, dtype=torch.int64, device=dev), torch.empty(max_runs, 3, dtype=torch.float64, device=dev),
                    torch.empty(max_runs, 2, dtype=torch.float32, device=dev))
         ends_paired, sums, extremes = out
-        if (ends_paired.dtype != torch.int64 or sums.dtype != torch.float64 or extremes.dtype != torch.float32
-                or ends_paired.numel() < max_runs or sums.numel() < 3 * max_runs or extremes.numel() < 2 * max_runs
-                or not all(t.is_cuda and t.is_contiguous() for t in out)):
-            raise ValueError("out must be contiguous CUDA tensors int64 [max_runs], float64 [max_runs, 3], float32 [max_runs, 2]")
+        self._tensors(what, [("out[0]", ends_paired, torch.int64, max_runs), ("out[1]", sums, torch.float64, 3 * max_runs),
+                             ("out[2]", extremes, torch.float32, 2 * max_runs)])
         if stream is None:
-            stream = torch.cuda.current_stream(dev)
+            stream = torch.cuda.current_stream(self.device)
         if labels is not None:
-            if labels.dtype != torch.uint8 or not labels.is_cuda or not labels.is_contiguous() or int(labels.numel()) != total:
-                raise ValueError("labels must be a contiguous uint8 CUDA tensor with as many samples as probs")
-            N.check(self._lib.cf_span_scores_labels(
-                self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(signal.data_ptr()) if signal is not None else None,
-                C.c_void_p(labels.data_ptr()), C.c_void_p(read_offsets.data_ptr()), C.c_void_p(read_lengths.data_ptr()), n_reads, total,
-                C.c_void_p(starts.data_ptr()), C.c_void_p(counts.data_ptr()), max_runs, C.c_void_p(ends_paired.data_ptr()),
-                C.c_void_p(sums.data_ptr()), C.c_void_p(extremes.data_ptr()), C.c_void_p(stream.cuda_stream)))
+            N.check(self._lib.cf_span_scores_labels(self._handle, N._p(probs), N._p(signal), N._p(labels), N._p(read_offsets),
+                                                    N._p(read_lengths), n_reads, total, N._p(starts), N._p(counts), max_runs,
+                                                    N._p(ends_paired), N._p(sums), N._p(extremes), N.stream_ptr(stream)))
             return out
-        N.check(self._lib.cf_span_scores(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(signal.data_ptr()) if signal is not None else None,
-                                         C.c_void_p(read_offsets.data_ptr()), C.c_void_p(read_lengths.data_ptr()), n_reads, total,
-                                         float(threshold), C.c_void_p(starts.data_ptr()), C.c_void_p(counts.data_ptr()), max_runs,
-                                         C.c_void_p(ends_paired.data_ptr()), C.c_void_p(sums.data_ptr()), C.c_void_p(extremes.data_ptr()),
-                                         C.c_void_p(stream.cuda_stream)))
+        N.check(self._lib.cf_span_scores(self._handle, N._p(probs), N._p(signal), N._p(read_offsets), N._p(read_lengths), n_reads, total,
+                                         float(threshold), N._p(starts), N._p(counts), max_runs, N._p(ends_paired), N._p(sums),
+                                         N._p(extremes), N.stream_ptr(stream)))
         return out
 
     def spans_device(self, labels, max_runs=None, stream=None):
         """Device run-length pass over corrected labels -> (starts, ends) numpy int64, sorted ascending
         (packed positions; ends exclusive).  Only the two short lists cross PCIe."""
         import torch
-        if labels.dtype != torch.uint8 or not labels.is_cuda or not labels.is_contiguous():
-            raise ValueError("labels must be a contiguous uint8 CUDA tensor")
+        self._tensors("spans_device", [("labels", labels, torch.uint8)])
         total = int(labels.numel())
         if max_runs is None:
             max_runs = total // 15 + 16          # correct_short leaves runs of >= 15 samples
@@ -329,10 +326,9 @@ class HipEngine(object):
         ends = torch.empty(max_runs, dtype=torch.int64, device=dev)
         counts = torch.empty(2, dtype=torch.int64, device=dev)
         if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        N.check(self._lib.cf_spans(self._handle, C.c_void_p(labels.data_ptr()), total, int(max_runs),
-                                   C.c_void_p(starts.data_ptr()), C.c_void_p(ends.data_ptr()),
-                                   C.c_void_p(counts.data_ptr()), C.c_void_p(stream.cuda_stream)))
+            stream = torch.cuda.current_stream(self.device)
+        N.check(self._lib.cf_spans(self._handle, N._p(labels), total, int(max_runs), N._p(starts), N._p(ends), N._p(counts),
+                                   N.stream_ptr(stream)))
         n_s, n_e = (int(v) for v in counts.cpu().tolist())      # synchronises the stream
         self.check_error()                                        # the labels came from asynchronous launches
         if n_s != n_e:
@@ -348,21 +344,19 @@ class HipEngine(object):
         -> float32 CUDA [n_windows, 35] (n_windows = win_offsets[-1], given by ``out`` or computed).
         """
         import torch
-        if dac.dtype != torch.int16 or not dac.is_cuda or not dac.is_contiguous():
-            raise ValueError("dac must be a contiguous int16 CUDA tensor")
-        for t in (dac_offsets, win_offsets):
-            if t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("offset tables must be contiguous int64 CUDA tensors")
+        self._tensors("normalize_device", [("dac", dac, torch.int16), ("dac_offsets", dac_offsets, torch.int64),
+                                           ("win_offsets", win_offsets, torch.int64)])
         n_reads = int(dac_offsets.numel()) - 1
         if int(win_offsets.numel()) != n_reads + 1:
-            raise ValueError("dac_offsets and win_offsets must have the same length")
+            raise ValueError("normalize_device: dac_offsets and win_offsets must have the same length")
         if out is None:
             out = torch.empty(int(win_offsets[-1].item()), WINDOW, dtype=torch.float32, device=dac.device)
+        else:
+            self._tensors("normalize_device", [("out", out, torch.float32)])
         if stream is None:
-            stream = torch.cuda.current_stream(dac.device)
-        N.check(self._lib.cf_normalize(self._handle, C.c_void_p(dac.data_ptr()), C.c_void_p(dac_offsets.data_ptr()),
-                                       C.c_void_p(win_offsets.data_ptr()), n_reads, C.c_void_p(out.data_ptr()),
-                                       C.c_void_p(stream.cuda_stream)))
+            stream = torch.cuda.current_stream(self.device)
+        N.check(self._lib.cf_normalize(self._handle, N._p(dac), N._p(dac_offsets), N._p(win_offsets), n_reads, N._p(out),
+                                       N.stream_ptr(stream)))
         return out
 
     # ------------------------------------------------------------------ shifted-window voting (csrc/tilings.hpp)
@@ -370,9 +364,7 @@ class HipEngine(object):
         import torch
         from .tilings import check_phases, tiling_size
         phases = check_phases(phases)
-        for name, t in (("offsets", offsets), ("lengths", lengths)):
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("%s: %s must be a contiguous int64 CUDA tensor" % (what, name))
+        self._tensors(what, [("offsets", offsets, torch.int64), ("lengths", lengths, torch.int64)])
         n, total = int(lengths.numel()), int(total)
         if int(offsets.numel()) != n + 1:
             raise ValueError("%s: offsets must have n_reads + 1 entries" % what)
@@ -387,14 +379,11 @@ class HipEngine(object):
         Asynchronous on the stream; one phase launches nothing.  Returns ``x_all``."""
         import torch
         phases, n, total, size, c_phases = self._check_tiling_tables("retile_device", offsets, lengths, total, phases)
-        if not isinstance(x_all, torch.Tensor) or not x_all.is_cuda or x_all.dtype != torch.float32 or not x_all.is_contiguous():
-            raise ValueError("retile_device: x_all must be a contiguous float32 CUDA tensor")
-        if int(x_all.numel()) < size:
-            raise ValueError("retile_device: x_all needs %d samples for %d tilings, has %d" % (size, len(phases), int(x_all.numel())))
+        self._tensors("retile_device", [("x_all", x_all, torch.float32, size)])
         if stream is None:
-            stream = torch.cuda.current_stream(x_all.device)
-        N.check(self._lib.cf_retile_windows(self._handle, C.c_void_p(x_all.data_ptr()), C.c_void_p(offsets.data_ptr()),
-                                            C.c_void_p(lengths.data_ptr()), n, total, c_phases, len(phases), C.c_void_p(stream.cuda_stream)))
+            stream = torch.cuda.current_stream(self.device)
+        N.check(self._lib.cf_retile_windows(self._handle, N._p(x_all), N._p(offsets), N._p(lengths), n, total, c_phases, len(phases),
+                                            N.stream_ptr(stream)))
         return x_all
 
     def vote_device(self, probs_all, offsets, lengths, total, phases, weight="mean", logits_all=None, out=None, logits_out=None, stream=None):
@@ -408,43 +397,24 @@ class HipEngine(object):
         from .tilings import check_weight
         phases, n, total, size, c_phases = self._check_tiling_tables("vote_device", offsets, lengths, total, phases)
         weight = check_weight(weight)
-
-        def checked(name, t, need):
-            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError("vote_device: %s must be a contiguous float32 CUDA tensor" % name)
-            if int(t.numel()) < need:
-                raise ValueError("vote_device: %s needs %d samples, has %d" % (name, need, int(t.numel())))
-            return t
-        checked("probs_all", probs_all, size)
+        self._tensors("vote_device", [("probs_all", probs_all, torch.float32, size)])
         if out is None:
             out = torch.empty(total, dtype=torch.float32, device=probs_all.device)
-        checked("out", out, total)
+        self._tensors("vote_device", [("out", out, torch.float32, total)])
         if logits_all is not None:
-            checked("logits_all", logits_all, size)
+            self._tensors("vote_device", [("logits_all", logits_all, torch.float32, size)])
             if logits_out is None:
                 logits_out = torch.empty(total, dtype=torch.float32, device=probs_all.device)
-            checked("logits_out", logits_out, total)
+            self._tensors("vote_device", [("logits_out", logits_out, torch.float32, total)])
         elif logits_out is not None:
             raise ValueError("vote_device: logits_out without logits_all")
         if stream is None:
-            stream = torch.cuda.current_stream(probs_all.device)
-        N.check(self._lib.cf_vote_tilings(self._handle, C.c_void_p(probs_all.data_ptr()),
-                                          C.c_void_p(logits_all.data_ptr()) if logits_all is not None else None,
-                                          C.c_void_p(offsets.data_ptr()), C.c_void_p(lengths.data_ptr()), n, total, c_phases, len(phases),
-                                          weight, C.c_void_p(out.data_ptr()),
-                                          C.c_void_p(logits_out.data_ptr()) if logits_all is not None else None,
-                                          C.c_void_p(stream.cuda_stream)))
+            stream = torch.cuda.current_stream(self.device)
+        N.check(self._lib.cf_vote_tilings(self._handle, N._p(probs_all), N._p(logits_all), N._p(offsets), N._p(lengths), n, total, c_phases,
+                                          len(phases), weight, N._p(out), N._p(logits_out), N.stream_ptr(stream)))
         return out if logits_all is None else (out, logits_out)
 
     # ------------------------------------------------------------------ validation rounds on the card (csrc/validation.hpp)
-    def _check_validation_tensors(self, what, tensors):
-        import torch
-        for name, t, dtype in tensors:
-            if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
-                raise ValueError("%s: %s must be a contiguous %s CUDA tensor" % (what, name, str(dtype).replace("torch.", "")))
-            if t.device.index != self.device:
-                raise ValueError("%s: %s lives on cuda:%s, model on cuda:%d" % (what, name, t.device.index, self.device))
-
     @staticmethod
     def _check_validation_sizes(what, probs, y, bounds, length, total, longest):
         """What the run-state, border and curve steps ask of their tables: -> (n, total, longest) as ints."""
@@ -461,7 +431,7 @@ class HipEngine(object):
         ``length`` [n] and ``bounds`` [n + 1] are int64 CUDA tensors; ``total`` = bounds[n] and ``longest`` = the largest packed
         read are the caller's host copies of those numbers.  Asynchronous on the stream."""
         import torch
-        self._check_validation_tensors("gather_validation", [
+        self._tensors("gather_validation", [
             ("signal", signal, torch.float32), ("labels", labels, torch.uint8), ("src_first", src_first, torch.int64),
             ("length", length, torch.int64), ("bounds", bounds, torch.int64), ("x_out", x_out, torch.float32), ("y_out", y_out, torch.uint8)])
         n, total, longest = int(src_first.numel()), int(total), int(longest)
@@ -472,11 +442,9 @@ class HipEngine(object):
         if total < 0 or int(x_out.numel()) < total or int(y_out.numel()) < total:
             raise ValueError("gather_validation: x_out and y_out need %d elements" % total)
         if stream is None:
-            stream = torch.cuda.current_stream(signal.device)
-        N.check(self._lib.cf_validation_gather(self._handle, C.c_void_p(signal.data_ptr()), C.c_void_p(labels.data_ptr()), int(signal.numel()),
-                                               C.c_void_p(src_first.data_ptr()), C.c_void_p(length.data_ptr()), C.c_void_p(bounds.data_ptr()),
-                                               n, total, longest, C.c_void_p(x_out.data_ptr()), C.c_void_p(y_out.data_ptr()),
-                                               C.c_void_p(stream.cuda_stream)))
+            stream = torch.cuda.current_stream(self.device)
+        N.check(self._lib.cf_validation_gather(self._handle, N._p(signal), N._p(labels), int(signal.numel()), N._p(src_first), N._p(length),
+                                               N._p(bounds), n, total, longest, N._p(x_out), N._p(y_out), N.stream_ptr(stream)))
 
     def score_validation(self, probs, logits, y, bounds, total, longest, thresholds, right_out, ce_sum_out, counts_out, partials, stream=None):
         """``cf_validation_score``: per read the number of samples with ``rint(p) == y`` (``right_out`` int64 [n]) and the fp64 sum
@@ -484,7 +452,7 @@ class HipEngine(object):
         1 <= K <= 16) tp / fp / raw tn / fn over all ``total`` samples (``counts_out`` int64 [K * 4]).  ``partials`` is float64
         work space of at least ``total // SCORE_CHUNK + n`` elements.  Asynchronous on the stream; equal inputs give equal bits."""
         import torch
-        self._check_validation_tensors("score_validation", [
+        self._tensors("score_validation", [
             ("probs", probs, torch.float32), ("logits", logits, torch.float32), ("y", y, torch.uint8), ("bounds", bounds, torch.int64),
             ("thresholds", thresholds, torch.float64), ("right_out", right_out, torch.int64), ("ce_sum_out", ce_sum_out, torch.float64),
             ("counts_out", counts_out, torch.int64), ("partials", partials, torch.float64)])
@@ -494,27 +462,25 @@ class HipEngine(object):
         if int(right_out.numel()) < n or int(ce_sum_out.numel()) < n or int(counts_out.numel()) < 4 * k:
             raise ValueError("score_validation: right_out and ce_sum_out need n entries, counts_out 4 per threshold")
         if stream is None:
-            stream = torch.cuda.current_stream(probs.device)
+            stream = torch.cuda.current_stream(self.device)
         # n, K and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
-        N.check(self._lib.cf_validation_score(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(logits.data_ptr()), C.c_void_p(y.data_ptr()),
-                                              C.c_void_p(bounds.data_ptr()), n, total, longest, C.c_void_p(thresholds.data_ptr()), k,
-                                              C.c_void_p(right_out.data_ptr()), C.c_void_p(ce_sum_out.data_ptr()),
-                                              C.c_void_p(counts_out.data_ptr()), C.c_void_p(partials.data_ptr()), int(partials.numel()),
-                                              C.c_void_p(stream.cuda_stream)))
+        N.check(self._lib.cf_validation_score(self._handle, N._p(probs), N._p(logits), N._p(y), N._p(bounds), n, total, longest,
+                                              N._p(thresholds), k, N._p(right_out), N._p(ce_sum_out), N._p(counts_out), N._p(partials),
+                                              int(partials.numel()), N.stream_ptr(stream)))
 
     def _run_step_arguments(self, what, probs, y, bounds, length, total, longest, thresholds, counts_out, work, stream, own=()):
         """What ``run_states_validation``, ``run_borders_validation`` and ``run_bases_validation`` check and convert alike (``own``:
         the step's own tensors, checked between ``y`` and ``bounds``) -> (n, total, longest, K, thresholds as a C array, stream).
         n, K, min_run, the (min_run, max_gap) pair and the work space are refused by the library (CF_ERR_INVALID -> ValueError)."""
         import torch
-        self._check_validation_tensors(what, [("probs", probs, torch.float32), ("y", y, torch.uint8)] + list(own) + [
+        self._tensors(what, [("probs", probs, torch.float32), ("y", y, torch.uint8)] + list(own) + [
             ("bounds", bounds, torch.int64), ("length", length, torch.int64), ("counts_out", counts_out, torch.int64),
             ("work", work, torch.uint8)])
         thresholds = [float(t) for t in thresholds]
         k = len(thresholds)
         n, total, longest = self._check_validation_sizes(what, probs, y, bounds, length, total, longest)
         if stream is None:
-            stream = torch.cuda.current_stream(probs.device)
+            stream = torch.cuda.current_stream(self.device)
         return n, total, longest, k, (C.c_double * max(k, 1))(*thresholds), stream
 
     def run_states_work_bytes(self, total, n_thresholds):
@@ -536,11 +502,10 @@ class HipEngine(object):
             raise ValueError("run_states_validation: counts_out needs 2 * (edges + 1) * 3 entries per threshold")
         # the edges are refused by the library too; ``max_gap`` 0 is ``cf_validation_run_states``, anything else bridges the
         # prediction first
-        N.check(self._lib.cf_validation_run_states_bridged(
-            self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
-            C.c_void_p(length.data_ptr()), n, total, longest, thresholds, k, (C.c_int64 * max(len(edges), 1))(*edges), len(edges),
-            int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()),
-            C.c_void_p(stream.cuda_stream)))
+        N.check(self._lib.cf_validation_run_states_bridged(self._handle, N._p(probs), N._p(y), N._p(bounds), N._p(length), n, total,
+                                                           longest, thresholds, k, (C.c_int64 * max(len(edges), 1))(*edges), len(edges),
+                                                           int(max_gap), int(min_run), N._p(counts_out), N._p(work), int(work.numel()),
+                                                           N.stream_ptr(stream)))
 
     def run_scores_work_bytes(self, total, n_thresholds):
         """Bytes of work space ``run_scores_validation`` needs: the labels of ``run_states_work_bytes`` and a byte of paint per sample
@@ -559,11 +524,9 @@ class HipEngine(object):
         if isinstance(shift, bool) or int(shift) != shift:
             raise ValueError("run_scores_validation: shift must be an int, got %r" % (shift,))
         # the shift, the room in table_out and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
-        N.check(self._lib.cf_validation_run_scores(
-            self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
-            C.c_void_p(length.data_ptr()), n, total, longest, thresholds, k, int(shift), int(max_gap), int(min_run),
-            C.c_void_p(table_out.data_ptr()), int(table_out.numel()), C.c_void_p(work.data_ptr()), int(work.numel()),
-            C.c_void_p(stream.cuda_stream)))
+        N.check(self._lib.cf_validation_run_scores(self._handle, N._p(probs), N._p(y), N._p(bounds), N._p(length), n, total, longest,
+                                                   thresholds, k, int(shift), int(max_gap), int(min_run), N._p(table_out),
+                                                   int(table_out.numel()), N._p(work), int(work.numel()), N.stream_ptr(stream)))
 
     def run_borders_work_bytes(self, total, n_thresholds):
         """Bytes of work space ``run_borders_validation`` needs (``run_states_work_bytes``' rule: the two can share a buffer)."""
@@ -585,10 +548,9 @@ class HipEngine(object):
         if int(counts_out.numel()) < k * 2 * (5 * reach + 3):
             raise ValueError("run_borders_validation: counts_out needs 2 * (5 * reach + 3) entries per threshold")
         # ``max_gap`` 0 is ``cf_validation_run_borders``, anything else bridges the prediction first
-        N.check(self._lib.cf_validation_run_borders_bridged(
-            self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(bounds.data_ptr()),
-            C.c_void_p(length.data_ptr()), n, total, longest, thresholds, k, reach, int(max_gap), int(min_run),
-            C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()), int(work.numel()), C.c_void_p(stream.cuda_stream)))
+        N.check(self._lib.cf_validation_run_borders_bridged(self._handle, N._p(probs), N._p(y), N._p(bounds), N._p(length), n, total,
+                                                            longest, thresholds, k, reach, int(max_gap), int(min_run), N._p(counts_out),
+                                                            N._p(work), int(work.numel()), N.stream_ptr(stream)))
 
     def run_bases_validation(self, probs, y, basemap, src_first, bounds, length, total, longest, thresholds, max_bases, counts_out, work,
                              min_run=15, max_gap=0, stream=None):
@@ -610,11 +572,9 @@ class HipEngine(object):
         if int(counts_out.numel()) < k * 2 * 3 * len(BASE_CLASSES) * (max_bases + 1):
             raise ValueError("run_bases_validation: counts_out needs 2 * 3 * 5 * (max_bases + 1) entries per threshold")
         # an empty base map is refused by the library too
-        N.check(self._lib.cf_validation_run_bases(
-            self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()), C.c_void_p(basemap.data_ptr()), int(basemap.numel()),
-            C.c_void_p(src_first.data_ptr()), C.c_void_p(bounds.data_ptr()), C.c_void_p(length.data_ptr()), n, total, longest,
-            thresholds, k, max_bases, int(max_gap), int(min_run), C.c_void_p(counts_out.data_ptr()), C.c_void_p(work.data_ptr()),
-            int(work.numel()), C.c_void_p(stream.cuda_stream)))
+        N.check(self._lib.cf_validation_run_bases(self._handle, N._p(probs), N._p(y), N._p(basemap), int(basemap.numel()), N._p(src_first),
+                                                  N._p(bounds), N._p(length), n, total, longest, thresholds, k, max_bases, int(max_gap),
+                                                  int(min_run), N._p(counts_out), N._p(work), int(work.numel()), N.stream_ptr(stream)))
 
     def base_votes_work_bytes(self, n_bases, n_thresholds):
         """Bytes of work space ``base_votes_validation`` needs for a set of ``n_bases`` bases and ``n_thresholds`` thresholds."""
@@ -632,7 +592,7 @@ class HipEngine(object):
         import torch
         from . import base_votes
         from .device_validation import BASE_CLASSES, check_max_bases
-        self._check_validation_tensors("base_votes_validation", [
+        self._tensors("base_votes_validation", [
             ("probs", probs, torch.float32), ("labels", labels, torch.uint8), ("basemap", basemap, torch.uint8), ("edges", edges, torch.int64),
             ("src_first", src_first, torch.int64), ("bounds", bounds, torch.int64), ("length", length, torch.int64),
             ("ranges", ranges, torch.int64), ("confusion_out", confusion_out, torch.int64), ("runs_out", runs_out, torch.int64),
@@ -649,7 +609,7 @@ class HipEngine(object):
         if int(confusion_out.numel()) < k * base_votes.CONFUSION_CELLS or int(runs_out.numel()) < k * 2 * 3 * len(BASE_CLASSES) * (max_bases + 1):
             raise ValueError("base_votes_validation: confusion_out needs 20 entries per threshold, runs_out 2 * 3 * 5 * (max_bases + 1)")
         if stream is None:
-            stream = torch.cuda.current_stream(probs.device)
+            stream = torch.cuda.current_stream(self.device)
         # K, the sizes and the work space are refused by the library (CF_ERR_INVALID -> ValueError)
         base_votes.launch(self._lib, self._handle, probs, total, labels, basemap, edges, int(edges.numel()) - 1, src_first, length, bounds,
                           ranges, longest_range, thresholds, max_bases, confusion_out, runs_out, work, stream)
@@ -660,18 +620,17 @@ class HipEngine(object):
         at least ``3 * curve_bins(shift)`` elements, zeroed and written by the call).  ``bounds`` [n + 1] and ``length`` [n] are
         int64 CUDA tensors; the zero tails are not counted.  Asynchronous on the stream; equal inputs give equal bits."""
         import torch
-        self._check_validation_tensors("curve_validation", [
+        self._tensors("curve_validation", [
             ("probs", probs, torch.float32), ("y", y, torch.uint8), ("bounds", bounds, torch.int64), ("length", length, torch.int64),
             ("hist_out", hist_out, torch.int64)])
         n, total, longest = self._check_validation_sizes("curve_validation", probs, y, bounds, length, total, longest)
         if isinstance(shift, bool) or int(shift) != shift:
             raise ValueError("curve_validation: shift must be an int, got %r" % (shift,))
         if stream is None:
-            stream = torch.cuda.current_stream(probs.device)
+            stream = torch.cuda.current_stream(self.device)
         # n, the shift and the room in hist_out are refused by the library (CF_ERR_INVALID -> ValueError)
-        N.check(self._lib.cf_validation_curve(self._handle, C.c_void_p(probs.data_ptr()), C.c_void_p(y.data_ptr()),
-                                              C.c_void_p(bounds.data_ptr()), C.c_void_p(length.data_ptr()), n, total, longest, int(shift),
-                                              C.c_void_p(hist_out.data_ptr()), int(hist_out.numel()), C.c_void_p(stream.cuda_stream)))
+        N.check(self._lib.cf_validation_curve(self._handle, N._p(probs), N._p(y), N._p(bounds), N._p(length), n, total, longest, int(shift),
+                                              N._p(hist_out), int(hist_out.numel()), N.stream_ptr(stream)))
 
     # ------------------------------------------------------------------ profiling / debug
     def profile_enable(self, on=True, every=1):
@@ -697,5 +656,5 @@ class HipEngine(object):
         the values are what the kernels stored, rounded to bf16; with ``"bf16x3"`` hi + lo of the stored split."""
         feats = self.layer_size_res if stage < self.n_layers_res else 2 * self.layer_size
         out = np.empty((n_windows, WINDOW, feats), dtype=np.float32)
-        N.check(self._lib.cf_debug_stage(self._handle, int(stage), int(n_windows), out.ctypes.data_as(C.c_void_p)))
+        N.check(self._lib.cf_debug_stage(self._handle, int(stage), int(n_windows), N.np_ptr(out)))
         return out

@@ -286,7 +286,7 @@ def label_on_card(batch, kmer, device, base_map):
     tables = batch.device_tables(lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device))
     work_bytes = int(getattr(lib, batch.WORK_BYTES)(*batch.work_args())) if total else 0
     work = torch.empty(work_bytes, dtype=torch.uint8, device=device)
-    p = lambda t: N._p(t) if total and t is not None else None     # noqa: E731   (an empty batch is a call without pointers)
+    p = lambda t: N._p(t) if total else None     # noqa: E731   (an empty batch is a call without pointers)
     with torch.cuda.device(device):
         N.check(getattr(lib, batch.ENTRY)(None, *[t if isinstance(t, int) else p(t) for t in tables], batch.n_reads, batch.n_events, total, k,
                                           p(labels), p(bmap), p(work), work_bytes, N.current_stream_ptr(torch, device) if total else None))

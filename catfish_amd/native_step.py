@@ -26,8 +26,6 @@ step of every other model.
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
 from . import _native as N
@@ -231,14 +229,14 @@ class NativeTrainStep(FlatTrainStep):
             _, _, bo, bn = self.per_layer[layer]
             dx = b["dx"][layer]
             N.check(lib.cf_gru_train_backward_dropout(h, cin, _p(self.packed[bo:bo + bn]), _p(b["y_frag"][layer]), _p(b["stash"][layer]),
-                                                      _p(g0), None if g1 is None else _p(g1), None if drop is None else _p(drop[layer]),
+                                                      _p(g0), _p(g1), _p(drop[layer] if drop else None),
                                                       _p(dx), _p(b["da"][layer]), npad, kp if in_kernel else 1.0, self.seed, layer, step_ptr,
                                                       stream))
             go = self.gru_off[layer]
             wstream = stream
             if side is not None:
                 side.wait_stream(main)                      # fork: everything up to this layer's backward recurrence
-                wstream = C.c_void_p(side.cuda_stream)
+                wstream = N.stream_ptr(side)
             N.check(lib.cf_gru_train_wgrad(h, cin, _p(inputs[layer]), _p(b["y_frag"][layer]), _p(b["stash"][layer]), _p(b["da"][layer]), npad,
                                            _p(b["wgrad_ws"][layer]), int(b["wgrad_ws"][layer].numel()), _p(gf[go:]), wstream))
             g0, g1 = dx[0], dx[1]

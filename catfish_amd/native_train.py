@@ -46,8 +46,7 @@ def pack_maps(cin, device):
             N.check(lib.cf_gru_pack_map(int(cin), backward, None, None, 0, C.byref(n)))
             idx = np.empty(n.value, dtype=np.int32)
             scale = np.empty(n.value, dtype=np.float32)
-            N.check(lib.cf_gru_pack_map(int(cin), backward, idx.ctypes.data_as(C.c_void_p), scale.ctypes.data_as(C.c_void_p),
-                                        n.value, C.byref(n)))
+            N.check(lib.cf_gru_pack_map(int(cin), backward, N.np_ptr(idx), N.np_ptr(scale), n.value, C.byref(n)))
             out += [torch.from_numpy(idx.astype(np.int64)).to(device), torch.from_numpy(scale).to(device)]
         _MAPS[key] = tuple(out)
     return _MAPS[key]
@@ -83,9 +82,8 @@ def _make_function():
             tiles = npad // 16
             y_frag = torch.empty(tiles, T, 8, 64, 4, dtype=torch.float32, device=x.device)
             stash = torch.empty(tiles, T, 2, 12, 64, 4, dtype=torch.float32, device=x.device)
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            N.check(lib.cf_gru_train_forward(handle, cin, C.c_void_p(wpack.data_ptr()), C.c_void_p(x_frag.data_ptr()),
-                                             C.c_void_p(y_frag.data_ptr()), C.c_void_p(stash.data_ptr()), npad, C.c_void_p(stream)))
+            stream = N.current_stream_ptr(torch, x.device)
+            N.check(lib.cf_gru_train_forward(handle, cin, N._p(wpack), N._p(x_frag), N._p(y_frag), N._p(stash), npad, stream))
             ctx.engine, ctx.n, ctx.npad = engine, n, npad
             ctx.save_for_backward(xp, y_frag, stash, wpack_bwd)
             return frag_to_nat(y_frag)[:n]
@@ -102,10 +100,9 @@ def _make_function():
             dy_frag = nat_to_frag(dyp.float().contiguous())
             dx_frag = torch.empty(2, tiles, T, cin // 16, 64, 4, dtype=torch.float32, device=dev)
             da = torch.empty(tiles, T, 2, 12, 64, 4, dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            N.check(lib.cf_gru_train_backward(handle, int(cin), C.c_void_p(wpack_bwd.data_ptr()), C.c_void_p(y_frag.data_ptr()),
-                                              C.c_void_p(stash.data_ptr()), C.c_void_p(dy_frag.data_ptr()), None, None,
-                                              C.c_void_p(dx_frag.data_ptr()), C.c_void_p(da.data_ptr()), npad, C.c_void_p(stream)))
+            stream = N.current_stream_ptr(torch, dev)
+            N.check(lib.cf_gru_train_backward(handle, int(cin), N._p(wpack_bwd), N._p(y_frag), N._p(stash), N._p(dy_frag), None, None,
+                                              N._p(dx_frag), N._p(da), npad, stream))
             dx = (frag_to_nat(dx_frag[0]) + frag_to_nat(dx_frag[1]))[:n]
             y = frag_to_nat(y_frag)                                   # [npad, 35, 128]
             grads = []
@@ -209,15 +206,14 @@ def _make_stack_function():
             tiles = npad // 16
             xp = x if npad == n else torch.cat([x, x.new_zeros(npad - n, T, cins[0])], 0)
             cur = nat_to_frag(xp.float())
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = N.current_stream_ptr(torch, dev)
             saved = []
             for layer in range(n_layers):
                 fo, fn, _, _ = per_layer[layer]
                 y_frag = torch.empty(tiles, T, 8, 64, 4, dtype=torch.float32, device=dev)
                 stash = torch.empty(tiles, T, 2, 12, 64, 4, dtype=torch.float32, device=dev)
-                N.check(lib.cf_gru_train_forward(handle, cins[layer], C.c_void_p(packed[fo:fo + fn].data_ptr()),
-                                                 C.c_void_p(cur.data_ptr()), C.c_void_p(y_frag.data_ptr()),
-                                                 C.c_void_p(stash.data_ptr()), npad, stream))
+                N.check(lib.cf_gru_train_forward(handle, cins[layer], N._p(packed[fo:fo + fn]), N._p(cur), N._p(y_frag), N._p(stash), npad,
+                                                 stream))
                 saved += [cur, y_frag, stash]
                 cur = y_frag if drop is None else y_frag * drop[layer]
             ctx.engine, ctx.n, ctx.npad, ctx.cins, ctx.per_layer = engine, n, npad, cins, per_layer
@@ -234,7 +230,7 @@ def _make_stack_function():
             dev = dy.device
             tiles = npad // 16
             n_layers = len(cins)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = N.current_stream_ptr(torch, dev)
             dyp = dy if npad == n else torch.cat([dy, dy.new_zeros(npad - n, T, dy.shape[2])], 0)
             g0 = nat_to_frag(dyp.float().contiguous())
             g1 = None
@@ -245,18 +241,14 @@ def _make_stack_function():
                 _, _, bo, bn = per_layer[layer]
                 dx_frag = torch.empty(2, tiles, T, cin // 16, 64, 4, dtype=torch.float32, device=dev)
                 da = torch.empty(tiles, T, 2, 12, 64, 4, dtype=torch.float32, device=dev)
-                N.check(lib.cf_gru_train_backward(
-                    handle, cin, C.c_void_p(packed[bo:bo + bn].data_ptr()), C.c_void_p(y_frag.data_ptr()), C.c_void_p(stash.data_ptr()),
-                    C.c_void_p(g0.data_ptr()), None if g1 is None else C.c_void_p(g1.data_ptr()),
-                    None if drop is None else C.c_void_p(drop[layer].data_ptr()),
-                    C.c_void_p(dx_frag.data_ptr()), C.c_void_p(da.data_ptr()), npad, stream))
+                N.check(lib.cf_gru_train_backward(handle, cin, N._p(packed[bo:bo + bn]), N._p(y_frag), N._p(stash), N._p(g0), N._p(g1),
+                                                  N._p(drop[layer] if drop else None), N._p(dx_frag), N._p(da), npad, stream))
                 ws_floats = int(lib.cf_gru_wgrad_workspace_floats(handle, cin, npad))
                 ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
                 rows = cin + 64
                 out = torch.empty(2, rows * 192 + 192, dtype=torch.float32, device=dev)
-                N.check(lib.cf_gru_train_wgrad(handle, cin, C.c_void_p(x_frag.data_ptr()), C.c_void_p(y_frag.data_ptr()),
-                                               C.c_void_p(stash.data_ptr()), C.c_void_p(da.data_ptr()), npad,
-                                               C.c_void_p(ws.data_ptr()), ws_floats, C.c_void_p(out.data_ptr()), stream))
+                N.check(lib.cf_gru_train_wgrad(handle, cin, N._p(x_frag), N._p(y_frag), N._p(stash), N._p(da), npad, N._p(ws), ws_floats,
+                                               N._p(out), stream))
                 for d in range(2):
                     o = out[d]
                     grads[8 * layer + 4 * d + 0] = o[:rows * 128].view(rows, 128)
@@ -336,9 +328,8 @@ def _make_res_function():
             xc = x.float().contiguous()
             z = torch.empty(4 * n_blocks, n * T, 32, dtype=torch.float32, device=dev)
             out = torch.empty(n, T, 32, dtype=torch.float32, device=dev)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            N.check(lib.cf_res_train_forward(handle, n_blocks, C.c_void_p(prm.data_ptr()), C.c_void_p(xc.data_ptr()),
-                                             C.c_void_p(z.data_ptr()), C.c_void_p(out.data_ptr()), n, stream))
+            stream = N.current_stream_ptr(torch, dev)
+            N.check(lib.cf_res_train_forward(handle, n_blocks, N._p(prm), N._p(xc), N._p(z), N._p(out), n, stream))
             ctx.engine, ctx.n_blocks, ctx.shapes = engine, n_blocks, [tuple(p.shape) for p in params]
             ctx.save_for_backward(prm, xc, z)
             return out
@@ -354,10 +345,9 @@ def _make_res_function():
             ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
             grads = torch.empty_like(prm)
             d = dout.float().contiguous()
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            N.check(lib.cf_res_train_backward(handle, n_blocks, C.c_void_p(prm.data_ptr()), C.c_void_p(xc.data_ptr()),
-                                              C.c_void_p(z.data_ptr()), C.c_void_p(d.data_ptr()), C.c_void_p(ws.data_ptr()), ws_floats,
-                                              C.c_void_p(grads.data_ptr()), n, stream))
+            stream = N.current_stream_ptr(torch, dev)
+            N.check(lib.cf_res_train_backward(handle, n_blocks, N._p(prm), N._p(xc), N._p(z), N._p(d), N._p(ws), ws_floats, N._p(grads), n,
+                                              stream))
             outs, off = [], 0
             for i, shp in enumerate(ctx.shapes):
                 cnt = int(np.prod(shp))

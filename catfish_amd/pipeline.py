@@ -100,7 +100,7 @@ class ReadPipeline(object):
         # threads: a quarter of the CPUs this rank owns (placement.bind: 32 per rank on an 8-GPU node), 2 .. 8: a 1110-file batch takes
         # 6.8 / 2.3 / 1.8 / 1.7 ms with 1 / 4 / 8 / 16 threads (tools/exp_loader_threads.py) -- past 8 nothing is gained, and in
         # bf16 the batch's forward pass takes 2.3 ms, so the loader sets the pace below that
-        rc = load(*head, C.c_void_p(self.stage[slot].data_ptr()), self.cap, lengths.ctypes.data_as(C.c_void_p), C.byref(total),
+        rc = load(*head, N._p(self.stage[slot]), self.cap, N.np_ptr(lengths), C.byref(total),
                   int(self._file_threads if n_threads is None else n_threads))
         msg = self.eng._lib.cf_last_error().decode("utf-8", "replace") if rc != N.CF_OK else ""
         return rc, lengths, int(total.value), msg
@@ -134,7 +134,7 @@ class ReadPipeline(object):
         blob = b"\x00".join(paths) + b"\x00"
         bounds = np.zeros(len(paths) + 1, dtype=np.int64)
         np.cumsum([len(p) + 1 for p in paths], out=bounds[1:])
-        head = (blob, bounds.ctypes.data_as(C.c_void_p), len(paths))
+        head = (blob, N.np_ptr(bounds), len(paths))
         return self._launch_loaded(slot, self._native_load(slot, self.eng._lib.cf_load_npy_int16, head, len(paths), n_threads))
 
     # ---- the same with the file reads one batch AHEAD, in a helper thread (the native call releases the GIL): while the main thread

@@ -174,7 +174,7 @@ class DirListing(object):
             return b"", np.zeros(1, dtype=np.int64)
         buf = C.create_string_buffer(max(1, int(need.value)))
         bounds = np.empty(hi - lo + 1, dtype=np.int64)
-        N.check(self._lib.cf_listing_names(self._handle, int(lo), int(hi), buf, int(need.value), bounds.ctypes.data_as(C.c_void_p), None))
+        N.check(self._lib.cf_listing_names(self._handle, int(lo), int(hi), buf, int(need.value), N.np_ptr(bounds), None))
         return buf.raw[:int(need.value)], bounds
 
     def __len__(self):
@@ -182,10 +182,9 @@ class DirListing(object):
 
     def sizes(self, lo, hi, n_threads=4):
         """int64 sizes on disk of entries [lo, hi)."""
-        import ctypes as C
         from . import _native as N
         out = np.empty(max(0, hi - lo), dtype=np.int64)
-        N.check(self._lib.cf_listing_sizes(self._handle, int(lo), int(hi), out.ctypes.data_as(C.c_void_p), int(n_threads)))
+        N.check(self._lib.cf_listing_sizes(self._handle, int(lo), int(hi), N.np_ptr(out), int(n_threads)))
         return out
 
     def names(self, lo=0, hi=None):
@@ -241,7 +240,6 @@ def stat_sizes(directory, names, n_threads=4):
     """Sizes on disk of ``names`` (entries of ``directory``) as int64 -- ``cf_stat_files``: fstatat from the library's host thread
     pool (a Python loop of os.stat costs 1.5 us per file, 19 ms for a rank's 12 500 reads; this about half).  A name that cannot
     be stat-ed raises ValueError naming it."""
-    import ctypes as C
     from . import _native as N
     sizes = np.empty(len(names), dtype=np.int64)
     if not names:
@@ -250,8 +248,8 @@ def stat_sizes(directory, names, n_threads=4):
     blob = b"\x00".join(enc) + b"\x00"
     bounds = np.zeros(len(enc) + 1, dtype=np.int64)
     np.cumsum(np.fromiter((len(e) + 1 for e in enc), dtype=np.int64, count=len(enc)), out=bounds[1:])
-    N.check(N.lib().cf_stat_files(os.fsencode(directory), blob, bounds.ctypes.data_as(C.c_void_p), len(enc),
-                                  sizes.ctypes.data_as(C.c_void_p), int(n_threads)))
+    N.check(N.lib().cf_stat_files(os.fsencode(directory), blob, N.np_ptr(bounds), len(enc),
+                                  N.np_ptr(sizes), int(n_threads)))
     return sizes
 
 
