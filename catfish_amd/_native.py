@@ -1,7 +1,8 @@
-"""ctypes binding of the C ABI declared in include/catfish_hip.h.
+"""ctypes binding of the C ABI declared in include/catfish_hip.h and, for the entry points added next to it,
+include/catfish_hip_ext.h.
 
-The header is the only statement of that ABI: the signature table, the constants and the layout of the four structs are read
-from it once, at import (``parse_header``); nothing here restates a signature.
+The headers are the only statement of that ABI: the signature tables, the constants and the layout of the four structs are read
+from them once, at import (``parse_header``); nothing here restates a signature.
 
 The product path has NO CPU fallback: if the HIP library has not been built
 (``python -c "import __graft_entry__ as g; g.build()"`` or
@@ -18,6 +19,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB_PATH = os.path.join(_HERE, "csrc", "libcatfish_hip.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "catfish_hip.h")
+EXT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "catfish_hip_ext.h")
 
 
 def debug_knobs_on():
@@ -102,12 +104,13 @@ def parse_header(text):
     return symbols, constants, structs
 
 
-def _read_header():
+def _read_header(path=None):
+    path = HEADER if path is None else path
     try:
-        with open(HEADER) as fh:
+        with open(path) as fh:
             return fh.read()
     except OSError as e:
-        raise NativeLibraryMissing("%s cannot be read (%s): the binding takes every signature from it" % (HEADER, e.strerror))
+        raise NativeLibraryMissing("%s cannot be read (%s): the binding takes every signature from it" % (path, e.strerror))
 
 
 # name -> (restype, argtypes) of every symbol the header declares; parsed here, once per process
@@ -122,6 +125,14 @@ CF_ERR_IO = _CONSTANTS["CF_ERR_IO"]
 CF_WINDOW = _CONSTANTS["CF_WINDOW"]
 CF_PROF_SLOTS = _CONSTANTS["CF_PROF_SLOTS"]
 PRECISIONS = {"fp32": _CONSTANTS["CF_PREC_FP32"], "bf16x3": _CONSTANTS["CF_PREC_BF16X3"], "bf16": _CONSTANTS["CF_PREC_BF16"]}
+
+# the second header's table: the core one above stays what include/catfish_hip.h declares, this one is everything next to it
+EXT_SYMBOLS, _EXT_CONSTANTS, _ = parse_header(_read_header(EXT_HEADER))
+CF_EXT_ABI_VERSION = _EXT_CONSTANTS["CF_EXT_ABI_VERSION"]
+CF_CLIP_SCALE = _EXT_CONSTANTS["CF_CLIP_SCALE"]
+CF_CLIP_SKIP_NONFINITE = _EXT_CONSTANTS["CF_CLIP_SKIP_NONFINITE"]
+CF_CLIP_SKIPPED = _EXT_CONSTANTS["CF_CLIP_SKIPPED"]
+CF_CLIP_CHUNK = _EXT_CONSTANTS["CF_CLIP_CHUNK"]
 
 _f32p = C.POINTER(C.c_float)
 
@@ -197,15 +208,16 @@ def lib():
                 "`python -m catfish_amd.build` (needs hipcc). There is no CPU fallback." % path)
         _preload_torch_hip_runtime()
         handle = C.CDLL(path)
-        try:
-            abi = getattr(handle, "cf_abi_version")
-        except AttributeError:
-            abi = None
-        built = int(abi()) if abi is not None else None
-        if built != CF_ABI_VERSION:
-            raise NativeLibraryMissing("%s was built for ABI %s, this binding needs %d: rebuild it "
-                                       "(`python -m catfish_amd.build --force`)" % (path, built, CF_ABI_VERSION))
-        for name, (res, args) in SYMBOLS.items():
+        for query, what, want in (("cf_abi_version", "ABI", CF_ABI_VERSION), ("cf_ext_abi_version", "extension ABI", CF_EXT_ABI_VERSION)):
+            try:
+                abi = getattr(handle, query)
+            except AttributeError:
+                abi = None
+            built = int(abi()) if abi is not None else None
+            if built != want:
+                raise NativeLibraryMissing("%s was built for %s %s, this binding needs %d: rebuild it "
+                                           "(`python -m catfish_amd.build --force`)" % (path, what, built, want))
+        for name, (res, args) in list(SYMBOLS.items()) + list(EXT_SYMBOLS.items()):
             try:
                 fn = getattr(handle, name)
             except AttributeError:                         # a library of the same ABI number from before the symbol was added

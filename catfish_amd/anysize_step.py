@@ -7,7 +7,8 @@ with more than ``train_mode.TUNED_MAX_BLOCKS`` blocks).
     dense head + loss, fwd + bwd  cf_gen_head
     biGRU layers backward         cf_gen_dropout + cf_gru_anysize_train_backward + cf_gen_gru_wgrad + cf_gen_gru_dx
     conv stack backward           cf_gen_bn_backward + cf_gen_conv_wgrad + cf_gen_conv_backward_data
-    optimizer + re-tiling         cf_opt_step (one gather map rebuilds every layer's wpack | bpack | wtpack)
+    optimizer + re-tiling         cf_opt_step (one gather map rebuilds every layer's wpack | bpack | wtpack); with clip_norm /
+                                  skip_nonfinite cf_clip_norm + cf_opt_step_guarded (``FlatTrainStep._opt_step``)
 
 The conv and biGRU launches, their buffers and the flat layout (params | grads | two optimizer slots, one layout for every
 geometry) are ``anysize_walk``'s, shared with the operator's backward; this module adds the dropout hooks, the head and the
@@ -50,9 +51,9 @@ class AnySizeTrainStep(FlatTrainStep):
                 self.packed_x3 = self.torch.empty(self.walk.n_packed_x3, dtype=self.torch.float32, device=self.dev)
             self.walk.repack_x3(self.packed, self.packed_x3, self._stream())
 
-    def _opt_step(self, stream):
-        super()._opt_step(stream)
-        if self.precision == "bf16x3":
+    def _opt_step(self, stream, loss=None):
+        super()._opt_step(stream, loss)
+        if self.precision == "bf16x3":                          # (after a skipped step the repack sees unchanged weights)
             self.walk.repack_x3(self.packed, self.packed_x3, stream)
 
     # ------------------------------------------------------------------ buffers per batch size
@@ -97,7 +98,7 @@ class AnySizeTrainStep(FlatTrainStep):
         g = w.gru_backward(b, b["dy_head"], inputs, pf, gf, packed, npad, stream, before=before, packed_x3=packed_x3)
         w.conv_backward(b, g, pf, gf, npad, stream)
         if update:
-            self._opt_step(stream)
+            self._opt_step(stream, b["loss"])
         return b["loss"]
 
     def dropout_scales(self, n, keep_prob=None):

@@ -12,7 +12,7 @@ import shutil
 import subprocess
 import sys
 
-from ._native import HEADER          # the one path to include/catfish_hip.h
+from ._native import EXT_HEADER, HEADER          # the one path to include/catfish_hip.h and to catfish_hip_ext.h
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(_HERE, "csrc", "catfish_hip.hip")
@@ -30,7 +30,7 @@ def needs_build():
     if not os.path.exists(OUT):
         return True
     csrc = os.path.dirname(SRC)
-    deps = [HEADER] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".h"))]
+    deps = [HEADER, EXT_HEADER] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".hpp", ".h"))]
     newest = max(os.path.getmtime(p) for p in deps)
     return os.path.getmtime(OUT) < newest
 

@@ -31,6 +31,7 @@
 #include <functional>
 
 #include "../../include/catfish_hip.h"
+#include "../../include/catfish_hip_ext.h"      // cf_clip_norm / cf_opt_step_guarded: declared there, defined below
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -2662,6 +2663,51 @@ extern "C" int cf_opt_step(cf_model* m, int32_t kind, float* params, const float
     const int64_t ng = std::max<int64_t>(n_packed, 1);
     hipLaunchKernelGGL(gather_scale_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, params, pack_idx, pack_scale, packed, n_packed,
                        step_count);
+    HIP_TRY(hipGetLastError());
+    return CF_OK;
+}
+
+// ---- global-norm clipping + non-finite-step guard (include/catfish_hip_ext.h; kernels in train_step.hpp) ----
+extern "C" int cf_ext_abi_version(void) { return CF_EXT_ABI_VERSION; }
+
+extern "C" int64_t cf_clip_workspace_doubles(int64_t n) { return n <= 0 ? 0 : (n + CF_CLIP_CHUNK - 1) / CF_CLIP_CHUNK; }
+
+extern "C" int cf_clip_norm(cf_model* m, const float* grads, int64_t n, double clip_norm, int32_t flags, const float* loss,
+                            double* workspace, int64_t workspace_doubles, double* record, void* stream) {
+    if (!m || !grads || !workspace || !record) return fail(CF_ERR_INVALID, "cf_clip_norm: null argument");
+    if (n <= 0) return fail(CF_ERR_INVALID, "cf_clip_norm: bad size");
+    if (reinterpret_cast<uintptr_t>(grads) % 16) return fail(CF_ERR_INVALID, "cf_clip_norm: grads must be 16-byte aligned");
+    if (flags <= 0 || (flags & ~(CF_CLIP_SCALE | CF_CLIP_SKIP_NONFINITE)))
+        return fail(CF_ERR_INVALID, "cf_clip_norm: flags must be CF_CLIP_SCALE and / or CF_CLIP_SKIP_NONFINITE");
+    if ((flags & CF_CLIP_SCALE) && !(std::isfinite(clip_norm) && clip_norm > 0.0))
+        return fail(CF_ERR_INVALID, "cf_clip_norm: clip_norm must be a finite positive number");
+    const int64_t n_parts = cf_clip_workspace_doubles(n);
+    if (workspace_doubles < n_parts) return fail(CF_ERR_INVALID, "cf_clip_norm: workspace too small (see cf_clip_workspace_doubles)");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(grad_sq_partial_kernel, dim3((unsigned)n_parts), dim3(256), 0, s, grads, n, workspace);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1), dim3(256), 0, s, workspace, n_parts, clip_norm, (int)flags, loss, record);
+    HIP_TRY(hipGetLastError());
+    return CF_OK;
+}
+
+extern "C" int cf_opt_step_guarded(cf_model* m, int32_t kind, float* params, const float* grads, float* slot1, float* slot2, int64_t n,
+                                   float lr, double* step_count, const int32_t* pack_idx, const float* pack_scale, float* packed,
+                                   int64_t n_packed, const double* record, void* stream) {
+    if (!m || !params || !grads || !slot1 || !slot2 || !step_count || !record)
+        return fail(CF_ERR_INVALID, "cf_opt_step_guarded: null argument");
+    if (kind != 0 && kind != 1) return fail(CF_ERR_INVALID, "cf_opt_step_guarded: kind must be 0 (RMSProp) or 1 (Adam)");
+    if (n <= 0 || n_packed < 0) return fail(CF_ERR_INVALID, "cf_opt_step_guarded: bad size");
+    if (n_packed > 0 && (!pack_idx || !pack_scale || !packed)) return fail(CF_ERR_INVALID, "cf_opt_step_guarded: null packing argument");
+    HIP_TRY(hipSetDevice(m->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(opt_step_guarded_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (int)kind, params, grads, slot1, slot2, n,
+                       lr, step_count, record);
+    HIP_TRY(hipGetLastError());
+    const int64_t ng = std::max<int64_t>(n_packed, 1);
+    hipLaunchKernelGGL(gather_scale_guarded_kernel, dim3((unsigned)((ng + 255) / 256)), dim3(256), 0, s, params, pack_idx, pack_scale, packed,
+                       n_packed, step_count, record);
     HIP_TRY(hipGetLastError());
     return CF_OK;
 }

@@ -98,17 +98,14 @@ __global__ __launch_bounds__(256) void train_head_reduce_kernel(const float* __r
 
 // kind 0 = RMSProp (decay 0.9, momentum 0, epsilon 1e-10; slot1 = rms (initialised to 1), slot2 = momentum)
 // kind 1 = Adam (beta 0.9 / 0.999, epsilon 1e-8; slot1 = m, slot2 = v); t_dev holds the number of steps taken BEFORE this one
-__global__ __launch_bounds__(256) void opt_step_kernel(int kind, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
-                                                       float* __restrict__ s2, int64_t n, float lr, const double* __restrict__ t_dev) {
-    __shared__ float lr_t_s;
-    if (kind == 1 && threadIdx.x == 0) {
-        const double t = t_dev[0] + 1.0;
-        lr_t_s = (float)((double)lr * sqrt(1.0 - pow(0.999, t)) / (1.0 - pow(0.9, t)));
-    }
-    __syncthreads();
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float gi = g[i];
+__device__ __forceinline__ float opt_adam_lr_t(float lr, const double* __restrict__ t_dev) {
+    const double t = t_dev[0] + 1.0;
+    return (float)((double)lr * sqrt(1.0 - pow(0.999, t)) / (1.0 - pow(0.9, t)));
+}
+
+// the update of element i with gradient gi: the one statement of the formulas, for opt_step_kernel and opt_step_guarded_kernel
+__device__ __forceinline__ void opt_update(int kind, float* __restrict__ p, float gi, float* __restrict__ s1, float* __restrict__ s2,
+                                           int64_t i, float lr, float lr_t) {
     if (kind == 0) {
         float ms = s1[i] * 0.9f;
         ms = fmaf(0.1f * gi, gi, ms);                    // addcmul(rms, g, g, value = 1 - decay)
@@ -123,8 +120,18 @@ __global__ __launch_bounds__(256) void opt_step_kernel(int kind, float* __restri
         v = fmaf(0.001f * gi, gi, v);
         s1[i] = m;
         s2[i] = v;
-        p[i] -= m / (sqrtf(v) + 1e-8f) * lr_t_s;
+        p[i] -= m / (sqrtf(v) + 1e-8f) * lr_t;
     }
+}
+
+__global__ __launch_bounds__(256) void opt_step_kernel(int kind, float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
+                                                       float* __restrict__ s2, int64_t n, float lr, const double* __restrict__ t_dev) {
+    __shared__ float lr_t_s;
+    if (kind == 1 && threadIdx.x == 0) lr_t_s = opt_adam_lr_t(lr, t_dev);
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    opt_update(kind, p, g[i], s1, s2, i, lr, lr_t_s);
 }
 
 __global__ __launch_bounds__(256) void gather_scale_kernel(const float* __restrict__ src, const int32_t* __restrict__ idx,
@@ -132,5 +139,84 @@ __global__ __launch_bounds__(256) void gather_scale_kernel(const float* __restri
                                                            double* __restrict__ t_dev) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i == 0 && t_dev) t_dev[0] += 1.0;                // the optimizer step that precedes this launch has read it
+    if (i < n) dst[i] = src[idx[i]] * scale[i];
+}
+
+// ---- global-norm gradient clipping and the non-finite-step guard (include/catfish_hip_ext.h) ----------------------------------
+// record (device double[4]): [0] g = sqrt(sum g_i^2) of the last step, [1] the scale applied (CF_CLIP_SKIPPED on a skipped step),
+// [2] steps clipped, [3] steps skipped.
+//   grad_sq_partial_kernel    one workgroup per chunk of CF_CLIP_CHUNK floats: part[chunk] = sum of double(g_i)^2
+//   grad_norm_finish_kernel   one workgroup: folds the partials, decides scale / skip, updates the record
+//   opt_step_guarded_kernel   opt_step_kernel on float32(g_i * scale); nothing on a skipped step
+//   gather_scale_guarded_kernel   gather_scale_kernel; neither the gather nor the step count on a skipped step
+// Every sum has a fixed shape that depends on n alone (a thread's terms in ascending order, then clip_block_sum's tree), and there
+// are no atomics: equal inputs give equal bits.
+
+// sum of v over the 256 threads of a workgroup, in one fixed order: xor butterfly within a wave, then waves 0..3 in order; the
+// result is valid in thread 0
+__device__ __forceinline__ double clip_block_sum(double v, double* __restrict__ wave_sums) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
+    if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((wave_sums[0] + wave_sums[1]) + wave_sums[2]) + wave_sums[3];
+}
+
+__global__ __launch_bounds__(256) void grad_sq_partial_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ part) {
+    __shared__ double wave_sums[4];
+    const int64_t base = (int64_t)blockIdx.x * CF_CLIP_CHUNK;
+    double acc = 0.0;
+#pragma unroll 4
+    for (int k = 0; k < CF_CLIP_CHUNK / 1024; ++k) {
+        const int64_t i = base + (int64_t)(k * 256 + (int)threadIdx.x) * 4;
+        if (i + 3 < n) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+            acc += (double)v.x * (double)v.x;                // the square of a float32 is exact in float64
+            acc += (double)v.y * (double)v.y;
+            acc += (double)v.z * (double)v.z;
+            acc += (double)v.w * (double)v.w;
+        } else {
+            for (int64_t j = i; j < n; ++j) acc += (double)g[j] * (double)g[j];
+        }
+    }
+    const double sum = clip_block_sum(acc, wave_sums);
+    if (threadIdx.x == 0) part[blockIdx.x] = sum;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const double* __restrict__ part, int64_t n_parts, double clip_norm, int flags,
+                                                               const float* __restrict__ loss, double* __restrict__ rec) {
+    __shared__ double wave_sums[4];
+    double acc = 0.0;
+    for (int64_t c = threadIdx.x; c < n_parts; c += 256) acc += part[c];
+    const double S = clip_block_sum(acc, wave_sums);
+    if (threadIdx.x != 0) return;
+    const double gn = sqrt(S);
+    const bool skip = (flags & CF_CLIP_SKIP_NONFINITE) && (!isfinite(S) || (loss && !isfinite(loss[0])));
+    const float s32 = (flags & CF_CLIP_SCALE) ? (float)(clip_norm / fmax(gn, clip_norm)) : 1.0f;
+    rec[0] = gn;
+    rec[1] = skip ? (double)CF_CLIP_SKIPPED : (double)s32;
+    if (skip) rec[3] += 1.0;
+    else if (s32 < 1.0f) rec[2] += 1.0;
+}
+
+__global__ __launch_bounds__(256) void opt_step_guarded_kernel(int kind, float* __restrict__ p, const float* __restrict__ g,
+                                                               float* __restrict__ s1, float* __restrict__ s2, int64_t n, float lr,
+                                                               const double* __restrict__ t_dev, const double* __restrict__ rec) {
+    __shared__ float lr_t_s;
+    const double scale = rec[1];
+    if (scale == (double)CF_CLIP_SKIPPED) return;            // uniform over the grid: a skipped step writes nothing
+    if (kind == 1 && threadIdx.x == 0) lr_t_s = opt_adam_lr_t(lr, t_dev);
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    opt_update(kind, p, __fmul_rn(g[i], (float)scale), s1, s2, i, lr, lr_t_s);      // one rounding; g_i * 1.0f is g_i
+}
+
+__global__ __launch_bounds__(256) void gather_scale_guarded_kernel(const float* __restrict__ src, const int32_t* __restrict__ idx,
+                                                                   const float* __restrict__ scale, float* __restrict__ dst, int64_t n,
+                                                                   double* __restrict__ t_dev, const double* __restrict__ rec) {
+    if (rec[1] == (double)CF_CLIP_SKIPPED) return;           // a skipped step is not counted and re-tiles nothing
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i == 0) t_dev[0] += 1.0;                            // the optimizer step that precedes this launch has read it
     if (i < n) dst[i] = src[idx[i]] * scale[i];
 }

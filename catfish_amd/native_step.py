@@ -7,6 +7,7 @@ catfish/models/rnn_class.py:201-210 = one ``optimizer.minimize(loss)``).
     biGRU layers backward         cf_gru_train_backward_dropout + cf_gru_train_wgrad
     conv stack backward           cf_res_train_backward
     optimizer + re-tiling         cf_opt_step                     (TF-1 RMSProp / Adam over ALL variables in one launch)
+                                  or, with clip_norm / skip_nonfinite, cf_clip_norm + cf_opt_step_guarded
 
 Every variable, its gradient and its two optimizer slots live in four flat device buffers of ONE layout
 (``anysize_walk.flat_layout``), so the kernels write their gradients straight into the optimizer's input and nothing is copied,
@@ -87,6 +88,9 @@ class FlatTrainStep(object):
                     opt.params[name] = view
                 net.params[name] = view
         self.packed = torch.empty(self.n_packed, dtype=torch.float32, device=self.dev)
+        self.norm_ws = None
+        if opt.guarded:                                      # the norm's partial sums: allocated here, never inside a capture
+            self.norm_ws = torch.empty(int(self.lib.cf_clip_workspace_doubles(self.n_total - 1)), dtype=torch.float64, device=self.dev)
         self.retile()
 
     def retile(self):
@@ -101,11 +105,20 @@ class FlatTrainStep(object):
     def _stream(self):
         return N.current_stream_ptr(self.torch, self.dev)
 
-    def _opt_step(self, stream):
-        """The optimizer over every variable + re-tiling of the biGRU weights."""
-        N.check(self.lib.cf_opt_step(self.handle, self.kind, _p(self.pflat), _p(self.gflat), _p(self.s1), _p(self.s2), self.n_total - 1,
-                                     float(self.opt.lr), _p(self.opt.t), _p(self.pack_idx), _p(self.pack_scale), _p(self.packed),
-                                     self.n_packed, stream))
+    def _opt_step(self, stream, loss=None):
+        """The optimizer over every variable + re-tiling of the biGRU weights.  With ``clip_norm`` or ``skip_nonfinite`` the global
+        norm of ``gflat`` and the decision for this step (which also looks at ``loss``) go in front, into ``opt.stats``, and the
+        guarded optimizer reads them there: all on ``stream``, nothing comes back to the host."""
+        opt = self.opt
+        args = (self.handle, self.kind, _p(self.pflat), _p(self.gflat), _p(self.s1), _p(self.s2), self.n_total - 1, float(opt.lr),
+                _p(opt.t), _p(self.pack_idx), _p(self.pack_scale), _p(self.packed), self.n_packed)
+        if not opt.guarded:
+            N.check(self.lib.cf_opt_step(*args, stream))
+            return
+        flags = (N.CF_CLIP_SCALE if opt.clip_norm is not None else 0) | (N.CF_CLIP_SKIP_NONFINITE if opt.skip_nonfinite else 0)
+        N.check(self.lib.cf_clip_norm(self.handle, _p(self.gflat), self.n_total - 1, opt.clip_norm or 0.0, flags, _p(loss),
+                                      _p(self.norm_ws), int(self.norm_ws.numel()), _p(opt.stats), stream))
+        N.check(self.lib.cf_opt_step_guarded(*args, _p(opt.stats), stream))
 
     def load_batch(self, b, x, y):
         """The batch into the step's static device buffers.  (Pinned staging was measured in round 6 and dropped: 0.764-0.781 ms per
@@ -246,7 +259,7 @@ class NativeTrainStep(FlatTrainStep):
         if side is not None:
             main.wait_stream(side)                          # join: the optimizer reads every gradient
         if update:
-            self._opt_step(stream)
+            self._opt_step(stream, b["loss"])
         return b["loss"]
 
     def dropout_scales(self, n, keep_prob=None):

@@ -30,6 +30,10 @@ class RNN(object):
         self.native_training = kwargs.get("native_training", None)
         # "fp32" | "bf16x3" (the any-size training recurrences on split bf16 products); ``precision`` below is inference only
         self.training_precision = kwargs.get("training_precision", "fp32")
+        # None | a finite float > 0: global-norm gradient clipping in front of the optimizer; skip_nonfinite (None: on with clip_norm)
+        # skips a step whose gradients or loss are not finite (training.Trainer)
+        self.clip_norm = kwargs.get("clip_norm", None)
+        self.skip_nonfinite = kwargs.get("skip_nonfinite", None)
 
         # set parameters (rnn_class.py:25-32)
         self.n_inputs = 1
@@ -340,8 +344,16 @@ class RNN(object):
                                     self.learning_rate, self.keep_prob, seed=self.train_seed,
                                     optimizer_state=getattr(self, "optimizer_state", None),
                                     native=getattr(self, "native_training", None),
-                                    precision=getattr(self, "training_precision", "fp32"))
+                                    precision=getattr(self, "training_precision", "fp32"),
+                                    clip_norm=getattr(self, "clip_norm", None), skip_nonfinite=getattr(self, "skip_nonfinite", None))
         return self._trainer
+
+    def step_stats(self):
+        """``Trainer.step_stats()`` of a network that trains with ``clip_norm`` or ``skip_nonfinite``; None for any other (and
+        before the first step).  One synchronise."""
+        if self._trainer is None or not self._trainer.opt.guarded:
+            return None
+        return self._trainer.step_stats()
 
     def train_network_steps(self, db, n_steps):
         """``n_steps`` optimizer steps of ``batch_size`` windows drawn from a ``device_db.DeviceExampleDb`` on the card

@@ -338,6 +338,29 @@ def _checkpoint_round(network, step, batch_x, batch_y, report, validation):
     return batch_acc
 
 
+def _train_device_fed(network, db, n_steps, step, report):
+    """``n_steps`` device-fed steps after step ``step`` -> (steps taken, whether the draw goes on).  A network that trains with
+    ``clip_norm`` / ``skip_nonfinite`` takes them one read-back chunk at a time (``Trainer.loss_log_capacity``; the same steps as
+    one call) and looks at the count of skipped steps after each: a chunk in which EVERY step was skipped ends the draw, with a
+    line in the report -- the weights no longer change, and unchanged weights on a diverged forward pass never recover."""
+    if getattr(network, "clip_norm", None) is None and not getattr(network, "skip_nonfinite", None):
+        network.train_network_steps(db, n_steps)
+        return n_steps, True
+    chunk = network._require_trainer().loss_log_capacity
+    skipped = network.step_stats()["skipped"]
+    done = 0
+    while done < n_steps:
+        k = min(chunk, n_steps - done)
+        network.train_network_steps(db, k)
+        done += k
+        before, skipped = skipped, network.step_stats()["skipped"]
+        if skipped - before == k:
+            _append(report, "\nDraw ended at step {}: all {} steps of the last chunk were skipped (non-finite gradients or loss)\n"
+                    .format(step + done, k))
+            return done, False
+    return done, True
+
+
 def train_and_validate(network, db, training_nr, squiggles, max_seq_length, file_path, validation_start, max_number,
                        checkpoint_every=10000):
     """networks/train_validate.py:114-185.  ``training_nr // batch_size`` optimizer steps on balanced batches from
@@ -363,8 +386,11 @@ def train_and_validate(network, db, training_nr, squiggles, max_seq_length, file
         step = 0
         while step < steps:
             upto = min(steps, (step // checkpoint_every + 1) * checkpoint_every)
-            network.train_network_steps(db, upto - step)
-            hp_labels += (upto - step) * (network.batch_size // 2) * network.window
+            took, alive = _train_device_fed(network, db, upto - step, step, report)
+            hp_labels += took * (network.batch_size // 2) * network.window
+            if not alive:                                        # diverged for good: no checkpoint of it, no further round
+                seen = (step + took) * network.batch_size
+                break
             step = upto
             if step == steps - 1:
                 print("This was the final checkpoint\n")
@@ -736,6 +762,9 @@ def main(argv):
     among them).
     CATFISH_TRAINING_PRECISION=bf16x3 trains with ``training_precision="bf16x3"`` (every draw that trains on the any-size kernels;
     refused where the tuned ones or plain torch train).
+    CATFISH_CLIP_NORM=<c> trains with ``clip_norm=c``: every step's gradients scaled to a global norm of at most c, and a step with
+    non-finite gradients or loss skipped (``training.Trainer``); a device-fed draw whose steps were all skipped for a whole
+    read-back chunk is ended, with a line in the report.
     CATFISH_DEVICE_DB=1 keeps the training windows on the card (``device_db.DeviceExampleDb``): the steps between two
     checkpoint rounds run back to back, each drawing its own batch.
     CATFISH_DEVICE_DB=reads trains from the labelled reads as they are (``device_db.DeviceReadDb``).  Despite the variable's name
@@ -798,6 +827,8 @@ def main(argv):
         hparams["native_training"] = True
     if os.environ.get("CATFISH_TRAINING_PRECISION"):             # "bf16x3": split bf16 products in the any-size training recurrences
         hparams["training_precision"] = os.environ["CATFISH_TRAINING_PRECISION"]
+    if os.environ.get("CATFISH_CLIP_NORM"):                      # global-norm gradient clipping + the non-finite-step guard
+        hparams["clip_norm"] = float(os.environ["CATFISH_CLIP_NORM"])
     network = build_model(kind, save=True, **hparams)
     network.initialize_network()
     from . import labelling

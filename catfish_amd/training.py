@@ -165,16 +165,37 @@ class TorchResNetRNN(object):
         return torch.nn.functional.binary_cross_entropy_with_logits(z, y, reduction="mean")
 
 
-class TFOptimizer(object):
-    """tf.train.AdamOptimizer / RMSPropOptimizer update rules with TF-1 defaults (rnn_class.py:62-71)."""
+def check_clip(clip_norm, skip_nonfinite):
+    """The two options of gradient clipping, checked -> (clip_norm as a float or None, skip_nonfinite as a bool).  ``clip_norm`` is
+    None or a finite number > 0 (anything else: ValueError); ``skip_nonfinite`` None means "on exactly when clipping is"."""
+    if clip_norm is not None:
+        if isinstance(clip_norm, bool) or not isinstance(clip_norm, (int, float, np.integer, np.floating)):
+            raise ValueError("clip_norm must be None or a finite number > 0, not %r" % (clip_norm,))
+        clip_norm = float(clip_norm)
+        if not (np.isfinite(clip_norm) and clip_norm > 0.0):
+            raise ValueError("clip_norm must be None or a finite number > 0, not %r" % (clip_norm,))
+    return clip_norm, (clip_norm is not None) if skip_nonfinite is None else bool(skip_nonfinite)
 
-    def __init__(self, params, choice, lr):
+
+class TFOptimizer(object):
+    """tf.train.AdamOptimizer / RMSPropOptimizer update rules with TF-1 defaults (rnn_class.py:62-71).
+
+    ``clip_norm`` / ``skip_nonfinite`` (both off by default; ``check_clip``) put global-norm clipping and a non-finite-step guard
+    in front of the update, for this class's own ``step`` and for the native steps, which read the options and share ``stats``:
+    S = the float64 sum of the squared gradients, g = sqrt(S), s32 = float32(clip_norm / max(g, clip_norm))
+    (``tf.clip_by_global_norm``; 1 without ``clip_norm``), the update consumes g_i * s32, and with ``skip_nonfinite`` a step whose S
+    or loss is not finite changes nothing, ``t`` included.  ``stats``: device float64 [4] = g of the last step, the scale applied
+    (-1 on a skipped step), steps clipped (s32 < 1), steps skipped."""
+
+    def __init__(self, params, choice, lr, clip_norm=None, skip_nonfinite=None):
         import torch
         self.torch = torch
         if choice not in ("Adam", "RMSProp"):
             raise ValueError("Given optimizer choice is not known. Choose 'Adam' or 'RMSProp'.")
         self.choice = choice
         self.lr = float(lr)
+        self.clip_norm, self.skip_nonfinite = check_clip(clip_norm, skip_nonfinite)
+        self.guarded = self.clip_norm is not None or self.skip_nonfinite
         self.keep_grads = False      # graph mode: gradients live in the captured pool and are overwritten on replay
         self.params = params
         first = next(iter(params.values()))
@@ -182,6 +203,8 @@ class TFOptimizer(object):
         self.t = torch.zeros((), dtype=torch.float64, device=first.device)
         self._b1 = torch.tensor(0.9, dtype=torch.float64, device=first.device)      # created outside any capture
         self._b2 = torch.tensor(0.999, dtype=torch.float64, device=first.device)
+        self.stats = torch.zeros(4, dtype=torch.float64, device=first.device)
+        self._clip = torch.tensor(self.clip_norm or 0.0, dtype=torch.float64, device=first.device)
         if choice == "Adam":
             self.m = {k: torch.zeros_like(v) for k, v in params.items()}
             self.v = {k: torch.zeros_like(v) for k, v in params.items()}
@@ -236,14 +259,42 @@ class TFOptimizer(object):
                 if t_new is not None:
                     self.t.fill_(max(0, t_new))
 
-    def step(self):
+    def _guard(self, gs, loss):
+        """The definition in the class docstring with device scalars only (graph-safe) -> (the scaled gradients, ok: a bool
+        scalar tensor, False for a step to skip); updates ``stats``."""
+        torch = self.torch
+        S = torch.stack([(g.detach().to(torch.float64) ** 2).sum() for g in gs]).sum()
+        gn = torch.sqrt(S)
+        ok = torch.ones((), dtype=torch.bool, device=S.device)
+        if self.skip_nonfinite:
+            ok = torch.isfinite(S)
+            if loss is not None:
+                ok = ok & torch.isfinite(loss.detach()).all()
+        one = torch.ones((), dtype=torch.float64, device=S.device)
+        s32 = one
+        if self.clip_norm is not None:
+            # max(g, c) as fmax: a NaN norm leaves c (only met with skip_nonfinite switched off)
+            s32 = (self._clip / torch.fmax(gn, self._clip)).to(torch.float32).to(torch.float64)
+        self.stats[0] = gn
+        self.stats[1] = torch.where(ok, s32, -one)
+        self.stats[2] += (ok & (s32 < 1.0)).to(torch.float64)
+        self.stats[3] += (~ok).to(torch.float64)
+        # a skipped step's gradients are not used; zeros keep NaN / Inf out of the arithmetic whose result is discarded
+        return [torch.where(ok, g * s32.to(g.dtype), torch.zeros_like(g)) for g in gs], ok
+
+    def step(self, loss=None):
         """One update of every parameter with multi-tensor (``torch._foreach_*``) ops: a handful of launches
-        instead of ~8 per parameter tensor (66 tensors)."""
+        instead of ~8 per parameter tensor (66 tensors).  ``loss``: the step's loss, which the non-finite guard also looks at."""
         torch = self.torch
         with torch.no_grad():
             keys = [k for k, p in self.params.items() if p.grad is not None]
             ps = [self.params[k] for k in keys]
             gs = [self.params[k].grad for k in keys]
+            if self.guarded:
+                gs, ok = self._guard(gs, loss)
+                first, second = (self.m, self.v) if self.choice == "Adam" else (self.ms, self.mom)
+                state = ps + [first[k] for k in keys] + [second[k] for k in keys] + [self.t]
+                before = [a.clone() for a in state]
             self.t.add_(1.0)
             if self.choice == "Adam":
                 b1, b2, eps = 0.9, 0.999, 1e-8
@@ -270,6 +321,9 @@ class TFOptimizer(object):
                 torch._foreach_mul_(upd, self.lr)
                 torch._foreach_sub_(ps, upd)
                 torch._foreach_copy_([self.mom[k] for k in keys], upd)
+            if self.guarded:                                       # a skipped step changes nothing, the counter included
+                for a, old in zip(state, before):
+                    a.copy_(torch.where(ok, a, old))
             if not self.keep_grads:
                 for p in ps:
                     p.grad = None
@@ -312,7 +366,7 @@ class AutogradStep(object):
         loss = self.net.loss(b["x"], b["y"], kp, None if captured else self.gen, self.engine, masks)
         loss.backward()
         if update:
-            self.opt.step()
+            self.opt.step(loss)
         else:
             self._grads = {k: p.grad for k, p in self.net.trainable().items()}
             self._clear()
@@ -344,10 +398,18 @@ class Trainer(object):
     ``precision="bf16x3"`` (opt-in; the default "fp32" changes nothing) evaluates the matrix products on the serial chain of the
     any-size biGRU recurrences, forward and backward, as split bf16 products; everything else stays fp32.  It exists where those
     kernels train: on a GPU, in float32, in the two ``anysize_*`` rows of that table.
+
+    ``clip_norm=c`` (opt-in) scales every step's gradients to a global norm of at most ``c`` (``tf.clip_by_global_norm`` in front of
+    the reference's ``optimizer.minimize``), and ``skip_nonfinite`` (on with ``clip_norm`` unless switched off; may be switched on
+    alone) skips a step whose gradients or loss are not finite: no variable, slot or packed weight changes and ``opt.t`` stays, so
+    the next batch meets the same dropout masks.  Both hold in every mode (``TFOptimizer``'s docstring has the definition; the native
+    steps run it as HIP kernels inside the captured step) and are orthogonal to ``train_mode``'s table.  ``step_stats()`` reads
+    what happened.
     """
 
     def __init__(self, weights, n_layers, n_layers_res, optimizer_choice, learning_rate, keep_prob, device=None,
-                 seed=None, use_graph=None, native=None, optimizer_state=None, dtype=None, loss_log_capacity=4096, precision="fp32"):
+                 seed=None, use_graph=None, native=None, optimizer_state=None, dtype=None, loss_log_capacity=4096, precision="fp32",
+                 clip_norm=None, skip_nonfinite=None):
         import torch
         from .anysize_train import check_precision
         self.precision = check_precision(precision)
@@ -361,7 +423,8 @@ class Trainer(object):
                 raise RuntimeError("Trainer: no HIP device visible; pass device='cpu' explicitly for the torch reference mode")
             device = "cuda"
         self.net = TorchResNetRNN(weights, n_layers, n_layers_res, device=device, dtype=dtype, precision=self.precision)
-        self.opt = TFOptimizer(self.net.trainable(), optimizer_choice, learning_rate)
+        self.opt = TFOptimizer(self.net.trainable(), optimizer_choice, learning_rate, clip_norm=clip_norm, skip_nonfinite=skip_nonfinite)
+        self.clip_norm, self.skip_nonfinite = self.opt.clip_norm, self.opt.skip_nonfinite
         if optimizer_state:
             self.opt.load_state_tf(optimizer_state)
         self.keep_prob = float(keep_prob)
@@ -518,6 +581,13 @@ class Trainer(object):
             done += k
         self.last_loss = float(out[-1])
         return out
+
+    def step_stats(self):
+        """{"grad_norm": g of the last step, "scale": the factor applied to its gradients (-1.0: the step was skipped),
+        "clipped": steps clipped so far, "skipped": steps skipped so far}; all zero until a step with ``clip_norm`` or
+        ``skip_nonfinite`` has run.  One synchronise: for the caller between chunks, never inside the loop."""
+        g, scale, clipped, skipped = self.opt.stats.cpu().tolist()
+        return {"grad_norm": g, "scale": scale, "clipped": int(clipped), "skipped": int(skipped)}
 
     def gradients(self, x, y, keep_prob=None, masks=None):
         """Loss and gradients of one batch WITHOUT an update: (loss, {TF name: ndarray}) -- what tests compare with the
