@@ -28,6 +28,12 @@ with the random subset of negatives drawn by the keyed bijection above, so that 
 It is a host database and feeds the per-step loop.  Building the tables and gathering on the card is not in the tree; the index rules
 such kernels would follow are (csrc/read_tables_plan.hpp, pieces of ``TABLE_PIECE`` window starts), replayed on the CPU against
 ``centre_tables`` and ``DeviceReadDb.gather`` (tests/test_read_tables_replay.py).
+
+``DeviceTiledDb`` (opt-in) departs from the reference's selection on purpose: it holds the windows a caller cuts -- every read cut into
+consecutive 35-sample windows -- with their true per-sample labels, so that a homopolymer's border lies inside a training window as it
+does inside a called one (``tiled_tables`` states which windows).  The sampler above is unchanged; the windows are copied into pools
+like ``DeviceExampleDb``'s, with one label byte per sample next to the first pool.  Like ``DeviceReadDb`` it is a host database and
+feeds the per-step loop: it has no ``device_pools``.
 """
 from __future__ import annotations
 
@@ -279,21 +285,26 @@ def centre_tables(labels, offsets, lessen=1, neg_per_read=None, seed=0):
         hits = hits[ones[hits] == WINDOW]                                # ... whose whole window is ones
         pos.append(first[hits])
         cand = np.flatnonzero(ones == 0)
-        m = cand.size
-        q = _neg_quota(neg_per_read, m, hits.size)
-        if q < m:
-            with np.errstate(over="ignore"):
-                key = fmix32(seed ^ fmix32(_U(((rho + 1) * 0x9E3779B9) & 0xFFFFFFFF)))
-            cand = cand[keyed_permutation(np.arange(m, dtype=np.uint32), m, key) < q]
-        neg.append(first[cand])
+        neg.append(first[_quota_subset(cand, _neg_quota(neg_per_read, cand.size, hits.size), rho, seed)])
     empty = np.zeros(0, dtype=np.int64)
     return (np.concatenate(pos) if pos else empty), (np.concatenate(neg) if neg else empty)
 
 
-def _table_sizes_fit(n_pos, n_neg):
+def _quota_subset(cand, q, rho, seed):
+    """Which of read ``rho``'s ``m`` candidates (in order) are kept when ``q`` of them are: all for q == m, else candidate j iff
+    ``keyed_permutation(j, m, key) < q`` with ``key = fmix32(seed ^ fmix32((rho + 1) * 0x9E3779B9))`` (``seed`` a uint32)."""
+    m = cand.size
+    if q < m:
+        with np.errstate(over="ignore"):
+            key = fmix32(seed ^ fmix32(_U(((rho + 1) * 0x9E3779B9) & 0xFFFFFFFF)))
+        cand = cand[keyed_permutation(np.arange(m, dtype=np.uint32), m, key) < q]
+    return cand
+
+
+def _table_sizes_fit(n_pos, n_neg, advice="raise lessen or cap neg_per_read"):
     """``keyed_permutation`` draws rows from [0, n) with n below 2^31."""
     if n_pos >= 2 ** 31 or n_neg >= 2 ** 31:
-        raise ValueError("a table of 2^31 or more windows (%d positives, %d negatives): raise lessen or cap neg_per_read" % (n_pos, n_neg))
+        raise ValueError("a table of 2^31 or more windows (%d positives, %d negatives): %s" % (n_pos, n_neg, advice))
 
 
 class DeviceReadDb(DeviceFedDb):
@@ -377,3 +388,137 @@ def synthetic_device_read_db(n_reads=8, read_len=20000, seed=0, lessen=1, neg_pe
     from .train_validate import synthetic_labelled_read
     reads = [synthetic_labelled_read(read_len, seed * 1000 + r) for r in range(n_reads)]
     return DeviceReadDb.from_arrays([raw for raw, _ in reads], [lab for _, lab in reads], seed, lessen, neg_per_read)
+
+
+# --------------------------------------------------------------------------- the windows the caller cuts, with their per-sample labels
+def _miss_quota(miss_per_read, m, n_hit):
+    """``_neg_quota`` with the tiled selection's name for the reference's rule: ``"hits"`` keeps as many misses as the read has hits."""
+    if isinstance(miss_per_read, str):
+        if miss_per_read != "hits":
+            raise ValueError("miss_per_read: None, an int or 'hits', got %r" % (miss_per_read,))
+        return min(m, n_hit)
+    return _neg_quota(miss_per_read, m, n_hit)
+
+
+def _check_stride(stride):
+    if isinstance(stride, (bool, np.bool_)) or not isinstance(stride, (int, np.integer)) or int(stride) < 1:
+        raise ValueError("stride must be an int of at least 1, got %r" % (stride,))
+    return int(stride)
+
+
+def tiled_tables(labels, offsets, stride=WINDOW, miss_per_read=None, seed=0):
+    """Which windows of the concatenated reads (the layout of ``centre_tables``) a caller that cuts every read into consecutive
+    windows would see -> (hit_start int64 [], miss_start int64 []): the index of each window's first sample, in (read, start) order.
+
+    For read ``rho`` of ``n`` samples at offset ``o`` the windows start at ``o + k * stride``, k = 0, 1, ... while
+    ``k * stride + 35 <= n``: none is padded, none straddles two reads, a read shorter than 35 samples contributes nothing.
+    ``stride`` 35 is the caller's own grid, 1 gives every window.  A window with at least one label 1 is a hit, one with none a miss.
+    Of a read's ``m`` misses q are kept: ``miss_per_read=None`` q = m, an int q = min(m, it), ``"hits"`` q = min(m, the read's hits);
+    which ones is ``centre_tables``' rule for its negatives (``_quota_subset``: the same key, the same ``keyed_permutation``, ``< q``).
+    Tables of 2^31 rows or more are refused.
+
+    This is NOT the reference's selection (``TrainingRead.get_pos`` / ``get_neg`` keep only windows whose 35 labels are all equal):
+    a hit here may hold a homopolymer's border, and the labels of a hit are the read's own, sample by sample."""
+    labels, offsets, _ = _read_layout(labels, offsets, 1)
+    stride = _check_stride(stride)
+    _miss_quota(miss_per_read, 0, 0)                                      # a bad rule is refused even when no read has a candidate
+    seed = _U(int(seed) & 0xFFFFFFFF)
+    running = np.zeros(labels.size + 1, dtype=np.int64)
+    np.cumsum(labels, out=running[1:])
+    hit, miss = [], []
+    for rho in range(offsets.size - 1):
+        o, n = int(offsets[rho]), int(offsets[rho + 1] - offsets[rho])
+        if n < WINDOW:
+            continue
+        first = o + np.arange(0, n - WINDOW + 1, stride, dtype=np.int64)
+        ones = running[first + WINDOW] - running[first]
+        hits = np.flatnonzero(ones > 0)
+        hit.append(first[hits])
+        cand = np.flatnonzero(ones == 0)
+        miss.append(first[_quota_subset(cand, _miss_quota(miss_per_read, cand.size, hits.size), rho, seed)])
+    empty = np.zeros(0, dtype=np.int64)
+    hit, miss = (np.concatenate(hit) if hit else empty), (np.concatenate(miss) if miss else empty)
+    _table_sizes_fit(hit.size, miss.size, "raise stride or cap miss_per_read")
+    return hit, miss
+
+
+class DeviceTiledDb(DeviceFedDb):
+    """The windows of ``tiled_tables`` copied into pools, as ``DeviceExampleDb`` keeps its windows: ``pos`` float32 [n_hit, 35] with
+    ``pos_labels`` uint8 [n_hit, 35] (the read's own labels: a hit may hold a border) and ``neg`` float32 [n_miss, 35], whose labels
+    are all zero by construction.  The sampler is ``draw_indices``, unchanged: ``size // ratio`` distinct hits and the remaining
+    distinct misses, shuffled over the slots.  A HOST database, like ``DeviceReadDb``: it has no ``device_pools``, so
+    ``Trainer.train_steps`` / ``RNN.train_network_steps`` and ``train_and_validate`` run it through ``get_training_set`` + one
+    host-fed step per batch, on a GPU as on the CPU, and the per-sample labels arrive through ``train_step``'s ``y``."""
+
+    def __init__(self, pos, pos_labels, neg, seed, device=None):
+        DeviceFedDb.__init__(self, seed, device)
+        self.pos = _pool(pos)
+        self.neg = _pool(neg)
+        lab = np.asarray(pos_labels)
+        if lab.dtype != np.uint8 or lab.shape != self.pos.shape:
+            raise ValueError("pos_labels must be uint8 %s, got %s %s" % (self.pos.shape, lab.dtype, lab.shape))
+        if lab.size and lab.max() > 1:
+            raise ValueError("labels must be 0 or 1")
+        self.pos_labels = np.ascontiguousarray(lab)
+        self.nb_pos, self.nb_neg = int(self.pos.shape[0]), int(self.neg.shape[0])
+        _table_sizes_fit(self.nb_pos, self.nb_neg, "raise stride or cap miss_per_read")
+
+    @classmethod
+    def from_layout(cls, signal, labels, offsets, seed=0, stride=WINDOW, miss_per_read=None, device=None):
+        """The pools of concatenated reads (``signal`` [total], ``labels`` uint8 [total], ``offsets`` int64 [R + 1])."""
+        hit, miss = tiled_tables(labels, offsets, stride, miss_per_read, seed)
+        signal = np.ascontiguousarray(signal, dtype=np.float32).reshape(-1)
+        labels = np.asarray(labels)
+        if signal.size != labels.size:
+            raise ValueError("%d samples but %d labels" % (signal.size, labels.size))
+        span = np.arange(WINDOW)
+        return cls(signal[hit[:, None] + span], labels[hit[:, None] + span], signal[miss[:, None] + span], seed, device)
+
+    @classmethod
+    def from_arrays(cls, signals, labels, seed=0, stride=WINDOW, miss_per_read=None, device=None):
+        """One read per (signal, labels) pair, in that order."""
+        from .device_validation import DeviceValidationSet
+        v = DeviceValidationSet.from_arrays(signals, labels)
+        return cls.from_layout(v.signal, v.labels, v.offsets, seed, stride, miss_per_read, device)
+
+    @classmethod
+    def from_npz(cls, paths, seed=0, stride=WINDOW, miss_per_read=None, loader=None, device=None):
+        """The reads of ``paths`` (``raw`` + ``base_labels``, ``train_validate.load_npz``), in that order."""
+        from .device_validation import DeviceValidationSet
+        v = DeviceValidationSet.from_npz(paths, loader)
+        return cls.from_layout(v.signal, v.labels, v.offsets, seed, stride, miss_per_read, device)
+
+    @classmethod
+    def from_source(cls, paths, source, seed=0, stride=WINDOW, miss_per_read=None, device=None):
+        """The reads of ``paths``, in that order, as ``source`` (a ``labelling.LabelSource``) says they are stored, labelled through
+        ``DeviceValidationSet.from_source`` (event and move files on the card where there is one)."""
+        from .device_validation import DeviceValidationSet
+        v = DeviceValidationSet.from_source(paths, source, device)
+        return cls.from_layout(v.signal, v.labels, v.offsets, seed, stride, miss_per_read, device)
+
+    # ------------------------------------------------------------------ the sampler on the host
+    def gather(self, d, size, ratio=2):
+        """Draw ``d`` as arrays: (x float32 [size, 35], y uint8 [size, 35]) -- the labels are the windows' own."""
+        is_pos, row = self.batch_indices(d, size, ratio)
+        x = np.empty((int(size), WINDOW), np.float32)
+        y = np.zeros((int(size), WINDOW), np.uint8)
+        x[is_pos] = self.pos[row[is_pos]]
+        y[is_pos] = self.pos_labels[row[is_pos]]
+        x[~is_pos] = self.neg[row[~is_pos]]
+        return x, y
+
+    def get_training_set(self, size, ratio=2):
+        """``WindowExampleDb.get_training_set``'s shapes for the next draw: (tuple of windows, tuple of label lists -- the true
+        per-sample labels --, number of 1 labels); advances the draw counter."""
+        x, y = self.gather(self.draw, size, ratio)
+        self.draw += 1
+        y = y.astype(np.int64)
+        self._last = ("host", x, y)
+        return tuple(x), tuple(y.tolist()), int(y.sum())
+
+
+def synthetic_device_tiled_db(n_reads=8, read_len=20000, seed=0, stride=WINDOW, miss_per_read=None, device=None):
+    """``train_validate.synthetic_example_db``'s reads (the same squiggles) in a ``DeviceTiledDb``."""
+    from .train_validate import synthetic_labelled_read
+    reads = [synthetic_labelled_read(read_len, seed * 1000 + r) for r in range(n_reads)]
+    return DeviceTiledDb.from_arrays([raw for raw, _ in reads], [lab for _, lab in reads], seed, stride, miss_per_read, device)

@@ -752,6 +752,37 @@ def device_read_db_from_env(npz_files):
     return DeviceReadDb.from_source(npz_files, labelling.LabelSource.from_env(), seed=0, neg_per_read=None if rule == "all" else rule)
 
 
+def tiled_options_from_env():
+    """CATFISH_TILED_STRIDE (an int of at least 1; default 35, the caller's grid) and CATFISH_TILED_MISSES (``hits``, the default: as
+    many windows without a positive sample as the read has windows with one; an integer; or ``all``) -> (stride, miss_per_read) as
+    ``device_db.tiled_tables`` takes them.  Anything else raises ValueError."""
+    text = os.environ.get("CATFISH_TILED_STRIDE", "35")
+    try:
+        stride = int(text)
+    except ValueError:
+        stride = 0
+    if stride < 1:
+        raise ValueError("CATFISH_TILED_STRIDE must be an integer of at least 1, got %r" % text)
+    rule = os.environ.get("CATFISH_TILED_MISSES", "hits")
+    if rule not in ("hits", "all"):
+        try:
+            rule = int(rule)
+        except ValueError:
+            rule = -1
+        if rule < 0:
+            raise ValueError("CATFISH_TILED_MISSES must be 'hits', 'all' or a non-negative integer, got %r" % os.environ["CATFISH_TILED_MISSES"])
+    return stride, None if rule == "all" else rule
+
+
+def device_tiled_db_from_env(npz_files):
+    """``CATFISH_DEVICE_DB=tiled``: a ``device_db.DeviceTiledDb`` over the NPZ reads, cut as ``tiled_options_from_env`` says; the reads
+    are what ``labelling.LabelSource.from_env()`` says they are (event and move files are labelled on the card where there is one)."""
+    from .device_db import DeviceTiledDb
+    from . import labelling
+    stride, misses = tiled_options_from_env()
+    return DeviceTiledDb.from_source(npz_files, labelling.LabelSource.from_env(), seed=0, stride=stride, miss_per_read=misses)
+
+
 def main(argv):
     """networks/train_validate.py:298-360: ``network_type train_npz_dir n_training_examples validation_npz_dir
     max_validation_length [validation_start [max_number]]``.  The training "database" argument is a directory of NPZ
@@ -772,6 +803,14 @@ def main(argv):
     more than with CATFISH_DEVICE_DB=1; what it offers is 5 B per sample and two tables of window starts instead of one array per
     window, the reference's negative rule and a reproducible selection.  CATFISH_DEVICE_NEG=positives|<int>|all sets the
     negatives a read contributes (``device_read_db_from_env``).
+    CATFISH_DEVICE_DB=tiled trains on the windows the caller will cut (``device_db.DeviceTiledDb``): every read cut into consecutive
+    35-sample windows from its first sample, each with its true per-sample labels, so that a homopolymer's border falls inside a
+    window.  Like ``reads`` it is a HOST database: every batch is gathered in numpy and copied over.  This departs from the
+    reference's selection (``TrainingRead.get_pos`` / ``get_neg`` keep only windows whose 35 labels are all equal), which never
+    shows the network the mixed windows it meets when calling.  CATFISH_TILED_STRIDE=<int> (default 35) sets the distance between
+    window starts, CATFISH_TILED_MISSES=hits|<int>|all (default ``hits``) how many windows without a positive sample a read
+    contributes (``tiled_options_from_env``; a bad value raises ValueError).  CATFISH_LABEL_KMER / CATFISH_LABEL_MOVES apply as for
+    ``reads``.
     CATFISH_DEVICE_VALIDATION=1 keeps the validation reads on the card too (``device_validation.DeviceValidationSet``, loaded
     once): a checkpoint round gathers and scores its stretches there instead of re-opening the files.
     CATFISH_VALIDATION_RUNS=1 (with CATFISH_DEVICE_VALIDATION=1) also counts, per round, the homopolymers found at threshold 0.5
@@ -852,6 +891,8 @@ def main(argv):
         db_train = device_db_from_npz(_npz_files(train_dir), **with_loader)
     elif os.environ.get("CATFISH_DEVICE_DB") == "reads":         # the labelled reads as they are, two tables of window starts: a HOST database
         db_train = device_read_db_from_env(_npz_files(train_dir))
+    elif os.environ.get("CATFISH_DEVICE_DB") == "tiled":         # the windows the caller cuts, labels per sample: a HOST database
+        db_train = device_tiled_db_from_env(_npz_files(train_dir))
     else:
         db_train = example_db_from_npz(_npz_files(train_dir), **with_loader)
     if source.has_tables:
